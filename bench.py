@@ -16,10 +16,20 @@ which runs in a child process of its own, started and finished before this proce
 
 Prints ONE JSON line (rank 0).  `roofline.achieved` = 19 algorithmic bytes per env-step (SURVEY.md
 §8(d): read 6 B state + 2 B actions, write 6 B state + 5 B obs/reward/terminated/truncated) x lanes
-per launch / ms_per_step, the host wall clock `value` is computed from; `roofline.achieved_device` /
-`frac_device` use device clock stamps captured around the K launches on the kernel's own stream instead.
-`cpu_baseline` = the CPU oracle (oracle/soccer_oracle.c, a port pinned bit-for-bit to the reference
-by tests/golden) timed on this box's host cores on a bounded sample of the same workload.
+per launch / ms_per_step, the host wall clock `value` is computed from.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what that headline needs: set-up, the W warm-up steps and
+the untimed replays, the K timed steps, the result line.  `--full` adds everything else, each after the timed region:
+`roofline.achieved_device` / `frac_device` (device clock stamps captured around the K launches on the kernel's own stream),
+the per-launch profile, the episode returns and output sanity checks (and the RCCL gather at N > 1), the fused and self-play
+rollouts, the VectorSoccerEnv leg (a torch child process run before this process touches the GPU) and `cpu_baseline` = the
+CPU oracle (oracle/soccer_oracle.c, a port pinned bit-for-bit to the reference by tests/golden) timed on this box's host
+cores on a bounded sample of the same workload.  The untimed work before the clock is the same in both, so the timed steps
+compute the same outputs.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0's lanes): obs, reward, terminated,
+truncated as DIR/<name>.npy in float32 (a fixed, seeded sample of the lanes, with DIR/lane_index.npy, when they would
+exceed 64 MB).  The inputs depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -71,6 +81,22 @@ def cpu_baseline(lanes_total, slip, seconds):
     return {"value": steps / dt, "unit": "env-steps/s", "cores": threads, "kind": "port", "value_1_core": one_core,
             "sample": "%d threads x %d lanes x ~%d steps of the same uniform-random workload (%.1f s), after 1 thread alone for %.1f s"
                       % (threads, per, counts[0], dt, dt1)}
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> [lanes] host array, what the caller of the timed path receives) as float32 .npy
+    files, at most DUMP_BYTES_MAX in all: beyond that a fixed, seeded sample of the lanes, whose indices go to lane_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    per_lane = 4 * len(arrays)
+    if n * per_lane > DUMP_BYTES_MAX:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=DUMP_BYTES_MAX // (per_lane + 8), replace=False))
+        arrays = dict({k: v[keep] for k, v in arrays.items()}, lane_index=keep.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else np.asarray(a, np.float32))
 
 
 REFERENCE_PYTHON = {"value": 5.3e4, "unit": "env-steps/s", "cores": 1, "where": "build container (Xeon 2.1 GHz)",
@@ -330,13 +356,18 @@ def main():
     ap.add_argument("--slip", type=float, default=0.0)
     ap.add_argument("--mode", choices=["graph", "eager"], default="graph")
     ap.add_argument("--envs-per-thread", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--rollout", type=int, default=100, help="also time a fused T-step rollout (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything the headline does not need: device-clock "
+                         "figures, launch profile, episode returns, rollouts, the VectorSoccerEnv leg, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's obs / reward / terminated / truncated (rank 0) as DIR/<name>.npy, float32")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: length of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--rollout", type=int, default=100, help="--full: also time a fused T-step rollout (0 = skip)")
     ap.add_argument("--comm", choices=["rccl", "host"], default="rccl",
                     help="rccl: the real path (RCCL over xGMI through soccer_comm_*); host: rehearse the multi-rank path on fewer GPUs "
                          "than ranks (ranks share devices, the exchange goes through files in host memory) — never a measured path")
-    ap.add_argument("--no-vector-env", action="store_true", help="skip the VectorSoccerEnv(io='device') timing (a torch child process)")
+    ap.add_argument("--no-vector-env", action="store_true", help="--full: skip the VectorSoccerEnv(io='device') timing (a torch child process)")
     ap.add_argument("--action-loads", choices=["auto", "nt", "plain"], default="auto",
                     help="how batched_step reads its action streams: nt = SOCCER_F_STREAM_ACTIONS, plain = the library default, "
                          "auto = nt when the synthetic action trajectory exceeds 96 MB")
@@ -376,7 +407,7 @@ def main():
 
     # the gym-style surface (a torch process of its own), run to completion before this process makes its first GPU call
     vec_env = None
-    if not args.no_vector_env and world == 1:
+    if args.full and not args.no_vector_env and world == 1:
         child = ["--lanes", str(args.lanes), "--steps", str(args.steps), "--slip", str(args.slip), "--rollout", str(args.rollout),
                  "--action-loads", args.action_loads]
         vec_env = run_vector_env_child(child, 600.0)
@@ -408,7 +439,7 @@ def main():
     # Cache between replays (K = 1000: 2 GB) the handle is told that its action streams stream in from HBM (SOCCER_F_STREAM_ACTIONS:
     # non-temporal loads); a short sequence (the driver's K = 20: 40 MB) is re-read from the cache like the action buffer of an
     # RL loop, the library's default (include/soccer_hip.h).  --action-loads overrides the choice.
-    KA = max(K, W, args.rollout, 1)
+    KA = max(K, W, args.rollout if args.full else 0, 1)      # (rows are drawn in order: the first ones do not depend on KA)
     act_bytes = max(K, W) * 2 * N
     stream_actions = {"auto": act_bytes > (96 << 20), "nt": True, "plain": False}[args.action_loads]
     b = SoccerBatch(N, 5, 4, args.slip, seed=0, autoreset=True, device=dev_index,
@@ -443,22 +474,27 @@ def main():
         for k in range(KG):
             enqueue(k)
         graph = b.graph_end()         # instantiated and uploaded (hipGraphUpload)
-        # its twin for the device-side figures: the same launches between two clock stamps (each stamp is a one-thread kernel
-        # of its own — ~1.9 us of device time that does not belong in a region that times K steps, which is why the timed graph
-        # has none); replayed after the timed region under the same conditions
-        b.graph_begin()
-        b.timer_start()
-        for k in range(KG):
-            enqueue(k)
-        b.timer_mark()
-        graph_s = b.graph_end()
+        if args.full:
+            # its twin for the device-side figures: the same launches between two clock stamps (each stamp is a one-thread kernel
+            # of its own — ~1.9 us of device time that does not belong in a region that times K steps, which is why the timed graph
+            # has none); replayed after the timed region under the same conditions
+            b.graph_begin()
+            b.timer_start()
+            for k in range(KG):
+                enqueue(k)
+            b.timer_mark()
+            graph_s = b.graph_end()
         # Untimed replays (the workload is stationary: advancing the state changes nothing): the timed region then pays none
         # of the path's one-off costs — three of the graph that is timed, each followed by a synchronisation like the timed
-        # one (a replay's first and second launch have been seen to cost the host 3x the usual hipGraphLaunch call), one of
-        # the twin.
+        # one (a replay's first and second launch have been seen to cost the host 3x the usual hipGraphLaunch call), and a
+        # fourth: of the twin with --full, of the timed graph itself without (the same K launches either way, so the timed
+        # steps start from the same state and tick).
         for _ in range(3):
             b.graph_launch(graph, 1); b.sync()
-        b.graph_launch(graph_s, 1); first_ms = b.timer_read()
+        if graph_s is not None:
+            b.graph_launch(graph_s, 1); first_ms = b.timer_read()
+        else:
+            b.graph_launch(graph, 1)
         warm_replays = 4
         b.sync()
     b.reset_stats()
@@ -491,6 +527,13 @@ def main():
         t0_, t_enq_, t_end_ = timed_region(job_barrier, device_sync, launch, time.perf_counter)
         if graph is not None:
             check(rc_box[0])
+        if args.dump_outputs and rank == 0:      # before anything else can write the result rows again
+            dump_outputs(args.dump_outputs, {"obs": obs.download_rows(K - 1, 1)[0], "reward": rew.download_rows(K - 1, 1)[0],
+                                             "terminated": term.download_rows(K - 1, 1)[0],
+                                             "truncated": trunc.download_rows(K - 1, 1)[0]})
+        if not args.full:
+            return t0_, t_enq_, t_end_, None
+        if graph is not None:
             # device-side duration of the same K launches: the stamped twin, replayed after an idle synchronisation like the timed
             # region was, three times; the median
             reps = []
@@ -516,18 +559,23 @@ def main():
     wall_own, ev_own = wall, ev_ms
     if comm:
         # every rank's own clocks, so that a scaling line shows rank skew; the job's time is the slowest rank's
-        allr = comm.gather_f64([wall, ev_ms])
-        per_rank = [{"rank": r, "wall_us": float(allr[r, 0]) * 1e6, "device_region_us": float(allr[r, 1]) * 1e3,
-                     "host_overhead_us": float(allr[r, 0]) * 1e6 - float(allr[r, 1]) * 1e3,
-                     "launch_us": float(allr[r, 1]) * 1e3 / K} for r in range(world)]
-        wall, ev_ms = float(allr[:, 0].max()), float(allr[:, 1].max())
+        if not args.full:
+            allr = comm.gather_f64([wall])
+            per_rank = [{"rank": r, "wall_us": float(allr[r, 0]) * 1e6} for r in range(world)]
+            wall = float(allr[:, 0].max())
+        else:
+            allr = comm.gather_f64([wall, ev_ms])
+            per_rank = [{"rank": r, "wall_us": float(allr[r, 0]) * 1e6, "device_region_us": float(allr[r, 1]) * 1e3,
+                         "host_overhead_us": float(allr[r, 0]) * 1e6 - float(allr[r, 1]) * 1e3,
+                         "launch_us": float(allr[r, 1]) * 1e3 / K} for r in range(world)]
+            wall, ev_ms = float(allr[:, 0].max()), float(allr[:, 1].max())
 
     # ---- after the timed region: where the launches of a replay spend their time --------------------------
     # The same K launches captured once more with a clock stamp between every two of them (a one-thread kernel: each
     # adds one more kernel boundary, so the deltas are launch + ~1.5 us; what matters is how they differ along the
     # replay).  Replayed right after an idle synchronisation like the timed region, three times; the last replay is reported.
     launch_profile = None
-    if graph is not None and world == 1 and 2 <= KG <= 200:
+    if args.full and graph is not None and world == 1 and 2 <= KG <= 200:
         b.graph_begin()
         b.stamp(2)
         for k in range(KG):
@@ -564,39 +612,44 @@ def main():
 
     # ---- after the timed region: episode returns from the trajectories the timed steps wrote ---------
     # (the only cross-GPU exchange: one all-gather of int8 per-lane returns + a 3-bin sum)
-    _, misuse = b.stats()
-    assert misuse == 0
-    last_ret = b.alloc(N, np.int8); ep_count = b.alloc(N, np.int32)
-    hist = b.trajectory_returns(K, rew, term, trunc, N, last_return=last_ret, episode_count=ep_count).astype(np.int64)
-    # cheap end-to-end sanity on this rank's real outputs of the timed steps (not a parity test)
-    n_fin = int(hist.sum()); r_sum = int(hist[2]) - int(hist[0])
-    assert n_fin < K * N and abs(r_sum) <= n_fin, "implausible outputs"
-    assert int(ep_count.download().sum()) == n_fin
-    for k in sorted({0, K // 2, K - 1}):
-        o_k, r_k = obs.download_rows(k, 1), rew.download_rows(k, 1)
-        te_k, tr_k = term.download_rows(k, 1), trunc.download_rows(k, 1)
-        assert int(o_k.max()) < b.nS and int(np.abs(r_k).max()) <= 1 and int(te_k.max()) <= 1 and int(tr_k.max()) <= 1, "implausible outputs"
-        assert not ((r_k != 0) & (te_k == 0)).any(), "a reward without a terminal step"
-    if K >= 50:                     # long enough for goals to have been scored
-        assert n_fin > 0 and hist[0] + hist[2] > 0, "implausible outputs"
-    gather_ms = None
-    if comm:
-        gathered_d = b.alloc(world * N, np.int8)
-        b.sync(); comm.barrier(); tg = time.perf_counter()
-        comm.all_gather_lanes(b, last_ret, gathered_d, N)            # RCCL all-gather over xGMI, int8[N] per rank, global lane order
-        hist = comm.sum_u64(hist.astype(np.uint64)).astype(np.int64)
-        b.sync(); gather_ms = (time.perf_counter() - tg) * 1e3       # the job's ONLY exchange (first call: incl. RCCL set-up)
-        gathered = gathered_d.download()
-        assert gathered.size == world * N
-        assert np.array_equal(gathered[lane_lo:lane_hi], last_ret.download()), "this rank's shard is not where its global lane ids say"
-    else:
-        gathered = last_ret.download()
+    episodes = None
+    if args.full:
+        _, misuse = b.stats()
+        assert misuse == 0
+        last_ret = b.alloc(N, np.int8); ep_count = b.alloc(N, np.int32)
+        hist = b.trajectory_returns(K, rew, term, trunc, N, last_return=last_ret, episode_count=ep_count).astype(np.int64)
+        # cheap end-to-end sanity on this rank's real outputs of the timed steps (not a parity test)
+        n_fin = int(hist.sum()); r_sum = int(hist[2]) - int(hist[0])
+        assert n_fin < K * N and abs(r_sum) <= n_fin, "implausible outputs"
+        assert int(ep_count.download().sum()) == n_fin
+        for k in sorted({0, K // 2, K - 1}):
+            o_k, r_k = obs.download_rows(k, 1), rew.download_rows(k, 1)
+            te_k, tr_k = term.download_rows(k, 1), trunc.download_rows(k, 1)
+            assert int(o_k.max()) < b.nS and int(np.abs(r_k).max()) <= 1 and int(te_k.max()) <= 1 and int(tr_k.max()) <= 1, "implausible outputs"
+            assert not ((r_k != 0) & (te_k == 0)).any(), "a reward without a terminal step"
+        if K >= 50:                     # long enough for goals to have been scored
+            assert n_fin > 0 and hist[0] + hist[2] > 0, "implausible outputs"
+        gather_ms = None
+        if comm:
+            gathered_d = b.alloc(world * N, np.int8)
+            b.sync(); comm.barrier(); tg = time.perf_counter()
+            comm.all_gather_lanes(b, last_ret, gathered_d, N)            # RCCL all-gather over xGMI, int8[N] per rank, global lane order
+            hist = comm.sum_u64(hist.astype(np.uint64)).astype(np.int64)
+            b.sync(); gather_ms = (time.perf_counter() - tg) * 1e3       # the job's ONLY exchange (first call: incl. RCCL set-up)
+            gathered = gathered_d.download()
+            assert gathered.size == world * N
+            assert np.array_equal(gathered[lane_lo:lane_hi], last_ret.download()), "this rank's shard is not where its global lane ids say"
+        else:
+            gathered = last_ret.download()
+        episodes = {"hist_minus1_0_plus1": [int(x) for x in hist],
+                    "gathered_last_returns": int(gathered.size), "gather_allreduce_ms": gather_ms,
+                    "gathered_mean": float(gathered.astype(np.float32).mean())}
     for x in (obs, rew, term, trunc):
         x.free()
 
     # ---- optional: fused T-step rollout (state in registers, same per-step results) -------------
     rollout = None
-    if args.rollout > 0:
+    if args.full and args.rollout > 0:
         T = args.rollout
         obs = b.alloc((T, N), np.uint16); rew = b.alloc((T, N), np.int8)
         term = b.alloc((T, N), np.uint8); trunc = b.alloc((T, N), np.uint8)
@@ -621,7 +674,7 @@ def main():
 
     # ---- optional: BASELINE config 5 shape — both players sample from [nS, 5] mixed policies in-kernel --
     selfplay = None
-    if args.rollout > 0:
+    if args.full and args.rollout > 0:
         T = 100
         rngp = np.random.default_rng(94)
         da = b.alloc((b.nS, 4), np.uint16).upload(SoccerBatch.mixed_policy_thresholds(rngp.dirichlet(np.ones(5) * 0.7, size=b.nS)))
@@ -643,11 +696,9 @@ def main():
     if rank == 0:
         # roofline.achieved / frac follow from the SAME clock as `value`: the host wall clock around the K steps.  The
         # device-side figure — clock stamps captured around the K launches, i.e. without the replay's
-        # start-up latency and the host's wake-up — is reported next to it as frac_device.
+        # start-up latency and the host's wake-up — is reported next to it as frac_device (--full).
         step_s = wall / K
         achieved = ALGO_BYTES_PER_ENV_STEP * N / step_s / 1e9
-        launch_s = ev_ms * 1e-3 / K
-        achieved_dev = ALGO_BYTES_PER_ENV_STEP * N / launch_s / 1e9
         # HBM-side bytes per launch: from a separate rocprofv3 --pmc run (tools/collect_profile.py), reported only when
         # that run measured THIS workload with THESE kernel sources (sha256 of csrc/ recorded next to the number)
         traffic, traffic_source = None, None
@@ -692,19 +743,21 @@ def main():
                                        % (working_set >> 20),
                          "kernel": "soccer::step_kernel_swar<0, %s, false, 1, false>" % ("2" if args.slip else "0"),   # as rocprofv3 prints it (slips the table form does not cover: 1)
                          "frac_from": "ms_per_step (host wall clock, the clock `value` uses)",
-                         "achieved_device": achieved_dev, "frac_device": achieved_dev / HBM_PEAK_GBPS,
-                         "launch_us": launch_s * 1e6, "device_region_us": ev_ms * 1e3,
-                         "host_overhead_us": wall_own * 1e6 - ev_own * 1e3,
                          # where the host's share of the timed region goes (rank 0): the launch call(s), and from their return to the
                          # return of the one synchronisation that closes the region
                          "host_timeline_us": {"launch_call": (t_enq - t0) * 1e6, "launch_return_to_synchronised": (t_end - t_enq) * 1e6},
-                         "device_figures_from": "a stamped twin of the timed graph (the same K launches between two device clock stamps), "
-                                                "median of three replays after the timed region" if graph is not None else "HIP events around the eager launches",
                          "algorithmic_bytes_per_launch": ALGO_BYTES_PER_ENV_STEP * N},
-            "episodes": {"hist_minus1_0_plus1": [int(x) for x in hist],
-                         "gathered_last_returns": int(gathered.size), "gather_allreduce_ms": gather_ms,
-                         "gathered_mean": float(gathered.astype(np.float32).mean())},
         }
+        if args.full:
+            launch_s = ev_ms * 1e-3 / K
+            achieved_dev = ALGO_BYTES_PER_ENV_STEP * N / launch_s / 1e9
+            out["roofline"].update({
+                "achieved_device": achieved_dev, "frac_device": achieved_dev / HBM_PEAK_GBPS,
+                "launch_us": launch_s * 1e6, "device_region_us": ev_ms * 1e3,
+                "host_overhead_us": wall_own * 1e6 - ev_own * 1e3,
+                "device_figures_from": "a stamped twin of the timed graph (the same K launches between two device clock stamps), "
+                                       "median of three replays after the timed region" if graph is not None else "HIP events around the eager launches"})
+            out["episodes"] = episodes
         if per_rank:
             out["per_rank"] = per_rank
         if launch_profile:
@@ -715,12 +768,15 @@ def main():
             out["selfplay_rollout_config5"] = selfplay
         if vec_env:
             out["vector_env_device"] = vec_env
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(N, args.slip, args.cpu_seconds)
-        out["reference_python"] = REFERENCE_PYTHON
+        if args.full:
+            out["reference_python"] = REFERENCE_PYTHON
         print(json.dumps(out))
     if graph is not None:
-        b.graph_destroy(graph); b.graph_destroy(graph_s)
+        b.graph_destroy(graph)
+    if graph_s is not None:
+        b.graph_destroy(graph_s)
     if comm:
         comm.close()
     b.close()

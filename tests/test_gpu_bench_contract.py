@@ -26,7 +26,7 @@ def _run(*flags):
 
 def test_single_gpu_line_keeps_the_contract():
     K, W, N = 6, 2, 1 << 18
-    d = _run("--steps", str(K), "--warmup", str(W), "--lanes", str(N), "--cpu-seconds", "2", "--rollout", "10", "--no-vector-env")
+    d = _run("--full", "--steps", str(K), "--warmup", str(W), "--lanes", str(N), "--cpu-seconds", "2", "--rollout", "10", "--no-vector-env")
     assert d["metric"].startswith("env-steps/sec") and d["unit"] == "env-steps/s" and d["higher_is_better"] is True
     assert (d["n_gpus"], d["steps"], d["warmup"], d["scaling"], d["vs_baseline"], d["dtype"], d["data"]) == (1, K, W, "weak", None, "int8", "synthetic")
     assert d["config"]["lanes_per_gpu"] == N and "workload" in d["config"] and "model" not in d["config"]
@@ -44,6 +44,37 @@ def test_single_gpu_line_keeps_the_contract():
     assert d["fused_rollout"]["steps_fused"] == 10 and d["selfplay_rollout_config5"]["env_steps_per_s"] > 0
 
 
+def test_plain_line_is_the_headline_alone(tmp_path):
+    """Without --full: the same headline fields, none of the extra legs; --dump-outputs writes the last timed step's results,
+    the same from run to run and the same as a --full run computes (the untimed work before the clock is the same)."""
+    import numpy as np
+    from oracle.oracle import Oracle
+    K, W, N = 6, 2, 1 << 16
+    d = _run("--steps", str(K), "--warmup", str(W), "--lanes", str(N), "--dump-outputs", str(tmp_path / "a"))
+    assert d["metric"].startswith("env-steps/sec") and d["unit"] == "env-steps/s" and d["higher_is_better"] is True
+    assert (d["n_gpus"], d["steps"], d["warmup"], d["dtype"]) == (1, K, W, "int8") and d["untimed"]["steps_per_replay"] == K
+    assert d["untimed"]["graph_replays_before_timing"] == 4
+    assert abs(d["value"] - N * K / (d["ms_per_step"] * 1e-3 * K)) / d["value"] < 1e-9
+    r = d["roofline"]
+    assert abs(r["achieved"] - 19 * N / (d["ms_per_step"] * 1e-3) / 1e9) / r["achieved"] < 1e-9 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
+    assert "frac_device" not in r and "launch_us" not in r
+    for key in ("episodes", "launch_profile", "fused_rollout", "selfplay_rollout_config5", "vector_env_device", "cpu_baseline", "reference_python"):
+        assert key not in d, key
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in ("obs", "reward", "terminated", "truncated")}
+    assert sorted(os.listdir(str(tmp_path / "a"))) == sorted(k + ".npy" for k in a)
+    for v in a.values():
+        assert v.dtype == np.float32 and v.shape == (N,)
+    assert a["obs"].min() >= 0 and a["obs"].max() < Oracle(5, 4, 0.0).nS and set(np.unique(a["reward"])) <= {-1.0, 0.0, 1.0}
+    assert set(np.unique(a["terminated"])) <= {0.0, 1.0} and set(np.unique(a["truncated"])) <= {0.0, 1.0}
+    assert not ((a["reward"] != 0) & (a["terminated"] == 0)).any()
+    _run("--steps", str(K), "--warmup", str(W), "--lanes", str(N), "--dump-outputs", str(tmp_path / "b"))
+    _run("--full", "--steps", str(K), "--warmup", str(W), "--lanes", str(N), "--no-cpu-baseline", "--rollout", "0", "--no-vector-env",
+         "--dump-outputs", str(tmp_path / "c"))
+    for k, v in a.items():
+        assert np.array_equal(np.load(str(tmp_path / "b" / (k + ".npy"))), v), k
+        assert np.array_equal(np.load(str(tmp_path / "c" / (k + ".npy"))), v), k
+
+
 def test_odd_step_count_is_one_captured_sequence():
     d = _run("--steps", "5", "--warmup", "1", "--lanes", str(1 << 16), "--no-cpu-baseline", "--rollout", "0", "--no-vector-env")
     assert d["steps"] == 5 and d["untimed"]["steps_per_replay"] == 5 and "cpu_baseline" not in d
@@ -51,7 +82,7 @@ def test_odd_step_count_is_one_captured_sequence():
 
 def test_two_rank_rehearsal_on_one_gpu():
     N, K = 1 << 16, 8
-    d = _run("--gpus", "2", "--comm", "host", "--steps", str(K), "--warmup", "2", "--lanes", str(N), "--no-cpu-baseline", "--rollout", "0")
+    d = _run("--full", "--gpus", "2", "--comm", "host", "--steps", str(K), "--warmup", "2", "--lanes", str(N), "--no-cpu-baseline", "--rollout", "0")
     assert d["n_gpus"] == 2 and d["config"]["global_lanes"] == 2 * N and d["config"]["host"]["comm"] == "host-files"
     assert len(d["per_rank"]) == 2 and {x["rank"] for x in d["per_rank"]} == {0, 1}
     assert abs(d["ms_per_step"] * 1e3 * K - max(x["wall_us"] for x in d["per_rank"])) < 1e-6       # the job's time is the slowest rank's
@@ -68,7 +99,7 @@ def test_two_real_ranks_when_the_box_has_two_gpus_else_a_loud_refusal():
     n = ctypes.c_int()
     assert _lib.load().soccer_device_count(ctypes.byref(n)) == 0
     N, K = 1 << 16, 8
-    flags = ["--gpus", "2", "--steps", str(K), "--warmup", "2", "--lanes", str(N), "--no-cpu-baseline", "--rollout", "0", "--rank-deadline", "120"]
+    flags = ["--full", "--gpus", "2", "--steps", str(K), "--warmup", "2", "--lanes", str(N), "--no-cpu-baseline", "--rollout", "0", "--rank-deadline", "120"]
     if n.value >= 2:
         d = _run(*flags)
         assert d["n_gpus"] == 2 and d["config"]["host"]["comm"] == "rccl" and len(d["per_rank"]) == 2

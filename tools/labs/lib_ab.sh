@@ -8,7 +8,7 @@ for rep in 1 2 3; do
   for v in "${NAMES[@]}"; do
     cp build/lib_$v.so gym_soccer_littman94_amd/libsoccer_hip.so
     if [ ${#EXTRA[@]} -eq 0 ]; then EXTRA=(--rollout 0 --no-vector-env); fi
-    out=$(python3 bench.py --steps 1000 --warmup 50 --no-cpu-baseline "${EXTRA[@]}" 2>/dev/null | tail -1)
+    out=$(python3 bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline "${EXTRA[@]}" 2>/dev/null | tail -1)
     python3 - "$v" "$out" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])

@@ -5,8 +5,8 @@ cd "$(dirname "$0")/../.."
 for rep in 1 2 3; do
   for v in "$@"; do
     cp build/lib_$v.so gym_soccer_littman94_amd/libsoccer_hip.so
-    a=$(python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --rollout 0 --no-vector-env 2>/dev/null | tail -1)
-    b=$(python3 bench.py --steps 1000 --warmup 50 --no-cpu-baseline --rollout 0 --no-vector-env 2>/dev/null | tail -1)
+    a=$(python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --rollout 0 --no-vector-env 2>/dev/null | tail -1)
+    b=$(python3 bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline --rollout 0 --no-vector-env 2>/dev/null | tail -1)
     python3 - "$v" "$a" "$b" <<'PY'
 import json, sys
 a, b = json.loads(sys.argv[2]), json.loads(sys.argv[3])

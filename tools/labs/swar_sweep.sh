@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../.."
 run() {
   local tag="$1"; shift
   local out
-  out=$(env "$@" python3 bench.py --steps 1000 --warmup 50 --no-cpu-baseline --rollout 0 --no-vector-env 2>/dev/null | tail -1)
+  out=$(env "$@" python3 bench.py --full --steps 1000 --warmup 50 --no-cpu-baseline --rollout 0 --no-vector-env 2>/dev/null | tail -1)
   python3 - "$tag" "$out" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])
