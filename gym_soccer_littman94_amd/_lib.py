@@ -109,6 +109,7 @@ PROTOTYPES = {
     "soccer_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint64)]),
     "soccer_reset_stats": (C.c_int, [C.c_void_p]),
     "soccer_peek_misuse": (C.c_uint32, [C.c_void_p]),
+    "soccer_exact_walk_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "soccer_tick": (C.c_uint64, [C.c_void_p]),
     "soccer_get_seed": (C.c_uint64, [C.c_void_p]),
     "soccer_set_tick": (C.c_int, [C.c_void_p, C.c_uint64]),

@@ -469,6 +469,13 @@ class SoccerBatch:
         self._check(self.lib.soccer_get_stats(self.h, None, C.byref(mis)))
         return int(mis.value)
 
+    def exact_walk_stats(self):
+        """(parts, groups): launches of the exact walk that caller-supplied uniforms on a slip list take for the 4-lane groups
+        within 2^-40 of a threshold, and the groups they walked, since create (synchronises)."""
+        parts = C.c_uint64(); groups = C.c_uint64()
+        self._check(self.lib.soccer_exact_walk_stats(self.h, C.byref(parts), C.byref(groups)))
+        return int(parts.value), int(groups.value)
+
     def peek_misuse(self):
         """The same flags WITHOUT synchronising: what the launches completed so far have raised."""
         return int(self.lib.soccer_peek_misuse(self.h))

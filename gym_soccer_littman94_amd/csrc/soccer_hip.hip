@@ -80,7 +80,8 @@ struct soccer_handle {
     unsigned long long swar_launch_lanes = kSwarLaunchLanes;   // lanes per step_kernel_swar / rollout_swar_kernel launch (SOCCER_SWAR_LAUNCH_LANES: tests of the split)
     int rollout_pref = 0;                   // SOCCER_ROLLOUT=1 (A/B runs, tests of the fallback): never the byte-parallel rollout
     SlipF64* d_slip_f64 = nullptr;          // SLIPM == 3: nominal float64 slip thresholds (step_kernel_swar with caller-supplied uniforms)
-    uint32_t* d_worklist = nullptr;         // ... and the groups it leaves to the exact walk: [n / 4] indices + the count behind them
+    uint32_t* d_worklist = nullptr;         // ... and the groups it leaves to the exact walk: [n / 4] indices, the count and the
+                                            // tail's statistics behind them (worklist_count)
     unsigned long long* d_traj_hist = nullptr;   // soccer_trajectory_returns: u64[3] the kernel adds into
     void* comm = nullptr; int comm_world = 0, comm_rank = 0;   // soccer_comm_init: the RCCL communicator of this handle's device
     unsigned long long* d_comm_scratch = nullptr;   // 64 B for the small reductions (barrier, histogram, clocks)
@@ -284,10 +285,7 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
             CREATE_TRY(hipMemcpy(h->d_slip_step_lut, img.data(), img.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
         {
-            SlipF64 F{};
-            for (int i = 0; i < 9; ++i) F.B[i] = ST.B[i];
-            for (int i = 0; i < 4; ++i) F.w[i] = ST.w[i];
-            F.act_pack = ST.act_pack; F.nb = ST.nb;
+            const SlipF64 F = make_slip_f64(ST);
             CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_slip_f64), sizeof F));
             CREATE_TRY(hipMemcpy(h->d_slip_f64, &F, sizeof F, hipMemcpyHostToDevice));
         }
@@ -441,13 +439,19 @@ extern "C" int batched_reset(soccer_handle* h, const uint8_t* mask, const double
 
 template <class T> static inline T* off(T* p, unsigned long long lanes) { return p ? p + lanes : nullptr; }   // NULL stays NULL
 
-// the work list of step_kernel_swar<.., SLIPM = 3, ..>: one index per 4-lane group of the handle, the count 16 bytes behind them
+// the work list of step_kernel_swar<.., SLIPM = 3, ..>: one index per 4-lane group of the handle, then the count at an 8-byte aligned
+// word at least 16 bytes behind them, then the tail kernel's two uint64 statistics (step_kernel: launch parts, groups walked)
+static inline size_t worklist_count_word(const soccer_handle* h) { return ((size_t)(h->P.n >> 2) + 5) & ~(size_t)1; }
+static inline uint32_t* worklist_count(const soccer_handle* h) { return h->d_worklist ? h->d_worklist + worklist_count_word(h) : nullptr; }
 static bool ensure_worklist(soccer_handle* h) {
     if (h->d_worklist) return true;
-    const size_t words = (size_t)(h->P.n >> 2) + 8;
+    const size_t words = worklist_count_word(h) + 2 + 4;
     if (hipMalloc(reinterpret_cast<void**>(&h->d_worklist), words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); h->d_worklist = nullptr; return false; }
     // (on the handle's own stream: a memset on the null stream is not ordered with a non-blocking stream's kernels)
-    if (hipMemsetAsync(h->d_worklist, 0, words * sizeof(uint32_t), h->stream) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (hipMemsetAsync(h->d_worklist, 0, words * sizeof(uint32_t), h->stream) != hipSuccess) {
+        // without a cleared count the list must not be used: give it back, a later call tries again
+        (void)hipGetLastError(); (void)hipFree(h->d_worklist); h->d_worklist = nullptr; return false;
+    }
     return true;
 }
 
@@ -495,12 +499,12 @@ static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& i
                          off(io.obs, c0), off(io.reward, c0), off(io.terminated, c0), off(io.truncated, c0), off(io.prob_code, c0),
                          off(io.final_obs, c0), off(io.reward_a_f32, c0), off(io.reward_b_f32, c0), off(io.finished, c0),
                          off(io.last_return, c0), off(io.u_step, c0), off(io.u_reset, c0),
-                         h->d_slip_f64, h->d_worklist, h->d_worklist ? h->d_worklist + (h->P.n >> 2) + 4 : nullptr};
+                         h->d_slip_f64, h->d_worklist, worklist_count(h)};
             if (P.policy_a || P.policy_b) SWAR_OUT(true); else SWAR_OUT(false);
             if (expl_slip) {
                 // the groups of THIS part that were listed: the per-lane kernel, one workgroup, same tick (it publishes nothing)
                 KernelParams R = P; R.first = c0; R.n = cn; R.tick_out = nullptr;
-                StepIO jo = io; jo.worklist = h->d_worklist; jo.work_count = h->d_worklist + (h->P.n >> 2) + 4;
+                StepIO jo = io; jo.worklist = h->d_worklist; jo.work_count = worklist_count(h);
                 hipLaunchKernelGGL((step_kernel<true, true, true, true>), dim3(1), dim3(kBlock), 0, h->stream, R, jo);
             }
         }
@@ -1282,6 +1286,21 @@ extern "C" int soccer_get_stats(soccer_handle* h, uint64_t hist[3], uint64_t* mi
         const volatile unsigned int* m = h->misuse_host;
         *misuse = (m[0] ? 1u : 0u) | (m[1] ? 2u : 0u);
     }
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_exact_walk_stats(const soccer_handle* h, uint64_t* parts, uint64_t* groups) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    soccer_handle* hm = const_cast<soccer_handle*>(h);                  // (the error text only)
+    if (h->capturing) return fail(hm, SOCCER_E_STATE, "soccer_exact_walk_stats during graph capture");
+    unsigned long long st[2] = {0ull, 0ull};
+    if (h->d_worklist) {
+        HIP_TRY(hm, hipSetDevice(h->cfg.device));
+        HIP_TRY(hm, hipStreamSynchronize(h->stream));
+        HIP_TRY(hm, hipMemcpy(st, worklist_count(h) + 2, sizeof st, hipMemcpyDeviceToHost));
+    }
+    if (parts) *parts = st[0];
+    if (groups) *groups = st[1];
     return SOCCER_OK;
 }
 

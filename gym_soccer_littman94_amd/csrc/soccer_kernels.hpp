@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "soccer_slip.hpp"
 #include "soccer_swar.hpp"
 
 namespace soccer {
@@ -88,7 +89,8 @@ struct StepIO {
     uint8_t* prob_code; uint16_t* final_obs; int8_t* last_return;
     float* reward_a_f32; float* reward_b_f32; uint8_t* finished;      // the gym surface's float rewards / terminated | truncated
     // the 4-lane groups step_kernel_swar<.., SLIPM = 3, ..> left to the exact float64 walk (a caller's uniform within 2^-40 of a
-    // nominal threshold): the per-lane kernel then steps exactly these groups and zeroes the count; nullptr: every group
+    // nominal threshold): the per-lane kernel then steps exactly these groups, zeroes the count and adds to the two uint64
+    // statistics 8 bytes behind it (work_count is 8-byte aligned); nullptr: every group
     const uint32_t* worklist; uint32_t* work_count;
 };
 
@@ -828,7 +830,12 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(const KernelParams P, const
     if (P.tick_out) publish_tick(P, tick, 1ull);
     if (IO.worklist) {                       // launched as ONE workgroup: everyone has read the count, the list is consumed
         __syncthreads();
-        if (threadIdx.x == 0) *IO.work_count = 0u;
+        if (threadIdx.x == 0) {
+            *IO.work_count = 0u;
+            // the statistics behind the count (8-byte aligned, soccer_exact_walk_stats): launch parts, groups walked
+            unsigned long long* st = reinterpret_cast<unsigned long long*>(IO.work_count + 2);
+            st[0] += 1ull; st[1] += todo;
+        }
     }
 }
 
@@ -965,8 +972,6 @@ __global__ __launch_bounds__(kBlock) void step_kernel_hot(uint8_t* state, unsign
 // Takes every Philox-driven, dword-aligned step of a slip_prob == 0 handle whose pitch fits the byte arithmetic
 // (swar::fits: every golden pitch up to 11x7 does).  GENERAL = false is the steady state of an auto-resetting
 // handle (no frozen lane, no lane in a goal tuple); FULL adds final_obs and prob_code (VectorSoccerEnv).
-// slip_prob > 0 with the caller's uniforms: the float64 form of the slip decision (SlipTables::B / w / act_pack / nb)
-struct SlipF64 { double B[9]; double w[4]; unsigned long long act_pack; uint32_t nb; uint32_t pad_; };
 struct SwarParams {
     swar::Consts C;
     uint32_t key0, key1;
@@ -1130,35 +1135,13 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
         swar::Rand4 rnd;
         bool listed = false;                                             // SLIPM == 3: the group goes to the exact walk of the per-lane kernel
         if (SLIPM == 3) {
-            // The caller's uniform against the NOMINAL thresholds of the slip list — the cumulative weights of the active
-            // combinations, then the quarter points of the selected one.  The reference's sequential float64 sums differ from
-            // these by < 1e-14 whatever the list's shape (lane_step, fast decision), so a uniform farther than 2^-40 from every
-            // threshold it is compared with is decided as the reference decides it; a group with a lane inside that margin (or
-            // beyond the last threshold) is left to the per-lane kernel's exact walk: listed, nothing stored here.
+            // The caller's uniforms against the NOMINAL thresholds of the slip list (slip_decide4_f64, soccer_slip.hpp); a group
+            // with a lane within 2^-40 of one (or beyond the last threshold) is left to the per-lane kernel's exact walk: listed,
+            // nothing stored here.
             const SlipF64& F = *Q.f64;
             const double us[4] = {us0, us1, us2, us3};
             uint32_t c4 = 0u, k4 = 0u; bool near = false;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double u = sane_uniform_walk(us[j]);
-                uint32_t idx = 0u; double S0 = 0.0;
-#pragma unroll
-                for (int i = 0; i < 9; ++i) {
-                    const double bi = F.B[i];                         // wave-uniform; +inf past the last active one
-                    const bool ge = u >= bi;
-                    idx += ge ? 1u : 0u; S0 = ge ? bi : S0;
-                    near |= fabs(u - bi) < 0x1.0p-40;
-                }
-                near |= idx >= F.nb;
-                const uint32_t c = (uint32_t)((F.act_pack >> (4u * idx)) & 0xfull);
-                constexpr uint32_t CL2 = 0u | (1u << 2) | (1u << 4) | (2u << 6) | (2u << 8) | (3u << 10) | (3u << 12) | (3u << 14) | (3u << 16);
-                const uint32_t cl = (CL2 >> (2u * c)) & 3u;           // weight class of combination c (:211-222), as in lane_step
-                const double wq = (cl & 2u) ? ((cl & 1u) ? F.w[3] : F.w[2]) : ((cl & 1u) ? F.w[1] : F.w[0]);
-                const double q = wq * 0.25, t1 = S0 + q, t2 = t1 + q, t3 = t2 + q;
-                const uint32_t kq = (u >= t1 ? 1u : 0u) + (u >= t2 ? 1u : 0u) + (u >= t3 ? 1u : 0u);
-                near |= fabs(u - t1) < 0x1.0p-40; near |= fabs(u - t2) < 0x1.0p-40; near |= fabs(u - t3) < 0x1.0p-40;
-                c4 |= c << (8 * j); k4 |= kq << (8 * j);
-            }
+            SOCCER_SLIP_DECIDE4_F64(F, us, c4, k4, near)
             if (near) {
                 const uint32_t slot = atomicAdd(Q.work_count, 1u);
                 Q.worklist[slot] = (uint32_t)g;

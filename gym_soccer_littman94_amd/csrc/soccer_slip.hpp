@@ -1,6 +1,7 @@
 // soccer_slip.hpp — host-side construction of the slip-combination weights and thresholds (reference
-// gym_soccer/envs/soccer_simultaneous_env.py:202-227, :241).  Host-only; shared by libsoccer_hip.so (soccer_create) and
-// the CPU test harness of the byte-parallel step (tests/host/swar_host.cpp).
+// gym_soccer/envs/soccer_simultaneous_env.py:202-227, :241), and the float64 slip decision of caller-supplied uniforms
+// (slip_decide4_f64, host and device).  Shared by libsoccer_hip.so (soccer_create, step_kernel_swar) and the CPU test
+// harness of the byte-parallel step (tests/host/swar_host.cpp).
 //
 // What the kernels need to know about a slip_prob > 0 handle is where a draw falls in the (state, joint action) list the
 // reference samples from (:395): the list holds, for each of the nine slip combinations with a non-zero weight (:209-227)
@@ -147,6 +148,61 @@ inline SlipTables build_slip_tables(double slip_prob) {
     T.lut_step_ok = ascending && fill(kSlipStepBucketBits, T.lut_step) <= (uint32_t)kSlipStepCompares;
     T.lut_ok = lut_ok;
     return T;
+}
+
+// slip_prob > 0 with the caller's uniforms: the float64 form of the slip decision (SlipTables::B / w / act_pack / nb), as the
+// kernels read it (step_kernel_swar<.., SLIPM = 3, ..>)
+struct SlipF64 { double B[9]; double w[4]; unsigned long long act_pack; uint32_t nb; uint32_t pad_; };
+
+inline SlipF64 make_slip_f64(const SlipTables& ST) {
+    SlipF64 F{};
+    for (int i = 0; i < 9; ++i) F.B[i] = ST.B[i];
+    for (int i = 0; i < 4; ++i) F.w[i] = ST.w[i];
+    F.act_pack = ST.act_pack; F.nb = ST.nb;
+    return F;
+}
+
+// The caller's uniforms of one 4-lane group against the NOMINAL thresholds of the slip list — the cumulative weights of the
+// active combinations, then the quarter points of the selected one.  Byte j of c4 / k4: lane j's combination / quarter.  The
+// reference's sequential float64 sums differ from these by < 1e-14 whatever the list's shape (lane_step, fast decision), so a
+// uniform farther than 2^-40 from every threshold it is compared with is decided as the reference decides it.  near is set
+// when a lane is inside that margin or at / beyond the last threshold: then c4 / k4 are not the reference's, and the group
+// must be left to the per-lane kernel's exact walk.  Negative values and NaN count as 0 (sane_uniform_walk).
+// c4, k4 and near are the caller's variables, zero / false on entry.  step_kernel_swar<.., SLIPM = 3, ..> expands this in place:
+// as a call (slip_decide4_f64 below) the compiler schedules those kernels differently — one of them then spills 68 bytes.
+#if defined(__clang__)
+#define SOCCER_UNROLL _Pragma("unroll")
+#else
+#define SOCCER_UNROLL
+#endif
+#define SOCCER_SLIP_DECIDE4_F64(F, us, c4, k4, near)                                                                        \
+    SOCCER_UNROLL                                                                                                           \
+    for (int j = 0; j < 4; ++j) {                                                                                           \
+        const double u = ((us)[j] >= 0.0) ? (us)[j] : 0.0;                                                                  \
+        uint32_t idx = 0u; double S0 = 0.0;                                                                                 \
+        SOCCER_UNROLL                                                                                                       \
+        for (int i = 0; i < 9; ++i) {                                                                                       \
+            const double bi = (F).B[i];                       /* wave-uniform; +inf past the last active one */             \
+            const bool ge = u >= bi;                                                                                        \
+            idx += ge ? 1u : 0u; S0 = ge ? bi : S0;                                                                         \
+            near |= fabs(u - bi) < 0x1.0p-40;                                                                               \
+        }                                                                                                                   \
+        near |= idx >= (F).nb;                                                                                              \
+        const uint32_t c = (uint32_t)(((F).act_pack >> (4u * idx)) & 0xfull);                                              \
+        constexpr uint32_t CL2 = 0u | (1u << 2) | (1u << 4) | (2u << 6) | (2u << 8) | (3u << 10) | (3u << 12) | (3u << 14) | (3u << 16); \
+        const uint32_t cl = (CL2 >> (2u * c)) & 3u;           /* weight class of combination c (:211-222), as in lane_step */ \
+        const double wq = (cl & 2u) ? ((cl & 1u) ? (F).w[3] : (F).w[2]) : ((cl & 1u) ? (F).w[1] : (F).w[0]);               \
+        const double q = wq * 0.25, t1 = S0 + q, t2 = t1 + q, t3 = t2 + q;                                                  \
+        const uint32_t kq = (u >= t1 ? 1u : 0u) + (u >= t2 ? 1u : 0u) + (u >= t3 ? 1u : 0u);                                \
+        near |= fabs(u - t1) < 0x1.0p-40; near |= fabs(u - t2) < 0x1.0p-40; near |= fabs(u - t3) < 0x1.0p-40;              \
+        c4 |= c << (8 * j); k4 |= kq << (8 * j);                                                                            \
+    }
+
+// the same as a function (the CPU test harness, tests/host/swar_host.cpp); returns near
+SOCCER_HD bool slip_decide4_f64(const SlipF64& F, const double us[4], uint32_t& c4, uint32_t& k4) {
+    c4 = 0u; k4 = 0u; bool near = false;
+    SOCCER_SLIP_DECIDE4_F64(F, us, c4, k4, near)
+    return near;
 }
 
 }  // namespace soccer

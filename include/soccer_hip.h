@@ -340,6 +340,11 @@ int soccer_prob_table(const soccer_handle* h, double prob[12]);
 #define SOCCER_MISUSE_FROZEN 1u
 #define SOCCER_MISUSE_ACTION 2u
 int soccer_get_stats(soccer_handle* h, uint64_t hist[3], uint64_t* misuse);
+/* caller-supplied uniforms on a slip_prob > 0 handle (batched_step_ex with u_step): the byte-parallel step decides them in
+ * float64 against the slip list's nominal thresholds and leaves each 4-lane group with a uniform within 2^-40 of one (or at /
+ * beyond the last) to an exact walk, one small extra launch per launch part.  parts = such launches, groups = groups they
+ * walked, since create (0, 0 before the first).  Diagnostics for tests; synchronises the stream. HOST outputs (nullable). */
+int soccer_exact_walk_stats(const soccer_handle* h, uint64_t* parts, uint64_t* groups);
 /* the misuse flags as they stand, WITHOUT synchronising (the kernels write them to host-mapped memory): what the
  * launches that have completed so far have raised. */
 uint32_t soccer_peek_misuse(const soccer_handle* h);

@@ -126,3 +126,62 @@ extern "C" void swar_slip_tables(double slip_prob, uint32_t* cb9, uint32_t* sub3
     flags[0] = T.slip_int; flags[1] = T.swar_ok ? 1u : 0u; flags[2] = T.nb; flags[3] = T.c_off; flags[4] = T.lut_ok ? 1u : 0u; flags[5] = T.lut_step_ok ? 1u : 0u;
     for (int i = 0; i < 4; ++i) w4[i] = T.w[i];
 }
+
+// What step_kernel_swar<.., SLIPM = 3, ..> does with caller-supplied step uniforms on a slip_prob > 0 handle: the float64 decision
+// against the nominal thresholds (slip_decide4_f64, soccer_slip.hpp), then the byte-parallel step of soccer_swar.hpp, in the
+// instantiation the kernel picks (frozen / goal-tuple code only where a lane needs it, byte tables on small pitches).
+// listed[g] = 1: the kernel leaves group g to the per-lane kernel's exact walk; its outputs here are not the reference's (the test
+// ignores them).  The reset draw is floor(4u) of u_reset (a value outside [0, 1) or NaN counts as 0), or, with u_reset NULL, the
+// lane's Philox word as the kernel reads it (w & 3).  Returns 0, -1 when the pitch does not qualify for the byte-parallel path.
+extern "C" int swar_step_f64_host(int width, int height, int max_steps, int autoreset, long n,
+                                  uint8_t* ra, uint8_t* ca, uint8_t* rb, uint8_t* cb, uint8_t* ps, uint8_t* tt,
+                                  const uint8_t* act_a, const uint8_t* act_b, const double* u_step, const double* u_reset,
+                                  const uint32_t* words, double slip_prob,
+                                  uint16_t* obs, uint16_t* final_obs, uint8_t* rew, uint8_t* term, uint8_t* trunc,
+                                  uint8_t* code, uint8_t* frozen, uint8_t* listed) {
+    Rules R;
+    if (!R.build(width, height).empty()) return -2;
+    if (!swar::fits(R.H, R.W, max_steps)) return -1;
+    const swar::Consts C = swar::make_consts(R.H, R.W, R.goal_lo, R.goal_hi, max_steps, R.n_isd, R.isd, autoreset != 0);
+    const SlipF64 F = make_slip_f64(build_slip_tables(slip_prob));
+    auto quarter = [](double u) { return (uint32_t)((((u >= 0.0) && (u < 1.0)) ? u : 0.0) * 4.0); };   // sane_uniform
+    for (long i = 0; i < n; i += 4) {
+        swar::Group S{ld4(ra + i), ld4(ca + i), ld4(rb + i), ld4(cb + i), ld4(ps + i), ld4(tt + i)};
+        swar::Out o{};
+        const uint32_t a = ld4(act_a + i), b = ld4(act_b + i);
+        uint32_t c4 = 0u, k4 = 0u, s_a = 0u, s_b = 0u, cls4 = 0u;
+        listed[i >> 2] = slip_decide4_f64(F, u_step + i, c4, k4) ? 1u : 0u;
+        swar::slip_moves4(c4, swar::canon4(a), swar::canon4(b), s_a, s_b, cls4);
+        const uint32_t rs = u_reset ? (quarter(u_reset[i]) | quarter(u_reset[i + 1]) << 8 | quarter(u_reset[i + 2]) << 16 | quarter(u_reset[i + 3]) << 24)
+                                    : swar::pack_byte0(words[i], words[i + 1], words[i + 2], words[i + 3]);
+        const swar::Rand4 rnd{k4 << 6, rs >> C.isd_shift};
+        const uint32_t edge = swar::is_zero(S.ca) | swar::is_zero(S.cb) | swar::is_zero(S.ca ^ C.Wm1x4) | swar::is_zero(S.cb ^ C.Wm1x4);
+        const bool special = C.autoreset == 0u || (((S.ps << 6) | edge) & swar::K80) != 0u;
+        if (special) { if (C.small) swar::step4<true, true, true, 1>(C, S, a, b, s_a, s_b, cls4, rnd, o);
+                       else swar::step4<true, true, true, 0>(C, S, a, b, s_a, s_b, cls4, rnd, o); }
+        else { if (C.small) swar::step4<false, true, true, 1>(C, S, a, b, s_a, s_b, cls4, rnd, o);
+               else swar::step4<false, true, true, 0>(C, S, a, b, s_a, s_b, cls4, rnd, o); }
+        st4(ra + i, S.ra); st4(ca + i, S.ca); st4(rb + i, S.rb); st4(cb + i, S.cb); st4(ps + i, S.ps); st4(tt + i, S.tt);
+        obs[i] = (uint16_t)o.obs_lo; obs[i + 1] = (uint16_t)(o.obs_lo >> 16); obs[i + 2] = (uint16_t)o.obs_hi; obs[i + 3] = (uint16_t)(o.obs_hi >> 16);
+        final_obs[i] = (uint16_t)o.fin_lo; final_obs[i + 1] = (uint16_t)(o.fin_lo >> 16);
+        final_obs[i + 2] = (uint16_t)o.fin_hi; final_obs[i + 3] = (uint16_t)(o.fin_hi >> 16);
+        st4(code + i, o.code); st4(rew + i, o.rew); st4(term + i, o.term); st4(trunc + i, o.trunc);
+        st4(frozen + i, (o.frozen >> 7) & 0x01010101u);
+    }
+    return 0;
+}
+
+// the float64 form of the slip list soccer_create hands the SLIPM = 3 kernels (make_slip_f64): nominal cumulative weights B
+// (+inf beyond the nb active ones), class weights w, active combination ids 4 bits each
+extern "C" void swar_slip_f64(double slip_prob, double* B9, double* w4, uint32_t* nb, unsigned long long* act_pack) {
+    const SlipF64 F = make_slip_f64(build_slip_tables(slip_prob));
+    for (int i = 0; i < 9; ++i) B9[i] = F.B[i];
+    for (int i = 0; i < 4; ++i) w4[i] = F.w[i];
+    *nb = F.nb; *act_pack = F.act_pack;
+}
+
+// the decision alone: listed[g] = 1 when slip_decide4_f64 leaves group g (lanes 4g .. 4g + 3 of u_step) to the exact walk
+extern "C" void swar_listed_f64(double slip_prob, long n, const double* u_step, uint8_t* listed) {
+    const SlipF64 F = make_slip_f64(build_slip_tables(slip_prob));
+    for (long i = 0; i + 4 <= n; i += 4) { uint32_t c4, k4; listed[i >> 2] = slip_decide4_f64(F, u_step + i, c4, k4) ? 1u : 0u; }
+}

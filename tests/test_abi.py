@@ -28,6 +28,16 @@ def test_library_exports_every_declared_symbol():
     assert lib.soccer_abi_version() == 3
 
 
+def test_exact_walk_stats_is_declared_and_rejects_a_null_handle():
+    """soccer_exact_walk_stats (the SLIPM = 3 work list's launch parts / listed groups) is part of the ABI and validates before any
+    device work"""
+    assert "soccer_exact_walk_stats" in _declared_symbols()
+    lib = _lib.load()
+    parts, groups = C.c_uint64(7), C.c_uint64(7)
+    assert lib.soccer_exact_walk_stats(None, C.byref(parts), C.byref(groups)) == _lib.E_INVALID
+    assert parts.value == 7 and groups.value == 7
+
+
 def test_struct_layouts_match_header(tmp_path):
     """ctypes mirrors of the ABI structs have the size and field offsets the C compiler gives the header."""
     import subprocess

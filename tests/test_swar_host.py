@@ -22,7 +22,7 @@ def host(tmp_path_factory):
     # SWAR_HOST_SANITIZE=1: the same tests with UndefinedBehaviorSanitizer in the host build of the byte-parallel rules
     # (shifts, signed overflow, misaligned access ...; any report aborts the process) — sanitizers run on the CPU build only
     san = ["-fsanitize=undefined", "-fno-sanitize-recover=all", "-g"] if os.environ.get("SWAR_HOST_SANITIZE") else []
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-Werror"] + san + ["-o", so,
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Wextra", "-Werror"] + san + ["-o", so,
                            os.path.join(ROOT, "tests", "host", "swar_host.cpp")])
     L = C.CDLL(so)
     L.swar_step_host.restype = C.c_int

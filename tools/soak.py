@@ -44,6 +44,14 @@ while time.time() - t0 < budget:
         du = b.alloc(n + 2, np.float64) if expl and rng.random() < 0.8 else None
         dr = b.alloc(n + 2, np.float64) if expl and (du is None or rng.random() < 0.7) else None
         edge = np.array([0.0, 0.25, 0.5, 0.75, 0.2499999999999999, 0.4999999999999999, 1.0 - 2.0 ** -53, 2.0 ** -53, 1.0, -0.5, np.nan, 7.0])
+        if b.slip_prob > 0:
+            # slip lists: the handle's own cumulative weights and their quarter points, and one ulp either side of each (the
+            # float64 decision of caller uniforms lists the groups near them for the exact walk)
+            w = np.array([b.prob_table[3 * cl] for cl in (0, 1, 1, 2, 2, 3, 3, 3, 3) if b.prob_table[3 * cl] > 0])
+            cum = np.add.accumulate(w)
+            quarters = np.concatenate([np.r_[0.0, cum[:-1]] + w * f for f in (0.25, 0.5, 0.75)])
+            pts = np.concatenate([cum, quarters])
+            edge = np.concatenate([edge, pts, np.nextafter(pts, 0.0), np.nextafter(pts, 2.0)])
         # single-agent single steps (the fixed side acts on the current observation, :187-188), with and without the caller's uniforms
         early_pol = rng.integers(0, 5, size=o.nS).astype(np.int8) if rng.random() < 0.2 else None
         if early_pol is not None:
