@@ -105,6 +105,10 @@ PROTOTYPES = {
                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "soccer_modified_policy_iteration": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "soccer_solve_matrix_games": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 4),
+    "soccer_minimax_backup": (C.c_int, [C.c_void_p, C.c_double] + [C.c_void_p] * 5),
+    "soccer_minimax_value_iteration": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int32] + [C.c_void_p] * 4
+                                       + [C.POINTER(C.c_int32)]),
     "soccer_prob_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 12)]),
     "soccer_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint64)]),
     "soccer_reset_stats": (C.c_int, [C.c_void_p]),

@@ -277,6 +277,40 @@ class SoccerBatch:
                                                               int(max_sweeps), V.ctypes.data, Q.ctypes.data, pi.ctypes.data, C.byref(it)))
         return pi.astype(np.int64), V, Q, int(it.value)
 
+    # -- minimax planners on the device (two-player handles; Shapley's value iteration) ------------
+    def solve_matrix_games(self, A):
+        """A[n, 5, 5] zero-sum games (row player's payoff) -> (value[n], x[n, 5] maximin of the row player,
+        y[n, 5] minimax of the column player), solved on the device; every result carries the eps certificate of
+        include/soccer_hip.h."""
+        A = np.ascontiguousarray(A, np.float64)
+        assert A.ndim == 3 and A.shape[1:] == (5, 5), "A must be [n, 5, 5]"
+        n = A.shape[0]
+        v = np.zeros(n, np.float64); x = np.zeros((n, 5), np.float64); y = np.zeros((n, 5), np.float64)
+        self._check(self.lib.soccer_solve_matrix_games(self.h, n, A.ctypes.data, v.ctypes.data, x.ctypes.data, y.ctypes.data))
+        return v, x, y
+
+    def _minimax_out(self):
+        return (np.zeros((self.nS, 5), np.float64), np.zeros((self.nS, 5), np.float64), np.zeros(self.nS, np.float64),
+                np.zeros((self.nS, 5, 5), np.float64))
+
+    def minimax_backup(self, V, discount_factor):
+        """One Shapley operator application from V: (pi_a[nS, 5], pi_b[nS, 5], V' = val(Q(V)), Q[nS, 5, 5], 1)."""
+        V = np.ascontiguousarray(np.asarray(V).reshape(-1), np.float64)
+        assert V.shape == (self.nS,), "V must have one value per observation index"
+        pa, pb, Vo, Q = self._minimax_out()
+        self._check(self.lib.soccer_minimax_backup(self.h, float(discount_factor), V.ctypes.data, Vo.ctypes.data, Q.ctypes.data,
+                                                   pa.ctypes.data, pb.ctypes.data))
+        return pa, pb, Vo, Q, 1
+
+    def minimax_value_iteration(self, theta, discount_factor, max_sweeps=1000000):
+        """Minimax value iteration from V = 0 until max|V_k - V_{k-1}| < theta: (pi_a[nS, 5], pi_b[nS, 5], V_k,
+        Q_k[nS, 5, 5], k), with V_k = val(Q_k) and the strategies those of Q_k.  RuntimeError if max_sweeps is reached."""
+        pa, pb, V, Q = self._minimax_out()
+        it = C.c_int32()
+        self._check(self.lib.soccer_minimax_value_iteration(self.h, float(theta), float(discount_factor), int(max_sweeps),
+                                                            V.ctypes.data, Q.ctypes.data, pa.ctypes.data, pb.ctypes.data, C.byref(it)))
+        return pa, pb, V, Q, int(it.value)
+
     # -- hot path -------------------------------------------------------------------------------
     def reset(self, mask=None, u_reset=None, obs=None):
         self._check(self.lib.batched_reset(self.h, _ptr(mask), _ptr(u_reset), _ptr(obs)))

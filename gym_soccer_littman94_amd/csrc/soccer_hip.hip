@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdarg>
@@ -88,6 +89,11 @@ struct soccer_handle {
     PlanIO plan{};                          // cached planner lists (single-agent mode), see build_plan
     std::vector<void*> plan_bufs;
     bool plan_ready = false;
+    MinimaxIO mm{};                         // cached two-player lists and buffers of the minimax planners, see build_minimax
+    double* mm_V[2] = {nullptr, nullptr};   // V double-buffered across sweeps
+    unsigned long long* mm_words = nullptr; // [kMinimaxBatch + 1] per-sweep max |V_k - V_{k-1}| (bits)
+    std::vector<void*> mm_bufs;
+    bool mm_ready = false;
     std::string err;
 };
 
@@ -142,6 +148,7 @@ static void free_handle(soccer_handle* h) {
                     h->d_traj_hist, h->d_comm_scratch, h->d_slip_f64, h->d_worklist};
     for (void* b : bufs) if (b) (void)hipFree(b);
     for (void* b : h->plan_bufs) if (b) (void)hipFree(b);
+    for (void* b : h->mm_bufs) if (b) (void)hipFree(b);
     if (h->stage_host) (void)hipHostFree(h->stage_host);
     if (h->rec_host) (void)hipHostFree(h->rec_host);
     if (h->misuse_host) (void)hipHostFree(h->misuse_host);
@@ -1220,6 +1227,208 @@ extern "C" int soccer_policy_eval_dense(soccer_handle* h, const double* policy, 
     if (h && !policy) return fail(h, SOCCER_E_INVALID, "policy is NULL");
     if (h && k < 1) return fail(h, SOCCER_E_INVALID, "k must be >= 1");
     return run_plan(h, "soccer_policy_eval_dense", kPlanEvalDense, theta, discount_factor, max_sweeps, k, nullptr, init, policy, v, nullptr, nullptr, sweeps);
+}
+
+// ------------------------------------------------------------------------------------------------
+// minimax value iteration (two-player handles).  The (state, joint action) lists are the ones build_plan would assemble
+// for a joint action (P[0] = the last goal tuple's lists, player A's reward), built on the device from enumerate_kernel's
+// output without a round trip of the transition relation through the host (at 11x7 that copy and the host loops were 95 %
+// of a solve), cached on the handle apart from the single-agent plan; every sweep is one launch of minimax_sweep_kernel
+// over the whole GPU.
+constexpr int kMinimaxBatch = 16;             // sweeps enqueued between two synchronisations
+
+template <class T>
+static int mm_alloc(soccer_handle* h, size_t count, T** out) {
+    void* d = nullptr;
+    if (hipMalloc(&d, count ? count * sizeof(T) : 1) != hipSuccess) return fail(h, SOCCER_E_NOMEM, "out of device memory for the minimax planner");
+    h->mm_bufs.push_back(d);
+    *out = static_cast<T*>(d);
+    return SOCCER_OK;
+}
+
+static void drop_minimax(soccer_handle* h) {
+    for (void* b : h->mm_bufs) if (b) (void)hipFree(b);
+    h->mm_bufs.clear(); h->mm_ready = false;
+}
+
+static int build_minimax(soccer_handle* h) {
+    if (h->mm_ready) return SOCCER_OK;
+    const Rules& R = h->rules;
+    const int nS = R.nS;
+    const size_t T = R.lut.size(), keys = T * 25, ent = keys * kMaxOutcomes, nkeys = (size_t)nS * 25;
+    // P[s]: goal tuples all write index 0 and overwrite each other (identical lists), live tuples own theirs
+    std::vector<int32_t> tuple_of(nS, -1);
+    for (size_t f = 0; f < T; ++f) if (R.kind[f] != 0) tuple_of[R.kind[f] == 2 ? 0 : (int)R.lut[f]] = (int32_t)f;
+    for (int s = 0; s < nS; ++s) if (tuple_of[s] < 0) return fail(h, SOCCER_E_INVALID, "internal error: observation index %d has no tuple", s);
+    // the transition relation stays on the device: enumerate, measure the lists, place them
+    void* tmp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t sizes[6] = {keys * sizeof(int32_t), ent * sizeof(double), ent * sizeof(int32_t), ent, ent, (size_t)nS * sizeof(int32_t)};
+    int rc = SOCCER_OK;
+    for (int i = 0; i < 6 && rc == SOCCER_OK; ++i)
+        if (hipMalloc(&tmp[i], sizes[i]) != hipSuccess) rc = fail(h, SOCCER_E_NOMEM, "out of device memory for the transition table");
+    int32_t* d_off = nullptr; PlanEntry* d_list = nullptr;
+    std::vector<int32_t> off(nkeys + 1, 0);
+    MinimaxListIO L{};
+    hipError_t e = hipSuccess;
+    if (rc == SOCCER_OK) rc = mm_alloc(h, off.size(), &d_off);
+    if (rc == SOCCER_OK) {
+        EnumIO io{};
+        io.n_tuples = static_cast<int32_t>(T); io.H = R.H;
+        io.count = static_cast<int32_t*>(tmp[0]); io.prob = static_cast<double*>(tmp[1]); io.next = static_cast<int32_t*>(tmp[2]);
+        io.reward = static_cast<int8_t*>(tmp[3]); io.done = static_cast<uint8_t*>(tmp[4]);
+        L.count = io.count; L.prob = io.prob; L.next = io.next; L.reward = io.reward; L.done = io.done;
+        L.tuple_of = static_cast<const int32_t*>(tmp[5]); L.lut = h->P.lut; L.offset = d_off; L.nS = nS;
+        e = hipMemcpyAsync(tmp[5], tuple_of.data(), sizes[5], hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_off, 0, off.size() * sizeof(int32_t), h->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(enumerate_kernel, dim3((unsigned)((keys + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->P, io);
+            hipLaunchKernelGGL(minimax_lists_kernel<false>, dim3((unsigned)((nkeys + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, L);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(off.data(), d_off, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = fail(h, SOCCER_E_HIP, "minimax list construction failed: %s", hipGetErrorString(e));
+    }
+    if (rc == SOCCER_OK) {
+        for (size_t k = 0; k < nkeys; ++k) off[k + 1] += off[k];                 // padded lengths -> offsets
+        rc = mm_alloc(h, (size_t)off[nkeys], &d_list);
+    }
+    if (rc == SOCCER_OK) {
+        L.list = d_list;
+        e = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(minimax_lists_kernel<true>, dim3((unsigned)((nkeys + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, L);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = fail(h, SOCCER_E_HIP, "minimax list construction failed: %s", hipGetErrorString(e));
+    }
+    for (void* b : tmp) if (b) (void)hipFree(b);
+    MinimaxIO io{};
+    if (!rc) rc = mm_alloc(h, (size_t)nS, &h->mm_V[0]);
+    if (!rc) rc = mm_alloc(h, (size_t)nS, &h->mm_V[1]);
+    if (!rc) rc = mm_alloc(h, (size_t)nS * 25, &io.Q);
+    if (!rc) rc = mm_alloc(h, (size_t)nS * 5, &io.pi_a);
+    if (!rc) rc = mm_alloc(h, (size_t)nS * 5, &io.pi_b);
+    if (!rc) rc = mm_alloc(h, (size_t)kMinimaxBatch + 1, &h->mm_words);
+    if (rc) { drop_minimax(h); return rc; }
+    io.offset = d_off; io.list = d_list; io.nS = nS;
+    h->mm = io;
+    h->mm_ready = true;
+    return SOCCER_OK;
+}
+
+static int minimax_check(soccer_handle* h, const char* what, double gamma) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "%s during graph capture", what);
+    if (h->P.policy_a != nullptr || h->P.policy_b != nullptr)
+        return fail(h, SOCCER_E_INVALID, "%s needs a two-player handle: neither side may have a fixed policy (soccer_set_policy)", what);
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(h, SOCCER_E_INVALID, "discount_factor must be in [0, 1]");
+    return SOCCER_OK;
+}
+
+// after every argument is checked: the device and the cached lists
+static int minimax_prepare(soccer_handle* h) {
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    return build_minimax(h);
+}
+
+// one sweep: V_in -> V_out (device buffers of the handle), Q and the strategies into the handle's buffers
+static void minimax_launch(soccer_handle* h, double gamma, double theta, const double* V_in, double* V_out,
+                           unsigned long long* delta, const unsigned long long* prev) {
+    MinimaxIO io = h->mm;
+    io.V = V_in; io.V_out = V_out; io.delta = delta; io.prev = prev; io.gamma = gamma; io.theta = theta;
+    const unsigned grid = (unsigned)((io.nS + kMinimaxWaves - 1) / kMinimaxWaves);
+    hipLaunchKernelGGL(minimax_sweep_kernel, dim3(grid), dim3(kMinimaxBlock), 0, h->stream, io);
+}
+
+static int minimax_outputs(soccer_handle* h, const double* V_dev, double* V, double* Q, double* pi_a, double* pi_b) {
+    const size_t nS = (size_t)h->mm.nS;
+    if (V) HIP_TRY(h, hipMemcpyAsync(V, V_dev, nS * 8, hipMemcpyDeviceToHost, h->stream));
+    if (Q) HIP_TRY(h, hipMemcpyAsync(Q, h->mm.Q, nS * 200, hipMemcpyDeviceToHost, h->stream));
+    if (pi_a) HIP_TRY(h, hipMemcpyAsync(pi_a, h->mm.pi_a, nS * 40, hipMemcpyDeviceToHost, h->stream));
+    if (pi_b) HIP_TRY(h, hipMemcpyAsync(pi_b, h->mm.pi_b, nS * 40, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_solve_matrix_games(soccer_handle* h, int64_t n_games, const double* A, double* value, double* x, double* y) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "soccer_solve_matrix_games during graph capture");
+    if (n_games < 0) return fail(h, SOCCER_E_INVALID, "n_games must be >= 0");
+    if (n_games > 0 && !A) return fail(h, SOCCER_E_INVALID, "A is NULL");
+    if (n_games == 0) return SOCCER_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t n = (size_t)n_games;
+    void* bufs[4] = {nullptr, nullptr, nullptr, nullptr};
+    const size_t sizes[4] = {n * 200, n * 8, n * 40, n * 40};
+    int rc = SOCCER_OK;
+    for (int i = 0; i < 4 && rc == SOCCER_OK; ++i)
+        if (hipMalloc(&bufs[i], sizes[i]) != hipSuccess) rc = fail(h, SOCCER_E_NOMEM, "out of device memory for %lld games", (long long)n_games);
+    if (rc == SOCCER_OK) {
+        hipError_t e = hipMemcpyAsync(bufs[0], A, sizes[0], hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) {
+            const unsigned grid = (unsigned)((n + kGamesBlock - 1) / kGamesBlock);
+            hipLaunchKernelGGL(games_kernel, dim3(grid), dim3(kGamesBlock), 0, h->stream, static_cast<const double*>(bufs[0]), (long long)n,
+                               static_cast<double*>(bufs[1]), static_cast<double*>(bufs[2]), static_cast<double*>(bufs[3]));
+            e = hipGetLastError();
+        }
+        void* dst[3] = {value, x, y};
+        for (int i = 0; i < 3 && e == hipSuccess; ++i) if (dst[i]) e = hipMemcpyAsync(dst[i], bufs[i + 1], sizes[i + 1], hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = fail(h, SOCCER_E_HIP, "soccer_solve_matrix_games failed: %s", hipGetErrorString(e));
+    }
+    for (void* b : bufs) if (b) (void)hipFree(b);
+    return rc;
+}
+
+extern "C" int soccer_minimax_backup(soccer_handle* h, double discount_factor, const double* V, double* V_out, double* Q,
+                                     double* pi_a, double* pi_b) {
+    if (int rc = minimax_check(h, "soccer_minimax_backup", discount_factor)) return rc;
+    if (!V) return fail(h, SOCCER_E_INVALID, "V is NULL");
+    if (int rc = minimax_prepare(h)) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->mm_V[0], V, (size_t)h->mm.nS * 8, hipMemcpyHostToDevice, h->stream));
+    minimax_launch(h, discount_factor, 0.0, h->mm_V[0], h->mm_V[1], nullptr, nullptr);
+    HIP_TRY(h, hipGetLastError());
+    return minimax_outputs(h, h->mm_V[1], V_out, Q, pi_a, pi_b);
+}
+
+extern "C" int soccer_minimax_value_iteration(soccer_handle* h, double theta, double discount_factor, int32_t max_sweeps,
+                                              double* V, double* Q, double* pi_a, double* pi_b, int32_t* iterations) {
+    if (int rc = minimax_check(h, "soccer_minimax_value_iteration", discount_factor)) return rc;
+    if (max_sweeps < 1) return fail(h, SOCCER_E_INVALID, "max_sweeps must be >= 1");
+    if (!(theta >= 0.0)) return fail(h, SOCCER_E_INVALID, "theta must be >= 0");
+    if (int rc = minimax_prepare(h)) return rc;
+    const int nS = h->mm.nS;
+    HIP_TRY(h, hipMemsetAsync(h->mm_V[0], 0, (size_t)nS * 8, h->stream));                  // V_0 = 0
+    // words[0] is the sweep before the batch's first: +inf (never converged) before sweep 1
+    unsigned long long words[kMinimaxBatch + 1];
+    const double inf = __builtin_huge_val();
+    std::memcpy(&words[0], &inf, 8);
+    int32_t k0 = 1, done_at = 0;                                                         // k0: first sweep of the batch
+    while (k0 <= max_sweeps && !done_at) {
+        const int nb = (int)std::min<int64_t>(kMinimaxBatch, (int64_t)max_sweeps - k0 + 1);
+        for (int j = 1; j <= kMinimaxBatch; ++j) words[j] = 0ull;
+        HIP_TRY(h, hipMemcpyAsync(h->mm_words, words, sizeof words, hipMemcpyHostToDevice, h->stream));
+        for (int j = 1; j <= nb; ++j) {
+            const int32_t k = k0 + j - 1;
+            minimax_launch(h, discount_factor, theta, h->mm_V[(k - 1) & 1], h->mm_V[k & 1], h->mm_words + j, h->mm_words + j - 1);
+        }
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(words, h->mm_words, sizeof words, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (int j = 1; j <= nb && !done_at; ++j) {
+            double d; std::memcpy(&d, &words[j], 8);
+            if (d < theta) done_at = k0 + j - 1;
+        }
+        words[0] = words[nb];
+        k0 += nb;
+    }
+    const int32_t k = done_at ? done_at : max_sweeps;
+    if (int rc = minimax_outputs(h, h->mm_V[k & 1], V, Q, pi_a, pi_b)) return rc;
+    if (iterations) *iterations = k;
+    if (!done_at) return fail(h, SOCCER_E_STATE, "soccer_minimax_value_iteration stopped after max_sweeps = %d sweeps without converging", max_sweeps);
+    return SOCCER_OK;
 }
 
 // single-agent mode: one side follows a fixed policy looked up by the current observation index

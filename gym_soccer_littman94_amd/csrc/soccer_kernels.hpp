@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "soccer_games.hpp"
 #include "soccer_slip.hpp"
 #include "soccer_swar.hpp"
 
@@ -2086,6 +2087,112 @@ __global__ __launch_bounds__(1024) void planner_kernel(const PlanIO IO) {
         for (int s = tid; s < nS; s += nt) IO.V[s] = IO.newV[s];
     }
     if (tid == 0) { IO.counters[0] = outer; IO.counters[1] = sweeps; IO.counters[2] = capped; }
+}
+
+// =================================================================================================
+// minimax value iteration on the two-player lists (Shapley's operator; Littman 1994)
+// =================================================================================================
+// One launch is one synchronous (Jacobi) sweep over all states:
+//   Q[s][a][b] = sum_k prob_k * (reward_k + (gamma * V[next_k]) * (done_k ? 0 : 1))   in list order, A's reward
+//   V'[s]      = val(Q[s])   (soccer_games.hpp: saddle point exactly, else simplex with Bland's rule)
+// A wave owns a state: lanes 0..24 gather the 25 joint actions' lists, lane 0 solves the stage game from LDS.  There is no
+// grid-wide barrier: V is double-buffered across launches, max |V' - V| goes into a word of this sweep by atomicMax on the
+// bit patterns of non-negative doubles, and a launch whose previous sweep's word is below theta returns at once — so the
+// host can enqueue sweeps in batches and synchronise once per batch, and the result does not depend on the order in which
+// workgroups run.
+constexpr int kMinimaxBlock = 256;
+constexpr int kMinimaxWaves = kMinimaxBlock / 64;
+
+struct MinimaxIO {
+    const int32_t* offset;           // [nS * 25 + 1] CSR by (state, joint action a * 5 + b)
+    const PlanEntry* list;           // padded to kPlanPad like the single-agent lists; reward is player A's
+    const double* V;                 // V_{k-1}
+    double* V_out;                   // V_k
+    double* Q;                       // [nS][5][5]
+    double* pi_a; double* pi_b;      // [nS][5]
+    unsigned long long* delta;       // this sweep's word (NULL: no reduction)
+    const unsigned long long* prev;  // the previous sweep's word (NULL: always run)
+    double gamma, theta;
+    int32_t nS;
+};
+
+// the Q expression of list_backup, over the joint action's list
+__device__ __forceinline__ double minimax_list_q(const MinimaxIO& IO, int key) {
+    double q = 0.0;
+    const int end = IO.offset[key + 1];
+    for (int e = IO.offset[key]; e < end; e += kPlanPad) {
+        PlanEntry x[kPlanPad];
+#pragma unroll
+        for (int j = 0; j < kPlanPad; ++j) x[j] = IO.list[e + j];
+#pragma unroll
+        for (int j = 0; j < kPlanPad; ++j) {
+            const double cont = (IO.gamma * IO.V[x[j].next_done & 0x7fffffff]) * (x[j].next_done < 0 ? 0.0 : 1.0);
+            q = q + x[j].prob * ((double)x[j].reward + cont);
+        }
+    }
+    return q;
+}
+
+__global__ __launch_bounds__(kMinimaxBlock) void minimax_sweep_kernel(const MinimaxIO IO) {
+    if (IO.prev && __longlong_as_double((long long)*IO.prev) < IO.theta) return;   // converged one sweep ago: nothing to do
+    __shared__ double sQ[kMinimaxWaves][25];
+    __shared__ GameWork sW[kMinimaxWaves];
+    __shared__ unsigned long long s_max;
+    const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
+    const int s = (int)blockIdx.x * kMinimaxWaves + wave;
+    if (threadIdx.x == 0) s_max = 0ull;
+    if (s < IO.nS && lane < 25) {
+        const double q = minimax_list_q(IO, s * 25 + lane);
+        sQ[wave][lane] = q;
+        IO.Q[(size_t)s * 25 + lane] = q;
+    }
+    __syncthreads();
+    if (s < IO.nS && lane == 0) {
+        double v = 0.0;
+        solve_game5(sQ[wave], &sW[wave], &v, IO.pi_a ? IO.pi_a + (size_t)s * 5 : nullptr, IO.pi_b ? IO.pi_b + (size_t)s * 5 : nullptr);
+        IO.V_out[s] = v;
+        if (IO.delta) atomicMax(&s_max, (unsigned long long)__double_as_longlong(fabs(v - IO.V[s])));
+    }
+    __syncthreads();
+    // a non-atomic look first: the word only grows, so a block whose maximum is not above what it sees has nothing to add
+    if (IO.delta && threadIdx.x == 0 && s_max > *reinterpret_cast<volatile unsigned long long*>(IO.delta)) atomicMax(IO.delta, s_max);
+}
+
+// the two-player lists assembled on the device from enumerate_kernel's output (build_minimax): a thread per (state, joint
+// action).  Pass 1 writes each list's padded length to offset[key + 1]; the host turns them into offsets; pass 2 copies the
+// entries in enumeration order and pads — the lists the host would assemble, entry for entry.
+struct MinimaxListIO {
+    const int32_t* count; const double* prob; const int32_t* next; const int8_t* reward; const uint8_t* done;   // EnumIO's
+    const int32_t* tuple_of;         // [nS] the tuple whose lists observation index s owns (index 0: the last goal tuple)
+    const uint16_t* lut;             // observation index of a tuple (goal tuples: 0)
+    int32_t* offset; PlanEntry* list;
+    int32_t nS;
+};
+template <bool SCATTER>
+__global__ __launch_bounds__(kBlock) void minimax_lists_kernel(const MinimaxListIO IO) {
+    const long long key = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (key >= (long long)IO.nS * 25) return;
+    const long long src = (long long)IO.tuple_of[key / 25] * 25 + key % 25;
+    const int n = IO.count[src] > 0 ? IO.count[src] : 0;
+    if (!SCATTER) { IO.offset[key + 1] = (n + kPlanPad - 1) / kPlanPad * kPlanPad; return; }
+    int e = IO.offset[key];
+    const int end = IO.offset[key + 1];
+    for (int k = 0; k < n; ++k, ++e) {
+        const long long x = src * kMaxOutcomes + k;
+        IO.list[e] = PlanEntry{IO.prob[x], (int32_t)IO.lut[IO.next[x]] | (IO.done[x] ? (int32_t)0x80000000 : 0), (float)IO.reward[x]};
+    }
+    for (; e < end; ++e) IO.list[e] = PlanEntry{0.0, (int32_t)0x80000000, 0.0f};
+}
+
+// n independent games, a thread per game (soccer_solve_matrix_games)
+constexpr int kGamesBlock = 64;
+__global__ __launch_bounds__(kGamesBlock) void games_kernel(const double* A, long long n, double* value, double* x, double* y) {
+    __shared__ GameWork sW[kGamesBlock];
+    const long long g = (long long)blockIdx.x * kGamesBlock + threadIdx.x;
+    if (g >= n) return;
+    double v = 0.0;
+    solve_game5(A + g * 25, &sW[threadIdx.x], &v, x ? x + g * 5 : nullptr, y ? y + g * 5 : nullptr);
+    if (value) value[g] = v;
 }
 
 // =================================================================================================

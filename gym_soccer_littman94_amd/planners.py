@@ -2,7 +2,8 @@
 with the same names, arguments and return values, each running as ONE HIP kernel over transition lists
 enumerated on the device (libsoccer_hip.so, include/soccer_hip.h "planners").
 
-Like the reference's they need a single-agent env (one side with a fixed policy).  The list-based planners
+Like the reference's they need a single-agent env (one side with a fixed policy); `minimax_value_iteration`, which the
+reference lacks, needs the two-player env instead.  The list-based planners
 (`value_iteration`, `policy_evaluation`, `policy_improvement`, `policy_iteration`) are bit-identical to the
 reference's float64 loops; the dense ones (`policy_eval`, `modified_policy_iteration`) follow its Pmat/Rmat
 algebra and agree to rounding (numpy's BLAS dot sums in another order).  `env` is a
@@ -51,3 +52,18 @@ def policy_eval(env, policy, theta, discount_factor, k=10000000, init=None):   #
 
 def modified_policy_iteration(env, k, theta, discount_factor):           # planners.py:73-87
     return _batch(env).modified_policy_iteration(k, theta, discount_factor)
+
+
+def minimax_value_iteration(env, theta, discount_factor, max_sweeps=1000000):
+    """Minimax (Shapley) value iteration of the two-player game on the device, Littman (1994)'s equilibrium values.
+    Returns (pi_a[nS, 5], pi_b[nS, 5], V, Q[nS, 5, 5], iterations): player A's maximin and player B's minimax stage-game
+    strategies, ready for VectorSoccerEnv.rollout(sample_actions=True, mixed_policies={...})."""
+    from .core import SoccerBatch
+    if isinstance(env, SoccerBatch):
+        b = env
+    else:
+        b = getattr(env, "_batch", None)
+        if b is None:
+            raise TypeError("planners expect a gym_soccer_littman94_amd environment")
+        assert env.multiagent, "minimax_value_iteration needs a two-player environment (no player with a fixed policy)"
+    return b.minimax_value_iteration(theta, discount_factor, max_sweeps=max_sweeps)

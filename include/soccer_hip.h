@@ -63,7 +63,8 @@ extern "C" {
 
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
-                                     (still 3: soccer_trajectory_returns, soccer_comm_* and batched_rollout_ex were ADDED, captured sequences may hold an odd
+                                     (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
+                                     soccer_minimax_backup and soccer_minimax_value_iteration were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -325,6 +326,32 @@ int soccer_policy_eval_dense(soccer_handle* h, const double* policy, int32_t k, 
                              int32_t max_sweeps, const double* init, double* v, int32_t* sweeps);
 int soccer_modified_policy_iteration(soccer_handle* h, int32_t k, double theta, double discount_factor,
                                      int32_t max_sweeps, double* V, double* Q, int32_t* pi, int32_t* iterations);
+/* ---- minimax planners (two-player handles; Shapley's value iteration, Littman 1994) ---------------------------
+ * A 5x5 zero-sum stage game is solved in float64 by csrc/soccer_games.hpp: a pure saddle point exactly (first row
+ * whose minimum is the max-min, first column whose maximum is the min-max), otherwise the simplex method with Bland's
+ * rule, whose answer is verified against the bracket its strategies certify and, where that is wider than eps, replaced
+ * by the first Shapley-Snow square-submatrix candidate that passes.  With eps = 1e-10 * max(1, max|A|) the result
+ * satisfies  min_b (x^T A)_b >= v - eps,  max_a (A y)_a <= v + eps,  x, y >= 0,  sum x = sum y = 1 within 1e-12
+ * (the strategies certify a bracket at most eps wide and v is its midpoint).  The same input gives the same bits.
+ * Inputs and outputs are HOST arrays; any output may be NULL.  None of these calls consumes a tick or touches the
+ * lanes' state; during a graph capture they return SOCCER_E_STATE. */
+/* n games of 5x5, A[g][a][b] = row player's (A's) payoff -> value[n], maximin x[n][5] of A, minimax y[n][5] of B */
+int soccer_solve_matrix_games(soccer_handle* h, int64_t n_games, const double* A,
+                              double* value, double* x, double* y);
+/* The planners need a two-player handle (SOCCER_E_INVALID with a fixed policy).  The (state, joint action) lists are
+ * the two-player P[s][(a, b)] of the reference's constructor (player A's reward), assembled from
+ * soccer_enumerate_transitions and cached on the handle.  Q[s][a][b] = sum_k prob * (reward + (discount_factor *
+ * V[next]) * (not done)) in list order — bit for bit the host sum over P[s][(a, b)] — and V'[s] = val(Q[s]).
+ * One Shapley operator application from the caller's V[n_states]: V_out = val(Q(V)), Q[n_states][5][5], the
+ * stage-game strategies pi_a / pi_b [n_states][5]. */
+int soccer_minimax_backup(soccer_handle* h, double discount_factor, const double* V,
+                          double* V_out, double* Q, double* pi_a, double* pi_b);
+/* V_0 = 0; sweep k: Q_k = Q(V_{k-1}), V_k = val(Q_k); stops at the first k with max|V_k - V_{k-1}| < theta.
+ * Returns V_k, Q_k, the strategies of Q_k and k: (V, Q, pi) is self-consistent, V[s] = val(Q[s]).
+ * (soccer_value_iteration returns the pre-update V, as the reference does; this one does not.)  SOCCER_E_STATE when
+ * max_sweeps is reached; the outputs then hold the last iterate. */
+int soccer_minimax_value_iteration(soccer_handle* h, double theta, double discount_factor, int32_t max_sweeps,
+                                   double* V, double* Q, double* pi_a, double* pi_b, int32_t* iterations);
 /* HOST output: prob[c*3+k] = slip-combination weight c (0: no slip, 1: B slips, 2: A slips,
  * 3: both; :211-222, evaluated left to right in float64) times outcome probability 1, 0.5, 0.25
  * (k = 0,1,2; :326-360).  prob_code values index this table (:241). */
