@@ -1,0 +1,175 @@
+// soccer_handle.hpp — what the translation units of libsoccer_hip.so share on the host side: the handle, error reporting,
+// and the few functions one unit needs from another.  Internal: not installed, not part of the C ABI (include/soccer_hip.h).
+//
+//   soccer_hip.hip       create / destroy, seed / tick, reset, state, staging, one-environment calls, statistics, timers, graphs
+//   soccer_step.hip      batched_step*
+//   soccer_rollout.hip   batched_rollout*
+//   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, the matrix-game solver
+//   soccer_comm.hip      the RCCL wrapper (host code only)
+//
+// Every unit carries its own code object: a kernel is instantiated, launched and given its attributes (hipFuncSetAttribute)
+// in ONE unit only — see the kernel headers named in soccer_kernels.hpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/soccer_hip.h"
+#include "soccer_kernels.hpp"
+#include "soccer_plan_io.hpp"
+#include "soccer_rules.hpp"
+
+#pragma GCC visibility push(hidden)      // nothing below is an export of the library
+
+using namespace soccer;
+
+// error text into the handle (or, without one, into the calling thread's slot that soccer_last_error(NULL) reads); returns `code`
+int fail(soccer_handle* h, int code, const char* fmt, ...);
+
+#define HIP_TRY(h, expr)                                                                         \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return fail((h), e_ == hipErrorOutOfMemory ? SOCCER_E_NOMEM : SOCCER_E_HIP,          \
+                        "%s failed: %s", #expr, hipGetErrorString(e_));                          \
+    } while (0)
+
+template <typename T>
+static inline bool aligned(const T* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+
+template <class T> static inline T* off(T* p, unsigned long long lanes) { return p ? p + lanes : nullptr; }   // NULL stays NULL
+
+// Device buffers that are built lazily and dropped together (the cached lists of the planners).  A failed build calls
+// clear(); so does whatever invalidates the lists, and free_handle.
+struct DeviceBufs {
+    const char* what;                       // for the out-of-memory message
+    std::vector<void*> ptrs;
+    bool ready = false;                     // set by the builder once every buffer holds its content
+    explicit DeviceBufs(const char* owner) : what(owner) {}
+
+    template <class T>
+    int alloc(soccer_handle* h, size_t count, T** out) {
+        void* d = nullptr;
+        if (hipMalloc(&d, count ? count * sizeof(T) : 1) != hipSuccess) return fail(h, SOCCER_E_NOMEM, "out of device memory for %s", what);
+        ptrs.push_back(d);
+        *out = static_cast<T*>(d);
+        return SOCCER_OK;
+    }
+    template <class T>
+    int upload(soccer_handle* h, const std::vector<T>& v, const T** out) {
+        T* d = nullptr;
+        if (int rc = alloc(h, v.size(), &d)) return rc;
+        if (!v.empty() && hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(h, SOCCER_E_HIP, "planner list upload failed");
+        *out = d;
+        return SOCCER_OK;
+    }
+    void clear() {
+        for (void* b : ptrs) if (b) (void)hipFree(b);
+        ptrs.clear(); ready = false;
+    }
+};
+
+struct soccer_graph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    uint64_t ticks = 0;       // ticks consumed by one replay
+    int start_slot = 0;       // tick slot the first captured launch reads
+    bool stamped = false;     // soccer_timer_start / _mark were captured: a replay writes stamp slots 0 and 1
+};
+
+struct soccer_handle {
+    soccer_config cfg{};
+    Rules rules;
+    KernelParams P{};
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // device buffers owned by the handle
+    uint16_t* d_lut = nullptr; uint32_t* d_nc = nullptr; uint32_t* d_isd = nullptr;
+    int8_t* d_policy[2] = {nullptr, nullptr};
+    unsigned long long* d_tick = nullptr;   // two slots, 128 B apart
+    unsigned long long* d_hist = nullptr;
+    unsigned int* d_misuse = nullptr;       // device alias of misuse_host
+    unsigned int* misuse_host = nullptr;    // pinned + mapped: kernels store to it only when a frozen lane is stepped (rare),
+                                            // the host reads it without a copy
+    uint8_t* d_state = nullptr;             // one allocation holding the six SoA streams back to back
+    size_t state_stride = 0;                // bytes between consecutive streams
+    uint8_t* stage_dev = nullptr;           // staging for the host-pointer entry points
+    uint8_t* stage_host = nullptr;          // pinned
+    bool mapped = false;                    // SOCCER_F_HOST_MAPPED: d_state and the staging block are pinned host memory
+    size_t stage_bytes = 0;
+    int tick_slot = 0;                      // slot the NEXT launch reads
+    uint64_t tick = 0;                      // host mirror of the device tick
+    bool slip = false, lut_lds = false;
+    size_t smem_bytes = 0;
+    int E = 4;
+    int grid_cap = 2048;
+    bool capturing = false;
+    uint64_t capture_ticks = 0;
+    int capture_calls = 0;
+    int capture_start_slot = 0;
+    int n_cu = 256;
+    size_t lds_limit = 64 * 1024;           // hipDeviceProp_t::sharedMemPerBlockOptin: what a workgroup may be given (160 KB on gfx950)
+    uint4* d_sub = nullptr;                 // integer slip thresholds (KernelParams::sub)
+    uint4* rec_host = nullptr; uint4* rec_dev = nullptr; uint32_t rec_seq = 0;   // soccer_step_scalar's mapped result record
+    // byte-parallel step (soccer_swar.hpp)
+    swar::Consts swar_c{}; bool swar_ok = false;
+    swar::SlipConsts slip_c{}; bool slip_swar_ok = false;   // integer slip selection usable by the byte-parallel kernels
+    uint32_t* d_slip_lut = nullptr;         // SlipTables::lut + T for the table form of the selection (when lut_ok)
+    uint32_t* d_slip_step_lut = nullptr;    // SlipTables::lut_step + T: the single step's table (when lut_step_ok)
+    size_t hist_slots = kHistSlots;         // per-wave histogram slots (a power of two; see soccer_create)
+    bool timer_stamped = false; int wall_clock_khz = 100000;   // captured timers: see stamp_kernel
+    bool capture_stamped = false;           // THIS capture recorded soccer_timer_start / _mark (what soccer_graph::stamped is copied from)
+    bool stamp_poll = false;                // soccer_timer_read may watch the closing stamp of the last soccer_graph_launch change ...
+    unsigned long long stamp_prev = 0;      // ... from this value (what the slot held when the replay was enqueued)
+    unsigned long long swar_launch_lanes = kSwarLaunchLanes;   // lanes per step_kernel_swar / rollout_swar_kernel launch (SOCCER_SWAR_LAUNCH_LANES: tests of the split)
+    int rollout_pref = 0;                   // SOCCER_ROLLOUT=1 (A/B runs, tests of the fallback): never the byte-parallel rollout
+    SlipF64* d_slip_f64 = nullptr;          // SLIPM == 3: nominal float64 slip thresholds (step_kernel_swar with caller-supplied uniforms)
+    uint32_t* d_worklist = nullptr;         // ... and the groups it leaves to the exact walk: [n / 4] indices, the count and the
+                                            // tail's statistics behind them (worklist_count)
+    unsigned long long* d_traj_hist = nullptr;   // soccer_trajectory_returns: u64[3] the kernel adds into
+    void* comm = nullptr; int comm_world = 0, comm_rank = 0;   // soccer_comm_init: the RCCL communicator of this handle's device
+    unsigned long long* d_comm_scratch = nullptr;   // 64 B for the small reductions (barrier, histogram, clocks)
+    PlanIO plan{};                          // cached planner lists (single-agent mode), see build_plan
+    DeviceBufs plan_bufs{"the planner lists"};   // dropped when the policy changes (soccer_set_policy)
+    MinimaxIO mm{};                         // cached two-player lists and buffers of the minimax planners, see build_minimax
+    double* mm_V[2] = {nullptr, nullptr};   // V double-buffered across sweeps
+    unsigned long long* mm_words = nullptr; // [kMinimaxBatch + 1] per-sweep max |V_k - V_{k-1}| (bits)
+    DeviceBufs mm_bufs{"the minimax planner"};
+    std::string err;
+};
+
+// the handle's host-mapped block: dwords 0 / 1 the sticky misuse words, from byte 64 on SOCCER_STAMP_SLOTS u64 clock stamps,
+// ONE PER 64-BYTE LINE: a line the host has written or is polling costs the device a coherence round trip to write, and a
+// stamp kernel's store must complete before the next kernel starts — with the opening and the closing stamp of a captured
+// timer in one line (and the host clearing the closing one before every replay) the opening stamp's kernel boundary took
+// microseconds longer and inflated the region it opens
+constexpr size_t kStampStride = 8;          // in u64
+constexpr size_t kMappedBytes = 64 + 8 * kStampStride * SOCCER_STAMP_SLOTS;
+
+// the tick lives in device memory so that a captured graph advances it on every replay: launch j
+// reads slot (j & 1) and writes slot ((j + 1) & 1)
+static inline void bind_tick(soccer_handle* h, KernelParams& P, uint64_t ticks) {
+    P.tick_in = h->d_tick + (h->tick_slot ? 16 : 0);
+    P.tick_out = h->d_tick + (h->tick_slot ? 0 : 16);
+    h->tick_slot ^= 1;
+    if (h->capturing) { h->capture_ticks += ticks; h->capture_calls += 1; }
+    else h->tick += ticks;
+}
+
+static inline int grid_for(const soccer_handle* h, uint64_t work_items) {
+    uint64_t blocks = (work_items + kBlock - 1) / kBlock;
+    if (blocks < 1) blocks = 1;
+    if (blocks > (uint64_t)h->grid_cap) blocks = h->grid_cap;
+    return static_cast<int>(blocks);
+}
+
+// ---- what one unit needs from another ------------------------------------------------------------
+// soccer_rollout.hip: lets rollout_kernel<E, slip, lut_lds, *> of this handle's shape take `bytes` of dynamic LDS (soccer_create)
+hipError_t rollout_raise_smem_limit(const soccer_handle* h, size_t bytes);
+// soccer_comm.hip: destroys the handle's communicator, if it has one (free_handle)
+void comm_release(soccer_handle* h);
+
+#pragma GCC visibility pop

@@ -1,0 +1,388 @@
+// soccer_planners.hip — the transition table, the single-agent planners, minimax value iteration and the matrix-game solver (see soccer_handle.hpp).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "soccer_handle.hpp"
+#include "soccer_planner_kernels.hpp"
+
+// the reference's P_readable, computed on the device by the rule functions of the step kernels
+extern "C" int soccer_enumerate_transitions(soccer_handle* h, int32_t* count, double* prob, int32_t* next_flat,
+                                            int8_t* reward, uint8_t* done) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "soccer_enumerate_transitions during graph capture");
+    if (!count || !prob || !next_flat || !reward || !done) return fail(h, SOCCER_E_INVALID, "all five outputs are required");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t keys = h->rules.lut.size() * 25, ent = keys * kMaxOutcomes;
+    EnumIO io{};
+    io.n_tuples = static_cast<int32_t>(h->rules.lut.size()); io.H = h->rules.H;
+    void* bufs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t sizes[5] = {keys * sizeof(int32_t), ent * sizeof(double), ent * sizeof(int32_t), ent, ent};
+    int rc = SOCCER_OK;
+    for (int i = 0; i < 5 && rc == SOCCER_OK; ++i)
+        if (hipMalloc(&bufs[i], sizes[i]) != hipSuccess) rc = fail(h, SOCCER_E_NOMEM, "out of device memory for the transition table");
+    if (rc == SOCCER_OK) {
+        io.count = static_cast<int32_t*>(bufs[0]); io.prob = static_cast<double*>(bufs[1]);
+        io.next = static_cast<int32_t*>(bufs[2]); io.reward = static_cast<int8_t*>(bufs[3]); io.done = static_cast<uint8_t*>(bufs[4]);
+        const unsigned grid = static_cast<unsigned>((keys + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(enumerate_kernel, dim3(grid), dim3(kBlock), 0, h->stream, h->P, io);
+        void* dst[5] = {count, prob, next_flat, reward, done};
+        hipError_t e = hipGetLastError();
+        for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipMemcpyAsync(dst[i], bufs[i], sizes[i], hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = fail(h, SOCCER_E_HIP, "transition table export failed: %s", hipGetErrorString(e));
+    }
+    for (void* b : bufs) if (b) (void)hipFree(b);
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// planners (reference gym_soccer/utils/planners.py).  The (state, learner action) lists are assembled on
+// the host from the device-enumerated transition relation exactly as the reference's constructor builds
+// P[s][a], Pmat and Rmat (:167-293), cached on the handle until the policy changes, and one
+// single-workgroup kernel runs the whole planner.
+static int build_plan(soccer_handle* h) {
+    if (h->plan_bufs.ready) return SOCCER_OK;
+    const bool fixed_a = h->P.policy_a != nullptr, fixed_b = h->P.policy_b != nullptr;
+    if (fixed_a == fixed_b)
+        return fail(h, SOCCER_E_INVALID, "planners need single-agent mode: exactly one side with a fixed policy (soccer_set_policy)");
+    const Rules& R = h->rules;
+    const int nS = R.nS;
+    if ((size_t)nS * sizeof(double) > 150 * 1024) return fail(h, SOCCER_E_INVALID, "too many states (%d) for the single-workgroup planner", nS);
+    const size_t T = R.lut.size(), keys = T * 25, ent = keys * kMaxOutcomes;
+    std::vector<int32_t> count(keys), nxt(ent); std::vector<double> prob(ent); std::vector<int8_t> rew(ent); std::vector<uint8_t> done(ent);
+    if (int rc = soccer_enumerate_transitions(h, count.data(), prob.data(), nxt.data(), rew.data(), done.data())) return rc;
+    std::vector<int8_t> policy(nS);
+    HIP_TRY(h, hipMemcpy(policy.data(), fixed_a ? h->P.policy_a : h->P.policy_b, (size_t)nS, hipMemcpyDeviceToHost));
+    auto obs_of = [&](size_t f) { return R.kind[f] == 2 ? 0 : (int)R.lut[f]; };
+    const bool flip = fixed_a;                                          // learner B sees -r (:243-244)
+    // P[s][a]: goal tuples all write index 0 and overwrite each other (identical lists), live tuples own theirs
+    std::vector<long> tuple_of(nS, -1);
+    for (size_t f = 0; f < T; ++f) if (R.kind[f] != 0) tuple_of[obs_of(f)] = (long)f;
+    const PlanEntry pad_entry{0.0, (int32_t)0x80000000, 0.0f};
+    auto pad = [&](std::vector<PlanEntry>& v) { while (v.size() % kPlanPad) v.push_back(pad_entry); };
+    std::vector<int32_t> off((size_t)nS * 5 + 1, 0); std::vector<PlanEntry> lists;
+    for (int s = 0; s < nS; ++s) for (int a = 0; a < 5; ++a) {
+        const long f = tuple_of[s];
+        if (f < 0) return fail(h, SOCCER_E_INVALID, "internal error: observation index %d has no tuple", s);
+        const size_t key = (size_t)f * 25 + (fixed_a ? policy[s] : a) * 5 + (fixed_b ? policy[s] : a);
+        for (int k = 0; k < count[key]; ++k) {
+            const size_t e = key * kMaxOutcomes + k;
+            const double rr = flip ? -1.0 * (double)rew[e] : (double)rew[e];
+            lists.push_back(PlanEntry{prob[e], obs_of((size_t)nxt[e]) | (done[e] ? (int32_t)0x80000000 : 0), (float)rr});
+        }
+        pad(lists);
+        off[(size_t)s * 5 + a + 1] = (int32_t)lists.size();
+    }
+    // Pmat[s][ns][a] += p and Rmat[s][a] (= 0, then += p * r) in the constructor's tuple order (:280-291):
+    // index 0 accumulates one unit of probability per goal tuple, its Rmat is the last goal tuple's (0)
+    std::vector<std::vector<double>> row((size_t)nS * 5);               // dense rows only for touched (s, a)
+    std::vector<double> Rm((size_t)nS * 5, 0.0);
+    for (size_t f = 0; f < T; ++f) {
+        if (R.kind[f] == 0) continue;
+        const int s = obs_of(f);
+        for (int a = 0; a < 5; ++a) {
+            const size_t key = f * 25 + (fixed_a ? policy[s] : a) * 5 + (fixed_b ? policy[s] : a);
+            std::vector<double>& r = row[(size_t)s * 5 + a];
+            if (r.empty()) r.assign(nS, 0.0);
+            double acc = 0.0;
+            for (int k = 0; k < count[key]; ++k) {
+                const size_t e = key * kMaxOutcomes + k;
+                const double rr = flip ? -1.0 * (double)rew[e] : (double)rew[e];
+                r[obs_of((size_t)nxt[e])] += prob[e];
+                acc = acc + prob[e] * rr;
+            }
+            Rm[(size_t)s * 5 + a] = acc;
+        }
+    }
+    std::vector<int32_t> m_off((size_t)nS * 5 + 1, 0); std::vector<PlanEntry> m_lists;
+    const PlanEntry m_pad{0.0, 0, 0.0f};
+    for (size_t q = 0; q < (size_t)nS * 5; ++q) {
+        for (int ns = 0; ns < nS; ++ns) if (row[q][ns] != 0.0) m_lists.push_back(PlanEntry{row[q][ns], ns, 0.0f});
+        while (m_lists.size() % kPlanPad) m_lists.push_back(m_pad);
+        m_off[q + 1] = (int32_t)m_lists.size();
+        std::vector<double>().swap(row[q]);
+    }
+    PlanIO& io = h->plan;
+    io = PlanIO{};
+    int rc = h->plan_bufs.upload(h, off, &io.offset);
+    if (!rc) rc = h->plan_bufs.upload(h, lists, &io.list);
+    if (!rc) rc = h->plan_bufs.upload(h, m_off, &io.m_offset);
+    if (!rc) rc = h->plan_bufs.upload(h, m_lists, &io.m_list);
+    if (!rc) rc = h->plan_bufs.upload(h, Rm, &io.m_R);
+    const std::vector<double> zV(nS, 0.0), zQ((size_t)nS * 5, 0.0); const std::vector<int32_t> zpi(nS, 0), zc(16, 0);
+    const double* cV = nullptr; const double* cN = nullptr; const double* cQ = nullptr; const int32_t* cpi = nullptr; const int32_t* cc = nullptr;
+    if (!rc) rc = h->plan_bufs.upload(h, zV, &cV);
+    if (!rc) rc = h->plan_bufs.upload(h, zV, &cN);
+    if (!rc) rc = h->plan_bufs.upload(h, zQ, &cQ);
+    if (!rc) rc = h->plan_bufs.upload(h, zpi, &cpi);
+    if (!rc) rc = h->plan_bufs.upload(h, zc, &cc);
+    if (rc) { h->plan_bufs.clear(); return rc; }
+    io.V = const_cast<double*>(cV); io.newV = const_cast<double*>(cN); io.Q = const_cast<double*>(cQ);
+    io.pi = const_cast<int32_t*>(cpi); io.counters = const_cast<int32_t*>(cc);
+    io.nS = nS;
+    const size_t smem = (size_t)nS * sizeof(double);
+    if (smem > 48 * 1024)
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&planner_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    h->plan_bufs.ready = true;
+    return SOCCER_OK;
+}
+
+// runs one planner; inputs pi_in / V_in and every output are HOST pointers (any output may be NULL)
+static int run_plan(soccer_handle* h, const char* what, int mode, double theta, double gamma, int32_t max_sweeps, int32_t k,
+                    const int32_t* pi_in, const double* V_in, const double* Q_in, double* V, double* Q, int32_t* pi, int32_t* iterations) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "%s during graph capture", what);
+    if (max_sweeps < 1) return fail(h, SOCCER_E_INVALID, "max_sweeps must be >= 1");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(h, SOCCER_E_INVALID, "discount_factor must be in [0, 1]");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (int rc = build_plan(h)) return rc;
+    PlanIO io = h->plan;
+    const int nS = io.nS;
+    if (pi_in) {
+        for (int s = 0; s < nS; ++s) if (pi_in[s] < 0 || pi_in[s] > 4) return fail(h, SOCCER_E_INVALID, "pi[%d] = %d is not an action", s, pi_in[s]);
+        HIP_TRY(h, hipMemcpyAsync(io.pi, pi_in, (size_t)nS * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (V_in) HIP_TRY(h, hipMemcpyAsync(io.V, V_in, (size_t)nS * 8, hipMemcpyHostToDevice, h->stream));
+    else if (mode == kPlanEvalDense) HIP_TRY(h, hipMemsetAsync(io.V, 0, (size_t)nS * 8, h->stream));
+    if (Q_in) HIP_TRY(h, hipMemcpyAsync(io.Q, Q_in, (size_t)nS * 40, hipMemcpyHostToDevice, h->stream));
+    io.mode = mode; io.theta = theta; io.gamma = gamma; io.max_sweeps = max_sweeps; io.k = k;
+    io.threshold = (theta * (1 - gamma)) / (2 * gamma);                  // planners.py:75
+    hipLaunchKernelGGL(planner_kernel, dim3(1), dim3(1024), (size_t)nS * sizeof(double), h->stream, io);
+    HIP_TRY(h, hipGetLastError());
+    int32_t counters[4] = {0, 0, 0, 0};
+    if (V) HIP_TRY(h, hipMemcpyAsync(V, io.V, (size_t)nS * 8, hipMemcpyDeviceToHost, h->stream));
+    if (Q) HIP_TRY(h, hipMemcpyAsync(Q, io.Q, (size_t)nS * 40, hipMemcpyDeviceToHost, h->stream));
+    if (pi) HIP_TRY(h, hipMemcpyAsync(pi, io.pi, (size_t)nS * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(counters, io.counters, 12, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (iterations) *iterations = counters[0];
+    if (counters[2]) return fail(h, SOCCER_E_STATE, "%s stopped after max_sweeps = %d sweeps without converging", what, max_sweeps);
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_value_iteration(soccer_handle* h, double theta, double discount_factor, int32_t max_sweeps,
+                                      double* V, double* Q, int32_t* pi, int32_t* iterations) {
+    return run_plan(h, "soccer_value_iteration", kPlanVI, theta, discount_factor, max_sweeps, 0, nullptr, nullptr, nullptr, V, Q, pi, iterations);
+}
+
+extern "C" int soccer_policy_evaluation(soccer_handle* h, const int32_t* pi, double theta, double discount_factor,
+                                        int32_t max_sweeps, double* V, int32_t* sweeps) {
+    if (h && !pi) return fail(h, SOCCER_E_INVALID, "pi is NULL");
+    return run_plan(h, "soccer_policy_evaluation", kPlanEval, theta, discount_factor, max_sweeps, 0, pi, nullptr, nullptr, V, nullptr, nullptr, sweeps);
+}
+
+extern "C" int soccer_policy_improvement(soccer_handle* h, const double* V, double discount_factor, double* Q, int32_t* new_pi) {
+    if (h && !V) return fail(h, SOCCER_E_INVALID, "V is NULL");
+    return run_plan(h, "soccer_policy_improvement", kPlanImprove, 0.0, discount_factor, 1, 0, nullptr, V, nullptr, nullptr, Q, new_pi, nullptr);
+}
+
+extern "C" int soccer_policy_iteration(soccer_handle* h, const int32_t* pi0, double theta, double discount_factor,
+                                       int32_t max_sweeps, double* V, double* Q, int32_t* pi, int32_t* iterations) {
+    if (h && !pi0) return fail(h, SOCCER_E_INVALID, "pi0 (the initial policy) is NULL");
+    return run_plan(h, "soccer_policy_iteration", kPlanPI, theta, discount_factor, max_sweeps, 0, pi0, nullptr, nullptr, V, Q, pi, iterations);
+}
+
+extern "C" int soccer_modified_policy_iteration(soccer_handle* h, int32_t k, double theta, double discount_factor,
+                                                int32_t max_sweeps, double* V, double* Q, int32_t* pi, int32_t* iterations) {
+    if (h && k < 1) return fail(h, SOCCER_E_INVALID, "k must be >= 1");
+    if (h && !(discount_factor > 0.0)) return fail(h, SOCCER_E_INVALID, "discount_factor must be > 0 for the stopping threshold");
+    return run_plan(h, "soccer_modified_policy_iteration", kPlanMPI, theta, discount_factor, max_sweeps, k, nullptr, nullptr, nullptr, V, Q, pi, iterations);
+}
+
+extern "C" int soccer_policy_eval_dense(soccer_handle* h, const double* policy, int32_t k, double theta, double discount_factor,
+                                        int32_t max_sweeps, const double* init, double* v, int32_t* sweeps) {
+    if (h && !policy) return fail(h, SOCCER_E_INVALID, "policy is NULL");
+    if (h && k < 1) return fail(h, SOCCER_E_INVALID, "k must be >= 1");
+    return run_plan(h, "soccer_policy_eval_dense", kPlanEvalDense, theta, discount_factor, max_sweeps, k, nullptr, init, policy, v, nullptr, nullptr, sweeps);
+}
+
+// ------------------------------------------------------------------------------------------------
+// minimax value iteration (two-player handles).  The (state, joint action) lists are the ones build_plan would assemble
+// for a joint action (P[0] = the last goal tuple's lists, player A's reward), built on the device from enumerate_kernel's
+// output without a round trip of the transition relation through the host (at 11x7 that copy and the host loops were 95 %
+// of a solve), cached on the handle apart from the single-agent plan; every sweep is one launch of minimax_sweep_kernel
+// over the whole GPU.
+constexpr int kMinimaxBatch = 16;             // sweeps enqueued between two synchronisations
+
+static int build_minimax(soccer_handle* h) {
+    if (h->mm_bufs.ready) return SOCCER_OK;
+    const Rules& R = h->rules;
+    const int nS = R.nS;
+    const size_t T = R.lut.size(), keys = T * 25, ent = keys * kMaxOutcomes, nkeys = (size_t)nS * 25;
+    // P[s]: goal tuples all write index 0 and overwrite each other (identical lists), live tuples own theirs
+    std::vector<int32_t> tuple_of(nS, -1);
+    for (size_t f = 0; f < T; ++f) if (R.kind[f] != 0) tuple_of[R.kind[f] == 2 ? 0 : (int)R.lut[f]] = (int32_t)f;
+    for (int s = 0; s < nS; ++s) if (tuple_of[s] < 0) return fail(h, SOCCER_E_INVALID, "internal error: observation index %d has no tuple", s);
+    // the transition relation stays on the device: enumerate, measure the lists, place them
+    void* tmp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t sizes[6] = {keys * sizeof(int32_t), ent * sizeof(double), ent * sizeof(int32_t), ent, ent, (size_t)nS * sizeof(int32_t)};
+    int rc = SOCCER_OK;
+    for (int i = 0; i < 6 && rc == SOCCER_OK; ++i)
+        if (hipMalloc(&tmp[i], sizes[i]) != hipSuccess) rc = fail(h, SOCCER_E_NOMEM, "out of device memory for the transition table");
+    int32_t* d_off = nullptr; PlanEntry* d_list = nullptr;
+    std::vector<int32_t> off(nkeys + 1, 0);
+    MinimaxListIO L{};
+    hipError_t e = hipSuccess;
+    if (rc == SOCCER_OK) rc = h->mm_bufs.alloc(h, off.size(), &d_off);
+    if (rc == SOCCER_OK) {
+        EnumIO io{};
+        io.n_tuples = static_cast<int32_t>(T); io.H = R.H;
+        io.count = static_cast<int32_t*>(tmp[0]); io.prob = static_cast<double*>(tmp[1]); io.next = static_cast<int32_t*>(tmp[2]);
+        io.reward = static_cast<int8_t*>(tmp[3]); io.done = static_cast<uint8_t*>(tmp[4]);
+        L.count = io.count; L.prob = io.prob; L.next = io.next; L.reward = io.reward; L.done = io.done;
+        L.tuple_of = static_cast<const int32_t*>(tmp[5]); L.lut = h->P.lut; L.offset = d_off; L.nS = nS;
+        e = hipMemcpyAsync(tmp[5], tuple_of.data(), sizes[5], hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(d_off, 0, off.size() * sizeof(int32_t), h->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(enumerate_kernel, dim3((unsigned)((keys + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->P, io);
+            hipLaunchKernelGGL(minimax_lists_kernel<false>, dim3((unsigned)((nkeys + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, L);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(off.data(), d_off, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = fail(h, SOCCER_E_HIP, "minimax list construction failed: %s", hipGetErrorString(e));
+    }
+    if (rc == SOCCER_OK) {
+        for (size_t k = 0; k < nkeys; ++k) off[k + 1] += off[k];                 // padded lengths -> offsets
+        rc = h->mm_bufs.alloc(h, (size_t)off[nkeys], &d_list);
+    }
+    if (rc == SOCCER_OK) {
+        L.list = d_list;
+        e = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(minimax_lists_kernel<true>, dim3((unsigned)((nkeys + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, L);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = fail(h, SOCCER_E_HIP, "minimax list construction failed: %s", hipGetErrorString(e));
+    }
+    for (void* b : tmp) if (b) (void)hipFree(b);
+    MinimaxIO io{};
+    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS, &h->mm_V[0]);
+    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS, &h->mm_V[1]);
+    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS * 25, &io.Q);
+    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS * 5, &io.pi_a);
+    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS * 5, &io.pi_b);
+    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)kMinimaxBatch + 1, &h->mm_words);
+    if (rc) { h->mm_bufs.clear(); return rc; }
+    io.offset = d_off; io.list = d_list; io.nS = nS;
+    h->mm = io;
+    h->mm_bufs.ready = true;
+    return SOCCER_OK;
+}
+
+static int minimax_check(soccer_handle* h, const char* what, double gamma) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "%s during graph capture", what);
+    if (h->P.policy_a != nullptr || h->P.policy_b != nullptr)
+        return fail(h, SOCCER_E_INVALID, "%s needs a two-player handle: neither side may have a fixed policy (soccer_set_policy)", what);
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(h, SOCCER_E_INVALID, "discount_factor must be in [0, 1]");
+    return SOCCER_OK;
+}
+
+// after every argument is checked: the device and the cached lists
+static int minimax_prepare(soccer_handle* h) {
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    return build_minimax(h);
+}
+
+// one sweep: V_in -> V_out (device buffers of the handle), Q and the strategies into the handle's buffers
+static void minimax_launch(soccer_handle* h, double gamma, double theta, const double* V_in, double* V_out,
+                           unsigned long long* delta, const unsigned long long* prev) {
+    MinimaxIO io = h->mm;
+    io.V = V_in; io.V_out = V_out; io.delta = delta; io.prev = prev; io.gamma = gamma; io.theta = theta;
+    const unsigned grid = (unsigned)((io.nS + kMinimaxWaves - 1) / kMinimaxWaves);
+    hipLaunchKernelGGL(minimax_sweep_kernel, dim3(grid), dim3(kMinimaxBlock), 0, h->stream, io);
+}
+
+static int minimax_outputs(soccer_handle* h, const double* V_dev, double* V, double* Q, double* pi_a, double* pi_b) {
+    const size_t nS = (size_t)h->mm.nS;
+    if (V) HIP_TRY(h, hipMemcpyAsync(V, V_dev, nS * 8, hipMemcpyDeviceToHost, h->stream));
+    if (Q) HIP_TRY(h, hipMemcpyAsync(Q, h->mm.Q, nS * 200, hipMemcpyDeviceToHost, h->stream));
+    if (pi_a) HIP_TRY(h, hipMemcpyAsync(pi_a, h->mm.pi_a, nS * 40, hipMemcpyDeviceToHost, h->stream));
+    if (pi_b) HIP_TRY(h, hipMemcpyAsync(pi_b, h->mm.pi_b, nS * 40, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_solve_matrix_games(soccer_handle* h, int64_t n_games, const double* A, double* value, double* x, double* y) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "soccer_solve_matrix_games during graph capture");
+    if (n_games < 0) return fail(h, SOCCER_E_INVALID, "n_games must be >= 0");
+    if (n_games > 0 && !A) return fail(h, SOCCER_E_INVALID, "A is NULL");
+    if (n_games == 0) return SOCCER_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t n = (size_t)n_games;
+    void* bufs[4] = {nullptr, nullptr, nullptr, nullptr};
+    const size_t sizes[4] = {n * 200, n * 8, n * 40, n * 40};
+    int rc = SOCCER_OK;
+    for (int i = 0; i < 4 && rc == SOCCER_OK; ++i)
+        if (hipMalloc(&bufs[i], sizes[i]) != hipSuccess) rc = fail(h, SOCCER_E_NOMEM, "out of device memory for %lld games", (long long)n_games);
+    if (rc == SOCCER_OK) {
+        hipError_t e = hipMemcpyAsync(bufs[0], A, sizes[0], hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) {
+            const unsigned grid = (unsigned)((n + kGamesBlock - 1) / kGamesBlock);
+            hipLaunchKernelGGL(games_kernel, dim3(grid), dim3(kGamesBlock), 0, h->stream, static_cast<const double*>(bufs[0]), (long long)n,
+                               static_cast<double*>(bufs[1]), static_cast<double*>(bufs[2]), static_cast<double*>(bufs[3]));
+            e = hipGetLastError();
+        }
+        void* dst[3] = {value, x, y};
+        for (int i = 0; i < 3 && e == hipSuccess; ++i) if (dst[i]) e = hipMemcpyAsync(dst[i], bufs[i + 1], sizes[i + 1], hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = fail(h, SOCCER_E_HIP, "soccer_solve_matrix_games failed: %s", hipGetErrorString(e));
+    }
+    for (void* b : bufs) if (b) (void)hipFree(b);
+    return rc;
+}
+
+extern "C" int soccer_minimax_backup(soccer_handle* h, double discount_factor, const double* V, double* V_out, double* Q,
+                                     double* pi_a, double* pi_b) {
+    if (int rc = minimax_check(h, "soccer_minimax_backup", discount_factor)) return rc;
+    if (!V) return fail(h, SOCCER_E_INVALID, "V is NULL");
+    if (int rc = minimax_prepare(h)) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->mm_V[0], V, (size_t)h->mm.nS * 8, hipMemcpyHostToDevice, h->stream));
+    minimax_launch(h, discount_factor, 0.0, h->mm_V[0], h->mm_V[1], nullptr, nullptr);
+    HIP_TRY(h, hipGetLastError());
+    return minimax_outputs(h, h->mm_V[1], V_out, Q, pi_a, pi_b);
+}
+
+extern "C" int soccer_minimax_value_iteration(soccer_handle* h, double theta, double discount_factor, int32_t max_sweeps,
+                                              double* V, double* Q, double* pi_a, double* pi_b, int32_t* iterations) {
+    if (int rc = minimax_check(h, "soccer_minimax_value_iteration", discount_factor)) return rc;
+    if (max_sweeps < 1) return fail(h, SOCCER_E_INVALID, "max_sweeps must be >= 1");
+    if (!(theta >= 0.0)) return fail(h, SOCCER_E_INVALID, "theta must be >= 0");
+    if (int rc = minimax_prepare(h)) return rc;
+    const int nS = h->mm.nS;
+    HIP_TRY(h, hipMemsetAsync(h->mm_V[0], 0, (size_t)nS * 8, h->stream));                  // V_0 = 0
+    // words[0] is the sweep before the batch's first: +inf (never converged) before sweep 1
+    unsigned long long words[kMinimaxBatch + 1];
+    const double inf = __builtin_huge_val();
+    std::memcpy(&words[0], &inf, 8);
+    int32_t k0 = 1, done_at = 0;                                                         // k0: first sweep of the batch
+    while (k0 <= max_sweeps && !done_at) {
+        const int nb = (int)std::min<int64_t>(kMinimaxBatch, (int64_t)max_sweeps - k0 + 1);
+        for (int j = 1; j <= kMinimaxBatch; ++j) words[j] = 0ull;
+        HIP_TRY(h, hipMemcpyAsync(h->mm_words, words, sizeof words, hipMemcpyHostToDevice, h->stream));
+        for (int j = 1; j <= nb; ++j) {
+            const int32_t k = k0 + j - 1;
+            minimax_launch(h, discount_factor, theta, h->mm_V[(k - 1) & 1], h->mm_V[k & 1], h->mm_words + j, h->mm_words + j - 1);
+        }
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(words, h->mm_words, sizeof words, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (int j = 1; j <= nb && !done_at; ++j) {
+            double d; std::memcpy(&d, &words[j], 8);
+            if (d < theta) done_at = k0 + j - 1;
+        }
+        words[0] = words[nb];
+        k0 += nb;
+    }
+    const int32_t k = done_at ? done_at : max_sweeps;
+    if (int rc = minimax_outputs(h, h->mm_V[k & 1], V, Q, pi_a, pi_b)) return rc;
+    if (iterations) *iterations = k;
+    if (!done_at) return fail(h, SOCCER_E_STATE, "soccer_minimax_value_iteration stopped after max_sweeps = %d sweeps without converging", max_sweeps);
+    return SOCCER_OK;
+}

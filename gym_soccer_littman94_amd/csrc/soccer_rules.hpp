@@ -7,7 +7,7 @@
 //   initial state distribution  :146-165  -> isd
 //   single-player cell move     :364-373  -> next_cell  (the "move/bounds table")
 // Nothing here runs per step; the per-step rules (collisions :296-362, slip list :202-256,
-// bookkeeping :393-406) are evaluated per lane in soccer_kernels.hpp.
+// bookkeeping :393-406) are evaluated per lane in soccer_kernels.hpp (lane_step).
 #pragma once
 #include <cstdint>
 #include <string>

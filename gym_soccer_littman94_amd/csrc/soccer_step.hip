@@ -1,0 +1,156 @@
+// soccer_step.hip — batched_step / batched_step_ex: which single-step kernel a call gets, and its launch (see soccer_handle.hpp).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "soccer_handle.hpp"
+#include "soccer_step_kernels.hpp"
+
+// the work list of step_kernel_swar<.., SLIPM = 3, ..>: one index per 4-lane group of the handle, then the count at an 8-byte aligned
+// word at least 16 bytes behind them, then the tail kernel's two uint64 statistics (step_kernel: launch parts, groups walked)
+static inline size_t worklist_count_word(const soccer_handle* h) { return ((size_t)(h->P.n >> 2) + 5) & ~(size_t)1; }
+static inline uint32_t* worklist_count(const soccer_handle* h) { return h->d_worklist ? h->d_worklist + worklist_count_word(h) : nullptr; }
+static bool ensure_worklist(soccer_handle* h) {
+    if (h->d_worklist) return true;
+    const size_t words = worklist_count_word(h) + 2 + 4;
+    if (hipMalloc(reinterpret_cast<void**>(&h->d_worklist), words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); h->d_worklist = nullptr; return false; }
+    // (on the handle's own stream: a memset on the null stream is not ordered with a non-blocking stream's kernels)
+    if (hipMemsetAsync(h->d_worklist, 0, words * sizeof(uint32_t), h->stream) != hipSuccess) {
+        // without a cleared count the list must not be used: give it back, a later call tries again
+        (void)hipGetLastError(); (void)hipFree(h->d_worklist); h->d_worklist = nullptr; return false;
+    }
+    return true;
+}
+
+template <bool EXPLICIT_U, bool VEC, bool SHARED>
+static void launch_step3(soccer_handle* h, const KernelParams& P, const StepIO& io) {
+    const int grid = grid_for(h, (P.n + 3) / 4);
+    const dim3 g(grid), b(kBlock);
+    if (h->slip) hipLaunchKernelGGL((step_kernel<true, EXPLICIT_U, VEC, SHARED>), g, b, 0, h->stream, P, io);
+    else hipLaunchKernelGGL((step_kernel<false, EXPLICIT_U, VEC, SHARED>), g, b, 0, h->stream, P, io);
+}
+static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& io, bool explicit_u, bool vec) {
+    const bool shared = ((P.lane_offset + P.first) & 3ull) == 0ull;
+    const bool policy_only = explicit_u && !io.u_step && !io.u_reset;       // fixed-policy handle, Philox draws
+    const bool swar_fit = vec && shared && h->swar_ok && (!h->slip || h->slip_swar_ok) && aligned(io.last_return, 4);
+    // caller-supplied uniforms at slip_prob == 0: floor(4u) is the reference's decision for any double (step_kernel_swar, EXPL)
+    const bool expl = explicit_u && !policy_only && !h->slip && aligned(io.u_step, 16) && aligned(io.u_reset, 16);
+    // ... and at slip_prob > 0 the float64 decision against the nominal thresholds (SLIPM = 3); the groups it cannot decide safely go
+    // to the per-lane kernel's exact walk through a work list (one extra small launch per call)
+    const bool expl_slip = explicit_u && !policy_only && h->slip && io.u_step && aligned(io.u_step, 16) && aligned(io.u_reset, 16) &&
+                           vec && shared && h->swar_ok && aligned(io.last_return, 4) && (P.n >> 2) < 0xffffffffull &&
+                           (h->d_worklist || (!h->capturing && ensure_worklist(h)));      // (no allocation inside a capture: the per-lane kernel then)
+    if (((policy_only || !explicit_u || expl) && swar_fit) || expl_slip) {
+        // the byte-parallel kernel (four lanes stay packed in their dwords, no rule-table reads)
+        // which outputs the launch needs decides the instantiation: 0 the four result streams, 1 + the gym floats /
+        // finished / last_return, 2 + final_obs / prob_code / episode histogram
+        const int out = (io.prob_code || io.final_obs || P.step_stats) ? 2
+                      : (io.reward_a_f32 || io.reward_b_f32 || io.finished || io.last_return) ? 1 : 0;
+        const dim3 b(kBlock);
+#define SWAR_ARGS P.state + c0, P.state_stride, off(io.act_a, c0), off(io.act_b, c0), (h->capturing ? P.tick_in : nullptr), cn, (unsigned long long)(h->tick - 1), Q
+#define SWAR_GO(OV, SV, PV, XV) do { if (h->swar_c.small) hipLaunchKernelGGL((step_kernel_swar<OV, SV, PV, 1, XV>), gh, b, 0, h->stream, SWAR_ARGS); \
+                                     else hipLaunchKernelGGL((step_kernel_swar<OV, SV, PV, 0, XV>), gh, b, 0, h->stream, SWAR_ARGS); } while (0)
+#define SWAR_SLIP(OV, PV) do { if (expl_slip) SWAR_GO(OV, 3, PV, true); else if (expl) SWAR_GO(OV, 0, PV, true); else if (!h->slip) SWAR_GO(OV, 0, PV, false); \
+                               else if (h->d_slip_step_lut) SWAR_GO(OV, 2, PV, false); else SWAR_GO(OV, 1, PV, false); } while (0)
+#define SWAR_OUT(PV) do { if (out == 2) SWAR_SLIP(2, PV); else if (out == 1) SWAR_SLIP(1, PV); else SWAR_SLIP(0, PV); } while (0)
+        // The kernel's byte offsets are 32-bit (soccer_kernels.hpp): a handle beyond kSwarLaunchLanes lanes is stepped by
+        // several launches on the same tick, each handed its part of every stream; only the last one publishes the tick.
+        for (unsigned long long c0 = P.first; c0 < P.first + P.n; c0 += h->swar_launch_lanes) {
+            const unsigned long long cn = std::min<unsigned long long>(h->swar_launch_lanes, P.first + P.n - c0);
+            const bool last = c0 + cn == P.first + P.n;
+            const dim3 gh(static_cast<unsigned>(((cn >> 2) + kBlock - 1) / kBlock));
+            SwarParams Q{h->swar_c, P.key0, P.key1, P.lane_offset + c0, 0ull, last ? P.tick_out : nullptr, P.misuse,
+                         P.step_stats ? P.hist : nullptr, P.hist_mask,
+                         h->slip_c, reinterpret_cast<const swar::Quad*>(P.sub), h->d_slip_step_lut,
+                         (h->cfg.flags & SOCCER_F_STREAM_ACTIONS) ? 1u : 0u, P.policy_a, P.policy_b,
+                         off(io.obs, c0), off(io.reward, c0), off(io.terminated, c0), off(io.truncated, c0), off(io.prob_code, c0),
+                         off(io.final_obs, c0), off(io.reward_a_f32, c0), off(io.reward_b_f32, c0), off(io.finished, c0),
+                         off(io.last_return, c0), off(io.u_step, c0), off(io.u_reset, c0),
+                         h->d_slip_f64, h->d_worklist, worklist_count(h)};
+            if (P.policy_a || P.policy_b) SWAR_OUT(true); else SWAR_OUT(false);
+            if (expl_slip) {
+                // the groups of THIS part that were listed: the per-lane kernel, one workgroup, same tick (it publishes nothing)
+                KernelParams R = P; R.first = c0; R.n = cn; R.tick_out = nullptr;
+                StepIO jo = io; jo.worklist = h->d_worklist; jo.work_count = worklist_count(h);
+                hipLaunchKernelGGL((step_kernel<true, true, true, true>), dim3(1), dim3(kBlock), 0, h->stream, R, jo);
+            }
+        }
+#undef SWAR_OUT
+#undef SWAR_SLIP
+#undef SWAR_GO
+#undef SWAR_ARGS
+    } else if (explicit_u) {    // caller-supplied uniforms (facade, tests) and fixed-policy handles beyond the byte arithmetic: generic kernel
+        if (vec && shared) launch_step3<true, true, true>(h, P, io); else launch_step3<true, false, false>(h, P, io);
+    } else if (vec && shared) {
+        // the hot instantiations of the per-lane kernel (slip handles, pitches beyond the byte arithmetic);
+        // LEAN drops the code for prob_code / final_obs / last_return / step stats
+        const bool lean = !io.prob_code && !io.final_obs && !io.last_return && !io.reward_a_f32 && !io.reward_b_f32 && !io.finished && !P.step_stats;
+        const int grid = grid_for(h, (P.n + 3) / 4);
+        const dim3 g(grid), b(kBlock);
+        if (lean) {                 // one 4-lane group per thread, as many workgroups as it takes
+            const unsigned long long blocks = ((P.n >> 2) + kBlock - 1) / kBlock;
+            const dim3 gh(static_cast<unsigned>(blocks));
+#define HOT_ARGS P.state, P.state_stride, io.act_a, io.act_b, (h->capturing ? P.tick_in : nullptr), P.n, (unsigned long long)(h->tick - 1), P, io
+            if (h->slip && P.slip_int == 1u) hipLaunchKernelGGL((step_kernel_hot<true, true>), gh, b, 0, h->stream, HOT_ARGS);
+            else if (h->slip) hipLaunchKernelGGL(step_kernel_hot<true>, gh, b, 0, h->stream, HOT_ARGS);
+            else hipLaunchKernelGGL(step_kernel_hot<false>, gh, b, 0, h->stream, HOT_ARGS);
+#undef HOT_ARGS
+        } else launch_step3<false, true, true>(h, P, io);
+    }
+    else if (vec) launch_step3<false, true, false>(h, P, io);
+    else launch_step3<false, false, false>(h, P, io);
+}
+
+extern "C" int batched_step_ex(soccer_handle* h, const soccer_step_args* a) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (!a || (!a->act_a && !h->P.policy_a) || (!a->act_b && !h->P.policy_b))
+        return fail(h, SOCCER_E_INVALID, "batched_step: an action stream is required for every player without a fixed policy");
+    if (!aligned(a->u_step, 8) || !aligned(a->u_reset, 8) || !aligned(a->obs, 2) || !aligned(a->final_obs, 2) ||
+        !aligned(a->reward_a_f32, 4) || !aligned(a->reward_b_f32, 4))
+        return fail(h, SOCCER_E_INVALID, "batched_step: u_* must be 8-byte, reward_*_f32 4-byte and obs/final_obs 2-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    // dword I/O needs every byte stream 4-aligned and the uint16 streams 8-aligned; else byte I/O
+    const bool vec = h->E != 1 && aligned(a->act_a, 4) && aligned(a->act_b, 4) && aligned(a->reward, 4) &&
+                     aligned(a->terminated, 4) && aligned(a->truncated, 4) && aligned(a->prob_code, 4) &&
+                     aligned(a->obs, 8) && aligned(a->final_obs, 8) && aligned(a->reward_a_f32, 16) && aligned(a->reward_b_f32, 16) &&
+                     aligned(a->finished, 4);
+    const bool explicit_u = a->u_step || a->u_reset || h->P.policy_a || h->P.policy_b;   // generic kernel
+    KernelParams P = h->P;
+    bind_tick(h, P, 1);
+    StepIO io{a->act_a, a->act_b, a->u_step, a->u_reset, a->obs, a->reward, a->terminated, a->truncated,
+              a->prob_code, a->final_obs, a->last_return, a->reward_a_f32, a->reward_b_f32, a->finished, nullptr, nullptr};
+    const unsigned long long n = h->P.n, n4 = vec ? (n & ~3ull) : 0ull;
+    if (n4) { P.first = 0; P.n = n4; launch_step(h, P, io, explicit_u, true); }
+    if (n4 < n) {               // ragged tail (or everything, when the buffers are not dword-aligned)
+        KernelParams Q = P;
+        Q.first = n4; Q.n = n - n4;
+        if (n4) Q.tick_out = nullptr;   // same tick as the main launch, which publishes it
+        launch_step(h, Q, io, explicit_u, false);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+extern "C" int batched_step(soccer_handle* h, const int8_t* act_a, const int8_t* act_b, uint16_t* obs,
+                            int8_t* reward, uint8_t* terminated, uint8_t* truncated, uint8_t* prob_code) {
+    soccer_step_args a{};
+    a.act_a = act_a; a.act_b = act_b; a.obs = obs; a.reward = reward;
+    a.terminated = terminated; a.truncated = truncated; a.prob_code = prob_code;
+    return batched_step_ex(h, &a);
+}
+
+// what the work list's tail launches have walked so far (the two statistics behind the count, see worklist_count_word)
+extern "C" int soccer_exact_walk_stats(const soccer_handle* h, uint64_t* parts, uint64_t* groups) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    soccer_handle* hm = const_cast<soccer_handle*>(h);                  // (the error text only)
+    if (h->capturing) return fail(hm, SOCCER_E_STATE, "soccer_exact_walk_stats during graph capture");
+    unsigned long long st[2] = {0ull, 0ull};
+    if (h->d_worklist) {
+        HIP_TRY(hm, hipSetDevice(h->cfg.device));
+        HIP_TRY(hm, hipStreamSynchronize(h->stream));
+        HIP_TRY(hm, hipMemcpy(st, worklist_count(h) + 2, sizeof st, hipMemcpyDeviceToHost));
+    }
+    if (parts) *parts = st[0];
+    if (groups) *groups = st[1];
+    return SOCCER_OK;
+}

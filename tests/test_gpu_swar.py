@@ -632,7 +632,7 @@ def test_clock_stamps_and_the_captured_timer():
 @pytest.mark.parametrize("slip", [0.0, 0.2])
 def test_a_step_split_into_several_launches_is_the_same_step(slip, monkeypatch):
     """step_kernel_swar addresses every stream with 32-bit byte offsets, so a handle beyond 2^30 lanes is stepped by several
-    launches on one tick, each handed its part of every stream (launch_step in soccer_hip.hip).  SOCCER_SWAR_LAUNCH_LANES
+    launches on one tick, each handed its part of every stream (launch_step in soccer_step.hip).  SOCCER_SWAR_LAUNCH_LANES
     (read by soccer_create) shrinks the part so that the split can be tested at a size the oracle finishes: 3 parts + a
     short one + a ragged 3-lane tail, every output stream, the histogram and last_return, eagerly and as a captured graph."""
     monkeypatch.setenv("SOCCER_SWAR_LAUNCH_LANES", "4096")
@@ -734,7 +734,7 @@ def test_action_streams_with_the_non_temporal_hint(slip, fixed):
 @pytest.mark.parametrize("slip", [0.0, 0.2])
 def test_a_rollout_split_into_several_launches_is_the_same_rollout(slip, monkeypatch):
     """rollout_swar_kernel addresses its streams with 32-bit byte offsets too: a handle beyond 2^30 lanes is rolled out part by
-    part (batched_rollout in soccer_hip.hip), every part over the same ticks, the last one publishing the tick.
+    part (batched_rollout in soccer_rollout.hip), every part over the same ticks, the last one publishing the tick.
     SOCCER_SWAR_LAUNCH_LANES shrinks the part: 3 parts + a short one, streams in and four trajectories out, per-lane return sums
     / episode counts, then sampled actions; the histogram; followed by single steps on the same ticks."""
     monkeypatch.setenv("SOCCER_SWAR_LAUNCH_LANES", "4096")

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Instruction mix of kernels in build/asm/soccer_hip.s (make -C gym_soccer_littman94_amd/csrc asm).
+"""Instruction mix of kernels in build/asm/*.s, one file per translation unit (make -C gym_soccer_littman94_amd/csrc asm).
 Usage: tools/isa_count.py [substring of the mangled kernel name ...]"""
-import collections, re, sys
+import collections, glob, re, sys
 pats = sys.argv[1:] or ['step_kernel_swar', 'step_kernel_hot']
-s = open('build/asm/soccer_hip.s').read().split('\n')
+s = [l for f in sorted(glob.glob('build/asm/*.s')) for l in open(f).read().split('\n')]
 name, body = None, []
 def report(name, body):
     ins = [l.strip() for l in body]
