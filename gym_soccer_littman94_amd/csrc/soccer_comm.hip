@@ -69,7 +69,7 @@ extern "C" int soccer_comm_init(soccer_handle* h, int32_t world, int32_t rank, c
     if (h->comm) return fail(h, SOCCER_E_STATE, "soccer_comm_init: this handle already has a communicator");
     if (!rccl().ok) return fail(h, SOCCER_E_HIP, "%s", rccl().why.c_str());
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    if (!h->d_comm_scratch) HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_comm_scratch), 64));
+    if (!h->d_comm_scratch) if (int rc = h->bufs.alloc(h, 64 / sizeof(unsigned long long), &h->d_comm_scratch)) return rc;
     IdByValue v; std::memcpy(v.internal, id, sizeof v.internal);
     RCCL_TRY(h, rccl().CommInitRank(&h->comm, world, v, rank));
     h->comm_world = world; h->comm_rank = rank;

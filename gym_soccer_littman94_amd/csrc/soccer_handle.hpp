@@ -40,34 +40,56 @@ static inline bool aligned(const T* p, size_t a) { return p == nullptr || (reint
 
 template <class T> static inline T* off(T* p, unsigned long long lanes) { return p ? p + lanes : nullptr; }   // NULL stays NULL
 
-// Device buffers that are built lazily and dropped together (the cached lists of the planners).  A failed build calls
-// clear(); so does whatever invalidates the lists, and free_handle.
-struct DeviceBufs {
-    const char* what;                       // for the out-of-memory message
-    std::vector<void*> ptrs;
-    bool ready = false;                     // set by the builder once every buffer holds its content
-    explicit DeviceBufs(const char* owner) : what(owner) {}
+// The one owner of memory the library allocates for itself: device memory (hipMalloc) and pinned host memory
+// (hipHostMalloc), each block freed once by clear(), which the destructor calls.  An allocation hands its typed pointer
+// back through an out-parameter; whoever keeps that pointer (the handle's d_* members, the planners' argument blocks)
+// does not own it.  The handle has one for what lives as long as it does, the planners' cached lists have their own
+// (dropped by a failed build and by whatever invalidates the lists), a call's temporaries a local one.
+struct OwnedBufs {
+    struct Buf { void* ptr; bool pinned; };
+    enum PinnedFlags : unsigned { kPinned = hipHostMallocDefault, kPinnedMapped = hipHostMallocMapped };   // (mapped: the device addresses it too)
+    const char* what;                       // for the error message
+    std::vector<Buf> bufs;
+    bool ready = false;                     // set by a builder once every buffer holds its content
+    explicit OwnedBufs(const char* owner) : what(owner) {}
+    OwnedBufs(const OwnedBufs&) = delete;
+    OwnedBufs& operator=(const OwnedBufs&) = delete;
+    ~OwnedBufs() { clear(); }
 
     template <class T>
-    int alloc(soccer_handle* h, size_t count, T** out) {
-        void* d = nullptr;
-        if (hipMalloc(&d, count ? count * sizeof(T) : 1) != hipSuccess) return fail(h, SOCCER_E_NOMEM, "out of device memory for %s", what);
-        ptrs.push_back(d);
-        *out = static_cast<T*>(d);
-        return SOCCER_OK;
-    }
+    int alloc(soccer_handle* h, size_t count, T** out) { return take(h, hipMalloc(out, bytes<T>(count)), false, out); }
+    template <class T>
+    int alloc_pinned(soccer_handle* h, size_t count, PinnedFlags flags, T** out) { return take(h, hipHostMalloc(out, bytes<T>(count), flags), true, out); }
     template <class T>
     int upload(soccer_handle* h, const std::vector<T>& v, const T** out) {
         T* d = nullptr;
         if (int rc = alloc(h, v.size(), &d)) return rc;
         if (!v.empty() && hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-            return fail(h, SOCCER_E_HIP, "planner list upload failed");
+            return fail(h, SOCCER_E_HIP, "upload of %s failed", what);
         *out = d;
         return SOCCER_OK;
     }
+    // gives one block back early (a buffer whose set-up failed half way)
+    void release(void* p) {
+        for (size_t i = 0; i < bufs.size(); ++i) if (bufs[i].ptr == p) { drop(bufs[i]); bufs.erase(bufs.begin() + i); return; }
+    }
     void clear() {
-        for (void* b : ptrs) if (b) (void)hipFree(b);
-        ptrs.clear(); ready = false;
+        for (const Buf& b : bufs) drop(b);
+        bufs.clear(); ready = false;
+    }
+
+private:
+    template <class T> static size_t bytes(size_t count) { return count ? count * sizeof(T) : 1; }
+    static void drop(const Buf& b) { (void)(b.pinned ? hipHostFree(b.ptr) : hipFree(b.ptr)); }
+    template <class T>
+    int take(soccer_handle* h, hipError_t e, bool pinned, T** out) {
+        if (e != hipSuccess) {
+            *out = nullptr;
+            return e == hipErrorOutOfMemory ? fail(h, SOCCER_E_NOMEM, "out of %s memory for %s", pinned ? "pinned host" : "device", what)
+                                            : fail(h, SOCCER_E_HIP, "allocation for %s failed: %s", what, hipGetErrorString(e));
+        }
+        bufs.push_back(Buf{*out, pinned});
+        return SOCCER_OK;
     }
 };
 
@@ -86,7 +108,9 @@ struct soccer_handle {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // device buffers owned by the handle
+    // what soccer_create allocates and what is allocated on first use and lives as long as the handle; the typed members
+    // below point into it and own nothing
+    OwnedBufs bufs{"the handle"};
     uint16_t* d_lut = nullptr; uint32_t* d_nc = nullptr; uint32_t* d_isd = nullptr;
     int8_t* d_policy[2] = {nullptr, nullptr};
     unsigned long long* d_tick = nullptr;   // two slots, 128 B apart
@@ -133,12 +157,17 @@ struct soccer_handle {
     void* comm = nullptr; int comm_world = 0, comm_rank = 0;   // soccer_comm_init: the RCCL communicator of this handle's device
     unsigned long long* d_comm_scratch = nullptr;   // 64 B for the small reductions (barrier, histogram, clocks)
     PlanIO plan{};                          // cached planner lists (single-agent mode), see build_plan
-    DeviceBufs plan_bufs{"the planner lists"};   // dropped when the policy changes (soccer_set_policy)
+    OwnedBufs plan_bufs{"the planner lists"};   // dropped when the policy changes (soccer_set_policy)
     MinimaxIO mm{};                         // cached two-player lists and buffers of the minimax planners, see build_minimax
     double* mm_V[2] = {nullptr, nullptr};   // V double-buffered across sweeps
     unsigned long long* mm_words = nullptr; // [kMinimaxBatch + 1] per-sweep max |V_k - V_{k-1}| (bits)
-    DeviceBufs mm_bufs{"the minimax planner"};
+    OwnedBufs mm_bufs{"the minimax planner"};
     std::string err;
+
+    soccer_handle() = default;
+    soccer_handle(const soccer_handle&) = delete;
+    soccer_handle& operator=(const soccer_handle&) = delete;
+    ~soccer_handle();                       // soccer_hip.hip: waits for the stream, then gives everything back
 };
 
 // the handle's host-mapped block: dwords 0 / 1 the sticky misuse words, from byte 64 on SOCCER_STAMP_SLOTS u64 clock stamps,
@@ -169,7 +198,7 @@ static inline int grid_for(const soccer_handle* h, uint64_t work_items) {
 // ---- what one unit needs from another ------------------------------------------------------------
 // soccer_rollout.hip: lets rollout_kernel<E, slip, lut_lds, *> of this handle's shape take `bytes` of dynamic LDS (soccer_create)
 hipError_t rollout_raise_smem_limit(const soccer_handle* h, size_t bytes);
-// soccer_comm.hip: destroys the handle's communicator, if it has one (free_handle)
+// soccer_comm.hip: destroys the handle's communicator, if it has one (the handle's destructor)
 void comm_release(soccer_handle* h);
 
 #pragma GCC visibility pop

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -43,24 +44,15 @@ extern "C" int soccer_device_count(int* count) {
 
 extern "C" const char* soccer_last_error(const soccer_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
 
-static void free_handle(soccer_handle* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->cfg.device);
-    (void)hipStreamSynchronize(h->stream);
-    if (h->mapped) { if (h->d_state) (void)hipHostFree(h->d_state); h->d_state = nullptr; if (h->stage_host) (void)hipHostFree(h->stage_host); h->stage_host = nullptr; h->stage_dev = nullptr; }
-    comm_release(h);
-    void* bufs[] = {h->d_state, h->d_lut, h->d_nc, h->d_isd, h->d_policy[0], h->d_policy[1], h->d_tick, h->d_hist, h->stage_dev, h->d_sub, h->d_slip_lut, h->d_slip_step_lut,
-                    h->d_traj_hist, h->d_comm_scratch, h->d_slip_f64, h->d_worklist};
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    h->plan_bufs.clear();
-    h->mm_bufs.clear();
-    if (h->stage_host) (void)hipHostFree(h->stage_host);
-    if (h->rec_host) (void)hipHostFree(h->rec_host);
-    if (h->misuse_host) (void)hipHostFree(h->misuse_host);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+// nothing is freed before the stream has drained; a handle whose creation failed early has no stream and no events
+soccer_handle::~soccer_handle() {
+    (void)hipSetDevice(cfg.device);
+    (void)hipStreamSynchronize(stream);
+    comm_release(this);
+    bufs.clear(); plan_bufs.clear(); mm_bufs.clear();      // here, not as members after this body: the stream is still alive
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
 static void set_key(soccer_handle* h, uint64_t seed) {
@@ -80,35 +72,23 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
     const uint32_t e = cfg->envs_per_thread;
     if (!(e == 0 || e == 1 || e == 4 || e == 8))
         return fail(nullptr, SOCCER_E_INVALID, "envs_per_thread must be 0, 1, 4 or 8");
-    soccer_handle* h = new soccer_handle();
+    std::unique_ptr<soccer_handle> owner(new soccer_handle());      // every failing exit below destroys the handle
+    soccer_handle* h = owner.get();
     h->cfg = *cfg;
     const std::string msg = h->rules.build(cfg->width, cfg->height);
-    if (!msg.empty()) { delete h; return fail(nullptr, SOCCER_E_INVALID, "%s", msg.c_str()); }
+    if (!msg.empty()) return fail(nullptr, SOCCER_E_INVALID, "%s", msg.c_str());
     int ndev = 0;
     hipError_t de = hipGetDeviceCount(&ndev);
-    if (de != hipSuccess || ndev < 1) {
-        delete h;
+    if (de != hipSuccess || ndev < 1)
         return fail(nullptr, SOCCER_E_HIP, "no HIP device available (%s); libsoccer_hip has no CPU path",
                     de == hipSuccess ? "device count is 0" : hipGetErrorString(de));
-    }
-    if (cfg->device < 0 || cfg->device >= ndev) {
-        delete h; return fail(nullptr, SOCCER_E_INVALID, "device %d out of range (0..%d)", cfg->device, ndev - 1);
-    }
-#define CREATE_TRY(expr)                                                                          \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            int code_ = fail(nullptr, e_ == hipErrorOutOfMemory ? SOCCER_E_NOMEM : SOCCER_E_HIP,  \
-                             "%s failed: %s", #expr, hipGetErrorString(e_));                      \
-            free_handle(h); return code_;                                                         \
-        }                                                                                         \
-    } while (0)
-    CREATE_TRY(hipSetDevice(cfg->device));
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(nullptr, SOCCER_E_INVALID, "device %d out of range (0..%d)", cfg->device, ndev - 1);
+    HIP_TRY(nullptr, hipSetDevice(cfg->device));
     if (cfg->flags & SOCCER_F_NULL_STREAM) { h->stream = nullptr; h->own_stream = false; }
     else if (cfg->stream) { h->stream = static_cast<hipStream_t>(cfg->stream); h->own_stream = false; }
-    else { CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
-    CREATE_TRY(hipEventCreate(&h->ev0));
-    CREATE_TRY(hipEventCreate(&h->ev1));
+    else { HIP_TRY(nullptr, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
+    HIP_TRY(nullptr, hipEventCreate(&h->ev0));
+    HIP_TRY(nullptr, hipEventCreate(&h->ev1));
 
     const Rules& R = h->rules;
     KernelParams& P = h->P;
@@ -116,40 +96,37 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
     const size_t padded = (n + 255) & ~size_t(255);
     h->state_stride = padded;
     h->mapped = (cfg->flags & SOCCER_F_HOST_MAPPED) != 0;
-    if (h->mapped) {
-        if (n > 4096) { free_handle(h); return fail(nullptr, SOCCER_E_INVALID, "SOCCER_F_HOST_MAPPED is for small handles (n_lanes <= 4096)"); }
-        CREATE_TRY(hipHostMalloc(&h->d_state, 6 * padded, hipHostMallocMapped));
-    } else {
-        CREATE_TRY(hipMalloc(&h->d_state, 6 * padded));
-    }
+    if (h->mapped && n > 4096) return fail(nullptr, SOCCER_E_INVALID, "SOCCER_F_HOST_MAPPED is for small handles (n_lanes <= 4096)");
+    if (int rc = h->mapped ? h->bufs.alloc_pinned(nullptr, 6 * padded, OwnedBufs::kPinnedMapped, &h->d_state)
+                           : h->bufs.alloc(nullptr, 6 * padded, &h->d_state)) return rc;
     P.state = h->d_state; P.state_stride = padded;
     // every lane starts needing a reset (:140), parked on the first ISD state so the tuple is valid
     if (h->mapped) {
         const uint8_t init[6] = {(uint8_t)R.isd[0][0], (uint8_t)R.isd[0][1], (uint8_t)R.isd[0][2], (uint8_t)R.isd[0][3], (uint8_t)(2 | R.isd[0][4]), 0};
         for (int k = 0; k < 6; ++k) std::memset(h->d_state + k * padded, init[k], padded);
     } else {
-    CREATE_TRY(hipMemsetAsync(h->d_state, R.isd[0][0], padded, h->stream));
-    CREATE_TRY(hipMemsetAsync(h->d_state + padded, R.isd[0][1], padded, h->stream));
-    CREATE_TRY(hipMemsetAsync(h->d_state + 2 * padded, R.isd[0][2], padded, h->stream));
-    CREATE_TRY(hipMemsetAsync(h->d_state + 3 * padded, R.isd[0][3], padded, h->stream));
-    CREATE_TRY(hipMemsetAsync(h->d_state + 4 * padded, 2 | R.isd[0][4], padded, h->stream));
-    CREATE_TRY(hipMemsetAsync(h->d_state + 5 * padded, 0, padded, h->stream));
+    HIP_TRY(nullptr, hipMemsetAsync(h->d_state, R.isd[0][0], padded, h->stream));
+    HIP_TRY(nullptr, hipMemsetAsync(h->d_state + padded, R.isd[0][1], padded, h->stream));
+    HIP_TRY(nullptr, hipMemsetAsync(h->d_state + 2 * padded, R.isd[0][2], padded, h->stream));
+    HIP_TRY(nullptr, hipMemsetAsync(h->d_state + 3 * padded, R.isd[0][3], padded, h->stream));
+    HIP_TRY(nullptr, hipMemsetAsync(h->d_state + 4 * padded, 2 | R.isd[0][4], padded, h->stream));
+    HIP_TRY(nullptr, hipMemsetAsync(h->d_state + 5 * padded, 0, padded, h->stream));
     }
 
-    CREATE_TRY(hipMalloc(&h->d_nc, R.next_cell.size() * sizeof(uint32_t)));
-    CREATE_TRY(hipMalloc(&h->d_isd, sizeof(R.isd_words)));
-    CREATE_TRY(hipMemcpy(h->d_isd, R.isd_words, sizeof(R.isd_words), hipMemcpyHostToDevice));
-    CREATE_TRY(hipMemcpy(h->d_nc, R.next_cell.data(), R.next_cell.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    CREATE_TRY(hipMalloc(&h->d_tick, 256));
-    CREATE_TRY(hipMemset(h->d_tick, 0, 256));
+    if (int rc = h->bufs.alloc(nullptr, R.next_cell.size(), &h->d_nc)) return rc;
+    if (int rc = h->bufs.alloc(nullptr, sizeof(R.isd_words) / sizeof(uint32_t), &h->d_isd)) return rc;
+    HIP_TRY(nullptr, hipMemcpy(h->d_isd, R.isd_words, sizeof(R.isd_words), hipMemcpyHostToDevice));
+    HIP_TRY(nullptr, hipMemcpy(h->d_nc, R.next_cell.data(), R.next_cell.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (int rc = h->bufs.alloc(nullptr, 256 / sizeof(unsigned long long), &h->d_tick)) return rc;
+    HIP_TRY(nullptr, hipMemset(h->d_tick, 0, 256));
     // one private histogram slot per wave of the largest grid that counts episodes: the capped grids (rollout, per-lane
     // step) stay below kHistSlots waves; the byte-parallel step launches one wave per 256 lanes, uncapped
     while (h->hist_slots < (n + 255) / 256) h->hist_slots <<= 1;
-    CREATE_TRY(hipMalloc(&h->d_hist, sizeof(unsigned long long) * h->hist_slots * kHistStride));
-    CREATE_TRY(hipMemset(h->d_hist, 0, sizeof(unsigned long long) * h->hist_slots * kHistStride));
-    CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->misuse_host), kMappedBytes, hipHostMallocMapped));
+    if (int rc = h->bufs.alloc(nullptr, h->hist_slots * kHistStride, &h->d_hist)) return rc;
+    HIP_TRY(nullptr, hipMemset(h->d_hist, 0, sizeof(unsigned long long) * h->hist_slots * kHistStride));
+    if (int rc = h->bufs.alloc_pinned(nullptr, kMappedBytes / sizeof(unsigned int), OwnedBufs::kPinnedMapped, &h->misuse_host)) return rc;
     std::memset(h->misuse_host, 0, kMappedBytes);
-    CREATE_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_misuse), h->misuse_host, 0));
+    HIP_TRY(nullptr, hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_misuse), h->misuse_host, 0));
 
     P.next_cell = h->d_nc; P.isd = h->d_isd;
     P.hist = h->d_hist; P.hist_mask = (uint32_t)(h->hist_slots - 1); P.misuse = h->d_misuse;
@@ -168,8 +145,8 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
         for (int i = 0; i < 9; ++i) { P.B[i] = ST.B[i]; P.CB[i] = ST.CB[i]; }
         P.nb = ST.nb; P.act_pack = ST.act_pack; P.slip_int = ST.slip_int;
         static_assert(sizeof(swar::Quad) == sizeof(uint4), "threshold rows are 16 bytes");
-        CREATE_TRY(hipMalloc(&h->d_sub, sizeof(ST.sub)));
-        CREATE_TRY(hipMemcpy(h->d_sub, ST.sub, sizeof(ST.sub), hipMemcpyHostToDevice));
+        if (int rc = h->bufs.alloc(nullptr, sizeof(ST.sub) / sizeof(uint4), &h->d_sub)) return rc;
+        HIP_TRY(nullptr, hipMemcpy(h->d_sub, ST.sub, sizeof(ST.sub), hipMemcpyHostToDevice));
         P.sub = h->d_sub;
         h->slip_swar_ok = ST.swar_ok;
         static_assert(kSlipBuckets == 16384 && kSlipThresholds == 40, "table layout shared with the kernels");
@@ -177,20 +154,20 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
             std::vector<uint32_t> img(kSlipLdsWords, 0xFFFFFFFFu);
             std::memcpy(img.data(), ST.lut, kSlipBuckets);
             std::memcpy(img.data() + kSlipBuckets / 4, ST.T, sizeof(ST.T));
-            CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_slip_lut), img.size() * sizeof(uint32_t)));
-            CREATE_TRY(hipMemcpy(h->d_slip_lut, img.data(), img.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            if (int rc = h->bufs.alloc(nullptr, img.size(), &h->d_slip_lut)) return rc;
+            HIP_TRY(nullptr, hipMemcpy(h->d_slip_lut, img.data(), img.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
         if (ST.lut_step_ok && !std::getenv("SOCCER_STEP_SLIP_ONE_BY_ONE")) {      // (the variable: tests and A/B runs of the other form)
             std::vector<uint32_t> img(kSlipStepLdsWords, 0xFFFFFFFFu);
             std::memcpy(img.data(), ST.lut_step, kSlipStepBuckets);
             std::memcpy(img.data() + kSlipStepBuckets / 4, ST.T, sizeof(ST.T));
-            CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_slip_step_lut), img.size() * sizeof(uint32_t)));
-            CREATE_TRY(hipMemcpy(h->d_slip_step_lut, img.data(), img.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            if (int rc = h->bufs.alloc(nullptr, img.size(), &h->d_slip_step_lut)) return rc;
+            HIP_TRY(nullptr, hipMemcpy(h->d_slip_step_lut, img.data(), img.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         }
         {
             const SlipF64 F = make_slip_f64(ST);
-            CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_slip_f64), sizeof F));
-            CREATE_TRY(hipMemcpy(h->d_slip_f64, &F, sizeof F, hipMemcpyHostToDevice));
+            if (int rc = h->bufs.alloc(nullptr, 1, &h->d_slip_f64)) return rc;
+            HIP_TRY(nullptr, hipMemcpy(h->d_slip_f64, &F, sizeof F, hipMemcpyHostToDevice));
         }
         h->slip_c = swar::SlipConsts{};
         for (int i = 0; i < 9; ++i) h->slip_c.CB[i] = ST.CB[i];
@@ -211,12 +188,10 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
     // staged into LDS by the rollout / reset kernels when it fits next to the move/bounds table.
     const size_t nc_bytes = (R.next_cell.size() + kIsdWords) * sizeof(uint32_t);
     const size_t lut_bytes = R.lut.size() * sizeof(uint16_t);
-    if (nc_bytes > 150 * 1024) {
-        free_handle(h);
+    if (nc_bytes > 150 * 1024)
         return fail(nullptr, SOCCER_E_INVALID, "pitch too large: the move/bounds table (%zu bytes) must fit the 160 KB LDS", nc_bytes);
-    }
-    CREATE_TRY(hipMalloc(&h->d_lut, lut_bytes));
-    CREATE_TRY(hipMemcpy(h->d_lut, R.lut.data(), lut_bytes, hipMemcpyHostToDevice));
+    if (int rc = h->bufs.alloc(nullptr, R.lut.size(), &h->d_lut)) return rc;
+    HIP_TRY(nullptr, hipMemcpy(h->d_lut, R.lut.data(), lut_bytes, hipMemcpyHostToDevice));
     P.lut = h->d_lut; P.lut_len = static_cast<int32_t>(R.lut.size());
     h->lut_lds = nc_bytes + lut_bytes <= 150 * 1024;
     h->smem_bytes = nc_bytes + (h->lut_lds ? lut_bytes : 0);
@@ -227,25 +202,23 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
             se = hipFuncSetAttribute(h->slip ? reinterpret_cast<const void*>(h->lut_lds ? &reset_kernel<true, true> : &reset_kernel<false, true>)
                                              : reinterpret_cast<const void*>(h->lut_lds ? &reset_kernel<true, false> : &reset_kernel<false, false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-        CREATE_TRY(se);
+        HIP_TRY(nullptr, se);
     }
     hipDeviceProp_t prop;
-    CREATE_TRY(hipGetDeviceProperties(&prop, cfg->device));
+    HIP_TRY(nullptr, hipGetDeviceProperties(&prop, cfg->device));
     { int khz = 0; if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, cfg->device) == hipSuccess && khz > 0) h->wall_clock_khz = khz; }
     h->grid_cap = prop.multiProcessorCount * 8;
     h->n_cu = prop.multiProcessorCount;
     if (prop.sharedMemPerBlockOptin > 0) h->lds_limit = prop.sharedMemPerBlockOptin;
     else if (prop.sharedMemPerBlock > 0) h->lds_limit = prop.sharedMemPerBlock;
-    CREATE_TRY(hipStreamSynchronize(h->stream));
-    CREATE_TRY(hipDeviceSynchronize());      // the hipMemset / hipMemcpy calls above went to the null stream, which a non-blocking stream does not wait for
-#undef CREATE_TRY
-    *out = h;
+    HIP_TRY(nullptr, hipStreamSynchronize(h->stream));
+    HIP_TRY(nullptr, hipDeviceSynchronize());      // the hipMemset / hipMemcpy calls above went to the null stream, which a non-blocking stream does not wait for
+    *out = owner.release();
     return SOCCER_OK;
 }
 
 extern "C" int soccer_destroy(soccer_handle* h) {
-    if (!h) return SOCCER_OK;
-    free_handle(h);
+    delete h;
     return SOCCER_OK;
 }
 
@@ -416,14 +389,12 @@ StageLayout stage_layout(size_t n) {
 }
 int ensure_stage(soccer_handle* h, const StageLayout& L) {
     if (h->stage_bytes >= L.total) return SOCCER_OK;
-    if (h->mapped) {            // the kernel reads inputs from / writes outputs to the pinned block in place
-        HIP_TRY(h, hipHostMalloc(&h->stage_host, L.total, hipHostMallocMapped));
-        h->stage_dev = h->stage_host;
-    } else {
-        HIP_TRY(h, hipMalloc(&h->stage_dev, L.total));
-        HIP_TRY(h, hipHostMalloc(&h->stage_host, L.total, hipHostMallocDefault));
-    }
-    h->stage_bytes = L.total;
+    // both halves or neither.  Mapped: the kernel reads inputs from / writes outputs to the pinned block in place
+    uint8_t* host = nullptr; uint8_t* dev = nullptr;
+    if (int rc = h->bufs.alloc_pinned(h, L.total, h->mapped ? OwnedBufs::kPinnedMapped : OwnedBufs::kPinned, &host)) return rc;
+    if (h->mapped) dev = host;
+    else if (int rc = h->bufs.alloc(h, L.total, &dev)) { h->bufs.release(host); return rc; }
+    h->stage_host = host; h->stage_dev = dev; h->stage_bytes = L.total;
     return SOCCER_OK;
 }
 }  // namespace
@@ -537,9 +508,12 @@ static int scalar_call(soccer_handle* h, const char* what, uint32_t op, soccer_s
     }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     if (!h->rec_host) {
-        HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->rec_host), 64, hipHostMallocMapped));
-        std::memset(h->rec_host, 0, 64);
-        HIP_TRY(h, hipHostGetDevicePointer(reinterpret_cast<void**>(&h->rec_dev), h->rec_host, 0));
+        uint4* rec = nullptr;
+        if (int rc = h->bufs.alloc_pinned(h, 64 / sizeof(uint4), OwnedBufs::kPinnedMapped, &rec)) return rc;
+        std::memset(rec, 0, 64);
+        const hipError_t e = hipHostGetDevicePointer(reinterpret_cast<void**>(&h->rec_dev), rec, 0);
+        if (e != hipSuccess) { h->bufs.release(rec); return fail(h, SOCCER_E_HIP, "%s: no device address for the result record: %s", what, hipGetErrorString(e)); }
+        h->rec_host = rec;
     }
     k.seq = ++h->rec_seq ? h->rec_seq : ++h->rec_seq;                    // never 0
     k.record = h->rec_dev;
@@ -636,7 +610,7 @@ extern "C" int soccer_set_policy(soccer_handle* h, int32_t player, const int8_t*
         return fail(h, SOCCER_E_INVALID, "Both players cannot have a policy. At least one must be None.");   // :38
     for (int i = 0; i < n_states; ++i)
         if (policy_host[i] < 0 || policy_host[i] > 4) return fail(h, SOCCER_E_INVALID, "policy[%d] = %d is not an action", i, (int)policy_host[i]);
-    if (!h->d_policy[player]) HIP_TRY(h, hipMalloc(&h->d_policy[player], (size_t)h->rules.nS));
+    if (!h->d_policy[player]) if (int rc = h->bufs.alloc(h, (size_t)h->rules.nS, &h->d_policy[player])) return rc;
     HIP_TRY(h, hipMemcpy(h->d_policy[player], policy_host, (size_t)n_states, hipMemcpyHostToDevice));
     *slot = h->d_policy[player];
     return SOCCER_OK;
@@ -940,7 +914,7 @@ extern "C" int soccer_trajectory_returns(soccer_handle* h, int32_t n_steps, cons
     if (!aligned(episode_count, 4)) return fail(h, SOCCER_E_INVALID, "soccer_trajectory_returns: episode_count must be 4-byte aligned");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t slots = (size_t)h->grid_cap * 2;       // one u64[4] per workgroup of the (at most two) launches
-    if (!h->d_traj_hist) HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_traj_hist), slots * 4 * sizeof(unsigned long long)));
+    if (!h->d_traj_hist) if (int rc = h->bufs.alloc(h, slots * 4, &h->d_traj_hist)) return rc;
     const unsigned long long n = h->P.n;
     const bool vec = stride % 4 == 0 && aligned(reward, 4) && aligned(terminated, 4) && aligned(truncated, 4) &&
                      aligned(last_return, 4) && aligned(episode_count, 16);

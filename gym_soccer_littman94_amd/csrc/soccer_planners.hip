@@ -18,24 +18,23 @@ extern "C" int soccer_enumerate_transitions(soccer_handle* h, int32_t* count, do
     const size_t keys = h->rules.lut.size() * 25, ent = keys * kMaxOutcomes;
     EnumIO io{};
     io.n_tuples = static_cast<int32_t>(h->rules.lut.size()); io.H = h->rules.H;
-    void* bufs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    OwnedBufs tmp("the transition table");                              // freed on every way out
+    int rc = tmp.alloc(h, keys, &io.count);
+    if (!rc) rc = tmp.alloc(h, ent, &io.prob);
+    if (!rc) rc = tmp.alloc(h, ent, &io.next);
+    if (!rc) rc = tmp.alloc(h, ent, &io.reward);
+    if (!rc) rc = tmp.alloc(h, ent, &io.done);
+    if (rc) return rc;
+    const unsigned grid = static_cast<unsigned>((keys + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(enumerate_kernel, dim3(grid), dim3(kBlock), 0, h->stream, h->P, io);
+    void* dst[5] = {count, prob, next_flat, reward, done};
+    const void* src[5] = {io.count, io.prob, io.next, io.reward, io.done};
     const size_t sizes[5] = {keys * sizeof(int32_t), ent * sizeof(double), ent * sizeof(int32_t), ent, ent};
-    int rc = SOCCER_OK;
-    for (int i = 0; i < 5 && rc == SOCCER_OK; ++i)
-        if (hipMalloc(&bufs[i], sizes[i]) != hipSuccess) rc = fail(h, SOCCER_E_NOMEM, "out of device memory for the transition table");
-    if (rc == SOCCER_OK) {
-        io.count = static_cast<int32_t*>(bufs[0]); io.prob = static_cast<double*>(bufs[1]);
-        io.next = static_cast<int32_t*>(bufs[2]); io.reward = static_cast<int8_t*>(bufs[3]); io.done = static_cast<uint8_t*>(bufs[4]);
-        const unsigned grid = static_cast<unsigned>((keys + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(enumerate_kernel, dim3(grid), dim3(kBlock), 0, h->stream, h->P, io);
-        void* dst[5] = {count, prob, next_flat, reward, done};
-        hipError_t e = hipGetLastError();
-        for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipMemcpyAsync(dst[i], bufs[i], sizes[i], hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(h, SOCCER_E_HIP, "transition table export failed: %s", hipGetErrorString(e));
-    }
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    return rc;
+    hipError_t e = hipGetLastError();
+    for (int i = 0; i < 5 && e == hipSuccess; ++i) e = hipMemcpyAsync(dst[i], src[i], sizes[i], hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, SOCCER_E_HIP, "transition table export failed: %s", hipGetErrorString(e));
+    return SOCCER_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -217,24 +216,25 @@ static int build_minimax(soccer_handle* h) {
     for (size_t f = 0; f < T; ++f) if (R.kind[f] != 0) tuple_of[R.kind[f] == 2 ? 0 : (int)R.lut[f]] = (int32_t)f;
     for (int s = 0; s < nS; ++s) if (tuple_of[s] < 0) return fail(h, SOCCER_E_INVALID, "internal error: observation index %d has no tuple", s);
     // the transition relation stays on the device: enumerate, measure the lists, place them
-    void* tmp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t sizes[6] = {keys * sizeof(int32_t), ent * sizeof(double), ent * sizeof(int32_t), ent, ent, (size_t)nS * sizeof(int32_t)};
-    int rc = SOCCER_OK;
-    for (int i = 0; i < 6 && rc == SOCCER_OK; ++i)
-        if (hipMalloc(&tmp[i], sizes[i]) != hipSuccess) rc = fail(h, SOCCER_E_NOMEM, "out of device memory for the transition table");
+    OwnedBufs tmp("the transition table");                              // freed below, or on an earlier way out
+    EnumIO io{};
+    io.n_tuples = static_cast<int32_t>(T); io.H = R.H;
+    int32_t* d_tuple_of = nullptr;
+    int rc = tmp.alloc(h, keys, &io.count);
+    if (!rc) rc = tmp.alloc(h, ent, &io.prob);
+    if (!rc) rc = tmp.alloc(h, ent, &io.next);
+    if (!rc) rc = tmp.alloc(h, ent, &io.reward);
+    if (!rc) rc = tmp.alloc(h, ent, &io.done);
+    if (!rc) rc = tmp.alloc(h, (size_t)nS, &d_tuple_of);
     int32_t* d_off = nullptr; PlanEntry* d_list = nullptr;
     std::vector<int32_t> off(nkeys + 1, 0);
     MinimaxListIO L{};
     hipError_t e = hipSuccess;
     if (rc == SOCCER_OK) rc = h->mm_bufs.alloc(h, off.size(), &d_off);
     if (rc == SOCCER_OK) {
-        EnumIO io{};
-        io.n_tuples = static_cast<int32_t>(T); io.H = R.H;
-        io.count = static_cast<int32_t*>(tmp[0]); io.prob = static_cast<double*>(tmp[1]); io.next = static_cast<int32_t*>(tmp[2]);
-        io.reward = static_cast<int8_t*>(tmp[3]); io.done = static_cast<uint8_t*>(tmp[4]);
         L.count = io.count; L.prob = io.prob; L.next = io.next; L.reward = io.reward; L.done = io.done;
-        L.tuple_of = static_cast<const int32_t*>(tmp[5]); L.lut = h->P.lut; L.offset = d_off; L.nS = nS;
-        e = hipMemcpyAsync(tmp[5], tuple_of.data(), sizes[5], hipMemcpyHostToDevice, h->stream);
+        L.tuple_of = d_tuple_of; L.lut = h->P.lut; L.offset = d_off; L.nS = nS;
+        e = hipMemcpyAsync(d_tuple_of, tuple_of.data(), (size_t)nS * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) e = hipMemsetAsync(d_off, 0, off.size() * sizeof(int32_t), h->stream);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(enumerate_kernel, dim3((unsigned)((keys + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, h->P, io);
@@ -259,17 +259,17 @@ static int build_minimax(soccer_handle* h) {
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         if (e != hipSuccess) rc = fail(h, SOCCER_E_HIP, "minimax list construction failed: %s", hipGetErrorString(e));
     }
-    for (void* b : tmp) if (b) (void)hipFree(b);
-    MinimaxIO io{};
+    tmp.clear();                                // before the solver's buffers are allocated
+    MinimaxIO mm{};
     if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS, &h->mm_V[0]);
     if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS, &h->mm_V[1]);
-    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS * 25, &io.Q);
-    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS * 5, &io.pi_a);
-    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS * 5, &io.pi_b);
+    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS * 25, &mm.Q);
+    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS * 5, &mm.pi_a);
+    if (!rc) rc = h->mm_bufs.alloc(h, (size_t)nS * 5, &mm.pi_b);
     if (!rc) rc = h->mm_bufs.alloc(h, (size_t)kMinimaxBatch + 1, &h->mm_words);
     if (rc) { h->mm_bufs.clear(); return rc; }
-    io.offset = d_off; io.list = d_list; io.nS = nS;
-    h->mm = io;
+    mm.offset = d_off; mm.list = d_list; mm.nS = nS;
+    h->mm = mm;
     h->mm_bufs.ready = true;
     return SOCCER_OK;
 }
@@ -316,26 +316,24 @@ extern "C" int soccer_solve_matrix_games(soccer_handle* h, int64_t n_games, cons
     if (n_games == 0) return SOCCER_OK;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     const size_t n = (size_t)n_games;
-    void* bufs[4] = {nullptr, nullptr, nullptr, nullptr};
-    const size_t sizes[4] = {n * 200, n * 8, n * 40, n * 40};
-    int rc = SOCCER_OK;
-    for (int i = 0; i < 4 && rc == SOCCER_OK; ++i)
-        if (hipMalloc(&bufs[i], sizes[i]) != hipSuccess) rc = fail(h, SOCCER_E_NOMEM, "out of device memory for %lld games", (long long)n_games);
-    if (rc == SOCCER_OK) {
-        hipError_t e = hipMemcpyAsync(bufs[0], A, sizes[0], hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) {
-            const unsigned grid = (unsigned)((n + kGamesBlock - 1) / kGamesBlock);
-            hipLaunchKernelGGL(games_kernel, dim3(grid), dim3(kGamesBlock), 0, h->stream, static_cast<const double*>(bufs[0]), (long long)n,
-                               static_cast<double*>(bufs[1]), static_cast<double*>(bufs[2]), static_cast<double*>(bufs[3]));
-            e = hipGetLastError();
-        }
-        void* dst[3] = {value, x, y};
-        for (int i = 0; i < 3 && e == hipSuccess; ++i) if (dst[i]) e = hipMemcpyAsync(dst[i], bufs[i + 1], sizes[i + 1], hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(h, SOCCER_E_HIP, "soccer_solve_matrix_games failed: %s", hipGetErrorString(e));
+    OwnedBufs tmp("the matrix games");                                  // freed on every way out
+    double* d_A = nullptr; double* d_out[3] = {nullptr, nullptr, nullptr};            // value, x, y
+    const size_t doubles[3] = {n, n * 5, n * 5};
+    int rc = tmp.alloc(h, n * 25, &d_A);
+    for (int i = 0; i < 3 && !rc; ++i) rc = tmp.alloc(h, doubles[i], &d_out[i]);
+    if (rc) return rc;
+    hipError_t e = hipMemcpyAsync(d_A, A, n * 200, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        const unsigned grid = (unsigned)((n + kGamesBlock - 1) / kGamesBlock);
+        hipLaunchKernelGGL(games_kernel, dim3(grid), dim3(kGamesBlock), 0, h->stream, static_cast<const double*>(d_A), (long long)n,
+                           d_out[0], d_out[1], d_out[2]);
+        e = hipGetLastError();
     }
-    for (void* b : bufs) if (b) (void)hipFree(b);
-    return rc;
+    double* dst[3] = {value, x, y};
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) if (dst[i]) e = hipMemcpyAsync(dst[i], d_out[i], doubles[i] * 8, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return fail(h, SOCCER_E_HIP, "soccer_solve_matrix_games failed: %s", hipGetErrorString(e));
+    return SOCCER_OK;
 }
 
 extern "C" int soccer_minimax_backup(soccer_handle* h, double discount_factor, const double* V, double* V_out, double* Q,

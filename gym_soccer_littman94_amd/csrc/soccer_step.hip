@@ -13,11 +13,11 @@ static inline uint32_t* worklist_count(const soccer_handle* h) { return h->d_wor
 static bool ensure_worklist(soccer_handle* h) {
     if (h->d_worklist) return true;
     const size_t words = worklist_count_word(h) + 2 + 4;
-    if (hipMalloc(reinterpret_cast<void**>(&h->d_worklist), words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); h->d_worklist = nullptr; return false; }
+    if (h->bufs.alloc(h, words, &h->d_worklist) != SOCCER_OK) { (void)hipGetLastError(); return false; }     // (no error: the per-lane kernel then)
     // (on the handle's own stream: a memset on the null stream is not ordered with a non-blocking stream's kernels)
     if (hipMemsetAsync(h->d_worklist, 0, words * sizeof(uint32_t), h->stream) != hipSuccess) {
         // without a cleared count the list must not be used: give it back, a later call tries again
-        (void)hipGetLastError(); (void)hipFree(h->d_worklist); h->d_worklist = nullptr; return false;
+        (void)hipGetLastError(); h->bufs.release(h->d_worklist); h->d_worklist = nullptr; return false;
     }
     return true;
 }
@@ -82,8 +82,8 @@ static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& i
     } else if (explicit_u) {    // caller-supplied uniforms (facade, tests) and fixed-policy handles beyond the byte arithmetic: generic kernel
         if (vec && shared) launch_step3<true, true, true>(h, P, io); else launch_step3<true, false, false>(h, P, io);
     } else if (vec && shared) {
-        // the hot instantiations of the per-lane kernel (slip handles, pitches beyond the byte arithmetic);
-        // LEAN drops the code for prob_code / final_obs / last_return / step stats
+        // the per-lane kernels (slip handles, pitches beyond the byte arithmetic): step_kernel_hot has no code for
+        // prob_code / final_obs / last_return / the gym outputs / step stats, step_kernel writes them
         const bool lean = !io.prob_code && !io.final_obs && !io.last_return && !io.reward_a_f32 && !io.reward_b_f32 && !io.finished && !P.step_stats;
         const int grid = grid_for(h, (P.n + 3) / 4);
         const dim3 g(grid), b(kBlock);

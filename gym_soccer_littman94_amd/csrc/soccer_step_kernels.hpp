@@ -10,7 +10,7 @@ namespace soccer {
 // =================================================================================================
 // Each thread owns the 4 consecutive lanes [4g, 4g+4) and walks them in a ROLLED loop: the code of one
 // lane step exists once, so a launch — which starts with a cold instruction cache — fetches ~4x less
-// code than an unrolled body (measured: 12.8 -> 10.2 us per launch at 2^20 lanes, tools/labs/kernel_lab).
+// code than an unrolled body (measured: 12.8 -> 10.2 us per launch at 2^20 lanes).
 // Bytes are peeled off the packed input dwords by shifting and results are shifted into packed output
 // dwords with v_alignbyte, so no per-lane register arrays are needed.  The rule tables are read
 // straight from global memory (4.3 KB, L1/L2 resident): with 3 lookups per lane a per-workgroup LDS
@@ -42,26 +42,25 @@ __device__ __forceinline__ void store4h(uint16_t* base, unsigned long long i, in
 // EXPLICIT_U ("generic"): caller-supplied uniforms (u_step / u_reset) may replace the Philox draw, and
 //         a fixed-policy side (single-agent mode, reference :187-188) takes its action from
 //         policy[observation of the current tuple] instead of the action stream.
-// LEAN:   no prob_code / final_obs / last_return outputs and no step statistics: their code is compiled
-//         out (a launch fetches its code into a cold instruction cache: -0.6 us per launch).
-// The hot instantiation <SLIP=false, EXPLICIT_U=false, VEC=true, SHARED=true, LEAN=true> carries none
-// of the fallback code.
-template <bool SLIP, bool EXPLICIT_U, bool VEC, bool SHARED, int UNROLL = 1, int BLOCK = kBlock, bool LEAN = false>
-__global__ __launch_bounds__(BLOCK) void step_kernel(const KernelParams P, const StepIO IO) {
+// This is the general kernel, with every optional output and the step statistics: it takes what the specialised
+// kernels below do not — ragged tails, misaligned buffers, pitches beyond the byte arithmetic, and the exact
+// float64 walk of the work list (IO.worklist).
+template <bool SLIP, bool EXPLICIT_U, bool VEC, bool SHARED>
+__global__ __launch_bounds__(kBlock) void step_kernel(const KernelParams P, const StepIO IO) {
     const unsigned long long groups = (P.n + 3) >> 2;
-    const unsigned long long stride = (unsigned long long)gridDim.x * BLOCK;
+    const unsigned long long stride = (unsigned long long)gridDim.x * kBlock;
     const unsigned long long tick = *P.tick_in;                 // scalar load; published at the end so that its miss
                                                                 // does not sit in front of the first data loads
     // the episode histogram of single steps is opt-in (SOCCER_F_STEP_STATS): counting, the wave
     // reduction and the slot update cost ~0.5 us of a ~9 us launch
-    const bool stats = !LEAN && P.step_stats != 0u;
+    const bool stats = P.step_stats != 0u;
     HistAcc<true> hist; hist.fin = 0u; hist.pos = 0u; hist.neg = 0u; hist.old01 = make_ulonglong2(0ull, 0ull); hist.old2 = 0ull;
     if (stats) hist.init(P);
     Tables T; T.lut = P.lut; T.nc = P.next_cell; T.isd = P.isd;
     bool mis = false;
     uint32_t bad_act = 0u;
     const unsigned long long todo = IO.worklist ? (unsigned long long)*IO.work_count : groups;      // (one workgroup when listed)
-    for (unsigned long long k = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; k < todo; k += stride) {
+    for (unsigned long long k = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; k < todo; k += stride) {
         const unsigned long long g = IO.worklist ? (unsigned long long)IO.worklist[k] : k;
         const unsigned long long i0 = P.first + (g << 2);
         const int cnt = VEC ? 4 : ((P.n - (g << 2)) < 4ull ? (int)(P.n - (g << 2)) : 4);
@@ -81,7 +80,7 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(const KernelParams P, const
         if (SHARED && need_philox) blk = lane_block(P, (P.lane_offset + i0) >> 2, block_tick<SLIP>(tick), 0u);
         uint32_t nra = 0, nca = 0, nrb = 0, ncb = 0, nps = 0, ntt = 0;
         uint32_t o_rew = 0, o_term = 0, o_trunc = 0, o_code = 0, o_lo = 0, o_hi = 0, f_lo = 0, f_hi = 0, fin_mask = 0;
-#pragma unroll UNROLL
+#pragma unroll 1
         for (int j = 0; j < cnt; ++j) {
             uint32_t w = j & 2 ? (j & 1 ? blk.w[3] : blk.w[2]) : (j & 1 ? blk.w[1] : blk.w[0]);
             if (!SHARED && need_philox) {
@@ -120,10 +119,10 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(const KernelParams P, const
             nps = __builtin_amdgcn_alignbyte(L.p | (L.need << 1), nps, 1); ntt = __builtin_amdgcn_alignbyte(L.t, ntt, 1);
             o_rew = __builtin_amdgcn_alignbyte((uint32_t)R.reward & 0xffu, o_rew, 1);
             o_term = __builtin_amdgcn_alignbyte(R.term, o_term, 1); o_trunc = __builtin_amdgcn_alignbyte(R.trunc, o_trunc, 1);
-            if (!LEAN) o_code = __builtin_amdgcn_alignbyte(R.code, o_code, 1);
+            o_code = __builtin_amdgcn_alignbyte(R.code, o_code, 1);
             o_lo = __builtin_amdgcn_alignbit(o_hi, o_lo, 16); o_hi = (o_hi >> 16) | (R.obs << 16);
-            if (!LEAN) { f_lo = __builtin_amdgcn_alignbit(f_hi, f_lo, 16); f_hi = (f_hi >> 16) | (R.final_obs << 16); }
-            if (!LEAN) fin_mask |= R.finished << j;
+            f_lo = __builtin_amdgcn_alignbit(f_hi, f_lo, 16); f_hi = (f_hi >> 16) | (R.final_obs << 16);
+            fin_mask |= R.finished << j;
             if (stats) hist.add(R.finished, R.reward);
         }
         if (!VEC && cnt < 4) {               // ragged tail: the shifted-in bytes sit at the top
@@ -143,13 +142,13 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(const KernelParams P, const
         if (IO.reward) store4<VEC>(IO.reward, i0, cnt, o_rew);
         if (IO.terminated) store4<VEC>(IO.terminated, i0, cnt, o_term);
         if (IO.truncated) store4<VEC>(IO.truncated, i0, cnt, o_trunc);
-        if (!LEAN && IO.prob_code) store4<VEC>(IO.prob_code, i0, cnt, o_code);
-        if (!LEAN && IO.final_obs) store4h<VEC>(IO.final_obs, i0, cnt, f_lo, f_hi);
-        if (!LEAN && IO.last_return && fin_mask) {
+        if (IO.prob_code) store4<VEC>(IO.prob_code, i0, cnt, o_code);
+        if (IO.final_obs) store4h<VEC>(IO.final_obs, i0, cnt, f_lo, f_hi);
+        if (IO.last_return && fin_mask) {
             for (int j = 0; j < cnt; ++j)
                 if ((fin_mask >> j) & 1u) IO.last_return[i0 + j] = (int8_t)(o_rew >> (8 * j));
         }
-        if (!LEAN && (IO.reward_a_f32 || IO.reward_b_f32 || IO.finished)) {
+        if (IO.reward_a_f32 || IO.reward_b_f32 || IO.finished) {
             for (int j = 0; j < cnt; ++j) {
                 const float f = (float)(int8_t)(o_rew >> (8 * j));
                 if (IO.reward_a_f32) IO.reward_a_f32[i0 + j] = f;
@@ -176,33 +175,22 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(const KernelParams P, const
 // The instantiation every Philox-driven, dword-aligned, 4-outputs-only step takes (bench.py's path):
 // one group of 4 lanes per thread, no grid-stride loop, no fallback or optional-output code at all.
 // Same lane loop as step_kernel; kept separate because a launch starts with a cold instruction cache
-// and every instruction that is not fetched counts (-0.4 us per launch against step_kernel<..., LEAN>).
-template <bool SLIP, bool INT_ONLY = false, int UNROLL = 1>
+// and every instruction that is not fetched counts (-0.4 us per launch against a step_kernel instantiation with the optional outputs compiled out).
+template <bool SLIP, bool INT_ONLY = false>
 __device__ __forceinline__ void hot_group(const KernelParams& P, const StepIO& IO, unsigned long long g,
                                           const unsigned long long* tick_ptr, unsigned long long tick_val) {
     const unsigned long long i0 = P.first + (g << 2);
     Tables T; T.lut = P.lut; T.nc = P.next_cell; T.isd = P.isd;
     const uint8_t* sp = P.state;
-#ifndef SOCCER_TEMPORAL_STATE
 #define SOCCER_LD(p) __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p))
-#else
-#define SOCCER_LD(p) (*reinterpret_cast<const uint32_t*>(p))
-#endif
     const uint32_t ra = SOCCER_LD(sp + i0);
     const uint32_t ca = SOCCER_LD(sp + P.state_stride + i0);
     const uint32_t rb = SOCCER_LD(sp + 2 * P.state_stride + i0);
     const uint32_t cb = SOCCER_LD(sp + 3 * P.state_stride + i0);
     const uint32_t ps = SOCCER_LD(sp + 4 * P.state_stride + i0);
     const uint32_t tt = SOCCER_LD(sp + 5 * P.state_stride + i0);
+    uint32_t aa = SOCCER_LD(IO.act_a + i0), ab = SOCCER_LD(IO.act_b + i0);
 #undef SOCCER_LD
-    uint32_t aa = 0u, ab = 0u;
-#ifndef SOCCER_TEMPORAL_IO
-    aa = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(IO.act_a + i0));
-    ab = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(IO.act_b + i0));
-#else
-    aa = *reinterpret_cast<const uint32_t*>(IO.act_a + i0);
-    ab = *reinterpret_cast<const uint32_t*>(IO.act_b + i0);
-#endif
     // action bytes execute as table[byte & 7] with 5..7 -> NOOP; anything outside 0..4 is reported (:393)
     const uint32_t aa_raw = aa, ab_raw = ab;
     aa = swar::canon4(aa); ab = swar::canon4(ab);
@@ -213,9 +201,9 @@ __device__ __forceinline__ void hot_group(const KernelParams& P, const StepIO& I
     // the thread's 4 lanes are exactly one Philox block; computed while the loads are in flight
     const Philox4 blk = lane_block(P, (P.lane_offset + i0) >> 2, block_tick<SLIP>(tick), 0u);
     uint32_t nra = 0, nca = 0, nrb = 0, ncb = 0, nps = 0, ntt = 0, o_rew = 0, o_term = 0, o_trunc = 0, o_lo = 0, o_hi = 0;
-    uint32_t posA[4] = {0u, 0u, 0u, 0u}, posB[4] = {0u, 0u, 0u, 0u};   // UNROLL == 4 only
+    uint32_t posA[4] = {0u, 0u, 0u, 0u}, posB[4] = {0u, 0u, 0u, 0u};
     bool mis = false;
-#pragma unroll UNROLL
+#pragma unroll 4
     for (int j = 0; j < 4; ++j) {
         const uint32_t w = j & 2 ? (j & 1 ? blk.w[3] : blk.w[2]) : (j & 1 ? blk.w[1] : blk.w[0]);
         const uint32_t sh = 8u * (uint32_t)j;
@@ -227,51 +215,34 @@ __device__ __forceinline__ void hot_group(const KernelParams& P, const StepIO& I
         StepResult R;
         const uint32_t a_now = __builtin_amdgcn_ubfe(aa, sh, 8u), b_now = __builtin_amdgcn_ubfe(ab, sh, 8u);
         mis |= lane_step<SLIP, true, INT_ONLY>(T, P, L, a_now, b_now, draw_from_word<SLIP>(w, tick), R);
-        if constexpr (UNROLL == 4) { posA[j] = L.A; posB[j] = L.B; }    // rows / columns gathered with v_perm after the loop
-        else {
-            nra = __builtin_amdgcn_alignbyte(L.A >> 24, nra, 1); nca = __builtin_amdgcn_alignbyte((L.A >> 16) & 0xffu, nca, 1);
-            nrb = __builtin_amdgcn_alignbyte(L.B >> 24, nrb, 1); ncb = __builtin_amdgcn_alignbyte((L.B >> 16) & 0xffu, ncb, 1);
-        }
+        posA[j] = L.A; posB[j] = L.B;                                   // rows / columns gathered with v_perm after the loop
         nps = __builtin_amdgcn_alignbyte(L.p | (L.need << 1), nps, 1); ntt = __builtin_amdgcn_alignbyte(L.t, ntt, 1);
         o_rew = __builtin_amdgcn_alignbyte((uint32_t)R.reward & 0xffu, o_rew, 1);
         o_term = __builtin_amdgcn_alignbyte(R.term, o_term, 1); o_trunc = __builtin_amdgcn_alignbyte(R.trunc, o_trunc, 1);
         o_lo = __builtin_amdgcn_alignbit(o_hi, o_lo, 16); o_hi = (o_hi >> 16) | (R.obs << 16);
     }
-    if constexpr (UNROLL == 4) {
-        // the row (byte 3) and column (byte 2) of four position words -> the packed row / column dwords: 4 byte
-        // permutes per player instead of a shift + funnel shift per lane and field (v_perm_b32 picks bytes 0-3 from
-        // its second operand, 4-7 from its first)
-        const uint32_t a01 = __builtin_amdgcn_perm(posA[1], posA[0], 0x07030602u), a23 = __builtin_amdgcn_perm(posA[3], posA[2], 0x07030602u);
-        const uint32_t b01 = __builtin_amdgcn_perm(posB[1], posB[0], 0x07030602u), b23 = __builtin_amdgcn_perm(posB[3], posB[2], 0x07030602u);
-        nca = __builtin_amdgcn_perm(a23, a01, 0x05040100u); nra = __builtin_amdgcn_perm(a23, a01, 0x07060302u);
-        ncb = __builtin_amdgcn_perm(b23, b01, 0x05040100u); nrb = __builtin_amdgcn_perm(b23, b01, 0x07060302u);
-    }
+    // the row (byte 3) and column (byte 2) of four position words -> the packed row / column dwords: 4 byte
+    // permutes per player instead of a shift + funnel shift per lane and field (v_perm_b32 picks bytes 0-3 from
+    // its second operand, 4-7 from its first)
+    const uint32_t a01 = __builtin_amdgcn_perm(posA[1], posA[0], 0x07030602u), a23 = __builtin_amdgcn_perm(posA[3], posA[2], 0x07030602u);
+    const uint32_t b01 = __builtin_amdgcn_perm(posB[1], posB[0], 0x07030602u), b23 = __builtin_amdgcn_perm(posB[3], posB[2], 0x07030602u);
+    nca = __builtin_amdgcn_perm(a23, a01, 0x05040100u); nra = __builtin_amdgcn_perm(a23, a01, 0x07060302u);
+    ncb = __builtin_amdgcn_perm(b23, b01, 0x05040100u); nrb = __builtin_amdgcn_perm(b23, b01, 0x07060302u);
     uint8_t* sw = P.state;
     // the state is re-read by the NEXT launch only, i.e. after the kernel-boundary write-back / invalidate of L2:
     // streaming it as well is worth another ~1 % (6.91 -> 6.83 us)
-#ifndef SOCCER_TEMPORAL_STATE
 #define SOCCER_ST(p, v) __builtin_nontemporal_store((v), reinterpret_cast<uint32_t*>(p))
-#else
-#define SOCCER_ST(p, v) (*reinterpret_cast<uint32_t*>(p) = (v))
-#endif
     SOCCER_ST(sw + i0, nra); SOCCER_ST(sw + P.state_stride + i0, nca);
     SOCCER_ST(sw + 2 * P.state_stride + i0, nrb); SOCCER_ST(sw + 3 * P.state_stride + i0, ncb);
     SOCCER_ST(sw + 4 * P.state_stride + i0, nps); SOCCER_ST(sw + 5 * P.state_stride + i0, ntt);
-#undef SOCCER_ST
     // Results are written once and never re-read by these kernels, actions are read once: non-temporal accesses
     // keep them from displacing the resident state in L2 / Infinity Cache (7.66 -> 6.97 us per launch).
-#ifndef SOCCER_TEMPORAL_IO
     if (IO.obs) __builtin_nontemporal_store((unsigned long long)o_lo | ((unsigned long long)o_hi << 32),
                                             reinterpret_cast<unsigned long long*>(IO.obs + i0));
-    if (IO.reward) __builtin_nontemporal_store(o_rew, reinterpret_cast<uint32_t*>(IO.reward + i0));
-    if (IO.terminated) __builtin_nontemporal_store(o_term, reinterpret_cast<uint32_t*>(IO.terminated + i0));
-    if (IO.truncated) __builtin_nontemporal_store(o_trunc, reinterpret_cast<uint32_t*>(IO.truncated + i0));
-#else
-    if (IO.obs) *reinterpret_cast<uint2*>(IO.obs + i0) = make_uint2(o_lo, o_hi);
-    if (IO.reward) *reinterpret_cast<uint32_t*>(IO.reward + i0) = o_rew;
-    if (IO.terminated) *reinterpret_cast<uint32_t*>(IO.terminated + i0) = o_term;
-    if (IO.truncated) *reinterpret_cast<uint32_t*>(IO.truncated + i0) = o_trunc;
-#endif
+    if (IO.reward) SOCCER_ST(IO.reward + i0, o_rew);
+    if (IO.terminated) SOCCER_ST(IO.terminated + i0, o_term);
+    if (IO.truncated) SOCCER_ST(IO.truncated + i0, o_trunc);
+#undef SOCCER_ST
     if (mis) P.misuse[0] = 1u;
     if ((aa ^ aa_raw) | (ab ^ ab_raw)) P.misuse[1] = 1u;
 }
@@ -280,7 +251,7 @@ __device__ __forceinline__ void hot_group(const KernelParams& P, const StepIO& I
 // (the hot path always starts at lane 0 of the handle):
 // the library is built with -mllvm -amdgpu-kernarg-preload-count=14, so they arrive in SGPRs at wave launch
 // and the nine data loads are issued without first waiting for a scalar load of the kernarg segment
-// (-0.3 .. -0.6 us per launch, tools/labs/pipeline_lab.hip); the rest of P is fetched while they are in flight.
+// (-0.3 .. -0.6 us per launch); the rest of P is fetched while they are in flight.
 template <bool SLIP, bool INT_ONLY = false>
 __global__ __launch_bounds__(kBlock) void step_kernel_hot(uint8_t* state, unsigned long long state_stride,
                                                           const int8_t* act_a, const int8_t* act_b,
@@ -293,7 +264,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel_hot(uint8_t* state, unsign
     if ((g << 2) >= n) return;                                      // n is a multiple of 4 here; the first lane is 0
     KernelParams Q = P; Q.state = state; Q.state_stride = state_stride; Q.n = n; Q.first = 0ull;
     StepIO J = IO; J.act_a = act_a; J.act_b = act_b;
-    hot_group<SLIP, INT_ONLY, SLIP ? SOCCER_HOT_UNROLL_SLIP : SOCCER_HOT_UNROLL>(Q, J, g, tick_in, tick_val);
+    hot_group<SLIP, INT_ONLY>(Q, J, g, tick_in, tick_val);
 }
 
 // =================================================================================================
@@ -304,8 +275,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel_hot(uint8_t* state, unsign
 // arguments preloaded into SGPRs) — but no byte peeling, no per-lane loop and NO rule-table read: ~45 vector
 // instructions per env-step instead of ~128 and no dependent gather between the loads and the stores.
 // Takes every Philox-driven, dword-aligned step of a slip_prob == 0 handle whose pitch fits the byte arithmetic
-// (swar::fits: every golden pitch up to 11x7 does).  GENERAL = false is the steady state of an auto-resetting
-// handle (no frozen lane, no lane in a goal tuple); FULL adds final_obs and prob_code (VectorSoccerEnv).
+// (swar::fits: every golden pitch up to 11x7 does); the template parameters are described above the kernel.
 struct SwarParams {
     swar::Consts C;
     uint32_t key0, key1;
