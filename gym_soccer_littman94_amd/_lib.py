@@ -87,6 +87,7 @@ PROTOTYPES = {
     "batched_reset_staged": (C.c_int, [C.c_void_p, C.c_uint32]),
     "soccer_set_policy": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "soccer_host_view": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
+    "soccer_state_streams": (C.c_int, [C.c_void_p]),
     "soccer_set_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 7),
     "soccer_get_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 7),
     "soccer_dims": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int32)] * 4),

@@ -461,6 +461,10 @@ class SoccerBatch:
         buf = (C.c_uint8 * (6 * stride.value)).from_address(p.value)
         return np.frombuffer(buf, dtype=np.uint8).reshape(6, stride.value)[:, :self.n]
 
+    def state_streams(self):
+        """3 when the handle keeps its resident state packed in three byte streams, 6 otherwise (results are the same)."""
+        return int(self.lib.soccer_state_streams(self.h))
+
     # -- state injection / readback -----------------------------------------------------------
     def set_state(self, row_a=None, col_a=None, row_b=None, col_b=None, poss=None, t=None, needs_reset=None):
         def arr(x, dt):

@@ -34,10 +34,11 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const KernelParams P, con
 }
 
 // batched_reset, byte-parallel (Philox draws, dword-aligned streams, pitches that fit the byte arithmetic): four lanes per
-// thread, 6 dword stores + one 8-byte observation store; MASKED also reads the six state dwords and the mask dword.
+// thread, the state's dword stores (3 packed, 6 wide) + one 8-byte observation store; MASKED also reads the state dwords and
+// the mask dword.
 struct ResetSwar {
     swar::Consts C;
-    uint8_t* state; unsigned long long state_stride;
+    uint8_t* state; unsigned long long state_stride; uint32_t layout;      // StateLayout (wave-uniform branches below)
     unsigned long long n, lane_offset;
     const unsigned long long* tick_in; unsigned long long* tick_out;
     uint32_t key0, key1;
@@ -51,15 +52,22 @@ __global__ __launch_bounds__(kBlock) void reset_kernel_swar(const ResetSwar R) {
     uint8_t* sp = R.state + i0;
     swar::Group S{0u, 0u, 0u, 0u, 0u, 0u};
     uint32_t mask4 = 0u;
+    const bool packed = R.layout == kStatePacked;
     if (MASKED) {
+        if (packed) {
+            swar::unpack3(*reinterpret_cast<const uint32_t*>(sp), *reinterpret_cast<const uint32_t*>(sp + R.state_stride),
+                          *reinterpret_cast<const uint32_t*>(sp + 2 * R.state_stride), S);
+        } else {
         S.ra = *reinterpret_cast<const uint32_t*>(sp); S.ca = *reinterpret_cast<const uint32_t*>(sp + R.state_stride);
         S.rb = *reinterpret_cast<const uint32_t*>(sp + 2 * R.state_stride); S.cb = *reinterpret_cast<const uint32_t*>(sp + 3 * R.state_stride);
         S.ps = *reinterpret_cast<const uint32_t*>(sp + 4 * R.state_stride); S.tt = *reinterpret_cast<const uint32_t*>(sp + 5 * R.state_stride);
+        }
         mask4 = *reinterpret_cast<const uint32_t*>(R.mask + i0);
     }
     const unsigned long long tick = *R.tick_in;
     if (blockIdx.x == 0 && threadIdx.x == 0) *R.tick_out = tick + 1ull;
-    if (!MASKED) {      // what a reset of every lane writes without a draw — both columns, the timestep — leaves before the Philox block
+    if (!MASKED && packed) *reinterpret_cast<uint32_t*>(sp + 2 * R.state_stride) = 0u;      // the timestep needs no draw
+    if (!MASKED && !packed) {      // what a reset of every lane writes without a draw — both columns, the timestep — leaves before the Philox block
         *reinterpret_cast<uint32_t*>(sp + R.state_stride) = R.C.isd_ca4; *reinterpret_cast<uint32_t*>(sp + 3 * R.state_stride) = R.C.isd_cb4;
         *reinterpret_cast<uint32_t*>(sp + 5 * R.state_stride) = 0u;
     }
@@ -70,11 +78,18 @@ __global__ __launch_bounds__(kBlock) void reset_kernel_swar(const ResetSwar R) {
     const swar::Rand4 rnd = SLIP ? swar::rand_words(R.C.isd_shift, blk.w[0], blk.w[1], blk.w[2], blk.w[3])
                                  : swar::rand_nibble(R.C.isd_shift, (uint32_t)tick & 7u, blk.w[0], blk.w[1], blk.w[2], blk.w[3]);
     swar::reset4<MASKED>(R.C, S, mask4, rnd, o_lo, o_hi);
+    if (packed) {
+        uint32_t pa, pb, pt;
+        swar::pack3(S, pa, pb, pt);
+        *reinterpret_cast<uint32_t*>(sp) = pa; *reinterpret_cast<uint32_t*>(sp + R.state_stride) = pb;
+        if (MASKED) *reinterpret_cast<uint32_t*>(sp + 2 * R.state_stride) = pt;
+    } else {
     *reinterpret_cast<uint32_t*>(sp) = S.ra; *reinterpret_cast<uint32_t*>(sp + 2 * R.state_stride) = S.rb;
     *reinterpret_cast<uint32_t*>(sp + 4 * R.state_stride) = S.ps;
     if (MASKED) {
         *reinterpret_cast<uint32_t*>(sp + R.state_stride) = S.ca; *reinterpret_cast<uint32_t*>(sp + 3 * R.state_stride) = S.cb;
         *reinterpret_cast<uint32_t*>(sp + 5 * R.state_stride) = S.tt;
+    }
     }
     if (R.obs) *reinterpret_cast<uint2*>(R.obs + i0) = make_uint2(o_lo, o_hi);
 }
@@ -121,10 +136,7 @@ __global__ __launch_bounds__(64) void scalar_kernel(const KernelParams P, const 
         const Draw d{SLIP ? sane_uniform_walk(IO.u_step) : u, (uint32_t)(u * 4.0), (uint32_t)(sane_uniform(IO.u_reset) * 4.0), 0u};
         (void)lane_step<SLIP>(T, P, L, a_now, b_now, d, R);
     }
-    uint8_t* sw = P.state;
-    sw[0] = (uint8_t)(L.A >> 24); sw[P.state_stride] = (uint8_t)(L.A >> 16);
-    sw[2 * P.state_stride] = (uint8_t)(L.B >> 24); sw[3 * P.state_stride] = (uint8_t)(L.B >> 16);
-    sw[4 * P.state_stride] = (uint8_t)(L.p | (L.need << 1)); sw[5 * P.state_stride] = (uint8_t)L.t;
+    { LaneVec<1> S; S.L[0] = L; S.store(P, 0ull); }             // the handle's one lane, in its layout
     const uint32_t res = R.obs | (((uint32_t)R.reward & 0xffu) << 16) | (R.term << 24) | (R.trunc << 25) | (R.code << 26);
     const uint32_t npos = (L.A >> 24) | (((L.A >> 16) & 0xffu) << 8) | ((L.B >> 24) << 16) | (((L.B >> 16) & 0xffu) << 24);
     __threadfence_system();                 // the resident state before the record

@@ -118,8 +118,9 @@ struct soccer_handle {
     unsigned int* d_misuse = nullptr;       // device alias of misuse_host
     unsigned int* misuse_host = nullptr;    // pinned + mapped: kernels store to it only when a frozen lane is stepped (rare),
                                             // the host reads it without a copy
-    uint8_t* d_state = nullptr;             // one allocation holding the six SoA streams back to back
+    uint8_t* d_state = nullptr;             // one allocation holding the SoA state streams back to back
     size_t state_stride = 0;                // bytes between consecutive streams
+    int state_streams = 6;                  // 3: the packed layout (KernelParams::state_layout == kStatePacked), 6: wide
     uint8_t* stage_dev = nullptr;           // staging for the host-pointer entry points
     uint8_t* stage_host = nullptr;          // pinned
     bool mapped = false;                    // SOCCER_F_HOST_MAPPED: d_state and the staging block are pinned host memory

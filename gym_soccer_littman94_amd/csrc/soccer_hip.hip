@@ -97,20 +97,27 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
     h->state_stride = padded;
     h->mapped = (cfg->flags & SOCCER_F_HOST_MAPPED) != 0;
     if (h->mapped && n > 4096) return fail(nullptr, SOCCER_E_INVALID, "SOCCER_F_HOST_MAPPED is for small handles (n_lanes <= 4096)");
-    if (int rc = h->mapped ? h->bufs.alloc_pinned(nullptr, 6 * padded, OwnedBufs::kPinnedMapped, &h->d_state)
-                           : h->bufs.alloc(nullptr, 6 * padded, &h->d_state)) return rc;
-    P.state = h->d_state; P.state_stride = padded;
+    // three packed streams (swar::pack3) where rows fit three bits and columns four; host-mapped handles keep the six that
+    // soccer_host_view hands out, and SOCCER_STATE_LAYOUT=wide forces them (tests and A/B runs of the other layout)
+    const char* lay = std::getenv("SOCCER_STATE_LAYOUT");
+    const bool packed = swar::packs(R.H, R.W) && !h->mapped && !(lay && std::strcmp(lay, "wide") == 0);
+    h->state_streams = packed ? 3 : 6;
+    const size_t state_bytes = (size_t)h->state_streams * padded;
+    if (int rc = h->mapped ? h->bufs.alloc_pinned(nullptr, state_bytes, OwnedBufs::kPinnedMapped, &h->d_state)
+                           : h->bufs.alloc(nullptr, state_bytes, &h->d_state)) return rc;
+    P.state = h->d_state; P.state_stride = padded; P.state_layout = packed ? kStatePacked : kStateWide;
     // every lane starts needing a reset (:140), parked on the first ISD state so the tuple is valid
-    if (h->mapped) {
-        const uint8_t init[6] = {(uint8_t)R.isd[0][0], (uint8_t)R.isd[0][1], (uint8_t)R.isd[0][2], (uint8_t)R.isd[0][3], (uint8_t)(2 | R.isd[0][4]), 0};
-        for (int k = 0; k < 6; ++k) std::memset(h->d_state + k * padded, init[k], padded);
-    } else {
-    HIP_TRY(nullptr, hipMemsetAsync(h->d_state, R.isd[0][0], padded, h->stream));
-    HIP_TRY(nullptr, hipMemsetAsync(h->d_state + padded, R.isd[0][1], padded, h->stream));
-    HIP_TRY(nullptr, hipMemsetAsync(h->d_state + 2 * padded, R.isd[0][2], padded, h->stream));
-    HIP_TRY(nullptr, hipMemsetAsync(h->d_state + 3 * padded, R.isd[0][3], padded, h->stream));
-    HIP_TRY(nullptr, hipMemsetAsync(h->d_state + 4 * padded, 2 | R.isd[0][4], padded, h->stream));
-    HIP_TRY(nullptr, hipMemsetAsync(h->d_state + 5 * padded, 0, padded, h->stream));
+    {
+        uint8_t init[6] = {(uint8_t)R.isd[0][0], (uint8_t)R.isd[0][1], (uint8_t)R.isd[0][2], (uint8_t)R.isd[0][3], (uint8_t)(2 | R.isd[0][4]), 0};
+        if (packed) {
+            uint32_t a, b, t;
+            swar::pack3(swar::Group{init[0], init[1], init[2], init[3], init[4], init[5]}, a, b, t);
+            init[0] = (uint8_t)a; init[1] = (uint8_t)b; init[2] = (uint8_t)t;
+        }
+        for (int k = 0; k < h->state_streams; ++k) {
+            if (h->mapped) std::memset(h->d_state + k * padded, init[k], padded);
+            else HIP_TRY(nullptr, hipMemsetAsync(h->d_state + k * padded, init[k], padded, h->stream));
+        }
     }
 
     if (int rc = h->bufs.alloc(nullptr, R.next_cell.size(), &h->d_nc)) return rc;
@@ -271,7 +278,7 @@ extern "C" int batched_reset(soccer_handle* h, const uint8_t* mask, const double
     unsigned long long n4 = 0;
     if (h->swar_ok && !u_reset && h->E != 1 && (P.lane_offset & 3ull) == 0ull && aligned(mask, 4) && aligned(obs, 8)) n4 = P.n & ~3ull;
     if (n4) {
-        ResetSwar RS{h->swar_c, P.state, P.state_stride, n4, P.lane_offset, P.tick_in, P.tick_out, P.key0, P.key1, mask, obs};
+        ResetSwar RS{h->swar_c, P.state, P.state_stride, P.state_layout, n4, P.lane_offset, P.tick_in, P.tick_out, P.key0, P.key1, mask, obs};
         const dim3 g(static_cast<unsigned>(((n4 >> 2) + kBlock - 1) / kBlock)), b(kBlock);
         if (h->slip) { if (mask) hipLaunchKernelGGL((reset_kernel_swar<true, true>), g, b, 0, h->stream, RS);
                        else hipLaunchKernelGGL((reset_kernel_swar<false, true>), g, b, 0, h->stream, RS); }
@@ -293,6 +300,25 @@ extern "C" int batched_reset(soccer_handle* h, const uint8_t* mask, const double
 }
 
 // ------------------------------------------------------------------------------------------------
+// the handle's state as six host streams of stride state_stride, whatever its layout (`img` holds 6 * state_stride bytes): one
+// copy, then the packed streams are taken apart in place (a lane's three bytes are read before any of its six is written)
+static int fetch_state(soccer_handle* h, std::vector<uint8_t>& img) {
+    const size_t n = h->P.n, S = h->state_stride, bytes = (size_t)h->state_streams * S;
+    if (h->mapped) std::memcpy(img.data(), h->d_state, bytes);
+    else HIP_TRY(h, hipMemcpy(img.data(), h->d_state, bytes, hipMemcpyDeviceToHost));
+    if (h->state_streams == 3) {
+        for (size_t i = 0; i < n; ++i) {
+            swar::Group G;
+            swar::unpack3(img[i], img[S + i], img[2 * S + i], G);
+            img[5 * S + i] = (uint8_t)G.tt; img[4 * S + i] = (uint8_t)G.ps; img[3 * S + i] = (uint8_t)G.cb;
+            img[2 * S + i] = (uint8_t)G.rb; img[S + i] = (uint8_t)G.ca; img[i] = (uint8_t)G.ra;
+        }
+    }
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_state_streams(const soccer_handle* h) { return h ? h->state_streams : 0; }
+
 extern "C" int soccer_set_state(soccer_handle* h, const int8_t* row_a, const int8_t* col_a, const int8_t* row_b,
                                 const int8_t* col_b, const uint8_t* poss, const uint8_t* t,
                                 const uint8_t* needs_reset) {
@@ -304,8 +330,7 @@ extern "C" int soccer_set_state(soccer_handle* h, const int8_t* row_a, const int
     const Rules& R = h->rules;
     // current device copy of whatever is not supplied, so the resulting tuple can be validated
     std::vector<uint8_t> img(6 * S);
-    if (h->mapped) std::memcpy(img.data(), h->d_state, 6 * S);
-    else HIP_TRY(h, hipMemcpy(img.data(), h->d_state, 6 * S, hipMemcpyDeviceToHost));
+    if (int rc = fetch_state(h, img)) return rc;
     int8_t* ra = reinterpret_cast<int8_t*>(img.data());
     int8_t* ca = ra + S; int8_t* rb = ra + 2 * S; int8_t* cb = ra + 3 * S;
     uint8_t* ps = img.data() + 4 * S; uint8_t* tt = img.data() + 5 * S;
@@ -326,8 +351,16 @@ extern "C" int soccer_set_state(soccer_handle* h, const int8_t* row_a, const int
             return fail(h, SOCCER_E_INVALID, "lane %zu: state (%d, %d, %d, %d, %d) is not a reachable state tuple",
                         i, (int)ra[i], (int)ca[i], (int)rb[i], (int)cb[i], (int)p);
     }
-    if (h->mapped) std::memcpy(h->d_state, img.data(), 6 * S);
-    else HIP_TRY(h, hipMemcpy(h->d_state, img.data(), 6 * S, hipMemcpyHostToDevice));
+    if (h->state_streams == 3) {                    // validated above: rows < H <= 8, columns < W <= 16
+        for (size_t i = 0; i < n; ++i) {
+            uint32_t a, b, t_;
+            swar::pack3(swar::Group{(uint8_t)ra[i], (uint8_t)ca[i], (uint8_t)rb[i], (uint8_t)cb[i], ps[i], tt[i]}, a, b, t_);
+            img[i] = (uint8_t)a; img[S + i] = (uint8_t)b; img[2 * S + i] = (uint8_t)t_;
+        }
+    }
+    const size_t bytes = (size_t)h->state_streams * S;
+    if (h->mapped) std::memcpy(h->d_state, img.data(), bytes);
+    else HIP_TRY(h, hipMemcpy(h->d_state, img.data(), bytes, hipMemcpyHostToDevice));
     return SOCCER_OK;
 }
 
@@ -346,8 +379,7 @@ extern "C" int soccer_get_state(soccer_handle* h, int8_t* row_a, int8_t* col_a, 
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     const size_t n = h->P.n, S = h->state_stride;
     std::vector<uint8_t> img(6 * S);
-    if (h->mapped) std::memcpy(img.data(), h->d_state, 6 * S);
-    else HIP_TRY(h, hipMemcpy(img.data(), h->d_state, 6 * S, hipMemcpyDeviceToHost));
+    if (int rc = fetch_state(h, img)) return rc;
     if (row_a) std::memcpy(row_a, img.data(), n);
     if (col_a) std::memcpy(col_a, img.data() + S, n);
     if (row_b) std::memcpy(row_b, img.data() + 2 * S, n);

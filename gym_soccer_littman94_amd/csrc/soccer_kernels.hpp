@@ -41,11 +41,17 @@ constexpr int kHistSlots = 16384;        // minimum: >= waves of the largest CAP
 constexpr int kHistStride = 4;           // u64 per slot: return -1, 0, +1, pad
 constexpr int kIsdWords = 16;            // LDS: 4 ISD entries x (A, B, poss|obs<<16, pad)
 
+// How a handle keeps its resident state (soccer_state_streams): six byte streams, or the three of swar::pack3 (handles
+// whose pitch packs and that are not host-mapped).  Every kernel that touches the state speaks both.
+enum StateLayout : uint32_t { kStateWide = 0u, kStatePacked = 1u };
+
 struct KernelParams {
-    // resident state: six byte streams back to back, `state_stride` bytes apart, in the order
-    // row_a, col_a, row_b, col_b, poss (bit0 possession, bit1 needs_reset), t
+    // resident state: byte streams back to back, `state_stride` bytes apart.  kStateWide: six, in the order
+    // row_a, col_a, row_b, col_b, poss (bit0 possession, bit1 needs_reset), t; kStatePacked: three,
+    // poss << 7 | row_a << 4 | col_a, needs_reset << 7 | row_b << 4 | col_b, t
     uint8_t* state;
     unsigned long long state_stride;
+    uint32_t state_layout;                // StateLayout
     // rule tables in global memory (staged to LDS)
     const uint16_t* lut;                  // [lut_len] observation index per state tuple
     const uint32_t* next_cell;            // [2][H*W][5]: (has_ball, cell, move) -> (row<<8|col)<<16 | (row*W+col) reached
@@ -544,6 +550,19 @@ struct RawState {
     PackB<E> ra, ca, rb, cb, ps, tt;
     __device__ __forceinline__ void load(const KernelParams& P, unsigned long long i) {
         const uint8_t* s = P.state;
+        if (P.state_layout == kStatePacked) {                       // wave-uniform
+            PackB<E> a, b;
+            a.load(s, i); b.load(s + P.state_stride, i); tt.load(s + 2 * P.state_stride, i);
+            if constexpr (E == 1) { swar::Group G; swar::unpack3(a.b, b.b, tt.b, G); ra.b = G.ra; ca.b = G.ca; rb.b = G.rb; cb.b = G.cb; ps.b = G.ps; }
+            else {
+#pragma unroll
+                for (int k = 0; k < PackB<E>::NW; ++k) {
+                    swar::Group G; swar::unpack3(a.w[k], b.w[k], tt.w[k], G);
+                    ra.w[k] = G.ra; ca.w[k] = G.ca; rb.w[k] = G.rb; cb.w[k] = G.cb; ps.w[k] = G.ps;
+                }
+            }
+            return;
+        }
         ra.load(s, i); ca.load(s + P.state_stride, i); rb.load(s + 2 * P.state_stride, i);
         cb.load(s + 3 * P.state_stride, i); ps.load(s + 4 * P.state_stride, i); tt.load(s + 5 * P.state_stride, i);
     }
@@ -574,6 +593,16 @@ struct LaneVec {
             ps.put(j, L[j].p | (L[j].need << 1)); tt.put(j, L[j].t);
         }
         uint8_t* s = P.state;
+        if (P.state_layout == kStatePacked) {                       // wave-uniform
+            PackB<E> a, b;
+            if constexpr (E == 1) { uint32_t t_; swar::pack3(swar::Group{ra.b, ca.b, rb.b, cb.b, ps.b, tt.b}, a.b, b.b, t_); }
+            else {
+#pragma unroll
+                for (int k = 0; k < PackB<E>::NW; ++k) { uint32_t t_; swar::pack3(swar::Group{ra.w[k], ca.w[k], rb.w[k], cb.w[k], ps.w[k], tt.w[k]}, a.w[k], b.w[k], t_); }
+            }
+            a.store(s, i); b.store(s + P.state_stride, i); tt.store(s + 2 * P.state_stride, i);
+            return;
+        }
         ra.store(s, i); ca.store(s + P.state_stride, i); rb.store(s + 2 * P.state_stride, i);
         cb.store(s + 3 * P.state_stride, i); ps.store(s + 4 * P.state_stride, i); tt.store(s + 5 * P.state_stride, i);
     }

@@ -94,7 +94,7 @@ extern "C" int batched_rollout_ex(soccer_handle* h, const soccer_rollout_args* a
         if (swar_roll) {
             P.n = n4;
             const bool dyn = io.sample_actions || P.policy_a || P.policy_b;
-            RolloutSwar RS{P.state, P.state_stride, P.first, P.n, P.lane_offset, P.tick_in, P.tick_out, P.hist, P.misuse,
+            RolloutSwar RS{P.state, P.state_stride, P.state_layout, P.first, P.n, P.lane_offset, P.tick_in, P.tick_out, P.hist, P.misuse,
                            P.policy_a, P.policy_b, P.key0, P.key1,
                            h->swar_c, h->slip_c, reinterpret_cast<const swar::Quad*>(P.sub), P.hist_mask, R0.nS, 0, 0u, 0u, h->d_slip_lut};
             const int sm = !h->slip ? 0 : (h->d_slip_lut ? 2 : 1);    // slip selection: none / threshold by threshold / by table

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(const KernelParams P, c
 //        or looked up from a fixed int8[nS] policy (single-agent mode); these are per-lane gathers keyed by the lane's
 //        current observation, which the step already produces.  The tables sit in LDS when they fit (`lds_tables`).
 struct RolloutSwar {       // everything the kernel needs, and nothing else (KernelParams is twice this: SGPR spills)
-    uint8_t* state; unsigned long long state_stride;
+    uint8_t* state; unsigned long long state_stride; uint32_t layout;      // StateLayout: read once on entry, written once on exit
     unsigned long long first, n, lane_offset;
     const unsigned long long* tick_in; unsigned long long* tick_out;
     unsigned long long* hist; unsigned int* misuse;
@@ -413,9 +413,14 @@ __global__ __launch_bounds__(kBlock) void rollout_swar_kernel(const RolloutSwar 
         const uint32_t i0 = (uint32_t)R.first + ((uint32_t)g << 2);
         const uint8_t* sp = R.state + i0;
         swar::Group S;
+        if (R.layout == kStatePacked) {
+            swar::unpack3(*reinterpret_cast<const uint32_t*>(sp), *reinterpret_cast<const uint32_t*>(sp + R.state_stride),
+                          *reinterpret_cast<const uint32_t*>(sp + 2 * R.state_stride), S);
+        } else {
         S.ra = *reinterpret_cast<const uint32_t*>(sp); S.ca = *reinterpret_cast<const uint32_t*>(sp + R.state_stride);
         S.rb = *reinterpret_cast<const uint32_t*>(sp + 2 * R.state_stride); S.cb = *reinterpret_cast<const uint32_t*>(sp + 3 * R.state_stride);
         S.ps = *reinterpret_cast<const uint32_t*>(sp + 4 * R.state_stride); S.tt = *reinterpret_cast<const uint32_t*>(sp + 5 * R.state_stride);
+        }
         uint32_t fin_tot = 0u, nz_tot = 0u, neg_tot = 0u;
         uint32_t acc[4] = {0u, 0u, 0u, 0u};     // per lane: int16 return (two pairs), uint16 finished episodes (two pairs); T <= 4096
         // any lane frozen, any player in a goal column (= a goal tuple), or no auto-reset: the general step
@@ -424,9 +429,15 @@ __global__ __launch_bounds__(kBlock) void rollout_swar_kernel(const RolloutSwar 
         if (special) rollout_swar_group<DYNM, SLIPM, true, GEO, FULL>(R, IO, slip, mix_a, mix_b, pol_a, pol_b, act_lds, i0, tick0, S, fin_tot, nz_tot, neg_tot, acc, frozen_any, bad_any);
         else rollout_swar_group<DYNM, SLIPM, false, GEO, FULL>(R, IO, slip, mix_a, mix_b, pol_a, pol_b, act_lds, i0, tick0, S, fin_tot, nz_tot, neg_tot, acc, frozen_any, bad_any);
         uint8_t* sw = R.state + i0;
+        if (R.layout == kStatePacked) {
+            uint32_t pa, pb, pt;
+            swar::pack3(S, pa, pb, pt);
+            *reinterpret_cast<uint32_t*>(sw) = pa; *reinterpret_cast<uint32_t*>(sw + R.state_stride) = pb; *reinterpret_cast<uint32_t*>(sw + 2 * R.state_stride) = pt;
+        } else {
         *reinterpret_cast<uint32_t*>(sw) = S.ra; *reinterpret_cast<uint32_t*>(sw + R.state_stride) = S.ca;
         *reinterpret_cast<uint32_t*>(sw + 2 * R.state_stride) = S.rb; *reinterpret_cast<uint32_t*>(sw + 3 * R.state_stride) = S.cb;
         *reinterpret_cast<uint32_t*>(sw + 4 * R.state_stride) = S.ps; *reinterpret_cast<uint32_t*>(sw + 5 * R.state_stride) = S.tt;
+        }
         hist.add_totals(fin_tot, (int32_t)nz_tot - 2 * (int32_t)neg_tot, nz_tot);
         if (IO.return_sum != nullptr || IO.episode_count != nullptr) {
             int32_t ret[4] = {(int32_t)(int16_t)(acc[0] & 0xffffu), (int32_t)(int16_t)(acc[0] >> 16), (int32_t)(int16_t)(acc[1] & 0xffffu), (int32_t)(int16_t)(acc[1] >> 16)};

@@ -48,8 +48,11 @@ static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& i
                       : (io.reward_a_f32 || io.reward_b_f32 || io.finished || io.last_return) ? 1 : 0;
         const dim3 b(kBlock);
 #define SWAR_ARGS P.state + c0, P.state_stride, off(io.act_a, c0), off(io.act_b, c0), (h->capturing ? P.tick_in : nullptr), cn, (unsigned long long)(h->tick - 1), Q
-#define SWAR_GO(OV, SV, PV, XV) do { if (h->swar_c.small) hipLaunchKernelGGL((step_kernel_swar<OV, SV, PV, 1, XV>), gh, b, 0, h->stream, SWAR_ARGS); \
-                                     else hipLaunchKernelGGL((step_kernel_swar<OV, SV, PV, 0, XV>), gh, b, 0, h->stream, SWAR_ARGS); } while (0)
+        // six-stream handles that fit the byte arithmetic are host-mapped facade handles, tall pitches and SOCCER_STATE_LAYOUT=wide:
+        // nobody times them, so they take the arithmetic geometry (GEO = 0, right for every pitch) instead of mirroring every shape
+#define SWAR_GO(OV, SV, PV, XV) do { if (P.state_layout == kStateWide) hipLaunchKernelGGL((step_kernel_swar<OV, SV, PV, 0, XV, kStateWide>), gh, b, 0, h->stream, SWAR_ARGS); \
+                                     else if (h->swar_c.small) hipLaunchKernelGGL((step_kernel_swar<OV, SV, PV, 1, XV, kStatePacked>), gh, b, 0, h->stream, SWAR_ARGS); \
+                                     else hipLaunchKernelGGL((step_kernel_swar<OV, SV, PV, 0, XV, kStatePacked>), gh, b, 0, h->stream, SWAR_ARGS); } while (0)
 #define SWAR_SLIP(OV, PV) do { if (expl_slip) SWAR_GO(OV, 3, PV, true); else if (expl) SWAR_GO(OV, 0, PV, true); else if (!h->slip) SWAR_GO(OV, 0, PV, false); \
                                else if (h->d_slip_step_lut) SWAR_GO(OV, 2, PV, false); else SWAR_GO(OV, 1, PV, false); } while (0)
 #define SWAR_OUT(PV) do { if (out == 2) SWAR_SLIP(2, PV); else if (out == 1) SWAR_SLIP(1, PV); else SWAR_SLIP(0, PV); } while (0)

@@ -65,9 +65,17 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const KernelParams P, cons
         const unsigned long long i0 = P.first + (g << 2);
         const int cnt = VEC ? 4 : ((P.n - (g << 2)) < 4ull ? (int)(P.n - (g << 2)) : 4);
         const uint8_t* sp = P.state;
-        uint32_t ra = load4<VEC>(sp, i0, cnt), ca = load4<VEC>(sp + P.state_stride, i0, cnt);
-        uint32_t rb = load4<VEC>(sp + 2 * P.state_stride, i0, cnt), cb = load4<VEC>(sp + 3 * P.state_stride, i0, cnt);
-        uint32_t ps = load4<VEC>(sp + 4 * P.state_stride, i0, cnt), tt = load4<VEC>(sp + 5 * P.state_stride, i0, cnt);
+        const bool packed = P.state_layout == kStatePacked;        // wave-uniform
+        uint32_t ra, ca, rb, cb, ps, tt;
+        if (packed) {
+            swar::Group G;
+            swar::unpack3(load4<VEC>(sp, i0, cnt), load4<VEC>(sp + P.state_stride, i0, cnt), load4<VEC>(sp + 2 * P.state_stride, i0, cnt), G);
+            ra = G.ra; ca = G.ca; rb = G.rb; cb = G.cb; ps = G.ps; tt = G.tt;
+        } else {
+            ra = load4<VEC>(sp, i0, cnt); ca = load4<VEC>(sp + P.state_stride, i0, cnt);
+            rb = load4<VEC>(sp + 2 * P.state_stride, i0, cnt); cb = load4<VEC>(sp + 3 * P.state_stride, i0, cnt);
+            ps = load4<VEC>(sp + 4 * P.state_stride, i0, cnt); tt = load4<VEC>(sp + 5 * P.state_stride, i0, cnt);
+        }
         uint32_t aa = 0u, ab = 0u;
         if (!EXPLICIT_U || !P.policy_a) aa = load4<VEC>(IO.act_a, i0, cnt);
         if (!EXPLICIT_U || !P.policy_b) ab = load4<VEC>(IO.act_b, i0, cnt);
@@ -135,9 +143,15 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const KernelParams P, cons
             }
         }
         uint8_t* sw = P.state;
-        store4<VEC>(sw, i0, cnt, nra); store4<VEC>(sw + P.state_stride, i0, cnt, nca);
-        store4<VEC>(sw + 2 * P.state_stride, i0, cnt, nrb); store4<VEC>(sw + 3 * P.state_stride, i0, cnt, ncb);
-        store4<VEC>(sw + 4 * P.state_stride, i0, cnt, nps); store4<VEC>(sw + 5 * P.state_stride, i0, cnt, ntt);
+        if (packed) {
+            uint32_t pa, pb, pt;
+            swar::pack3(swar::Group{nra, nca, nrb, ncb, nps, ntt}, pa, pb, pt);
+            store4<VEC>(sw, i0, cnt, pa); store4<VEC>(sw + P.state_stride, i0, cnt, pb); store4<VEC>(sw + 2 * P.state_stride, i0, cnt, pt);
+        } else {
+            store4<VEC>(sw, i0, cnt, nra); store4<VEC>(sw + P.state_stride, i0, cnt, nca);
+            store4<VEC>(sw + 2 * P.state_stride, i0, cnt, nrb); store4<VEC>(sw + 3 * P.state_stride, i0, cnt, ncb);
+            store4<VEC>(sw + 4 * P.state_stride, i0, cnt, nps); store4<VEC>(sw + 5 * P.state_stride, i0, cnt, ntt);
+        }
         if (IO.obs) store4h<VEC>(IO.obs, i0, cnt, o_lo, o_hi);
         if (IO.reward) store4<VEC>(IO.reward, i0, cnt, o_rew);
         if (IO.terminated) store4<VEC>(IO.terminated, i0, cnt, o_term);
@@ -183,13 +197,22 @@ __device__ __forceinline__ void hot_group(const KernelParams& P, const StepIO& I
     Tables T; T.lut = P.lut; T.nc = P.next_cell; T.isd = P.isd;
     const uint8_t* sp = P.state;
 #define SOCCER_LD(p) __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p))
-    const uint32_t ra = SOCCER_LD(sp + i0);
-    const uint32_t ca = SOCCER_LD(sp + P.state_stride + i0);
-    const uint32_t rb = SOCCER_LD(sp + 2 * P.state_stride + i0);
-    const uint32_t cb = SOCCER_LD(sp + 3 * P.state_stride + i0);
-    const uint32_t ps = SOCCER_LD(sp + 4 * P.state_stride + i0);
-    const uint32_t tt = SOCCER_LD(sp + 5 * P.state_stride + i0);
+    const bool packed = P.state_layout == kStatePacked;            // wave-uniform
+    uint32_t ra, ca, rb, cb, ps, tt;
+    if (packed) {
+        const uint32_t pa = SOCCER_LD(sp + i0), pb = SOCCER_LD(sp + P.state_stride + i0);
+        tt = SOCCER_LD(sp + 2 * P.state_stride + i0);
+        ra = pa; ca = pb; rb = 0u; cb = 0u; ps = 0u;                // taken apart below, behind the action loads
+    } else {
+        ra = SOCCER_LD(sp + i0);
+        ca = SOCCER_LD(sp + P.state_stride + i0);
+        rb = SOCCER_LD(sp + 2 * P.state_stride + i0);
+        cb = SOCCER_LD(sp + 3 * P.state_stride + i0);
+        ps = SOCCER_LD(sp + 4 * P.state_stride + i0);
+        tt = SOCCER_LD(sp + 5 * P.state_stride + i0);
+    }
     uint32_t aa = SOCCER_LD(IO.act_a + i0), ab = SOCCER_LD(IO.act_b + i0);
+    if (packed) { swar::Group G; swar::unpack3(ra, ca, tt, G); ra = G.ra; ca = G.ca; rb = G.rb; cb = G.cb; ps = G.ps; }
 #undef SOCCER_LD
     // action bytes execute as table[byte & 7] with 5..7 -> NOOP; anything outside 0..4 is reported (:393)
     const uint32_t aa_raw = aa, ab_raw = ab;
@@ -232,9 +255,15 @@ __device__ __forceinline__ void hot_group(const KernelParams& P, const StepIO& I
     // the state is re-read by the NEXT launch only, i.e. after the kernel-boundary write-back / invalidate of L2:
     // streaming it as well is worth another ~1 % (6.91 -> 6.83 us)
 #define SOCCER_ST(p, v) __builtin_nontemporal_store((v), reinterpret_cast<uint32_t*>(p))
-    SOCCER_ST(sw + i0, nra); SOCCER_ST(sw + P.state_stride + i0, nca);
-    SOCCER_ST(sw + 2 * P.state_stride + i0, nrb); SOCCER_ST(sw + 3 * P.state_stride + i0, ncb);
-    SOCCER_ST(sw + 4 * P.state_stride + i0, nps); SOCCER_ST(sw + 5 * P.state_stride + i0, ntt);
+    if (packed) {
+        uint32_t pa, pb, pt;
+        swar::pack3(swar::Group{nra, nca, nrb, ncb, nps, ntt}, pa, pb, pt);
+        SOCCER_ST(sw + i0, pa); SOCCER_ST(sw + P.state_stride + i0, pb); SOCCER_ST(sw + 2 * P.state_stride + i0, pt);
+    } else {
+        SOCCER_ST(sw + i0, nra); SOCCER_ST(sw + P.state_stride + i0, nca);
+        SOCCER_ST(sw + 2 * P.state_stride + i0, nrb); SOCCER_ST(sw + 3 * P.state_stride + i0, ncb);
+        SOCCER_ST(sw + 4 * P.state_stride + i0, nps); SOCCER_ST(sw + 5 * P.state_stride + i0, ntt);
+    }
     // Results are written once and never re-read by these kernels, actions are read once: non-temporal accesses
     // keep them from displacing the resident state in L2 / Infinity Cache (7.66 -> 6.97 us per launch).
     if (IO.obs) __builtin_nontemporal_store((unsigned long long)o_lo | ((unsigned long long)o_hi << 32),
@@ -270,8 +299,9 @@ __global__ __launch_bounds__(kBlock) void step_kernel_hot(uint8_t* state, unsign
 // =================================================================================================
 // batched_step, byte-parallel: the four lanes of a thread stay packed in their dwords (soccer_swar.hpp)
 // =================================================================================================
-// Same launch shape and memory behaviour as step_kernel_hot (one 4-lane group per thread, eight non-temporal
-// dword loads, the Philox block computed while they are in flight, ten non-temporal stores, leading scalar
+// Same launch shape and memory behaviour as step_kernel_hot (one 4-lane group per thread, non-temporal dword
+// loads — five with the packed state, eight with six streams —, the Philox block computed while they are in
+// flight, seven or ten non-temporal stores, leading scalar
 // arguments preloaded into SGPRs) — but no byte peeling, no per-lane loop and NO rule-table read: ~45 vector
 // instructions per env-step instead of ~128 and no dependent gather between the loads and the stores.
 // Takes every Philox-driven, dword-aligned step of a slip_prob == 0 handle whose pitch fits the byte arithmetic
@@ -325,7 +355,9 @@ struct SwarParams {
 // or 1/4 and the ISD is uniform over 4 or 2 entries, so floor(4u) IS the reference's first-exceeds decision for any double
 // (:395, :414; values outside [0, 1) and NaN select index 0 like argmax of an all-False array): four doubles per stream and
 // thread, two 16-byte loads each, issued with the state loads; round 3 sent these calls to the per-lane kernel (11.0 us).
-template <int OUT, int SLIPM = 0, bool POLICY = false, int GEO = 0, bool EXPL = false>
+// LAYOUT (StateLayout): three packed state streams (5 loads + 7 stores, 13 B per env-step) or six (8 + 10, 19 B) — a compile-time
+// shape because a uniform branch ahead of the loads costs the SGPR-base addressing (see the action loads).
+template <int OUT, int SLIPM = 0, bool POLICY = false, int GEO = 0, bool EXPL = false, uint32_t LAYOUT = kStatePacked>
 __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_in, unsigned long long state_stride,
                                                            const int8_t* act_a, const int8_t* act_b,
                                                            const unsigned long long* tick_in,
@@ -382,12 +414,19 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
             if (ld_b) ab = __hip_atomic_load(reinterpret_cast<const uint32_t*>(AT(act_b, la)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
         }
         uint32_t ls = l0; asm("" : "+v"(ls));
-        S.ra = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp, ls)));
-        S.ca = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + state_stride, ls)));
-        S.rb = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + 2 * state_stride, ls)));
-        S.cb = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + 3 * state_stride, ls)));
-        S.ps = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + 4 * state_stride, ls)));
-        S.tt = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + 5 * state_stride, ls)));
+        if (LAYOUT == kStatePacked) {
+            // (held in ra / ca until the step needs them: swar::unpack3 below, behind everything that does not depend on the state)
+            S.ra = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp, ls)));
+            S.ca = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + state_stride, ls)));
+            S.tt = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + 2 * state_stride, ls)));
+        } else {
+            S.ra = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp, ls)));
+            S.ca = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + state_stride, ls)));
+            S.rb = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + 2 * state_stride, ls)));
+            S.cb = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + 3 * state_stride, ls)));
+            S.ps = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + 4 * state_stride, ls)));
+            S.tt = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + 5 * state_stride, ls)));
+        }
     }
     // EXPL: the four lanes' uniforms, as floor(4u) (two bits each) — behind the state loads, ahead of the Philox block
     uint32_t xq = 0u, xr = 0u;
@@ -424,6 +463,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
         if (!FULL && !active) return;
     }
     if (active) {
+        if (LAYOUT == kStatePacked) swar::unpack3(S.ra, S.ca, S.tt, S);
         if (POLICY) {                                               // the fixed side acts on the current observation (:187-188)
             uint32_t s_lo, s_hi;
             const uint32_t cc0 = swar::bfi(swar::mask_of(S.ps << 7), S.cb, S.ca);
@@ -484,12 +524,20 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
         uint32_t j0 = i0; asm volatile("" : "+v"(j0));
         const uint32_t j0x2 = j0 << 1, j0x4 = j0 << 2;
 #define ATW(base, off) (reinterpret_cast<uint8_t*>(base) + (off))
-        __builtin_nontemporal_store(S.ra, reinterpret_cast<uint32_t*>(ATW(sw, j0)));
-        __builtin_nontemporal_store(S.ca, reinterpret_cast<uint32_t*>(ATW(sw + state_stride, j0)));
-        __builtin_nontemporal_store(S.rb, reinterpret_cast<uint32_t*>(ATW(sw + 2 * state_stride, j0)));
-        __builtin_nontemporal_store(S.cb, reinterpret_cast<uint32_t*>(ATW(sw + 3 * state_stride, j0)));
-        __builtin_nontemporal_store(S.ps, reinterpret_cast<uint32_t*>(ATW(sw + 4 * state_stride, j0)));
-        __builtin_nontemporal_store(S.tt, reinterpret_cast<uint32_t*>(ATW(sw + 5 * state_stride, j0)));
+        if (LAYOUT == kStatePacked) {
+            uint32_t pa, pb, pt;
+            swar::pack3(S, pa, pb, pt);
+            __builtin_nontemporal_store(pa, reinterpret_cast<uint32_t*>(ATW(sw, j0)));
+            __builtin_nontemporal_store(pb, reinterpret_cast<uint32_t*>(ATW(sw + state_stride, j0)));
+            __builtin_nontemporal_store(pt, reinterpret_cast<uint32_t*>(ATW(sw + 2 * state_stride, j0)));
+        } else {
+            __builtin_nontemporal_store(S.ra, reinterpret_cast<uint32_t*>(ATW(sw, j0)));
+            __builtin_nontemporal_store(S.ca, reinterpret_cast<uint32_t*>(ATW(sw + state_stride, j0)));
+            __builtin_nontemporal_store(S.rb, reinterpret_cast<uint32_t*>(ATW(sw + 2 * state_stride, j0)));
+            __builtin_nontemporal_store(S.cb, reinterpret_cast<uint32_t*>(ATW(sw + 3 * state_stride, j0)));
+            __builtin_nontemporal_store(S.ps, reinterpret_cast<uint32_t*>(ATW(sw + 4 * state_stride, j0)));
+            __builtin_nontemporal_store(S.tt, reinterpret_cast<uint32_t*>(ATW(sw + 5 * state_stride, j0)));
+        }
         if (Q.obs) __builtin_nontemporal_store((unsigned long long)o.obs_lo | ((unsigned long long)o.obs_hi << 32),
                                                reinterpret_cast<unsigned long long*>(ATW(Q.obs, j0x2)));
         if (Q.reward) __builtin_nontemporal_store(o.rew, reinterpret_cast<uint32_t*>(ATW(Q.reward, j0)));

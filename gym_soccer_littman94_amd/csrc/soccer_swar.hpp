@@ -249,8 +249,23 @@ SOCCER_HD Rand4 rand_pair(const uint32_t isd_shift, uint32_t t, uint32_t p) {
 // four lanes of the six state streams
 struct Group { uint32_t ra, ca, rb, cb, ps, tt; };
 
+// The packed resident state: the same 23 bits in THREE byte streams (still one byte per lane and stream, so a thread's
+// dword holds its four lanes), for pitches whose rows fit three bits and columns four (packs):
+//   a = poss << 7 | row_a << 4 | col_a      b = need_reset << 7 | row_b << 4 | col_b      t = timestep
+inline bool packs(int H, int W) { return H <= 8 && W <= 16; }
+SOCCER_HD void unpack3(uint32_t a, uint32_t b, uint32_t t, Group& S) {
+    S.ra = (a >> 4) & 0x07070707u; S.ca = a & 0x0f0f0f0fu;
+    S.rb = (b >> 4) & 0x07070707u; S.cb = b & 0x0f0f0f0fu;
+    S.ps = ((a >> 7) & K01) | ((b >> 6) & 0x02020202u); S.tt = t;
+}
+SOCCER_HD void pack3(const Group& S, uint32_t& a, uint32_t& b, uint32_t& t) {
+    a = ((S.ps << 7) & K80) | (S.ra << 4) | S.ca;
+    b = ((S.ps << 6) & K80) | (S.rb << 4) | S.cb;
+    t = S.tt;
+}
+
 struct Out {
-    uint32_t obs_lo, obs_hi;       // observation after any auto-reset: lanes 0,1 / 2,3 as uint16 pairs
+    uint32_t obs_lo, obs_hi;      // observation after any auto-reset: lanes 0,1 / 2,3 as uint16 pairs
     uint32_t fin_lo, fin_hi;       // FULL: observation before the reset (gym's final_observation)
     uint32_t rew, term, trunc;     // bytes
     uint32_t code;                 // FULL: prob_code = slip class * 3 + outcome class

@@ -265,8 +265,16 @@ int soccer_reset_scalar(soccer_handle* h, soccer_scalar_io* io);
 
 /* SOCCER_F_HOST_MAPPED handles only: HOST address of the six state streams (row_a, col_a, row_b, col_b,
  * poss|needs_reset<<1, t; `stride` bytes apart).  Valid to read/write whenever the stream is idle
- * (after a *_host call or soccer_sync); writes bypass the tuple validation of soccer_set_state. */
+ * (after a *_host call or soccer_sync); writes bypass the tuple validation of soccer_set_state.
+ * Only mapped handles are sure to have these six streams: how any other handle lays out its resident
+ * state is private to the library (soccer_state_streams), reached through soccer_get_state / soccer_set_state. */
 int soccer_host_view(soccer_handle* h, uint8_t** state, uint64_t* stride);
+
+/* Number of byte streams the handle's resident state occupies: 3 (packed: possession, rows and columns of a
+ * player share a byte; pitches of at most 8 rows and 16 columns incl. the goal columns, not host-mapped) or 6.
+ * Results never depend on it.  The environment variable SOCCER_STATE_LAYOUT=wide, read by soccer_create,
+ * forces 6 (tests and A/B runs).  0 for a NULL handle. */
+int soccer_state_streams(const soccer_handle* h);
 
 /* ---- state injection / readback (`env.state = tuple`, tests/test_deterministic...py:43) -- */
 /* HOST pointers of n_lanes elements; any pointer may be NULL (field left unchanged / not read).
