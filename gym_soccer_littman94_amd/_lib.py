@@ -63,6 +63,15 @@ class StagingView(C.Structure):
                                          "reward", "terminated", "truncated", "prob_code")]
 
 
+class MinimaxQConfig(C.Structure):
+    """soccer_minimax_q_config"""
+    _fields_ = [("discount_factor", C.c_double), ("alpha", C.c_double), ("decay", C.c_double), ("explor", C.c_double),
+                ("q_init", C.c_double), ("opponent", C.c_int32), ("reserved_", C.c_int32), ("opponent_policy", C.c_void_p)]
+
+
+MQ_UNIFORM, MQ_SELF, MQ_FIXED = 0, 1, 2
+MQ_MAX_LANES = 1 << 22
+MISUSE_FROZEN, MISUSE_ACTION, MISUSE_OBSERVATION = 1, 2, 4
 STAGE_ACT_A, STAGE_ACT_B, STAGE_U_STEP, STAGE_U_RESET, STAGE_MASK = 1, 2, 4, 8, 16
 COMM_ID_BYTES = 128
 
@@ -110,6 +119,12 @@ PROTOTYPES = {
     "soccer_minimax_backup": (C.c_int, [C.c_void_p, C.c_double] + [C.c_void_p] * 5),
     "soccer_minimax_value_iteration": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int32] + [C.c_void_p] * 4
                                        + [C.POINTER(C.c_int32)]),
+    "soccer_minimax_q_create": (C.c_int, [C.c_void_p, C.POINTER(MinimaxQConfig), C.POINTER(C.c_void_p)]),
+    "soccer_minimax_q_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "soccer_minimax_q_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "soccer_minimax_q_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
+    "soccer_minimax_q_read": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "soccer_minimax_q_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "soccer_prob_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 12)]),
     "soccer_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint64)]),
     "soccer_reset_stats": (C.c_int, [C.c_void_p]),

@@ -88,6 +88,143 @@ def _ptr(x):
     raise TypeError("expected a DeviceArray, a device tensor or an integer address, got %r" % type(x))
 
 
+def minimax_q_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, opponent="uniform"):
+    """Checks the parameters of a minimax-Q learner (AssertionError, before any library call) and returns
+    (soccer_minimax_q_config, the array it points into or None)."""
+    g, a, d, e, q0 = float(discount_factor), float(alpha), float(decay), float(explor), float(q_init)
+    assert 0.0 <= g < 1.0, "discount_factor must be in [0, 1)"
+    assert 0.0 <= a <= 1.0, "alpha must be in [0, 1]"
+    assert 0.0 < d <= 1.0, "decay must be in (0, 1]"
+    assert 0.0 <= e <= 1.0, "explor must be in [0, 1]"
+    assert -1.0 <= q0 <= 1.0, "q_init must be in [-1, 1]"
+    pol = None
+    if isinstance(opponent, str):
+        assert opponent in ("uniform", "self"), "opponent must be 'uniform', 'self' or an [nS, 5] mixed policy"
+        kind = _lib.MQ_UNIFORM if opponent == "uniform" else _lib.MQ_SELF
+    else:
+        pol = np.ascontiguousarray(opponent, np.float64)
+        assert pol.shape == (int(nS), 5) and (pol >= 0).all() and np.allclose(pol.sum(1), 1.0), \
+            "a fixed opponent must be [n_states, 5] rows summing to 1"
+        kind = _lib.MQ_FIXED
+    return _lib.MinimaxQConfig(g, a, d, e, q0, kind, 0, None if pol is None else pol.ctypes.data), pol
+
+
+class MinimaxQLearner:
+    """A minimax-Q learner (Littman 1994) on a two-player auto-reset SoccerBatch: one shared Q[nS, 5, 5] on the device,
+    the batch's lanes as actors (include/soccer_hip.h, "learners").  run() enqueues and returns; the properties
+    synchronise and copy."""
+
+    def __init__(self, batch, discount_factor, **params):
+        cfg, keep = minimax_q_config(batch.nS, discount_factor, **params)
+        self.batch, self.q = batch, None
+        q = C.c_void_p()
+        batch._check(batch.lib.soccer_minimax_q_create(batch.h, C.byref(cfg), C.byref(q)))
+        del keep                                   # (create has copied the opponent's thresholds)
+        self.q = q
+        self.nS = batch.nS
+        batch._learners.add(self)
+
+    def run(self, n_steps):
+        """n_steps learner steps (every lane acts, the environment steps, Q / V / pi are updated), enqueued."""
+        b = self.batch
+        b._check(b.lib.soccer_minimax_q_run(b.h, self.q, int(n_steps)))
+        return self
+
+    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
+        """One learner step's reduce / update / re-solve on a batch of transitions: DeviceArrays (or device tensors) of one
+        length, or numpy arrays, which are copied to the device first."""
+        b = self.batch
+        args = (obs, act_a, act_b, reward, terminated, next_obs)
+        dts = (np.uint16, np.int8, np.int8, np.int8, np.uint8, np.uint16)
+        tmp = []
+        if all(isinstance(x, (np.ndarray, list, tuple)) for x in args):
+            host = [np.ascontiguousarray(x, dt).reshape(-1) for x, dt in zip(args, dts)]
+            n = host[0].size
+            assert all(x.size == n for x in host), "the six transition arrays must have one length"
+            assert n <= _lib.MQ_MAX_LANES, "at most 2**22 transitions per update"
+            if n:
+                tmp = [DeviceArray(b, n, dt).upload(x) for x, dt in zip(host, dts)]
+            ptrs = [a.ptr for a in tmp] if n else [None] * 6
+        else:
+            def length(x):
+                return int(np.prod(x.shape)) if hasattr(x, "shape") else None
+            n = length(obs)
+            assert n is not None and all(length(x) == n for x in args), "the six transition arrays must have one length"
+            ptrs = [_ptr(x) for x in args]
+        try:
+            b._check(b.lib.soccer_minimax_q_update(b.h, self.q, n, *ptrs))
+        finally:
+            if tmp:
+                b.sync()
+                for a in tmp:
+                    a.free()
+        return self
+
+    def read(self):
+        """dict: Q[nS, 5, 5], V[nS], pi_a / pi_b [nS, 5], visits[nS, 25], alpha, steps (synchronises)."""
+        nS, b = self.nS, self.batch
+        out = {"Q": np.zeros((nS, 5, 5)), "V": np.zeros(nS), "pi_a": np.zeros((nS, 5)), "pi_b": np.zeros((nS, 5)),
+               "visits": np.zeros((nS, 25), np.uint64)}
+        al, st = C.c_double(), C.c_uint64()
+        b._check(b.lib.soccer_minimax_q_read(b.h, self.q, *[out[k].ctypes.data for k in ("Q", "V", "pi_a", "pi_b", "visits")],
+                                             C.byref(al), C.byref(st)))
+        out["alpha"], out["steps"] = float(al.value), int(st.value)
+        return out
+
+    def _one(self, key, shape, dtype=np.float64):
+        b = self.batch
+        a = np.zeros(shape, dtype)
+        ptrs = [a.ctypes.data if k == key else None for k in ("Q", "V", "pi_a", "pi_b", "visits")]
+        b._check(b.lib.soccer_minimax_q_read(b.h, self.q, *ptrs, None, None))
+        return a
+
+    Q = property(lambda self: self._one("Q", (self.nS, 5, 5)))
+    V = property(lambda self: self._one("V", self.nS))
+    pi_a = property(lambda self: self._one("pi_a", (self.nS, 5)))
+    pi_b = property(lambda self: self._one("pi_b", (self.nS, 5)))
+    visits = property(lambda self: self._one("visits", (self.nS, 25), np.uint64))
+
+    @property
+    def alpha(self):
+        b, al = self.batch, C.c_double()
+        b._check(b.lib.soccer_minimax_q_read(b.h, self.q, None, None, None, None, None, C.byref(al), None))
+        return float(al.value)
+
+    @property
+    def steps(self):
+        b, st = self.batch, C.c_uint64()
+        b._check(b.lib.soccer_minimax_q_read(b.h, self.q, None, None, None, None, None, None, C.byref(st)))
+        return int(st.value)
+
+    def load(self, Q, visits=None, alpha=None, steps=None):
+        """Resume from a checkpoint: Q[nS, 5, 5] in, V and the strategies re-solved on the device.  With `visits` (and the
+        `alpha` / `steps` of read()) a fresh learner continues bit for bit; without, every state is solved."""
+        b = self.batch
+        Q = np.ascontiguousarray(Q, np.float64)
+        assert Q.shape == (self.nS, 5, 5), "Q must be [n_states, 5, 5]"
+        assert (np.abs(Q[1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
+        v = None
+        if visits is not None:
+            v = np.ascontiguousarray(visits, np.uint64)
+            assert v.shape == (self.nS, 25), "visits must be [n_states, 25]"
+        assert alpha is None or 0.0 <= float(alpha) <= 1.0, "alpha must be in [0, 1]"
+        al = None if alpha is None else C.byref(C.c_double(float(alpha)))
+        st = None if steps is None else C.byref(C.c_uint64(int(steps)))
+        b._check(b.lib.soccer_minimax_q_load(b.h, self.q, Q.ctypes.data, None if v is None else v.ctypes.data, al, st))
+        return self
+
+    def close(self):
+        if self.q and self.batch.h:
+            self.batch.lib.soccer_minimax_q_destroy(self.batch.h, self.q)
+        self.q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SoccerBatch:
     """N lanes of the Littman-94 soccer game resident on one GPU.
 
@@ -108,6 +245,7 @@ class SoccerBatch:
         self.lib = _lib.load()
         self.h = None
         self._arrays = weakref.WeakSet()        # device buffers handed out by alloc(); freed with the handle
+        self._learners = weakref.WeakSet()      # minimax_q(): their memory goes with the handle
         cfg = Config(n_lanes=int(n_lanes), width=int(width), height=int(height),
                      slip_prob=float(slip_prob), max_steps=int(max_steps), device=int(device),
                      seed=int(seed) & 0xFFFFFFFFFFFFFFFF, lane_offset=int(lane_offset),
@@ -138,6 +276,8 @@ class SoccerBatch:
         if self.h:
             for a in list(self._arrays):            # buffers that outlived their users: no leak past the handle
                 a.free()
+            for q in list(self._learners):          # soccer_destroy frees them: their wrappers must not touch them again
+                q.q = None
             self.lib.soccer_destroy(self.h)
             self.h = None
 
@@ -310,6 +450,12 @@ class SoccerBatch:
         self._check(self.lib.soccer_minimax_value_iteration(self.h, float(theta), float(discount_factor), int(max_sweeps),
                                                             V.ctypes.data, Q.ctypes.data, pa.ctypes.data, pb.ctypes.data, C.byref(it)))
         return pa, pb, V, Q, int(it.value)
+
+    # -- learners -------------------------------------------------------------------------------
+    def minimax_q(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, opponent="uniform"):
+        """A MinimaxQLearner on this batch (two players, autoreset=True, at most 2**22 lanes).  opponent: 'uniform', 'self'
+        (player B follows its own minimax strategy of the learned Q, with the same exploration) or a fixed [nS, 5] policy."""
+        return MinimaxQLearner(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, opponent=opponent)
 
     # -- hot path -------------------------------------------------------------------------------
     def reset(self, mask=None, u_reset=None, obs=None):
@@ -498,7 +644,7 @@ class SoccerBatch:
         self._check(self.lib.soccer_get_stats(self.h, C.byref(hist), C.byref(mis)))
         return np.array(hist, dtype=np.uint64), int(mis.value)
 
-    MISUSE_FROZEN, MISUSE_ACTION = 1, 2
+    MISUSE_FROZEN, MISUSE_ACTION, MISUSE_OBSERVATION = 1, 2, 4
 
     def misuse(self):
         """The sticky misuse flags alone (no histogram copy; synchronises): MISUSE_FROZEN if a lane was stepped while

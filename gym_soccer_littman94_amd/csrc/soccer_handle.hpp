@@ -5,6 +5,7 @@
 //   soccer_step.hip      batched_step*
 //   soccer_rollout.hip   batched_rollout*
 //   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, the matrix-game solver
+//   soccer_learners.hip  the minimax-Q learner
 //   soccer_comm.hip      the RCCL wrapper (host code only)
 //
 // Every unit carries its own code object: a kernel is instantiated, launched and given its attributes (hipFuncSetAttribute)
@@ -163,6 +164,7 @@ struct soccer_handle {
     double* mm_V[2] = {nullptr, nullptr};   // V double-buffered across sweeps
     unsigned long long* mm_words = nullptr; // [kMinimaxBatch + 1] per-sweep max |V_k - V_{k-1}| (bits)
     OwnedBufs mm_bufs{"the minimax planner"};
+    std::vector<soccer_minimax_q*> learners; // soccer_minimax_q_create: the learners that were not destroyed (freed with the handle)
     std::string err;
 
     soccer_handle() = default;
@@ -171,7 +173,7 @@ struct soccer_handle {
     ~soccer_handle();                       // soccer_hip.hip: waits for the stream, then gives everything back
 };
 
-// the handle's host-mapped block: dwords 0 / 1 the sticky misuse words, from byte 64 on SOCCER_STAMP_SLOTS u64 clock stamps,
+// the handle's host-mapped block: dwords 0 / 1 / 2 the sticky misuse words (frozen, action, observation), from byte 64 on SOCCER_STAMP_SLOTS u64 clock stamps,
 // ONE PER 64-BYTE LINE: a line the host has written or is polling costs the device a coherence round trip to write, and a
 // stamp kernel's store must complete before the next kernel starts — with the opening and the closing stamp of a captured
 // timer in one line (and the host clearing the closing one before every replay) the opening stamp's kernel boundary took
@@ -201,5 +203,7 @@ static inline int grid_for(const soccer_handle* h, uint64_t work_items) {
 hipError_t rollout_raise_smem_limit(const soccer_handle* h, size_t bytes);
 // soccer_comm.hip: destroys the handle's communicator, if it has one (the handle's destructor)
 void comm_release(soccer_handle* h);
+// soccer_learners.hip: frees the learners the caller did not destroy (the handle's destructor; the stream has drained)
+void learners_release(soccer_handle* h);
 
 #pragma GCC visibility pop

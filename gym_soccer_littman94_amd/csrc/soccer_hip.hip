@@ -49,6 +49,7 @@ soccer_handle::~soccer_handle() {
     (void)hipSetDevice(cfg.device);
     (void)hipStreamSynchronize(stream);
     comm_release(this);
+    learners_release(this);
     bufs.clear(); plan_bufs.clear(); mm_bufs.clear();      // here, not as members after this body: the stream is still alive
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
@@ -688,7 +689,7 @@ extern "C" int soccer_get_stats(soccer_handle* h, uint64_t hist[3], uint64_t* mi
     }
     if (misuse) {                                   // the stream is idle: no copy needed
         const volatile unsigned int* m = h->misuse_host;
-        *misuse = (m[0] ? 1u : 0u) | (m[1] ? 2u : 0u);
+        *misuse = (m[0] ? 1u : 0u) | (m[1] ? 2u : 0u) | (m[2] ? 4u : 0u);
     }
     return SOCCER_OK;
 }
@@ -696,7 +697,7 @@ extern "C" int soccer_get_stats(soccer_handle* h, uint64_t hist[3], uint64_t* mi
 extern "C" uint32_t soccer_peek_misuse(const soccer_handle* h) {
     if (!h || !h->misuse_host) return 0u;
     const volatile unsigned int* m = h->misuse_host;
-    return (m[0] ? SOCCER_MISUSE_FROZEN : 0u) | (m[1] ? SOCCER_MISUSE_ACTION : 0u);
+    return (m[0] ? SOCCER_MISUSE_FROZEN : 0u) | (m[1] ? SOCCER_MISUSE_ACTION : 0u) | (m[2] ? SOCCER_MISUSE_OBSERVATION : 0u);
 }
 
 extern "C" int soccer_reset_stats(soccer_handle* h) {

@@ -472,6 +472,13 @@ class VectorSoccerEnv:
             plan.update(step_args=step_args, step_ref=ctypes.byref(step_args), step_call=b.lib.batched_step_ex)
         return plan
 
+    def minimax_q(self, discount_factor, **params):
+        """A MinimaxQLearner (SoccerBatch.minimax_q) whose actors are this env's lanes: learner.run(T) steps them T times
+        from where they stand, and rollout() / step() on the env keep working between run() calls.  Needs the two-player
+        env with autoreset=True; the env must have been reset."""
+        assert self.multiagent, "minimax_q needs a two-player environment (no player with a fixed policy)"
+        return self._batch.minimax_q(discount_factor, **params)
+
     @property
     def reward_int8(self):
         """device io: player A's reward of the last step as the int8 tensor the kernel wrote (-1 / 0 / +1), no cast
@@ -485,6 +492,9 @@ class VectorSoccerEnv:
             if flags & SoccerBatch.MISUSE_ACTION:
                 raise AssertionError("actions must be in 0..4 (an action byte outside that range reached the device; "
                                      "it was executed as a move inside the pitch)")
+            if not flags & SoccerBatch.MISUSE_FROZEN:
+                raise AssertionError("a transition handed to a learner's update() had an observation index no lane can be in "
+                                     "(it was left out)")
             raise AssertionError("Please reset the environment before taking a step "
                                  "(some lanes had terminated or truncated; they were left untouched)")
 

@@ -54,6 +54,38 @@ def modified_policy_iteration(env, k, theta, discount_factor):           # plann
     return _batch(env).modified_policy_iteration(k, theta, discount_factor)
 
 
+def _two_player_batch(env, what):
+    from .core import SoccerBatch
+    if isinstance(env, SoccerBatch):
+        return env
+    b = getattr(env, "_batch", None)
+    if b is None:
+        raise TypeError("planners expect a gym_soccer_littman94_amd environment")
+    assert env.multiagent, "%s needs a two-player environment (no player with a fixed policy)" % what
+    return b
+
+
+def minimax_q_learning(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, opponent="uniform"):
+    """Minimax-Q (Littman 1994) on the device: n_steps learner steps with every lane of `env` acting, from the lanes'
+    current states (lanes that were never reset are reset first).  decay None: alpha falls to 1 % over the run.
+    Returns (pi_a[nS, 5], pi_b[nS, 5], V, Q[nS, 5, 5], visits[nS, 25]) — minimax_value_iteration's order with the visit
+    counts in place of the iteration count, ready for VectorSoccerEnv.rollout(sample_actions=True, mixed_policies={...})."""
+    b = _two_player_batch(env, "minimax_q_learning")
+    n_steps = int(n_steps)
+    assert n_steps >= 0, "n_steps must be >= 0"
+    if decay is None:
+        decay = 0.01 ** (1.0 / max(n_steps, 1))
+    learner = b.minimax_q(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, opponent=opponent)
+    try:
+        if b.get_state()["needs_reset"].any():
+            (env if hasattr(env, "_batch") else b).reset()
+        learner.run(n_steps)
+        r = learner.read()
+    finally:
+        learner.close()
+    return r["pi_a"], r["pi_b"], r["V"], r["Q"], r["visits"]
+
+
 def minimax_value_iteration(env, theta, discount_factor, max_sweeps=1000000):
     """Minimax (Shapley) value iteration of the two-player game on the device, Littman (1994)'s equilibrium values.
     Returns (pi_a[nS, 5], pi_b[nS, 5], V, Q[nS, 5, 5], iterations): player A's maximin and player B's minimax stage-game

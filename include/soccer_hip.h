@@ -64,7 +64,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup and soccer_minimax_value_iteration were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration and soccer_minimax_q_* were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -360,6 +360,67 @@ int soccer_minimax_backup(soccer_handle* h, double discount_factor, const double
  * max_sweeps is reached; the outputs then hold the last iterate. */
 int soccer_minimax_value_iteration(soccer_handle* h, double theta, double discount_factor, int32_t max_sweeps,
                                    double* V, double* Q, double* pi_a, double* pi_b, int32_t* iterations);
+/* ---- learners (two-player handles; minimax-Q, Littman 1994) ------------------------------------------------------
+ * A learner lives on a two-player SOCCER_F_AUTORESET handle of at most 2^22 lanes and keeps ONE shared table
+ * Q[n_states][5][5] (float64) on the device, with V[n_states] = val(Q[s]) and the stage-game strategies
+ * pi_a / pi_b [n_states][5] (csrc/soccer_games.hpp), visits[n_states][25] (uint64), the learning rate alpha and a step
+ * counter.  The handle's lanes are its actors.  One learner step, in this order:
+ *   1. behaviour policies: player A draws from p = (1.0 - explor) * pi_a[s] + explor / 5.0, turned into the uint16[4]
+ *      threshold row of soccer_rollout_args::mix_a (sequential float64 cumulative sum c, floor(c * 32768.0 + 1e-9),
+ *      clipped to 0..32768); player B uniformly (SOCCER_MQ_UNIFORM), by the same expression on pi_b (SOCCER_MQ_SELF)
+ *      or from the thresholds of a fixed mixed policy (SOCCER_MQ_FIXED, computed once)
+ *   2. act and step: for the environment the step IS batched_rollout(n_steps = 1, sample_actions = 1, mix_a, mix_b) —
+ *      same tick, same Philox words, same action draw, same auto-reset, same episode histogram, same misuse flags.  A
+ *      lane yields s (its observation before the step), a, b, r (player A's reward), terminated and s' = final_obs
+ *   3. reduce: with Vq[s] = rint(V[s] * 2^40) as int64, cell = s * 25 + a * 5 + b:  c[cell] += 1, R[cell] += r,
+ *      SV[cell] += terminated ? 0 : Vq[s']  — INTEGER sums, so the result does not depend on the order in which lanes
+ *      arrive (|V| <= 1 and at most 2^22 samples: the sums fit int64; the grid costs < 5e-13 per sample)
+ *   4. update, for every cell with c > 0:  m = ((double)R + discount_factor * ((double)SV * 2^-40)) / (double)c,
+ *      Q = Q + alpha * (m - Q),  visits += c
+ *   5. re-solve: (V[s], pi_a[s], pi_b[s]) = solve(Q[s]) for every state with a touched cell
+ *   6. alpha = alpha * decay, steps += 1
+ * Initially Q[s] = V[s] = q_init and pi_a[s] = pi_b[s] = 0.2 for every live s (set, not solved), Q[0] = V[0] = 0 (index
+ * 0 is the terminal observation and never a current state), visits = 0.  With alpha, q_init and the rewards in range
+ * every Q and V stays in [-1, 1].  The learner's state is a fixed function of (seed, parameters, number of steps): it
+ * does not depend on launch geometry, vector width or state layout.  Lanes that still need their first reset are left
+ * untouched (SOCCER_MISUSE_FROZEN) and contribute nothing.
+ * Errors: a handle with a fixed policy, without SOCCER_F_AUTORESET or with more than 2^22 lanes, and parameters out of
+ * range, are SOCCER_E_INVALID; every call below returns SOCCER_E_STATE during a graph capture.  A learner's memory
+ * belongs to its handle: soccer_destroy frees the learners that were not destroyed. */
+#define SOCCER_MQ_UNIFORM 0
+#define SOCCER_MQ_SELF    1
+#define SOCCER_MQ_FIXED   2
+#define SOCCER_MQ_MAX_LANES (1ull << 22)
+typedef struct soccer_minimax_q soccer_minimax_q;
+typedef struct soccer_minimax_q_config {
+    double  discount_factor;        /* [0, 1) */
+    double  alpha;                  /* initial learning rate, [0, 1] (Littman: 1.0) */
+    double  decay;                  /* alpha's factor per learner step, (0, 1] (Littman: 0.01 ** (1 / 1e6)) */
+    double  explor;                 /* [0, 1] probability mass spread uniformly over the five actions (Littman: 0.2) */
+    double  q_init;                 /* [-1, 1] (Littman: 1.0) */
+    int32_t opponent;               /* SOCCER_MQ_* : how player B acts */
+    int32_t reserved_;              /* 0 */
+    const double* opponent_policy;  /* SOCCER_MQ_FIXED: HOST [n_states][5] rows >= 0 summing to 1; else NULL */
+} soccer_minimax_q_config;
+int soccer_minimax_q_create(soccer_handle* h, const soccer_minimax_q_config* cfg, soccer_minimax_q** out);
+int soccer_minimax_q_destroy(soccer_handle* h, soccer_minimax_q* q);
+/* n_steps learner steps, two launches each, enqueued on the handle's stream: no synchronisation, no copy.  Consumes n_steps ticks. */
+int soccer_minimax_q_run(soccer_handle* h, soccer_minimax_q* q, int32_t n_steps);
+/* steps 3-6 on the caller's batch of n <= 2^22 transitions (DEVICE pointers, n elements each; n = 0: steps 4-6 alone).
+ * A transition with an action byte outside 0..4 (SOCCER_MISUSE_ACTION) or with obs = 0, obs >= n_states or
+ * next_obs >= n_states (SOCCER_MISUSE_OBSERVATION) sets the sticky flag and is left out.  Consumes no tick. */
+int soccer_minimax_q_update(soccer_handle* h, soccer_minimax_q* q, int64_t n, const uint16_t* obs, const int8_t* act_a,
+                            const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs);
+/* HOST outputs, any may be NULL: Q[n_states][5][5], V[n_states], pi_a / pi_b [n_states][5], visits[n_states][25].  Synchronises. */
+int soccer_minimax_q_read(soccer_handle* h, soccer_minimax_q* q, double* Q, double* V, double* pi_a, double* pi_b,
+                          uint64_t* visits, double* alpha, uint64_t* steps);
+/* Resume from a checkpoint: HOST Q[n_states][5][5] in (row 0 is taken as zeros), V and the strategies re-solved on the
+ * device.  visits (HOST [n_states][25], or NULL: every state counts as visited and the table is left as it is) restores
+ * the counts, and a state without a visit gets what creation gives it — V = Q[s][0][0], uniform strategies — not the
+ * solver's answer, so that read -> load on a fresh learner continues bit for bit.  alpha / steps: HOST, NULL = unchanged. */
+int soccer_minimax_q_load(soccer_handle* h, soccer_minimax_q* q, const double* Q, const uint64_t* visits,
+                          const double* alpha, const uint64_t* steps);
+
 /* HOST output: prob[c*3+k] = slip-combination weight c (0: no slip, 1: B slips, 2: A slips,
  * 3: both; :211-222, evaluated left to right in float64) times outcome probability 1, 0.5, 0.25
  * (k = 0,1,2; :326-360).  prob_code values index this table (:241). */
@@ -370,10 +431,12 @@ int soccer_prob_table(const soccer_handle* h, double prob[12]);
  * batched_rollout and — on handles created with SOCCER_F_STEP_STATS — by batched_step;
  * misuse = sticky flags: SOCCER_MISUSE_FROZEN if any lane was stepped while it needed reset (the reference's
  * assert, :376; such lanes are left untouched), SOCCER_MISUSE_ACTION if any action byte on a device-pointer
- * path was outside 0..4 (the reference raises IndexError, :393; see "action bytes" above).
+ * path was outside 0..4 (the reference raises IndexError, :393; see "action bytes" above), SOCCER_MISUSE_OBSERVATION
+ * if soccer_minimax_q_update was handed a transition whose observation indices no lane can be in.
  * Synchronises the stream. HOST outputs. */
 #define SOCCER_MISUSE_FROZEN 1u
 #define SOCCER_MISUSE_ACTION 2u
+#define SOCCER_MISUSE_OBSERVATION 4u
 int soccer_get_stats(soccer_handle* h, uint64_t hist[3], uint64_t* misuse);
 /* caller-supplied uniforms on a slip_prob > 0 handle (batched_step_ex with u_step): the byte-parallel step decides them in
  * float64 against the slip list's nominal thresholds and leaves each 4-lane group with a uniform within 2^-40 of one (or at /
