@@ -71,6 +71,7 @@ class MinimaxQConfig(C.Structure):
 
 MQ_UNIFORM, MQ_SELF, MQ_FIXED = 0, 1, 2
 MQ_MAX_LANES = 1 << 22
+BR_MAX_POLICIES = 256
 MISUSE_FROZEN, MISUSE_ACTION, MISUSE_OBSERVATION = 1, 2, 4
 STAGE_ACT_A, STAGE_ACT_B, STAGE_U_STEP, STAGE_U_RESET, STAGE_MASK = 1, 2, 4, 8, 16
 COMM_ID_BYTES = 128
@@ -119,6 +120,10 @@ PROTOTYPES = {
     "soccer_minimax_backup": (C.c_int, [C.c_void_p, C.c_double] + [C.c_void_p] * 5),
     "soccer_minimax_value_iteration": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int32] + [C.c_void_p] * 4
                                        + [C.POINTER(C.c_int32)]),
+    "soccer_best_response": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_int32]
+                             + [C.c_void_p] * 4),
+    "soccer_evaluate_policies": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32,
+                                           C.c_void_p, C.c_void_p]),
     "soccer_minimax_q_create": (C.c_int, [C.c_void_p, C.POINTER(MinimaxQConfig), C.POINTER(C.c_void_p)]),
     "soccer_minimax_q_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "soccer_minimax_q_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),

@@ -122,6 +122,7 @@ class MinimaxQLearner:
         del keep                                   # (create has copied the opponent's thresholds)
         self.q = q
         self.nS = batch.nS
+        self.discount_factor = float(discount_factor)
         batch._learners.add(self)
 
     def run(self, n_steps):
@@ -195,6 +196,13 @@ class MinimaxQLearner:
         b, st = self.batch, C.c_uint64()
         b._check(b.lib.soccer_minimax_q_read(b.h, self.q, None, None, None, None, None, None, C.byref(st)))
         return int(st.value)
+
+    def exploitability(self, theta=1e-10):
+        """How badly the best possible opponent beats the strategies the learner holds now, at its discount:
+        planners.exploitability of (pi_a, pi_b).  Synchronises and copies; run() does not."""
+        from . import planners
+        r = self.read()
+        return planners.exploitability(self.batch, r["pi_a"], r["pi_b"], theta, self.discount_factor)
 
     def load(self, Q, visits=None, alpha=None, steps=None):
         """Resume from a checkpoint: Q[nS, 5, 5] in, V and the strategies re-solved on the device.  With `visits` (and the
@@ -450,6 +458,51 @@ class SoccerBatch:
         self._check(self.lib.soccer_minimax_value_iteration(self.h, float(theta), float(discount_factor), int(max_sweeps),
                                                             V.ctypes.data, Q.ctypes.data, pa.ctypes.data, pb.ctypes.data, C.byref(it)))
         return pa, pb, V, Q, int(it.value)
+
+    # -- best responses to mixed policies (two-player handles) ----------------------------------------
+    def _policies(self, policy, name):
+        """[nS, 5] or [P, nS, 5] -> (contiguous float64 [P, nS, 5], whether a leading axis was given)"""
+        p = np.ascontiguousarray(policy, np.float64)
+        assert p.ndim in (2, 3) and p.shape[-2:] == (self.nS, 5), "%s must be [n_states, 5] or [P, n_states, 5]" % name
+        return (p if p.ndim == 3 else p[None]), p.ndim == 3
+
+    def _response_result(self, code, out, batched):
+        out = tuple(x if batched else x[0] for x in out[:-1]) + (out[-1].astype(np.int64) if batched else int(out[-1][0]),)
+        try:
+            self._check(code)
+        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
+            e.results = out
+            raise
+        return out
+
+    def best_response(self, policy, player, theta, discount_factor, max_sweeps=1000000):
+        """The best response to a mixed policy of `player` (0: the policy is player A's and B answers, minimising; 1: it is
+        B's and A answers, maximising), by value iteration from V = 0 until max|V_k - V_{k-1}| < theta.  policy is
+        [nS, 5], or [P, nS, 5] for P <= 256 policies solved in one batch, each to the bits and the sweep count it has alone.
+        Returns (br, V, Qr, iterations) like value_iteration: the answering side's action per state (the first optimum),
+        player A's value V = the policy's worst case, Qr[.., nS, 5] per action of the answering side; with a leading axis
+        only if one was given.  RuntimeError if max_sweeps is reached (its .results holds the tuple, iterations ==
+        max_sweeps marks the policies that had not converged)."""
+        assert player in (0, 1), "player must be 0 (the policy is player A's) or 1 (player B's)"
+        p, batched = self._policies(policy, "policy")
+        n = p.shape[0]
+        V = np.zeros((n, self.nS)); Qr = np.zeros((n, self.nS, 5)); br = np.zeros((n, self.nS), np.int32); it = np.zeros(n, np.int32)
+        code = self.lib.soccer_best_response(self.h, int(player), n, p.ctypes.data, float(theta), float(discount_factor),
+                                             int(max_sweeps), V.ctypes.data, Qr.ctypes.data, br.ctypes.data, it.ctypes.data)
+        return self._response_result(code, (br.astype(np.int64), V, Qr, it), batched)
+
+    def evaluate_policies(self, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000):
+        """Player A's value of the pair (pi_a, pi_b) of mixed policies, iterated like best_response: (V, iterations).
+        [nS, 5] each, or [P, nS, 5] (one of them may be a single policy: it meets every policy of the other)."""
+        a, ba = self._policies(pi_a, "pi_a")
+        b, bb = self._policies(pi_b, "pi_b")
+        n = max(a.shape[0], b.shape[0])
+        assert a.shape[0] in (1, n) and b.shape[0] in (1, n), "pi_a and pi_b must hold one policy or the same number of policies"
+        a = np.ascontiguousarray(np.broadcast_to(a, (n, self.nS, 5))); b = np.ascontiguousarray(np.broadcast_to(b, (n, self.nS, 5)))
+        V = np.zeros((n, self.nS)); it = np.zeros(n, np.int32)
+        code = self.lib.soccer_evaluate_policies(self.h, n, a.ctypes.data, b.ctypes.data, float(theta), float(discount_factor),
+                                                 int(max_sweeps), V.ctypes.data, it.ctypes.data)
+        return self._response_result(code, (V, it), ba or bb)
 
     # -- learners -------------------------------------------------------------------------------
     def minimax_q(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, opponent="uniform"):

@@ -4,7 +4,7 @@
 //   soccer_hip.hip       create / destroy, seed / tick, reset, state, staging, one-environment calls, statistics, timers, graphs
 //   soccer_step.hip      batched_step*
 //   soccer_rollout.hip   batched_rollout*
-//   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, the matrix-game solver
+//   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, the matrix-game solver
 //   soccer_learners.hip  the minimax-Q learner
 //   soccer_comm.hip      the RCCL wrapper (host code only)
 //
@@ -164,6 +164,15 @@ struct soccer_handle {
     double* mm_V[2] = {nullptr, nullptr};   // V double-buffered across sweeps
     unsigned long long* mm_words = nullptr; // [kMinimaxBatch + 1] per-sweep max |V_k - V_{k-1}| (bits)
     OwnedBufs mm_bufs{"the minimax planner"};
+    // soccer_best_response / soccer_evaluate_policies: buffers for br_cap policies (br_pairs: and a second policy block),
+    // allocated on first use and again when a larger batch comes, see response_buffers
+    double* br_pol[2] = {nullptr, nullptr}; // [br_cap][nS][5] the fixed side's policies; [1]: player B's of a pair
+    double* br_V[2] = {nullptr, nullptr};   // [br_cap][nS] V double-buffered across sweeps
+    double* br_Qr = nullptr;                // [br_cap][nS][5]
+    int32_t* br_arg = nullptr;              // [br_cap][nS]
+    unsigned long long* br_words = nullptr; // [br_cap][kMinimaxBatch + 1] per-policy, per-sweep max |V_k - V_{k-1}| (bits)
+    int br_cap = 0; bool br_pairs = false;
+    OwnedBufs br_bufs{"the best-response solver"};
     std::vector<soccer_minimax_q*> learners; // soccer_minimax_q_create: the learners that were not destroyed (freed with the handle)
     std::string err;
 

@@ -39,4 +39,20 @@ struct MinimaxIO {
     int32_t nS;
 };
 
+// best responses to, and evaluations of, a batch of mixed policies over the same lists (response_sweep_kernel)
+enum ResponseMode : int32_t { kRespondB = 0, kRespondA = 1, kEvalPair = 2 };   // B answers x, A answers y, the pair (x, y)
+
+struct ResponseIO {
+    MinimaxIO mm;                    // offset, list, gamma, theta, nS; the kernel points mm.V at its policy's V_{k-1}
+    const double* x;                 // [n][nS][5] player A's policies (kRespondB, kEvalPair)
+    const double* y;                 // [n][nS][5] player B's policies (kRespondA, kEvalPair)
+    const double* V;                 // [n][nS] V_{k-1}
+    double* V_out;                   // [n][nS] V_k
+    double* Qr;                      // [n][nS][5] (not kEvalPair)
+    int32_t* br;                     // [n][nS]    (not kEvalPair)
+    unsigned long long* delta;       // this sweep's word of policy 0; policy i's is word_stride words further per policy
+    const unsigned long long* prev;  // likewise the previous sweep's (never NULL)
+    int32_t word_stride;
+};
+
 }  // namespace soccer

@@ -1,4 +1,4 @@
-// soccer_planner_kernels.hpp — enumerate_kernel (the transition table), planner_kernel, the minimax kernels, games_kernel.
+// soccer_planner_kernels.hpp — enumerate_kernel (the transition table), planner_kernel, the minimax kernels, response_sweep_kernel, games_kernel.
 // Included by soccer_planners.hip only: every kernel is emitted by exactly one translation unit.
 #pragma once
 #include "soccer_kernels.hpp"
@@ -327,6 +327,67 @@ __global__ __launch_bounds__(kMinimaxBlock) void minimax_sweep_kernel(const Mini
     __syncthreads();
     // a non-atomic look first: the word only grows, so a block whose maximum is not above what it sees has nothing to add
     if (IO.delta && threadIdx.x == 0 && s_max > *reinterpret_cast<volatile unsigned long long*>(IO.delta)) atomicMax(IO.delta, s_max);
+}
+
+// =================================================================================================
+// best responses to mixed policies, and the value of a pair of them (soccer_best_response, soccer_evaluate_policies)
+// =================================================================================================
+// One launch is one synchronous sweep over all (policy, state) pairs, the policy in blockIdx.y, by minimax_sweep_kernel's
+// scheme: V double-buffered per policy, max |V_k - V_{k-1}| by atomicMax into the policy's word of this sweep, and a block
+// whose policy's previous word is below theta returns at once — a policy that has converged keeps the V, Qr and br of its
+// own last sweep while the others go on, and solves to the bits it gives alone.  Half a wave owns a state (lanes 0..24 and
+// 32..56): its 25 lanes gather the joint actions' lists into LDS, five of them form the five mixed sums in index order
+// (acc = acc + p[i] * q[i] from 0.0, not contracted), its first lane takes the first minimum / maximum, or the outer sum.
+constexpr int kResponseStates = 2 * kMinimaxWaves;      // states per workgroup
+
+template <int MODE>
+__global__ __launch_bounds__(kMinimaxBlock) void response_sweep_kernel(const ResponseIO IO) {
+    const size_t pol = blockIdx.y;
+    if (__longlong_as_double((long long)IO.prev[pol * (size_t)IO.word_stride]) < IO.mm.theta) return;   // this policy converged earlier
+    __shared__ double sQ[kResponseStates][25];
+    __shared__ double sR[kResponseStates][5];
+    __shared__ unsigned long long s_max;
+    const int slot = (int)(threadIdx.x >> 5), lane = (int)(threadIdx.x & 31u);
+    const int nS = IO.mm.nS;
+    const int s = (int)blockIdx.x * kResponseStates + slot;
+    const size_t row = pol * (size_t)nS + (size_t)(s < nS ? s : 0);
+    MinimaxIO M = IO.mm;
+    M.V = IO.V + pol * (size_t)nS;
+    if (threadIdx.x == 0) s_max = 0ull;
+    if (s < nS && lane < 25) sQ[slot][lane] = minimax_list_q(M, s * 25 + lane);
+    __syncthreads();
+    if (s < nS && lane < 5) {
+        // the fixed side's row; the lane's index belongs to the side that answers (kEvalPair: to A, the inner sum is over B's)
+        const double* p = (MODE == kRespondB ? IO.x : IO.y) + row * 5;
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) acc = acc + p[i] * (MODE == kRespondB ? sQ[slot][i * 5 + lane] : sQ[slot][lane * 5 + i]);
+        sR[slot][lane] = acc;
+        if (MODE != kEvalPair) IO.Qr[row * 5 + lane] = acc;
+    }
+    __syncthreads();
+    if (s < nS && lane == 0) {
+        double v = 0.0;
+        if (MODE == kEvalPair) {
+            const double* p = IO.x + row * 5;
+#pragma unroll
+            for (int i = 0; i < 5; ++i) v = v + p[i] * sR[slot][i];
+        } else {
+            int arg = 0;
+            v = sR[slot][0];
+#pragma unroll
+            for (int i = 1; i < 5; ++i) {
+                const double r = sR[slot][i];
+                if (MODE == kRespondB ? r < v : r > v) { v = r; arg = i; }       // the first index that attains it
+            }
+            IO.br[row] = arg;
+        }
+        IO.V_out[row] = v;
+        atomicMax(&s_max, (unsigned long long)__double_as_longlong(fabs(v - M.V[s])));
+    }
+    __syncthreads();
+    unsigned long long* word = IO.delta + pol * (size_t)IO.word_stride;
+    if (threadIdx.x == 0 && s_max > *reinterpret_cast<volatile unsigned long long*>(word)) atomicMax(word, s_max);
 }
 
 // the two-player lists assembled on the device from enumerate_kernel's output (build_minimax): a thread per (state, joint

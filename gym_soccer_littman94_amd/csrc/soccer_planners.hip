@@ -1,4 +1,4 @@
-// soccer_planners.hip — the transition table, the single-agent planners, minimax value iteration and the matrix-game solver (see soccer_handle.hpp).
+// soccer_planners.hip — the transition table, the single-agent planners, minimax value iteration, best responses to mixed policies and the matrix-game solver (see soccer_handle.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -383,4 +383,134 @@ extern "C" int soccer_minimax_value_iteration(soccer_handle* h, double theta, do
     if (iterations) *iterations = k;
     if (!done_at) return fail(h, SOCCER_E_STATE, "soccer_minimax_value_iteration stopped after max_sweeps = %d sweeps without converging", max_sweeps);
     return SOCCER_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// best responses to mixed policies and the value of a pair of them, for a batch of policies at once (two-player handles).
+// The lists are build_minimax's; a sweep is one launch of response_sweep_kernel over all (policy, state) pairs, and every
+// policy has its own word per sweep, so it stops at its own sweep and its result does not depend on what shares the batch.
+static int response_buffers(soccer_handle* h, int n, bool pairs) {
+    if (n <= h->br_cap && (!pairs || h->br_pairs)) return SOCCER_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t cap = (size_t)std::max(n, h->br_cap), rows = cap * (size_t)h->mm.nS;
+    pairs = pairs || h->br_pairs;
+    h->br_bufs.clear();
+    h->br_cap = 0; h->br_pairs = false;
+    int rc = h->br_bufs.alloc(h, rows * 5, &h->br_pol[0]);
+    if (!rc && pairs) rc = h->br_bufs.alloc(h, rows * 5, &h->br_pol[1]);
+    if (!rc) rc = h->br_bufs.alloc(h, rows, &h->br_V[0]);
+    if (!rc) rc = h->br_bufs.alloc(h, rows, &h->br_V[1]);
+    if (!rc) rc = h->br_bufs.alloc(h, rows * 5, &h->br_Qr);
+    if (!rc) rc = h->br_bufs.alloc(h, rows, &h->br_arg);
+    if (!rc) rc = h->br_bufs.alloc(h, cap * (kMinimaxBatch + 1), &h->br_words);
+    if (rc) { h->br_bufs.clear(); return rc; }
+    h->br_cap = (int)cap; h->br_pairs = pairs;
+    return SOCCER_OK;
+}
+
+// soccer_minimax_q_create's check of opponent_policy, on every live row of every policy (row 0 is not read)
+static int response_rows(soccer_handle* h, const char* what, const char* name, int n, const double* pol) {
+    if (!pol) return fail(h, SOCCER_E_INVALID, "%s: %s is NULL", what, name);
+    const int nS = h->rules.nS;
+    for (int i = 0; i < n; ++i) for (int s = 1; s < nS; ++s) {
+        const double* p = pol + ((size_t)i * nS + s) * 5;
+        double sum = 0.0;
+        for (int k = 0; k < 5; ++k) {
+            if (!(p[k] >= 0.0)) return fail(h, SOCCER_E_INVALID, "%s: %s[%d][%d][%d] is negative or not a number", what, name, i, s, k);
+            sum = sum + p[k];
+        }
+        if (!(std::fabs(sum - 1.0) <= 1e-8 + 1e-5)) return fail(h, SOCCER_E_INVALID, "%s: %s[%d][%d] does not sum to 1", what, name, i, s);
+    }
+    return SOCCER_OK;
+}
+
+// the caller's policies into a device block, row 0 of each as zeros
+static int response_upload(soccer_handle* h, double* dst, const double* pol, int n) {
+    const size_t pitch = (size_t)h->mm.nS * 40;
+    HIP_TRY(h, hipMemcpyAsync(dst, pol, (size_t)n * pitch, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemset2DAsync(dst, pitch, 0, 40, (size_t)n, h->stream));
+    return SOCCER_OK;
+}
+
+static int response_solve(soccer_handle* h, const char* what, int mode, int32_t n, const double* x, const double* y, double theta,
+                          double gamma, int32_t max_sweeps, double* V, double* Qr, int32_t* br, int32_t* iterations) {
+    if (int rc = minimax_check(h, what, gamma)) return rc;
+    if (n < 1 || n > SOCCER_BR_MAX_POLICIES)
+        return fail(h, SOCCER_E_INVALID, "%s: the number of policies must be 1 .. %d, not %d", what, SOCCER_BR_MAX_POLICIES, n);
+    if (max_sweeps < 1) return fail(h, SOCCER_E_INVALID, "max_sweeps must be >= 1");
+    if (!(theta >= 0.0)) return fail(h, SOCCER_E_INVALID, "theta must be >= 0");
+    if (mode != kRespondA) if (int rc = response_rows(h, what, mode == kEvalPair ? "pi_a" : "policy", n, x)) return rc;
+    if (mode != kRespondB) if (int rc = response_rows(h, what, mode == kEvalPair ? "pi_b" : "policy", n, y)) return rc;
+    if (int rc = minimax_prepare(h)) return rc;
+    if (int rc = response_buffers(h, n, mode == kEvalPair)) return rc;
+    const int nS = h->mm.nS;
+    constexpr int kWords = kMinimaxBatch + 1;
+    ResponseIO io{};
+    io.mm = h->mm; io.mm.gamma = gamma; io.mm.theta = theta;
+    io.Qr = h->br_Qr; io.br = h->br_arg; io.word_stride = kWords;
+    if (mode != kRespondA) { io.x = h->br_pol[0]; if (int rc = response_upload(h, h->br_pol[0], x, n)) return rc; }
+    if (mode != kRespondB) {
+        double* d = h->br_pol[mode == kEvalPair ? 1 : 0];
+        io.y = d;
+        if (int rc = response_upload(h, d, y, n)) return rc;
+    }
+    HIP_TRY(h, hipMemsetAsync(h->br_V[0], 0, (size_t)n * nS * 8, h->stream));                // V_0 = 0
+    // words[i][0] is the sweep before the batch's first: +inf (never converged) before sweep 1
+    std::vector<unsigned long long> words((size_t)n * kWords, 0ull);
+    std::vector<int32_t> done_at((size_t)n, 0);
+    const double inf = __builtin_huge_val();
+    for (int i = 0; i < n; ++i) std::memcpy(&words[(size_t)i * kWords], &inf, 8);
+    const dim3 grid((unsigned)((nS + kResponseStates - 1) / kResponseStates), (unsigned)n);
+    int32_t k0 = 1, open = n;                                                              // k0: first sweep of the batch
+    while (k0 <= max_sweeps && open) {
+        const int nb = (int)std::min<int64_t>(kMinimaxBatch, (int64_t)max_sweeps - k0 + 1);
+        for (int i = 0; i < n; ++i) for (int j = 1; j < kWords; ++j) words[(size_t)i * kWords + j] = 0ull;
+        HIP_TRY(h, hipMemcpyAsync(h->br_words, words.data(), words.size() * 8, hipMemcpyHostToDevice, h->stream));
+        for (int j = 1; j <= nb; ++j) {
+            const int32_t k = k0 + j - 1;
+            io.V = h->br_V[(k - 1) & 1]; io.V_out = h->br_V[k & 1]; io.delta = h->br_words + j; io.prev = h->br_words + j - 1;
+            if (mode == kRespondB) hipLaunchKernelGGL(response_sweep_kernel<kRespondB>, grid, dim3(kMinimaxBlock), 0, h->stream, io);
+            else if (mode == kRespondA) hipLaunchKernelGGL(response_sweep_kernel<kRespondA>, grid, dim3(kMinimaxBlock), 0, h->stream, io);
+            else hipLaunchKernelGGL(response_sweep_kernel<kEvalPair>, grid, dim3(kMinimaxBlock), 0, h->stream, io);
+        }
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemcpyAsync(words.data(), h->br_words, words.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (int i = 0; i < n; ++i) {
+            unsigned long long* w = &words[(size_t)i * kWords];
+            for (int j = 1; j <= nb && !done_at[i]; ++j) {
+                double d; std::memcpy(&d, &w[j], 8);
+                if (d < theta) { done_at[i] = k0 + j - 1; --open; }
+            }
+            w[0] = w[nb];                       // a policy that has converged keeps a word below theta: its blocks go on returning
+        }
+        k0 += nb;
+    }
+    int first_open = -1;
+    for (int i = 0; i < n; ++i) {
+        const int32_t k = done_at[i] ? done_at[i] : max_sweeps;
+        if (!done_at[i] && first_open < 0) first_open = i;
+        if (iterations) iterations[i] = k;
+        if (V) HIP_TRY(h, hipMemcpyAsync(V + (size_t)i * nS, h->br_V[k & 1] + (size_t)i * nS, (size_t)nS * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (Qr) HIP_TRY(h, hipMemcpyAsync(Qr, h->br_Qr, (size_t)n * nS * 40, hipMemcpyDeviceToHost, h->stream));
+    if (br) HIP_TRY(h, hipMemcpyAsync(br, h->br_arg, (size_t)n * nS * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (open) return fail(h, SOCCER_E_STATE, "%s: %d of %d policies had not converged after max_sweeps = %d sweeps (the first: policy %d)",
+                          what, open, n, max_sweeps, first_open);
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_best_response(soccer_handle* h, int32_t player, int32_t n_policies, const double* policy, double theta,
+                                    double discount_factor, int32_t max_sweeps, double* V, double* Qr, int32_t* br, int32_t* iterations) {
+    if (h && player != 0 && player != 1) return fail(h, SOCCER_E_INVALID, "soccer_best_response: player must be 0 (the policy is A's) or 1 (B's)");
+    const bool a_fixed = player == 0;
+    return response_solve(h, "soccer_best_response", a_fixed ? kRespondB : kRespondA, n_policies, a_fixed ? policy : nullptr,
+                          a_fixed ? nullptr : policy, theta, discount_factor, max_sweeps, V, Qr, br, iterations);
+}
+
+extern "C" int soccer_evaluate_policies(soccer_handle* h, int32_t n_pairs, const double* pi_a, const double* pi_b, double theta,
+                                        double discount_factor, int32_t max_sweeps, double* V, int32_t* iterations) {
+    return response_solve(h, "soccer_evaluate_policies", kEvalPair, n_pairs, pi_a, pi_b, theta, discount_factor, max_sweeps,
+                          V, nullptr, nullptr, iterations);
 }

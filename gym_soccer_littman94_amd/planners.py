@@ -99,3 +99,25 @@ def minimax_value_iteration(env, theta, discount_factor, max_sweeps=1000000):
             raise TypeError("planners expect a gym_soccer_littman94_amd environment")
         assert env.multiagent, "minimax_value_iteration needs a two-player environment (no player with a fixed policy)"
     return b.minimax_value_iteration(theta, discount_factor, max_sweeps=max_sweeps)
+
+
+def best_response(env, policy, player, theta, discount_factor, max_sweeps=1000000):
+    """The best response to a mixed policy of `player` (0: player A's policy, B answers; 1: player B's, A answers) in the
+    two-player game, on the device (include/soccer_hip.h, "best responses").  policy is [nS, 5], or [P, nS, 5] for a batch
+    solved in one sequence of launches.  Returns (br, V, Qr, iterations) like value_iteration; V is player A's value,
+    i.e. the policy's worst case."""
+    return _two_player_batch(env, "best_response").best_response(policy, player, theta, discount_factor, max_sweeps=max_sweeps)
+
+
+def exploitability(env, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000):
+    """How badly the best possible opponent beats each of two mixed policies: one best-response solve per side.  Either
+    policy is [nS, 5] or a batch [P, nS, 5].  Returns a dict, everything from player A's side:
+      v_a   worst case of pi_a (B answers it): a lower bound on the game's value
+      v_b   worst case of pi_b (A answers it): an upper bound
+      gap   v_b - v_a per state, >= 0 up to theta, and 0 exactly at an equilibrium pair
+      br_a  player A's best-response actions to pi_b,  br_b  player B's to pi_a
+      iterations  (sweeps of the solve behind v_a, sweeps of the solve behind v_b)"""
+    b = _two_player_batch(env, "exploitability")
+    br_b, v_a, _, k_a = b.best_response(pi_a, 0, theta, discount_factor, max_sweeps=max_sweeps)
+    br_a, v_b, _, k_b = b.best_response(pi_b, 1, theta, discount_factor, max_sweeps=max_sweeps)
+    return {"v_a": v_a, "v_b": v_b, "gap": v_b - v_a, "br_a": br_a, "br_b": br_b, "iterations": (k_a, k_b)}

@@ -64,7 +64,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration and soccer_minimax_q_* were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_best_response and soccer_evaluate_policies were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -360,6 +360,36 @@ int soccer_minimax_backup(soccer_handle* h, double discount_factor, const double
  * max_sweeps is reached; the outputs then hold the last iterate. */
 int soccer_minimax_value_iteration(soccer_handle* h, double theta, double discount_factor, int32_t max_sweeps,
                                    double* V, double* Q, double* pi_a, double* pi_b, int32_t* iterations);
+/* ---- best responses to mixed policies, and their exploitability (two-player handles) ---------------------------------
+ * How badly can the best possible opponent beat a mixed policy?  n policies are solved in ONE sequence of launches, a
+ * sweep over all (policy, state) pairs each.  With Q_k[s][a][b] the expression above over V_{k-1} (V_0 = 0, player A's
+ * reward) and every sum below a sequential float64 sum from 0.0 in index order, acc = acc + p[i] * q[i], not contracted:
+ *   response by B to A's mixed policy x (player = 0, the side that is held fixed):
+ *       Qr_k[s][b] = sum_a x[s][a] * Q_k[s][a][b],   V_k[s] = min_b Qr_k[s][b],   br[s] = the first b that attains it
+ *   response by A to B's mixed policy y (player = 1):
+ *       Qr_k[s][a] = sum_b y[s][b] * Q_k[s][a][b],   V_k[s] = max_a Qr_k[s][a],   br[s] = the first a that attains it
+ *   evaluation of a pair (x, y):
+ *       V_k[s] = sum_a x[s][a] * (sum_b y[s][b] * Q_k[s][a][b])
+ * Every mode stops at the first k with max_s |V_k[s] - V_{k-1}[s]| < theta and returns V_k, the Qr_k and br that belong
+ * to it and k — a self-consistent triple, as soccer_minimax_value_iteration's is.  V is always player A's value: the
+ * response to x is x's worst case, a lower bound on the game's value, the response to y an upper bound, and
+ * (response to y) - (response to x) >= 0 is the exploitability of the pair.
+ * Row 0 of a policy (the terminal observation) is not read: it counts as zeros, so V[0] = 0, Qr[0] = 0 and br[0] = 0.
+ * Every other row must be >= 0 and sum to 1 as soccer_minimax_q_config::opponent_policy must (SOCCER_E_INVALID, the
+ * message names policy and state); n is 1 .. SOCCER_BR_MAX_POLICIES, discount_factor in [0, 1], theta >= 0,
+ * max_sweeps >= 1.  policy / pi_a / pi_b are HOST [n][n_states][5]; the outputs are HOST V[n][n_states],
+ * Qr[n][n_states][5], br[n][n_states], iterations[n], and any of them may be NULL.
+ * Batches: policy i returns exactly the bits it returns when it is solved alone.  Each has its own stopping sweep k_i
+ * (iterations[i]); once it has converged its V, Qr and br stay those of sweep k_i while the others continue.
+ * SOCCER_E_STATE when some policy has not converged after max_sweeps: iterations[i] = max_sweeps for those, whose outputs
+ * hold the last iterate, and the others' results are complete.  Like the minimax planners these calls consume no tick,
+ * leave the lanes alone and return SOCCER_E_STATE during a graph capture. */
+#define SOCCER_BR_MAX_POLICIES 256
+int soccer_best_response(soccer_handle* h, int32_t player, int32_t n_policies, const double* policy,
+                         double theta, double discount_factor, int32_t max_sweeps,
+                         double* V, double* Qr, int32_t* br, int32_t* iterations);
+int soccer_evaluate_policies(soccer_handle* h, int32_t n_pairs, const double* pi_a, const double* pi_b,
+                             double theta, double discount_factor, int32_t max_sweeps, double* V, int32_t* iterations);
 /* ---- learners (two-player handles; minimax-Q, Littman 1994) ------------------------------------------------------
  * A learner lives on a two-player SOCCER_F_AUTORESET handle of at most 2^22 lanes and keeps ONE shared table
  * Q[n_states][5][5] (float64) on the device, with V[n_states] = val(Q[s]) and the stage-game strategies
