@@ -47,7 +47,10 @@ static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& i
         const int out = (io.prob_code || io.final_obs || P.step_stats) ? 2
                       : (io.reward_a_f32 || io.reward_b_f32 || io.finished || io.last_return) ? 1 : 0;
         const dim3 b(kBlock);
-#define SWAR_ARGS P.state + c0, P.state_stride, off(io.act_a, c0), off(io.act_b, c0), (h->capturing ? P.tick_in : nullptr), cn, (unsigned long long)(h->tick - 1), Q
+        // every launch part covers a multiple of 4 lanes (h->swar_launch_lanes is one), so bit 0 of the lane count is free: it carries
+        // the action-load policy into the kernel in a preloaded register (step_kernel_swar)
+        const unsigned long long act_stream = (h->cfg.flags & SOCCER_F_STREAM_ACTIONS) ? 1ull : 0ull;
+#define SWAR_ARGS P.state + c0, P.state_stride, off(io.act_a, c0), off(io.act_b, c0), (h->capturing ? P.tick_in : nullptr), cn | act_stream, (unsigned long long)(h->tick - 1), Q
         // six-stream handles that fit the byte arithmetic are host-mapped facade handles, tall pitches and SOCCER_STATE_LAYOUT=wide:
         // nobody times them, so they take the arithmetic geometry (GEO = 0, right for every pitch) instead of mirroring every shape
 #define SWAR_GO(OV, SV, PV, XV) do { if (P.state_layout == kStateWide) hipLaunchKernelGGL((step_kernel_swar<OV, SV, PV, 0, XV, kStateWide>), gh, b, 0, h->stream, SWAR_ARGS); \
@@ -62,13 +65,13 @@ static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& i
             const unsigned long long cn = std::min<unsigned long long>(h->swar_launch_lanes, P.first + P.n - c0);
             const bool last = c0 + cn == P.first + P.n;
             const dim3 gh(static_cast<unsigned>(((cn >> 2) + kBlock - 1) / kBlock));
-            SwarParams Q{h->swar_c, P.key0, P.key1, P.lane_offset + c0, 0ull, last ? P.tick_out : nullptr, P.misuse,
+            SwarParams Q{h->swar_c, P.key0, P.key1, P.lane_offset + c0, last ? P.tick_out : nullptr, P.misuse,
+                         off(io.obs, c0), off(io.reward, c0), off(io.terminated, c0), off(io.truncated, c0),
+                         off(io.reward_a_f32, c0), off(io.reward_b_f32, c0), off(io.finished, c0), off(io.last_return, c0),
+                         off(io.prob_code, c0), off(io.final_obs, c0),
                          P.step_stats ? P.hist : nullptr, P.hist_mask,
                          h->slip_c, reinterpret_cast<const swar::Quad*>(P.sub), h->d_slip_step_lut,
-                         (h->cfg.flags & SOCCER_F_STREAM_ACTIONS) ? 1u : 0u, P.policy_a, P.policy_b,
-                         off(io.obs, c0), off(io.reward, c0), off(io.terminated, c0), off(io.truncated, c0), off(io.prob_code, c0),
-                         off(io.final_obs, c0), off(io.reward_a_f32, c0), off(io.reward_b_f32, c0), off(io.finished, c0),
-                         off(io.last_return, c0), off(io.u_step, c0), off(io.u_reset, c0),
+                         P.policy_a, P.policy_b, off(io.u_step, c0), off(io.u_reset, c0),
                          h->d_slip_f64, h->d_worklist, worklist_count(h)};
             if (P.policy_a || P.policy_b) SWAR_OUT(true); else SWAR_OUT(false);
             if (expl_slip) {

@@ -279,8 +279,10 @@ __device__ __forceinline__ void hot_group(const KernelParams& P, const StepIO& I
 // The seven leading scalar arguments (14 dwords) repeat the fields of P / IO that the first loads depend on
 // (the hot path always starts at lane 0 of the handle):
 // the library is built with -mllvm -amdgpu-kernarg-preload-count=14, so they arrive in SGPRs at wave launch
-// and the nine data loads are issued without first waiting for a scalar load of the kernarg segment
-// (-0.3 .. -0.6 us per launch); the rest of P is fetched while they are in flight.
+// and the data loads can be issued without first waiting for a scalar load of the kernarg segment — as long as nothing
+// else the addresses or the branches ahead of the loads need lives in P / IO: whatever does is one scalar-memory round trip
+// in front of the first load again.  (Measured when it was introduced: -0.16 us per launch; the floor lab's copy kernel
+// does not see such a round trip at all, profiles/kernarg_floor.md.)  The rest of P is fetched while the loads are in flight.
 template <bool SLIP, bool INT_ONLY = false>
 __global__ __launch_bounds__(kBlock) void step_kernel_hot(uint8_t* state, unsigned long long state_stride,
                                                           const int8_t* act_a, const int8_t* act_b,
@@ -304,23 +306,35 @@ __global__ __launch_bounds__(kBlock) void step_kernel_hot(uint8_t* state, unsign
 // flight, seven or ten non-temporal stores, leading scalar
 // arguments preloaded into SGPRs) — but no byte peeling, no per-lane loop and NO rule-table read: ~45 vector
 // instructions per env-step instead of ~128 and no dependent gather between the loads and the stores.
+// What is fetched when (profiles/kernarg_ab.md):
+//   preloaded (14 dwords)   the state base and stride, the two action bases, tick_in, the lane count with the action-load policy
+//                           in its bit 0, tick_val: all the addresses of the data loads and the branch ahead of the action loads
+//                           need — no scalar memory load stands between wave start and the data loads (SLIPM == 2 fetches the
+//                           pointer of its table, the one thing its table loads need beyond that);
+//   one batch of s_loads    everything else the launch reads of SwarParams (constants, keys, lane_offset, the result pointers,
+//                           tick_out, misuse), issued around the data loads and waited for ONCE, together with the tick,
+//                           ahead of the Philox block;
+//   nothing                 between the arithmetic and the stores.
 // Takes every Philox-driven, dword-aligned step of a slip_prob == 0 handle whose pitch fits the byte arithmetic
 // (swar::fits: every golden pitch up to 11x7 does); the template parameters are described above the kernel.
+// What the OUT = 0 shape reads comes first and contiguous, so that the one batch of scalar loads the kernel issues behind its
+// data loads touches as few cache lines of the argument block as possible; what only other shapes read goes behind.  (No
+// `first`: the host offsets every pointer itself, the kernel's lane 0 is the launch part's first lane.  The action-load
+// policy rides in bit 0 of the preloaded lane count.)
 struct SwarParams {
     swar::Consts C;
     uint32_t key0, key1;
-    unsigned long long lane_offset;
-    unsigned long long first;               // first lane (within the handle) this launch covers; multiple of 4
+    unsigned long long lane_offset;         // global lane of the launch part's lane 0; multiple of 4
     unsigned long long* tick_out;
     unsigned int* misuse;                   // [0] a frozen lane was stepped (:376), [1] an action byte outside 0..4 (:393)
+    uint16_t* obs; int8_t* reward; uint8_t* terminated; uint8_t* truncated;
+    // ---- other shapes only ----
+    float* reward_a_f32; float* reward_b_f32; uint8_t* finished; int8_t* last_return;   // OUT >= 1
+    uint8_t* prob_code; uint16_t* final_obs;                          // OUT == 2
     unsigned long long* hist; uint32_t hist_mask;   // OUT == 2: episode histogram slots (SOCCER_F_STEP_STATS), or nullptr
     swar::SlipConsts L; const swar::Quad* sub;   // SLIPM == 1: integer cumulative weights / the nine rows of quarter thresholds
     const uint32_t* slip_lut;               // SLIPM == 2: SlipTables::lut_step (kSlipStepBuckets bytes), then T (kSlipThresholds words)
-    uint32_t act_stream;                    // SOCCER_F_STREAM_ACTIONS: the action streams are read with the non-temporal hint
     const int8_t* policy_a; const int8_t* policy_b;   // POLICY: the fixed side's int8[nS] policy (the other is nullptr)
-    uint16_t* obs; int8_t* reward; uint8_t* terminated; uint8_t* truncated;
-    uint8_t* prob_code; uint16_t* final_obs;                          // OUT == 2
-    float* reward_a_f32; float* reward_b_f32; uint8_t* finished; int8_t* last_return;   // OUT >= 1
     const double* u_step; const double* u_reset;   // EXPL: caller-supplied uniforms (16-byte aligned; either may be nullptr: Philox then)
     const SlipF64* f64;                            // SLIPM == 3: the nominal float64 thresholds of the slip list
     uint32_t* worklist; uint32_t* work_count;      // SLIPM == 3: groups left to the exact walk (see StepIO)
@@ -361,14 +375,19 @@ template <int OUT, int SLIPM = 0, bool POLICY = false, int GEO = 0, bool EXPL = 
 __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_in, unsigned long long state_stride,
                                                            const int8_t* act_a, const int8_t* act_b,
                                                            const unsigned long long* tick_in,
-                                                           unsigned long long n, unsigned long long tick_val,
+                                                           unsigned long long n_policy, unsigned long long tick_val,
                                                            const SwarParams Q) {
     constexpr bool FULL = OUT == 2;
     constexpr bool SLIP = SLIPM != 0;
     static_assert((SLIPM == 3) ? EXPL : (!EXPL || SLIPM == 0), "caller-supplied uniforms: SLIPM 0 (dyadic lists) or 3 (float64 slip decision)");
     static_assert(kSlipStepBuckets == 64 * 16 && kSlipThresholds <= 64, "one 16-byte piece of the table per lane of a wave");
     const unsigned long long g = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
-    const bool active = (g << 2) < n;                                // n is a multiple of 4 here
+    // the lane count is a multiple of 4 here; its bit 0 is the action-load policy (SOCCER_F_STREAM_ACTIONS), which the branch
+    // ahead of the action loads needs: all 14 preloaded dwords are taken, and a policy fetched from the argument block would put
+    // a scalar-memory round trip in front of the first data load
+    const unsigned long long n = n_policy & ~3ull;
+    const bool act_stream = ((uint32_t)n_policy & 1u) != 0u;
+    const bool active = (g << 2) < n;
     // SLIPM == 2: this lane's 16 bytes of the bucket table and its entry of the threshold list — the oldest loads
     // of the wave, so the wait for them does not wait for the state.  Every WAVE keeps a copy of its own: no workgroup barrier.
     const uint32_t lane = threadIdx.x & 63u;
@@ -379,13 +398,13 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
     }
     if (SLIPM != 2 && !FULL && !active) return;
     HistAcc<true> hist;
-    const bool stats = FULL && Q.hist != nullptr;                    // wave-uniform
     if (FULL) { hist.fin = 0u; hist.pos = 0u; hist.neg = 0u; hist.old01 = make_ulonglong2(0ull, 0ull); hist.old2 = 0ull; }
-    if (stats) hist.init_at(Q.hist, Q.hist_mask);
     // Byte offsets are 32-bit (the host launches at most kSwarLaunchLanes lanes at a time): a uniform base plus a 32-bit
     // per-thread offset is what the compiler turns into SGPR-base addressing (global_load v, v_off, s[base:base+1]) — no
     // 64-bit vector add per stream (20 vector instructions of about 245 with 64-bit offsets).
-    const uint32_t i0 = (uint32_t)Q.first + ((uint32_t)g << 2);
+    // The offset is made of the thread's index alone, and the bases are preloaded: NOTHING is fetched from the argument block
+    // between wave start and the data loads.
+    const uint32_t i0 = (uint32_t)g << 2;
 #define AT(base, off) (reinterpret_cast<const uint8_t*>(base) + (off))
     const uint8_t* sp = state_in;
     swar::Group S{0u, 0u, 0u, 0u, 0u, 0u};
@@ -393,7 +412,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
     // SLIPM == 2: the state loads are issued by every lane (lanes beyond n re-read the first group) — under a branch the wait for
     // the table loads ahead of them could no longer count on their order and would become a wait for everything
     const bool fetch = SLIPM == 2 ? true : active;
-    const uint32_t l0 = SLIPM == 2 ? (active ? i0 : (uint32_t)Q.first) : i0;
+    const uint32_t l0 = SLIPM == 2 ? (active ? i0 : 0u) : i0;
     if (fetch) {
         // The action streams first, by plain loads unless the caller asked for the non-temporal hint (include/soccer_hip.h): buffers
         // written or read a few steps ago are served from the Infinity Cache, and a non-temporal load gives that up — 0.2 us per
@@ -402,7 +421,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
         const bool ld_a = !POLICY || !Q.policy_a, ld_b = !POLICY || !Q.policy_b;
         // (each block gets the offset through an empty asm of its own: instruction selection works a block at a time and only
         // turns base + offset into SGPR-base addressing when it sees the addition in the block of the access)
-        if (Q.act_stream) {
+        if (act_stream) {
             uint32_t la = l0; asm("" : "+v"(la));
             if (ld_a) aa = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(act_a, la)));
             if (ld_b) ab = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(act_b, la)));
@@ -428,6 +447,32 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
             S.tt = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(AT(sp + 5 * state_stride, ls)));
         }
     }
+    // the tick: by value for eager launches, from the device slot for captured ones (read after the data loads are issued)
+    const unsigned long long tick = tick_in ? *tick_in : tick_val;
+    // Everything else the launch needs of the argument block is requested HERE, in one batch right behind the data loads and
+    // beside the tick: the pointers the stores need and the constants that only the step reads — which the compiler would
+    // otherwise fetch where they are used, one scalar-memory round trip after the other between the arithmetic and the
+    // stores — are inputs of an empty statement whose output is the Philox key, so they are in registers before the Philox
+    // block starts.  Scalar loads return out of order: the one wait ahead of the Philox block, which the tick needs anyway,
+    // covers the batch.  (The pointers are inputs only, so they keep their address space; the statement is not `volatile`: a
+    // volatile asm counts as a write to memory, and scalar loads behind it would become vector loads.)
+    // (not with SLIPM == 3: those shapes hold the float64 thresholds in scalar registers across the comparisons, and another
+    // dozen live pointers there end in scratch memory; their stores fetch their pointers where they are used, as before)
+    constexpr bool PIN = SLIPM != 3;
+    uint32_t key0 = Q.key0;
+    unsigned long long* const tick_out = Q.tick_out; unsigned int* const misuse = Q.misuse;
+    uint16_t* const o_obs = Q.obs; int8_t* const o_reward = Q.reward; uint8_t* const o_term = Q.terminated; uint8_t* const o_trunc = Q.truncated;
+    if (PIN) asm("" : "+s"(key0) : "s"(tick_out), "s"(misuse), "s"(o_obs), "s"(o_reward), "s"(o_term), "s"(o_trunc),
+                                   "s"(Q.C.Wx2), "s"(Q.C.Wm2x2), "s"(Q.C.Wm1x4), "s"(Q.C.trunc_add), "s"(Q.C.obs_mul));
+    float* const o_raf = OUT >= 1 ? Q.reward_a_f32 : nullptr; float* const o_rbf = OUT >= 1 ? Q.reward_b_f32 : nullptr;
+    uint8_t* const o_fin = OUT >= 1 ? Q.finished : nullptr; int8_t* const o_last = OUT >= 1 ? Q.last_return : nullptr;
+    if (PIN && OUT >= 1) asm("" : "+s"(key0) : "s"(o_raf), "s"(o_rbf), "s"(o_fin), "s"(o_last));
+    uint8_t* const o_code = FULL ? Q.prob_code : nullptr; uint16_t* const o_fobs = FULL ? Q.final_obs : nullptr;
+    unsigned long long* const hist_at = FULL ? Q.hist : nullptr; const uint32_t hist_mask = FULL ? Q.hist_mask : 0u;
+    if (PIN && FULL) asm("" : "+s"(key0) : "s"(o_code), "s"(o_fobs), "s"(hist_at), "s"(hist_mask));
+    // (the wave's histogram slot is read behind the data loads as well: its address comes from the argument block)
+    const bool stats = FULL && hist_at != nullptr;                   // wave-uniform
+    if (stats) hist.init_at(hist_at, hist_mask);
     // EXPL: the four lanes' uniforms, as floor(4u) (two bits each) — behind the state loads, ahead of the Philox block
     uint32_t xq = 0u, xr = 0u;
     double us0 = 0.0, us1 = 0.0, us2 = 0.0, us3 = 0.0;               // SLIPM == 3: the step uniforms themselves
@@ -444,13 +489,11 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
         if (SLIPM != 3 && Q.u_step) xq = quarters(Q.u_step);
         if (Q.u_reset) xr = quarters(Q.u_reset);
     }
-    // the tick: by value for eager launches, from the device slot for captured ones (read after the data loads are issued)
-    const unsigned long long tick = tick_in ? *tick_in : tick_val;
     const unsigned long long q = (Q.lane_offset + i0) >> 2;     // the thread's 4 lanes are exactly one Philox block
     const unsigned long long bt = block_tick<SLIP>(tick);
     Philox4 blk{{0u, 0u, 0u, 0u}};
     if (!EXPL || !Q.u_step || !Q.u_reset)                           // (wave-uniform; both uniforms supplied: no block is needed)
-        blk = philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)bt, (uint32_t)(bt >> 32), Q.key0, Q.key1);
+        blk = philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)bt, (uint32_t)(bt >> 32), key0, Q.key1);
     const uint8_t* slip_lut = nullptr; const uint32_t* slip_thr = nullptr;
     if (SLIPM == 2) {                                                // park the table: all 64 lanes, whether their lanes exist or not
         __shared__ __attribute__((aligned(16))) uint32_t s_slip[SLIPM == 2 ? kBlock / 64 : 1][SLIPM == 2 ? kSlipStepLdsWords : 4];
@@ -463,7 +506,8 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
         if (!FULL && !active) return;
     }
     if (active) {
-        if (LAYOUT == kStatePacked) swar::unpack3(S.ra, S.ca, S.tt, S);
+        // (without a fixed policy nothing ahead of the step reads the state: it is taken apart behind step4_moves, below)
+        if (LAYOUT == kStatePacked && POLICY) swar::unpack3(S.ra, S.ca, S.tt, S);
         if (POLICY) {                                               // the fixed side acts on the current observation (:187-188)
             uint32_t s_lo, s_hi;
             const uint32_t cc0 = swar::bfi(swar::mask_of(S.ps << 7), S.cb, S.ca);
@@ -510,14 +554,20 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
                 if (Q.u_reset) rnd.rs = xr >> Q.C.isd_shift;
             }
         }
+        // What the step needs of the actions and the draws alone goes ahead of the state: the actions are the wave's oldest loads,
+        // so this runs while the state is still in flight.  (The empty statement ties the state words to it: the scheduler works a
+        // block at a time and would otherwise be free to put the wait for the state first.)
+        const swar::Moves4 M = swar::step4_moves<SLIP>(Q.C, aa, ab, sa, sb, rnd);
+        asm("" : "+v"(S.ra), "+v"(S.ca), "+v"(S.tt) : "v"(M.dra), "v"(M.dca), "v"(M.drb), "v"(M.dcb), "v"(M.ira), "v"(M.irb), "v"(M.ip), "v"(M.bad_action));
+        if (LAYOUT == kStatePacked && !POLICY) swar::unpack3(S.ra, S.ca, S.tt, S);
         if (!listed) {
         // Frozen lanes and goal tuples exist only without auto-reset or after a state injection; a thread none of whose lanes is
         // in either condition (nearly every thread of an auto-resetting handle) takes the step without the code for them —
         // 31 vector instructions fewer, 12 for the test: in this kernel every instruction shows (5.6 ns).
         const uint32_t edge = swar::is_zero(S.ca) | swar::is_zero(S.cb) | swar::is_zero(S.ca ^ Q.C.Wm1x4) | swar::is_zero(S.cb ^ Q.C.Wm1x4);
         const bool special = Q.C.autoreset == 0u || (((S.ps << 6) | edge) & swar::K80) != 0u;
-        if (special) swar::step4<true, FULL, SLIP, GEO>(Q.C, S, aa, ab, sa, sb, cls4, rnd, o);
-        else swar::step4<false, FULL, SLIP, GEO>(Q.C, S, aa, ab, sa, sb, cls4, rnd, o);
+        if (special) swar::step4_state<true, FULL, SLIP, GEO>(Q.C, S, M, cls4, rnd, o);
+        else swar::step4_state<false, FULL, SLIP, GEO>(Q.C, S, M, cls4, rnd, o);
         uint8_t* sw = const_cast<uint8_t*>(sp);
         // the stores' offset is opaque to the optimiser: it would otherwise hoist the 64-bit addresses of the loads above the
         // branch and reuse them (instruction selection works a block at a time and then no longer sees base + offset)
@@ -538,47 +588,47 @@ __global__ __launch_bounds__(kBlock) void step_kernel_swar(const uint8_t* state_
             __builtin_nontemporal_store(S.ps, reinterpret_cast<uint32_t*>(ATW(sw + 4 * state_stride, j0)));
             __builtin_nontemporal_store(S.tt, reinterpret_cast<uint32_t*>(ATW(sw + 5 * state_stride, j0)));
         }
-        if (Q.obs) __builtin_nontemporal_store((unsigned long long)o.obs_lo | ((unsigned long long)o.obs_hi << 32),
-                                               reinterpret_cast<unsigned long long*>(ATW(Q.obs, j0x2)));
-        if (Q.reward) __builtin_nontemporal_store(o.rew, reinterpret_cast<uint32_t*>(ATW(Q.reward, j0)));
-        if (Q.terminated) __builtin_nontemporal_store(o.term, reinterpret_cast<uint32_t*>(ATW(Q.terminated, j0)));
-        if (Q.truncated) __builtin_nontemporal_store(o.trunc, reinterpret_cast<uint32_t*>(ATW(Q.truncated, j0)));
+        if (o_obs) __builtin_nontemporal_store((unsigned long long)o.obs_lo | ((unsigned long long)o.obs_hi << 32),
+                                               reinterpret_cast<unsigned long long*>(ATW(o_obs, j0x2)));
+        if (o_reward) __builtin_nontemporal_store(o.rew, reinterpret_cast<uint32_t*>(ATW(o_reward, j0)));
+        if (o_term) __builtin_nontemporal_store(o.term, reinterpret_cast<uint32_t*>(ATW(o_term, j0)));
+        if (o_trunc) __builtin_nontemporal_store(o.trunc, reinterpret_cast<uint32_t*>(ATW(o_trunc, j0)));
         if (OUT >= 1) {
-            if (Q.reward_a_f32 || Q.reward_b_f32) {                 // the rewards as the floats a gym caller reads (:400-402)
+            if (o_raf || o_rbf) {                                   // the rewards as the floats a gym caller reads (:400-402)
                 const int32_t r = (int32_t)o.rew;
                 const float f0 = (float)((r << 24) >> 24), f1 = (float)((r << 16) >> 24), f2 = (float)((r << 8) >> 24), f3 = (float)(r >> 24);
                 typedef float f4 __attribute__((ext_vector_type(4)));
-                if (Q.reward_a_f32) { const f4 va = {f0, f1, f2, f3}; __builtin_nontemporal_store(va, reinterpret_cast<f4*>(ATW(Q.reward_a_f32, j0x4))); }
-                if (Q.reward_b_f32) { const f4 vb = {0.0f - f0, 0.0f - f1, 0.0f - f2, 0.0f - f3};
-                                      __builtin_nontemporal_store(vb, reinterpret_cast<f4*>(ATW(Q.reward_b_f32, j0x4))); }
+                if (o_raf) { const f4 va = {f0, f1, f2, f3}; __builtin_nontemporal_store(va, reinterpret_cast<f4*>(ATW(o_raf, j0x4))); }
+                if (o_rbf) { const f4 vb = {0.0f - f0, 0.0f - f1, 0.0f - f2, 0.0f - f3};
+                             __builtin_nontemporal_store(vb, reinterpret_cast<f4*>(ATW(o_rbf, j0x4))); }
             }
-            if (Q.finished) __builtin_nontemporal_store(o.term | o.trunc, reinterpret_cast<uint32_t*>(ATW(Q.finished, j0)));
+            if (o_fin) __builtin_nontemporal_store(o.term | o.trunc, reinterpret_cast<uint32_t*>(ATW(o_fin, j0)));
             // A's return of the episode that just ended = the reward of its last step (only that step can carry one);
             // lanes whose episode goes on keep what the stream holds.  Rare: one read-modify-write of the thread's own dword.
-            if (Q.last_return && (o.finished & swar::K80)) {
-                uint32_t* lr = reinterpret_cast<uint32_t*>(ATW(Q.last_return, j0));
+            if (o_last && (o.finished & swar::K80)) {
+                uint32_t* lr = reinterpret_cast<uint32_t*>(ATW(o_last, j0));
                 *lr = swar::bfi(swar::mask_of(o.finished), o.rew, *lr);
             }
         }
         if (FULL) {
-            if (Q.prob_code) __builtin_nontemporal_store(o.code, reinterpret_cast<uint32_t*>(ATW(Q.prob_code, j0)));
-            if (Q.final_obs) __builtin_nontemporal_store((unsigned long long)o.fin_lo | ((unsigned long long)o.fin_hi << 32),
-                                                         reinterpret_cast<unsigned long long*>(ATW(Q.final_obs, j0x2)));
+            if (o_code) __builtin_nontemporal_store(o.code, reinterpret_cast<uint32_t*>(ATW(o_code, j0)));
+            if (o_fobs) __builtin_nontemporal_store((unsigned long long)o.fin_lo | ((unsigned long long)o.fin_hi << 32),
+                                                         reinterpret_cast<unsigned long long*>(ATW(o_fobs, j0x2)));
             // finished episodes by return: a reward byte is 0x01 / 0xff only on the step that ends the episode
             if (stats) hist.add_totals((uint32_t)__builtin_popcount(o.finished & swar::K80),
                                        (int32_t)__builtin_popcount(o.rew & swar::K01) - 2 * (int32_t)__builtin_popcount(o.rew & swar::K80),
                                        (uint32_t)__builtin_popcount(o.rew & swar::K01));
         }
-        if (o.frozen) Q.misuse[0] = 1u;
-        if (o.bad_action) Q.misuse[1] = 1u;
+        if (o.frozen) misuse[0] = 1u;
+        if (o.bad_action) misuse[1] = 1u;
         }
         // (published last: a store in flight ahead of the loads' waits would turn them into waits for everything — loads and
         // stores share the wave's counter and complete out of order with respect to each other)
-        if (Q.tick_out && blockIdx.x == 0 && threadIdx.x == 0) *Q.tick_out = tick + 1ull;
+        if (tick_out && blockIdx.x == 0 && threadIdx.x == 0) *tick_out = tick + 1ull;
 #undef AT
 #undef ATW
     }
-    if (stats) hist.flush_at(Q.hist, Q.hist_mask);
+    if (stats) hist.flush_at(hist_at, hist_mask);
 }
 
 }  // namespace soccer

@@ -293,9 +293,15 @@ constexpr uint32_t T_SLIP2_LO = 0x01030400u, T_SLIP2_HI = 0x00000002u;
 // one player's tentative cell (_next_cell :364-373) for four lanes: rows clamped to the pitch, a step into a goal
 // column reverted unless the player holds the ball and stands in a goal row.  `mv` = the (possibly slipped) move,
 // `score` = flag word "holds the ball and is in a goal row" (an EAST / WEST move never changes the row).
-template <int GEO>
-SOCCER_HD void move4(const Consts& C, uint32_t r, uint32_t c, uint32_t mv, uint32_t score, uint32_t& nr, uint32_t& nc) {
-    const uint32_t u = r + lut8(T_DR1_HI, T_DR1_LO, mv);                   // row + 1 + drow, in 0 .. H + 1
+// DELTAS: the caller has looked the move up already (move_delta): `mv` is the row delta + 1 per byte and `dc` the column
+// delta, east - west, as ONE 32-bit word whose borrows cancel when it is added to the columns.
+SOCCER_HD void move_delta(uint32_t mv, uint32_t& dr1, uint32_t& dc) {
+    dr1 = lut8(T_DR1_HI, T_DR1_LO, mv);
+    dc = lut8(T_E_HI, T_E_LO, mv) - lut8(T_W_HI, T_W_LO, mv);
+}
+template <int GEO, bool DELTAS = false>
+SOCCER_HD void move4(const Consts& C, uint32_t r, uint32_t c, uint32_t mv, uint32_t dc, uint32_t score, uint32_t& nr, uint32_t& nc) {
+    const uint32_t u = r + (DELTAS ? mv : lut8(T_DR1_HI, T_DR1_LO, mv));   // row + 1 + drow, in 0 .. H + 1
     if (GEO == 1) {
         nr = perm(C.row_hi, C.row_lo, u);                                  // clamp (:365) by table
     } else {
@@ -303,7 +309,7 @@ SOCCER_HD void move4(const Consts& C, uint32_t r, uint32_t c, uint32_t mv, uint3
         const uint32_t at_bot = one_of(is_zero(u ^ C.Hp1x4));              // stepped south off row H - 1
         nr = u + at_top + 0xFEFEFEFFu - at_bot;                            // (u + at_top) >= 1 in every byte
     }
-    const uint32_t ct = c + lut8(T_E_HI, T_E_LO, mv) - lut8(T_W_HI, T_W_LO, mv);   // :366
+    const uint32_t ct = DELTAS ? c + dc : c + lut8(T_E_HI, T_E_LO, mv) - lut8(T_W_HI, T_W_LO, mv);   // :366
     if (GEO == 1) {
         // a step into a goal column that is not a score is undone (:369-372): from column 1 / W - 2 that is a clamp
         nc = bfi(mask_of(score), ct, perm(C.col_hi, C.col_lo, ct));
@@ -438,6 +444,34 @@ SOCCER_HD void reset4(const Consts& C, Group& S, uint32_t mask4, const Rand4& R,
     obs4<MASKED>(C, S.ra, S.ca, S.rb, S.cb, S.ps & K01, zero7, obs_lo, obs_hi);
 }
 
+// A step in two parts, for a kernel whose state is still in flight when its actions have arrived (step_kernel_swar: the
+// actions are the wave's oldest loads).  step4_moves takes what does NOT depend on the state — the action words, with SLIP
+// the selected moves, and the reset draw: the canonical actions and the misuse report, the row / column deltas of both
+// players' moves and the ISD entry of each lane's reset draw (~20 vector instructions); step4_state takes the state.
+// GENERAL lanes replace the actions by NOOP once the hold mask is known, so that shape looks the tables up again from
+// the replaced actions, in place, and reads only aa / ab / sa / sb / bad_action.  (The two not-NOOP flag words are one
+// v_perm_b32 each from aa / ab, which the GENERAL shape needs anyway: carried across the wait for the state as well they
+// cost step_kernel_swar two more registers than it had, so they stay behind it.)
+// step4 itself — the rollout, the reset path, the host checker — looks everything up in place: one body (step4_body,
+// PRE = false) serves both, so the rules are stated once.
+struct Moves4 {
+    uint32_t aa, ab;               // the actions as executed (canon4)
+    uint32_t sa, sb;               // the moves: the actions, or with SLIP the selected combination's (low three bits)
+    uint32_t dra, dca, drb, dcb;   // move_delta of sa / sb
+    uint32_t ira, irb, ip;         // the ISD entry (row of A, row of B, possession) of each lane's reset draw (:414)
+    uint32_t bad_action;           // non-zero: some action byte was outside 0..4
+};
+template <bool SLIP>
+SOCCER_HD Moves4 step4_moves(const Consts& C, uint32_t aa_raw, uint32_t ab_raw, uint32_t sa, uint32_t sb, const Rand4& R) {
+    Moves4 M;
+    M.aa = canon4(aa_raw); M.ab = canon4(ab_raw); M.bad_action = (M.aa ^ aa_raw) | (M.ab ^ ab_raw);
+    if (!SLIP) { M.sa = M.aa; M.sb = M.ab; } else { M.sa = sa & 0x07070707u; M.sb = sb & 0x07070707u; }
+    move_delta(M.sa, M.dra, M.dca); move_delta(M.sb, M.drb, M.dcb);
+    const uint32_t idx = R.rs & C.isd_mask;                                // lane j's reset draw
+    M.ira = perm(0u, C.isd_ra, idx); M.irb = perm(0u, C.isd_rb, idx); M.ip = perm(0u, C.isd_p, idx);
+    return M;
+}
+
 // GENERAL = false: the steady state of an auto-resetting handle — no lane is frozen or stands in a goal tuple on
 //   entry (so none ever will): the code for those cases is compiled out.  The host tracks when that holds.
 // FULL: also produce final_obs and prob_code (VectorSoccerEnv's info / final_observation).
@@ -450,13 +484,16 @@ SOCCER_HD void reset4(const Consts& C, Group& S, uint32_t mask4, const Rand4& R,
 // R: the lanes' random bits of this tick (Rand4); with SLIP its kq is the quarter from slip_select4, k4 << 6.
 // TRUSTED: the action bytes were produced by the kernel itself (sampled in 0..4): no canonical form, no misuse report.
 // GEO: 0 the pitch geometry by arithmetic (any pitch that fits), 1 by byte tables (Consts::small).
-template <bool GENERAL, bool FULL, bool SLIP, int GEO = 0, bool TRUSTED = false>
-SOCCER_HD void step4(const Consts& C, Group& S, uint32_t aa_raw, uint32_t ab_raw, uint32_t sa, uint32_t sb,
-                     uint32_t cls4, const Rand4& R, Out& o) {
+// PRE (step4_state): the actions, the moves and, unless GENERAL, their tables come from M (step4_moves).
+template <bool GENERAL, bool FULL, bool SLIP, int GEO, bool TRUSTED, bool PRE>
+SOCCER_HD void step4_body(const Consts& C, Group& S, uint32_t aa_raw, uint32_t ab_raw, uint32_t sa, uint32_t sb,
+                          uint32_t cls4, const Rand4& R, const Moves4& M, Out& o) {
+    constexpr bool TABLES = PRE && !GENERAL;                               // M's deltas and ISD entry are the lanes'
     const uint32_t ra = S.ra, ca = S.ca, rb = S.rb, cb = S.cb, ps = S.ps, t = S.tt;
     // ---- actions: the low three bits select the move, 5..7 are NOOP; any byte outside 0..4 is reported ---------------
     uint32_t aa = aa_raw, ab = ab_raw;
-    if (TRUSTED) o.bad_action = 0u;
+    if (PRE) { aa = M.aa; ab = M.ab; sa = M.sa; sb = M.sb; o.bad_action = M.bad_action; }
+    else if (TRUSTED) o.bad_action = 0u;
     else { aa = canon4(aa_raw); ab = canon4(ab_raw); o.bad_action = (aa ^ aa_raw) | (ab ^ ab_raw); }
     const uint32_t p7 = ps << 7;                                           // flag: B has the ball
     const uint32_t pm = mask_of(p7);
@@ -476,8 +513,8 @@ SOCCER_HD void step4(const Consts& C, Group& S, uint32_t aa_raw, uint32_t ab_raw
     if (GEO == 1) { gra = perm(C.grow_hi, C.grow_lo, ra); grb = perm(C.grow_hi, C.grow_lo, rb); }
     else { gra = bfi(ra + C.gr_hi_add, 0u, ra + C.gr_lo_add); grb = bfi(rb + C.gr_hi_add, 0u, rb + C.gr_lo_add); }
     uint32_t nra, nca, nrb, ncb;
-    move4<GEO>(C, ra, ca, sa, bfi(p7, 0u, gra), nra, nca);                 // A holds the ball when p == 0
-    move4<GEO>(C, rb, cb, sb, grb & p7, nrb, ncb);
+    move4<GEO, TABLES>(C, ra, ca, TABLES ? M.dra : sa, M.dca, bfi(p7, 0u, gra), nra, nca);   // A holds the ball when p == 0
+    move4<GEO, TABLES>(C, rb, cb, TABLES ? M.drb : sb, M.dcb, grb & p7, nrb, ncb);
     // ---- ordered collision resolution (:315-360) on cell ids ---------------------------------------------------------
     const uint32_t A = pk_mad(ra, C.Wx2, ca), B = pk_mad(rb, C.Wx2, cb);
     const uint32_t nA = pk_mad(nra, C.Wx2, nca), nB = pk_mad(nrb, C.Wx2, ncb);
@@ -533,9 +570,9 @@ SOCCER_HD void step4(const Consts& C, Group& S, uint32_t aa_raw, uint32_t ab_raw
     if (!GENERAL || C.autoreset) {                                         // wave-uniform
         const uint32_t rm = mask_of(fin7);
         const uint32_t idx = R.rs & C.isd_mask;                            // lane j's reset draw
-        fra = bfi(rm, perm(0u, C.isd_ra, idx), fra); fca = bfi(rm, C.isd_ca4, fca);
-        frb = bfi(rm, perm(0u, C.isd_rb, idx), frb); fcb = bfi(rm, C.isd_cb4, fcb);
-        p01 = bfi(rm, perm(0u, C.isd_p, idx), p01);
+        fra = bfi(rm, TABLES ? M.ira : perm(0u, C.isd_ra, idx), fra); fca = bfi(rm, C.isd_ca4, fca);
+        frb = bfi(rm, TABLES ? M.irb : perm(0u, C.isd_rb, idx), frb); fcb = bfi(rm, C.isd_cb4, fcb);
+        p01 = bfi(rm, TABLES ? M.ip : perm(0u, C.isd_p, idx), p01);
         tt = bfi(rm, 0u, tt);
         need_out7 = frz7;
         obs_zero7 = bfi(fin7, 0u, goal7);                                  // only a frozen lane can still sit in a goal tuple
@@ -544,6 +581,15 @@ SOCCER_HD void step4(const Consts& C, Group& S, uint32_t aa_raw, uint32_t ab_raw
     obs4<GENERAL>(C, fra, fca, frb, fcb, p01, obs_zero7, o.obs_lo, o.obs_hi);
     S.ra = fra; S.ca = fca; S.rb = frb; S.cb = fcb; S.tt = tt;
     S.ps = p01 | ((need_out7 >> 6) & 0x02020202u);
+}
+template <bool GENERAL, bool FULL, bool SLIP, int GEO = 0, bool TRUSTED = false>
+SOCCER_HD void step4(const Consts& C, Group& S, uint32_t aa_raw, uint32_t ab_raw, uint32_t sa, uint32_t sb,
+                     uint32_t cls4, const Rand4& R, Out& o) {
+    step4_body<GENERAL, FULL, SLIP, GEO, TRUSTED, false>(C, S, aa_raw, ab_raw, sa, sb, cls4, R, Moves4{}, o);
+}
+template <bool GENERAL, bool FULL, bool SLIP, int GEO = 0>
+SOCCER_HD void step4_state(const Consts& C, Group& S, const Moves4& M, uint32_t cls4, const Rand4& R, Out& o) {
+    step4_body<GENERAL, FULL, SLIP, GEO, false, true>(C, S, 0u, 0u, 0u, 0u, cls4, R, M, o);
 }
 
 }  // namespace swar
