@@ -69,7 +69,14 @@ class MinimaxQConfig(C.Structure):
                 ("q_init", C.c_double), ("opponent", C.c_int32), ("reserved_", C.c_int32), ("opponent_policy", C.c_void_p)]
 
 
+class QLearnerConfig(C.Structure):
+    """soccer_q_learner_config"""
+    _fields_ = [("discount_factor", C.c_double), ("alpha", C.c_double), ("decay", C.c_double), ("explor", C.c_double),
+                ("q_init", C.c_double), ("act_a", C.c_int32), ("act_b", C.c_int32), ("policy_a", C.c_void_p), ("policy_b", C.c_void_p)]
+
+
 MQ_UNIFORM, MQ_SELF, MQ_FIXED = 0, 1, 2
+QL_GREEDY, QL_UNIFORM, QL_FIXED = 0, 1, 2
 MQ_MAX_LANES = 1 << 22
 BR_MAX_POLICIES = 256
 MISUSE_FROZEN, MISUSE_ACTION, MISUSE_OBSERVATION = 1, 2, 4
@@ -130,6 +137,12 @@ PROTOTYPES = {
     "soccer_minimax_q_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
     "soccer_minimax_q_read": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "soccer_minimax_q_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "soccer_q_learner_create": (C.c_int, [C.c_void_p, C.POINTER(QLearnerConfig), C.POINTER(C.c_void_p)]),
+    "soccer_q_learner_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "soccer_q_learner_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "soccer_q_learner_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
+    "soccer_q_learner_read": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 3 + [C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "soccer_q_learner_load": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 3 + [C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "soccer_prob_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 12)]),
     "soccer_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint64)]),
     "soccer_reset_stats": (C.c_int, [C.c_void_p]),

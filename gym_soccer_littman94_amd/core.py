@@ -109,6 +109,34 @@ def minimax_q_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), ex
     return _lib.MinimaxQConfig(g, a, d, e, q0, kind, 0, None if pol is None else pol.ctypes.data), pol
 
 
+def _learner_update(b, call, q, obs, act_a, act_b, reward, terminated, next_obs):
+    """a learner's update(): numpy arrays are copied to the device first and freed after the call"""
+    args = (obs, act_a, act_b, reward, terminated, next_obs)
+    dts = (np.uint16, np.int8, np.int8, np.int8, np.uint8, np.uint16)
+    tmp = []
+    if all(isinstance(x, (np.ndarray, list, tuple)) for x in args):
+        host = [np.ascontiguousarray(x, dt).reshape(-1) for x, dt in zip(args, dts)]
+        n = host[0].size
+        assert all(x.size == n for x in host), "the six transition arrays must have one length"
+        assert n <= _lib.MQ_MAX_LANES, "at most 2**22 transitions per update"
+        if n:
+            tmp = [DeviceArray(b, n, dt).upload(x) for x, dt in zip(host, dts)]
+        ptrs = [a.ptr for a in tmp] if n else [None] * 6
+    else:
+        def length(x):
+            return int(np.prod(x.shape)) if hasattr(x, "shape") else None
+        n = length(obs)
+        assert n is not None and all(length(x) == n for x in args), "the six transition arrays must have one length"
+        ptrs = [_ptr(x) for x in args]
+    try:
+        b._check(call(b.h, q, n, *ptrs))
+    finally:
+        if tmp:
+            b.sync()
+            for a in tmp:
+                a.free()
+
+
 class MinimaxQLearner:
     """A minimax-Q learner (Littman 1994) on a two-player auto-reset SoccerBatch: one shared Q[nS, 5, 5] on the device,
     the batch's lanes as actors (include/soccer_hip.h, "learners").  run() enqueues and returns; the properties
@@ -134,31 +162,7 @@ class MinimaxQLearner:
     def update(self, obs, act_a, act_b, reward, terminated, next_obs):
         """One learner step's reduce / update / re-solve on a batch of transitions: DeviceArrays (or device tensors) of one
         length, or numpy arrays, which are copied to the device first."""
-        b = self.batch
-        args = (obs, act_a, act_b, reward, terminated, next_obs)
-        dts = (np.uint16, np.int8, np.int8, np.int8, np.uint8, np.uint16)
-        tmp = []
-        if all(isinstance(x, (np.ndarray, list, tuple)) for x in args):
-            host = [np.ascontiguousarray(x, dt).reshape(-1) for x, dt in zip(args, dts)]
-            n = host[0].size
-            assert all(x.size == n for x in host), "the six transition arrays must have one length"
-            assert n <= _lib.MQ_MAX_LANES, "at most 2**22 transitions per update"
-            if n:
-                tmp = [DeviceArray(b, n, dt).upload(x) for x, dt in zip(host, dts)]
-            ptrs = [a.ptr for a in tmp] if n else [None] * 6
-        else:
-            def length(x):
-                return int(np.prod(x.shape)) if hasattr(x, "shape") else None
-            n = length(obs)
-            assert n is not None and all(length(x) == n for x in args), "the six transition arrays must have one length"
-            ptrs = [_ptr(x) for x in args]
-        try:
-            b._check(b.lib.soccer_minimax_q_update(b.h, self.q, n, *ptrs))
-        finally:
-            if tmp:
-                b.sync()
-                for a in tmp:
-                    a.free()
+        _learner_update(self.batch, self.batch.lib.soccer_minimax_q_update, self.q, obs, act_a, act_b, reward, terminated, next_obs)
         return self
 
     def read(self):
@@ -233,6 +237,124 @@ class MinimaxQLearner:
             pass
 
 
+def q_learning_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
+    """Checks the parameters of the independent Q-learners (AssertionError, before any library call) and returns
+    (soccer_q_learner_config, the arrays it points into)."""
+    g, a, d, e, q0 = float(discount_factor), float(alpha), float(decay), float(explor), float(q_init)
+    assert 0.0 <= g < 1.0, "discount_factor must be in [0, 1)"
+    assert 0.0 <= a <= 1.0, "alpha must be in [0, 1]"
+    assert 0.0 < d <= 1.0, "decay must be in (0, 1]"
+    assert 0.0 <= e <= 1.0, "explor must be in [0, 1]"
+    assert -1.0 <= q0 <= 1.0, "q_init must be in [-1, 1]"
+    kinds, pols = [], []
+    for name, act in (("act_a", act_a), ("act_b", act_b)):
+        pol = None
+        if isinstance(act, str):
+            assert act in ("greedy", "uniform"), "%s must be 'greedy', 'uniform' or an [nS, 5] mixed policy" % name
+            kinds.append(_lib.QL_GREEDY if act == "greedy" else _lib.QL_UNIFORM)
+        else:
+            pol = np.ascontiguousarray(act, np.float64)
+            assert pol.shape == (int(nS), 5) and (pol >= 0).all() and np.allclose(pol.sum(1), 1.0), \
+                "a fixed %s must be [n_states, 5] rows summing to 1" % name
+            kinds.append(_lib.QL_FIXED)
+        pols.append(pol)
+    return _lib.QLearnerConfig(g, a, d, e, q0, kinds[0], kinds[1], *[None if x is None else x.ctypes.data for x in pols]), pols
+
+
+class QLearner:
+    """Independent Q-learners for both players (Littman 1994's baseline and challenger) on a two-player auto-reset
+    SoccerBatch: Q_a[nS, 5] and Q_b[nS, 5] (player B's in its own reward) on the device, the batch's lanes as actors
+    (include/soccer_hip.h, "learners, independent Q").  run() enqueues and returns; read() and the properties synchronise
+    and copy."""
+
+    def __init__(self, batch, discount_factor, **params):
+        cfg, keep = q_learning_config(batch.nS, discount_factor, **params)
+        self.batch, self.q = batch, None
+        q = C.c_void_p()
+        batch._check(batch.lib.soccer_q_learner_create(batch.h, C.byref(cfg), C.byref(q)))
+        del keep                                   # (create has copied the fixed policies' thresholds)
+        self.q = q
+        self.nS = batch.nS
+        self.discount_factor = float(discount_factor)
+        batch._learners.add(self)
+
+    def run(self, n_steps):
+        """n_steps learner steps (every lane acts, the environment steps, both tables are updated), enqueued."""
+        b = self.batch
+        b._check(b.lib.soccer_q_learner_run(b.h, self.q, int(n_steps)))
+        return self
+
+    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
+        """One learner step's reduce / update on a batch of transitions (reward is player A's): DeviceArrays (or device
+        tensors) of one length, or numpy arrays, which are copied to the device first."""
+        _learner_update(self.batch, self.batch.lib.soccer_q_learner_update, self.q, obs, act_a, act_b, reward, terminated, next_obs)
+        return self
+
+    def read(self):
+        """dict: Q_a / Q_b [nS, 5], V_a / V_b [nS] (the row maxima), pi_a / pi_b [nS, 5] (one-hot of the first greedy action:
+        they plug into rollout(mixed_policies=...) and planners.exploitability as they are; row 0, the terminal observation,
+        is whatever argmax of zeros gives and is never read), visits[nS, 25], alpha, steps.  Synchronises."""
+        nS, b = self.nS, self.batch
+        out = {"Q_a": np.zeros((nS, 5)), "Q_b": np.zeros((nS, 5)), "visits": np.zeros((nS, 25), np.uint64)}
+        al, st = C.c_double(), C.c_uint64()
+        b._check(b.lib.soccer_q_learner_read(b.h, self.q, *[out[k].ctypes.data for k in ("Q_a", "Q_b", "visits")],
+                                             C.byref(al), C.byref(st)))
+        for p in "ab":
+            out["V_" + p] = out["Q_" + p].max(1)
+            out["pi_" + p] = np.eye(5)[out["Q_" + p].argmax(1)]
+        out["alpha"], out["steps"] = float(al.value), int(st.value)
+        return out
+
+    @property
+    def alpha(self):
+        b, al = self.batch, C.c_double()
+        b._check(b.lib.soccer_q_learner_read(b.h, self.q, None, None, None, C.byref(al), None))
+        return float(al.value)
+
+    @property
+    def steps(self):
+        b, st = self.batch, C.c_uint64()
+        b._check(b.lib.soccer_q_learner_read(b.h, self.q, None, None, None, None, C.byref(st)))
+        return int(st.value)
+
+    def exploitability(self, theta=1e-10):
+        """How badly the best possible opponent beats the greedy pair the learners hold now, at their discount:
+        planners.exploitability of (pi_a, pi_b).  Synchronises and copies; run() does not."""
+        from . import planners
+        r = self.read()
+        return planners.exploitability(self.batch, r["pi_a"], r["pi_b"], theta, self.discount_factor)
+
+    def load(self, Q_a, Q_b, visits=None, alpha=None, steps=None):
+        """Resume from a checkpoint: Q_a / Q_b [nS, 5] in; everything derived from them is recomputed on the device.  With
+        the `visits`, `alpha` and `steps` of read() a fresh learner continues bit for bit; without `visits` the counts are
+        zeroed."""
+        b = self.batch
+        Q = [np.ascontiguousarray(x, np.float64) for x in (Q_a, Q_b)]
+        for x in Q:
+            assert x.shape == (self.nS, 5), "Q_a / Q_b must be [n_states, 5]"
+            assert (np.abs(x[1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
+        v = None
+        if visits is not None:
+            v = np.ascontiguousarray(visits, np.uint64)
+            assert v.shape == (self.nS, 25), "visits must be [n_states, 25]"
+        assert alpha is None or 0.0 <= float(alpha) <= 1.0, "alpha must be in [0, 1]"
+        al = None if alpha is None else C.byref(C.c_double(float(alpha)))
+        st = None if steps is None else C.byref(C.c_uint64(int(steps)))
+        b._check(b.lib.soccer_q_learner_load(b.h, self.q, Q[0].ctypes.data, Q[1].ctypes.data, None if v is None else v.ctypes.data, al, st))
+        return self
+
+    def close(self):
+        if self.q and self.batch.h:
+            self.batch.lib.soccer_q_learner_destroy(self.batch.h, self.q)
+        self.q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SoccerBatch:
     """N lanes of the Littman-94 soccer game resident on one GPU.
 
@@ -253,7 +375,7 @@ class SoccerBatch:
         self.lib = _lib.load()
         self.h = None
         self._arrays = weakref.WeakSet()        # device buffers handed out by alloc(); freed with the handle
-        self._learners = weakref.WeakSet()      # minimax_q(): their memory goes with the handle
+        self._learners = weakref.WeakSet()      # minimax_q(), q_learning(): their memory goes with the handle
         cfg = Config(n_lanes=int(n_lanes), width=int(width), height=int(height),
                      slip_prob=float(slip_prob), max_steps=int(max_steps), device=int(device),
                      seed=int(seed) & 0xFFFFFFFFFFFFFFFF, lane_offset=int(lane_offset),
@@ -509,6 +631,11 @@ class SoccerBatch:
         """A MinimaxQLearner on this batch (two players, autoreset=True, at most 2**22 lanes).  opponent: 'uniform', 'self'
         (player B follows its own minimax strategy of the learned Q, with the same exploration) or a fixed [nS, 5] policy."""
         return MinimaxQLearner(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, opponent=opponent)
+
+    def q_learning(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
+        """A QLearner on this batch (two players, autoreset=True, at most 2**22 lanes).  act_a / act_b: 'greedy'
+        (epsilon-greedy on the player's own table), 'uniform', or a fixed [nS, 5] mixed policy.  Both tables always learn."""
+        return QLearner(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
 
     # -- hot path -------------------------------------------------------------------------------
     def reset(self, mask=None, u_reset=None, obs=None):

@@ -5,7 +5,7 @@
 //   soccer_step.hip      batched_step*
 //   soccer_rollout.hip   batched_rollout*
 //   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, the matrix-game solver
-//   soccer_learners.hip  the minimax-Q learner
+//   soccer_learners.hip  the minimax-Q learner, the independent Q-learners
 //   soccer_comm.hip      the RCCL wrapper (host code only)
 //
 // Every unit carries its own code object: a kernel is instantiated, launched and given its attributes (hipFuncSetAttribute)
@@ -174,6 +174,7 @@ struct soccer_handle {
     int br_cap = 0; bool br_pairs = false;
     OwnedBufs br_bufs{"the best-response solver"};
     std::vector<soccer_minimax_q*> learners; // soccer_minimax_q_create: the learners that were not destroyed (freed with the handle)
+    std::vector<soccer_q_learner*> q_learners; // soccer_q_learner_create: the same for the independent Q-learners
     std::string err;
 
     soccer_handle() = default;

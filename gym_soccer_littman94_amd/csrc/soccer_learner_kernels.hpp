@@ -1,5 +1,6 @@
 // soccer_learner_kernels.hpp — the minimax-Q learner (Littman 1994): learner_act_kernel, learner_reduce_kernel,
-// learner_update_kernel, learner_init_kernel.
+// learner_update_kernel, learner_init_kernel; and the independent Q-learners of both players: q_act_kernel, q_reduce_kernel,
+// q_update_kernel, q_init_kernel (at the end: they share the act-and-step body, the reduce body and learner_thresholds).
 // Included by soccer_learners.hip only: every kernel is emitted by exactly one translation unit.
 //
 // One learner step (include/soccer_hip.h, "learners") is two launches in stream order, no grid barrier between them:
@@ -82,8 +83,10 @@ __device__ __forceinline__ void learner_publish(const LearnerIO& L, int s, doubl
 // ---- act, step, reduce ---------------------------------------------------------------------------
 // A thread per lane, through the per-lane rule functions (lane_step) that batched_rollout's own per-lane kernel uses: the
 // step costs a fraction of the three atomics behind it.
-template <bool SLIP, bool LUT_LDS>
-__global__ __launch_bounds__(kBlock) void learner_act_kernel(const KernelParams P, const LearnerIO L) {
+// The body both act kernels share.  NULL_A: player A's row table may be absent too (the Q-learners; minimax-Q always has
+// one).  P and L by value, as a kernel takes them: by reference learner_act_kernel came out in another instruction order.
+template <bool SLIP, bool LUT_LDS, bool NULL_A, class IO>
+__device__ __forceinline__ void learner_act(const KernelParams P, const IO L) {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     HistAcc<false> hist; hist.init(P);
     const Tables T = stage_tables<LUT_LDS>(P, smem);
@@ -102,7 +105,8 @@ __global__ __launch_bounds__(kBlock) void learner_act_kernel(const KernelParams 
         // two actions from one 32-bit word, 15 bits each (rollout_group): the number of thresholds <= the draw
         const uint32_t ha = awords[0] & 0x7fffu, hb = (awords[0] >> 16) & 0x7fffu;
         uint32_t a, b = (hb * 5u) >> 15;
-        {
+        if (NULL_A) a = (ha * 5u) >> 15;
+        if (!NULL_A || L.mix_a) {
             const uint2 th = *reinterpret_cast<const uint2*>(L.mix_a + 4u * s_now);
             a = (ha >= (th.x & 0xffffu)) + (ha >= (th.x >> 16)) + (ha >= (th.y & 0xffffu)) + (ha >= (th.y >> 16));
         }
@@ -122,10 +126,15 @@ __global__ __launch_bounds__(kBlock) void learner_act_kernel(const KernelParams 
     hist.flush(P);
 }
 
-// soccer_minimax_q_update: step 3 on the caller's transitions, a thread each
-__global__ __launch_bounds__(kBlock) void learner_reduce_kernel(const LearnerIO L, long long n, const uint16_t* obs, const int8_t* act_a,
-                                                                const int8_t* act_b, const int8_t* reward, const uint8_t* terminated,
-                                                                const uint16_t* next_obs) {
+template <bool SLIP, bool LUT_LDS>
+__global__ __launch_bounds__(kBlock) void learner_act_kernel(const KernelParams P, const LearnerIO L) {
+    learner_act<SLIP, LUT_LDS, false>(P, L);
+}
+
+// step 3 on the caller's transitions, a thread each
+template <class IO>
+__device__ __forceinline__ void learner_reduce(const IO& L, long long n, const uint16_t* obs, const int8_t* act_a, const int8_t* act_b,
+                                               const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs) {
     bool bad_act = false, bad_obs = false;
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
         const uint32_t s = obs[i], s2 = next_obs[i], a = (uint8_t)act_a[i], b = (uint8_t)act_b[i];
@@ -135,6 +144,13 @@ __global__ __launch_bounds__(kBlock) void learner_reduce_kernel(const LearnerIO 
     }
     if (bad_act) L.misuse[1] = 1u;
     if (bad_obs) L.misuse[2] = 1u;
+}
+
+// soccer_minimax_q_update
+__global__ __launch_bounds__(kBlock) void learner_reduce_kernel(const LearnerIO L, long long n, const uint16_t* obs, const int8_t* act_a,
+                                                                const int8_t* act_b, const int8_t* reward, const uint8_t* terminated,
+                                                                const uint16_t* next_obs) {
+    learner_reduce(L, n, obs, act_a, act_b, reward, terminated, next_obs);
 }
 
 // ---- update, re-solve ----------------------------------------------------------------------------
@@ -193,6 +209,139 @@ __global__ __launch_bounds__(kBlock) void learner_init_kernel(const LearnerIO L,
         const double u[5] = {0.2, 0.2, 0.2, 0.2, 0.2};
         learner_publish(L, s, s ? q_init : 0.0, u, u);
     }
+    if (cell == 0) { L.alpha[0] = alpha0; L.alpha[1] = alpha0; *L.steps = 0ull; }
+}
+
+// =================================================================================================
+// independent Q-learners of both players (include/soccer_hip.h, "learners, independent Q")
+// =================================================================================================
+// A step is the same two launches.  q_act_kernel is learner_act with the joint cell's FOUR integer accumulators (count,
+// reward sum, sum of Vq_a[s'], sum of Vq_b[s']): integer sums are exact in any grouping, so the update can form a player's
+// (s, own action) sums from them, and the atomics spread over 25 cells per state as minimax-Q's do.
+// q_update_kernel has no stage game to solve, so a wave per state would idle: half a wave owns a state (lanes 0..24 and
+// 32..56, response_sweep_kernel's layout).  Its 25 lanes bring the joint accumulators into LDS, count the visits and zero
+// what they read; ten lanes (player x action) form the five sums of each player and move Q; two lanes (a player each)
+// take the first maximum and write Vq and, for a GREEDY player, the threshold row of the next step.
+constexpr int kQStates = 2 * kLearnerWaves;        // states per workgroup
+
+struct QLearnerIO {
+    double* Q[2];                       // [nS][5] player A's table, player B's (in B's own reward)
+    long long* Vq[2];                   // [nS] rint(max_k Q_p[s][k] * 2^40)
+    unsigned long long* visits;         // [nS][25]
+    unsigned int* cnt;                  // [nS][25] samples of this step
+    int* rsum;                          // [nS][25] sum of player A's rewards
+    long long* sv[2];                   // [nS][25] sum of Vq_p[s'] over the non-terminated samples
+    uint16_t* mix_a;                    // [nS][4] behaviour thresholds, or nullptr (SOCCER_QL_UNIFORM: the null row table)
+    uint16_t* mix_b;
+    double* alpha;                      // [2]: a step reads one slot and writes the other
+    unsigned long long* steps;
+    unsigned int* misuse;               // the handle's sticky words
+    double gamma, decay, explor;
+    int32_t nS;
+    int32_t greedy[2];                  // the player's row follows its table (else it is fixed or absent)
+};
+
+__device__ __forceinline__ void learner_accumulate(const QLearnerIO& L, uint32_t s, uint32_t a, uint32_t b, int32_t r,
+                                                   uint32_t term, uint32_t s2) {
+    const uint32_t cell = s * 25u + a * 5u + b;
+    atomicAdd(&L.cnt[cell], 1u);
+    if (r != 0) atomicAdd(&L.rsum[cell], r);
+    if (!term) {
+        const long long va = L.Vq[0][s2], vb = L.Vq[1][s2];
+        if (va != 0ll) atomicAdd(reinterpret_cast<unsigned long long*>(&L.sv[0][cell]), (unsigned long long)va);
+        if (vb != 0ll) atomicAdd(reinterpret_cast<unsigned long long*>(&L.sv[1][cell]), (unsigned long long)vb);
+    }
+}
+
+template <bool SLIP, bool LUT_LDS>
+__global__ __launch_bounds__(kBlock) void q_act_kernel(const KernelParams P, const QLearnerIO L) {
+    learner_act<SLIP, LUT_LDS, true>(P, L);
+}
+
+// soccer_q_learner_update
+__global__ __launch_bounds__(kBlock) void q_reduce_kernel(const QLearnerIO L, long long n, const uint16_t* obs, const int8_t* act_a,
+                                                          const int8_t* act_b, const int8_t* reward, const uint8_t* terminated,
+                                                          const uint16_t* next_obs) {
+    learner_reduce(L, n, obs, act_a, act_b, reward, terminated, next_obs);
+}
+
+// MODE 0: steps 4-6 of a learner step.  MODE 1 (creation, soccer_q_learner_load): every row derived from Q is recomputed,
+// row 0 included; the accumulators, the counts, alpha and the step counter are left alone.
+template <int MODE>
+__global__ __launch_bounds__(kLearnerBlock) void q_update_kernel(const QLearnerIO L, int slot) {
+    __shared__ unsigned int sC[kQStates][25];
+    __shared__ int sR[kQStates][25];
+    __shared__ long long sS[2][kQStates][25];
+    __shared__ double sQ[kQStates][10];
+    const int st = (int)(threadIdx.x >> 5), lane = (int)(threadIdx.x & 31u);
+    const int s = (int)blockIdx.x * kQStates + st;
+    const bool live = s < L.nS && (MODE == 1 || s >= 1);        // index 0 is the terminal observation: Q_p[0] = 0 for good
+    const double alpha = L.alpha[slot];
+    unsigned int c = 0u;
+    if (MODE == 0 && live && lane < 25) {
+        // both players' sums are read here, before anything is zeroed
+        const size_t cell = (size_t)s * 25 + lane;
+        c = L.cnt[cell];
+        sC[st][lane] = c;
+        if (c != 0u) {
+            sR[st][lane] = L.rsum[cell]; sS[0][st][lane] = L.sv[0][cell]; sS[1][st][lane] = L.sv[1][cell];
+            L.visits[cell] += (unsigned long long)c;
+            L.cnt[cell] = 0u; L.rsum[cell] = 0; L.sv[0][cell] = 0ll; L.sv[1][cell] = 0ll;
+        } else {
+            sR[st][lane] = 0; sS[0][st][lane] = 0ll; sS[1][st][lane] = 0ll;
+        }
+    }
+    // the half-wave's 25 bits of the wave's ballot: was any cell of this state touched?
+    const bool any = MODE == 1 || (((unsigned long long)__ballot(c != 0u) >> (threadIdx.x & 32u)) & 0x1ffffffull) != 0ull;
+    __syncthreads();
+    if (live && lane < 10) {
+        const int p = lane / 5, k = lane - 5 * p;                // player, own action
+        const size_t row = (size_t)s * 5 + k;
+        double q = L.Q[p][row];
+        if (MODE == 0) {
+            unsigned int cc = 0u; long long R = 0ll, SV = 0ll;
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {                        // over the other player's action
+                const int x = p ? j * 5 + k : k * 5 + j;
+                cc += sC[st][x]; R += (long long)sR[st][x]; SV += sS[p][st][x];
+            }
+            if (cc != 0u) {
+                if (p) R = -R;                                   // player B's own reward
+                const double m = ((double)R + L.gamma * ((double)SV * kVqInv)) / (double)cc;
+                q = q + alpha * (m - q);
+                L.Q[p][row] = q;
+            }
+        }
+        sQ[st][lane] = q;
+    }
+    __syncthreads();
+    if (live && any && lane < 2) {
+        const int p = lane;
+        double v = sQ[st][p * 5];
+        int g = 0;
+#pragma unroll
+        for (int k = 1; k < 5; ++k) {
+            const double r = sQ[st][p * 5 + k];
+            if (r > v) { v = r; g = k; }                         // the first index that attains it
+        }
+        L.Vq[p][s] = (long long)rint(v * kVqScale);
+        if (L.greedy[p]) {
+            double pi[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) pi[k] = k == g ? 1.0 : 0.0;
+            learner_thresholds(pi, L.explor, (p ? L.mix_b : L.mix_a) + (size_t)s * 4);
+        }
+    }
+    if (MODE == 0 && blockIdx.x == 0 && threadIdx.x == 0) { L.alpha[slot ^ 1] = alpha * L.decay; *L.steps += 1ull; }
+}
+
+// creation: Q_p = q_init on the live states, everything else zero (q_update_kernel<1> then derives the rows)
+__global__ __launch_bounds__(kBlock) void q_init_kernel(const QLearnerIO L, double q_init, double alpha0) {
+    const int cell = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (cell >= L.nS * 25) return;
+    const int s = cell / 25, k = cell % 25;
+    if (k < 10) L.Q[k / 5][(size_t)s * 5 + k % 5] = s ? q_init : 0.0;
+    L.visits[cell] = 0ull; L.cnt[cell] = 0u; L.rsum[cell] = 0; L.sv[0][cell] = 0ll; L.sv[1][cell] = 0ll;
     if (cell == 0) { L.alpha[0] = alpha0; L.alpha[1] = alpha0; *L.steps = 0ull; }
 }
 

@@ -1,4 +1,5 @@
-// soccer_learners.hip — the minimax-Q learner: soccer_minimax_q_* (see soccer_handle.hpp).
+// soccer_learners.hip — the minimax-Q learner: soccer_minimax_q_*, and the independent Q-learners: soccer_q_learner_*
+// (see soccer_handle.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,9 +23,19 @@ static bool owns(const soccer_handle* h, const soccer_minimax_q* q) {
     return q && std::find(h->learners.begin(), h->learners.end(), q) != h->learners.end();
 }
 
+// The independent Q-learners of both players: the same shape.
+struct soccer_q_learner {
+    soccer_handle* h = nullptr;
+    QLearnerIO io{};
+    OwnedBufs bufs{"the Q-learner"};
+    int slot = 0;                       // alpha slot the NEXT update reads
+};
+
 void learners_release(soccer_handle* h) {
     for (soccer_minimax_q* q : h->learners) delete q;
     h->learners.clear();
+    for (soccer_q_learner* q : h->q_learners) delete q;
+    h->q_learners.clear();
 }
 
 // what every entry point checks first
@@ -32,6 +43,27 @@ static int learner_check(soccer_handle* h, soccer_minimax_q* q, const char* what
     if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
     if (h->capturing) return fail(h, SOCCER_E_STATE, "%s during graph capture", what);
     if (!owns(h, q)) return fail(h, SOCCER_E_INVALID, "%s: not a learner of this handle", what);
+    return SOCCER_OK;
+}
+
+// a fixed mixed policy's threshold rows, once: SoccerBatch.mixed_policy_thresholds
+static int fixed_thresholds(soccer_handle* h, const char* name, const double* policy, int nS, std::vector<uint16_t>& rows) {
+    rows.resize((size_t)nS * 4);
+    for (int s = 0; s < nS; ++s) {
+        const double* p = policy + (size_t)s * 5;
+        double c = 0.0, sum = 0.0;
+        for (int k = 0; k < 5; ++k) {
+            if (!(p[k] >= 0.0)) return fail(h, SOCCER_E_INVALID, "%s[%d][%d] is negative or not a number", name, s, k);
+            sum = sum + p[k];
+        }
+        if (!(std::fabs(sum - 1.0) <= 1e-8 + 1e-5)) return fail(h, SOCCER_E_INVALID, "%s[%d] does not sum to 1", name, s);
+        for (int k = 0; k < 4; ++k) {
+            c = c + p[k];
+            double f = std::floor(c * 32768.0 + 1e-9);
+            f = f < 0.0 ? 0.0 : (f > 32768.0 ? 32768.0 : f);
+            rows[(size_t)s * 4 + k] = (uint16_t)f;
+        }
+    }
     return SOCCER_OK;
 }
 
@@ -77,26 +109,9 @@ extern "C" int soccer_minimax_q_create(soccer_handle* h, const soccer_minimax_q_
     if ((cfg->opponent == SOCCER_MQ_FIXED) != (cfg->opponent_policy != nullptr))
         return fail(h, SOCCER_E_INVALID, "opponent_policy goes with SOCCER_MQ_FIXED, and only with it");
     const int nS = h->rules.nS;
-    // a fixed opponent's threshold rows, once: SoccerBatch.mixed_policy_thresholds
     std::vector<uint16_t> fixed;
-    if (cfg->opponent == SOCCER_MQ_FIXED) {
-        fixed.resize((size_t)nS * 4);
-        for (int s = 0; s < nS; ++s) {
-            const double* p = cfg->opponent_policy + (size_t)s * 5;
-            double c = 0.0, sum = 0.0;
-            for (int k = 0; k < 5; ++k) {
-                if (!(p[k] >= 0.0)) return fail(h, SOCCER_E_INVALID, "opponent_policy[%d][%d] is negative or not a number", s, k);
-                sum = sum + p[k];
-            }
-            if (!(std::fabs(sum - 1.0) <= 1e-8 + 1e-5)) return fail(h, SOCCER_E_INVALID, "opponent_policy[%d] does not sum to 1", s);
-            for (int k = 0; k < 4; ++k) {
-                c = c + p[k];
-                double f = std::floor(c * 32768.0 + 1e-9);
-                f = f < 0.0 ? 0.0 : (f > 32768.0 ? 32768.0 : f);
-                fixed[(size_t)s * 4 + k] = (uint16_t)f;
-            }
-        }
-    }
+    if (cfg->opponent == SOCCER_MQ_FIXED)
+        if (int rc = fixed_thresholds(h, "opponent_policy", cfg->opponent_policy, nS, fixed)) return rc;
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     HIP_TRY(h, act(h, h->P, LearnerIO{}));                   // (an empty block: the LDS limit of this handle's act kernel, nothing launched)
     std::unique_ptr<soccer_minimax_q> owner(new soccer_minimax_q());
@@ -207,6 +222,184 @@ extern "C" int soccer_minimax_q_load(soccer_handle* h, soccer_minimax_q* q, cons
     const unsigned grid = (unsigned)((io.nS + kLearnerWaves - 1) / kLearnerWaves);
     if (visits) hipLaunchKernelGGL(learner_update_kernel<1>, dim3(grid), dim3(kLearnerBlock), 0, h->stream, io, q->slot);
     else hipLaunchKernelGGL(learner_update_kernel<2>, dim3(grid), dim3(kLearnerBlock), 0, h->stream, io, q->slot);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // the caller's arrays are pageable host memory
+    return SOCCER_OK;
+}
+
+// =================================================================================================
+// independent Q-learners: soccer_q_learner_*
+// =================================================================================================
+static int q_check(soccer_handle* h, soccer_q_learner* q, const char* what) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "%s during graph capture", what);
+    if (!q || std::find(h->q_learners.begin(), h->q_learners.end(), q) == h->q_learners.end())
+        return fail(h, SOCCER_E_INVALID, "%s: not a learner of this handle", what);
+    return SOCCER_OK;
+}
+
+template <bool SLIP, bool LUT_LDS>
+static hipError_t launch_q_act(soccer_handle* h, const KernelParams& P, const QLearnerIO& io) {
+    if (io.nS == 0)                     // soccer_q_learner_create: the LDS limit, as launch_act
+        return h->smem_bytes > 48 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&q_act_kernel<SLIP, LUT_LDS>),
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_bytes) : hipSuccess;
+    hipLaunchKernelGGL((q_act_kernel<SLIP, LUT_LDS>), dim3(grid_for(h, P.n)), dim3(kBlock), h->smem_bytes, h->stream, P, io);
+    return hipSuccess;
+}
+
+static hipError_t q_act(soccer_handle* h, const KernelParams& P, const QLearnerIO& io) {
+    return h->slip ? (h->lut_lds ? launch_q_act<true, true>(h, P, io) : launch_q_act<true, false>(h, P, io))
+                   : (h->lut_lds ? launch_q_act<false, true>(h, P, io) : launch_q_act<false, false>(h, P, io));
+}
+
+static unsigned q_update_grid(const QLearnerIO& io) { return (unsigned)((io.nS + kQStates - 1) / kQStates); }
+
+static void launch_q_update(soccer_q_learner* q) {
+    hipLaunchKernelGGL(q_update_kernel<0>, dim3(q_update_grid(q->io)), dim3(kLearnerBlock), 0, q->h->stream, q->io, q->slot);
+    q->slot ^= 1;
+}
+
+static bool ql_kind(int32_t k) { return k == SOCCER_QL_GREEDY || k == SOCCER_QL_UNIFORM || k == SOCCER_QL_FIXED; }
+
+extern "C" int soccer_q_learner_create(soccer_handle* h, const soccer_q_learner_config* cfg, soccer_q_learner** out) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "soccer_q_learner_create during graph capture");
+    if (!cfg || !out) return fail(h, SOCCER_E_INVALID, "soccer_q_learner_create: cfg/out is NULL");
+    *out = nullptr;
+    if (h->P.policy_a != nullptr || h->P.policy_b != nullptr)
+        return fail(h, SOCCER_E_INVALID, "soccer_q_learner_create needs a two-player handle: neither side may have a fixed policy (soccer_set_policy)");
+    if (!(h->cfg.flags & SOCCER_F_AUTORESET))
+        return fail(h, SOCCER_E_INVALID, "soccer_q_learner_create needs a handle created with SOCCER_F_AUTORESET");
+    if (h->cfg.n_lanes > SOCCER_MQ_MAX_LANES)
+        return fail(h, SOCCER_E_INVALID, "soccer_q_learner_create: more than 2^22 lanes (%llu): the integer sums of a step could overflow",
+                    (unsigned long long)h->cfg.n_lanes);
+    if (!(cfg->discount_factor >= 0.0 && cfg->discount_factor < 1.0)) return fail(h, SOCCER_E_INVALID, "discount_factor must be in [0, 1)");
+    if (!(cfg->alpha >= 0.0 && cfg->alpha <= 1.0)) return fail(h, SOCCER_E_INVALID, "alpha must be in [0, 1]");
+    if (!(cfg->decay > 0.0 && cfg->decay <= 1.0)) return fail(h, SOCCER_E_INVALID, "decay must be in (0, 1]");
+    if (!(cfg->explor >= 0.0 && cfg->explor <= 1.0)) return fail(h, SOCCER_E_INVALID, "explor must be in [0, 1]");
+    if (!(cfg->q_init >= -1.0 && cfg->q_init <= 1.0)) return fail(h, SOCCER_E_INVALID, "q_init must be in [-1, 1]");
+    if (!ql_kind(cfg->act_a) || !ql_kind(cfg->act_b))
+        return fail(h, SOCCER_E_INVALID, "act_a / act_b must be SOCCER_QL_GREEDY, SOCCER_QL_UNIFORM or SOCCER_QL_FIXED");
+    if ((cfg->act_a == SOCCER_QL_FIXED) != (cfg->policy_a != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_a goes with act_a == SOCCER_QL_FIXED, and only with it");
+    if ((cfg->act_b == SOCCER_QL_FIXED) != (cfg->policy_b != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_b goes with act_b == SOCCER_QL_FIXED, and only with it");
+    const int nS = h->rules.nS;
+    std::vector<uint16_t> fixed[2];
+    if (cfg->policy_a) if (int rc = fixed_thresholds(h, "policy_a", cfg->policy_a, nS, fixed[0])) return rc;
+    if (cfg->policy_b) if (int rc = fixed_thresholds(h, "policy_b", cfg->policy_b, nS, fixed[1])) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, q_act(h, h->P, QLearnerIO{}));                // (an empty block: the LDS limit of this handle's act kernel, nothing launched)
+    std::unique_ptr<soccer_q_learner> owner(new soccer_q_learner());
+    soccer_q_learner* q = owner.get();
+    q->h = h;
+    QLearnerIO& io = q->io;
+    const size_t cells = (size_t)nS * 25;
+    int rc = SOCCER_OK;
+    for (int p = 0; p < 2; ++p) {
+        if (!rc) rc = q->bufs.alloc(h, (size_t)nS * 5, &io.Q[p]);
+        if (!rc) rc = q->bufs.alloc(h, (size_t)nS, &io.Vq[p]);
+        if (!rc) rc = q->bufs.alloc(h, cells, &io.sv[p]);
+    }
+    if (!rc) rc = q->bufs.alloc(h, cells, &io.visits);
+    if (!rc) rc = q->bufs.alloc(h, cells, &io.cnt);
+    if (!rc) rc = q->bufs.alloc(h, cells, &io.rsum);
+    if (!rc && cfg->act_a != SOCCER_QL_UNIFORM) rc = q->bufs.alloc(h, (size_t)nS * 4, &io.mix_a);
+    if (!rc && cfg->act_b != SOCCER_QL_UNIFORM) rc = q->bufs.alloc(h, (size_t)nS * 4, &io.mix_b);
+    if (!rc) rc = q->bufs.alloc(h, 2, &io.alpha);
+    if (!rc) rc = q->bufs.alloc(h, 1, &io.steps);
+    if (rc) return rc;
+    io.misuse = h->d_misuse;
+    io.gamma = cfg->discount_factor; io.decay = cfg->decay; io.explor = cfg->explor;
+    io.nS = nS;
+    io.greedy[0] = cfg->act_a == SOCCER_QL_GREEDY ? 1 : 0; io.greedy[1] = cfg->act_b == SOCCER_QL_GREEDY ? 1 : 0;
+    if (cfg->policy_a) HIP_TRY(h, hipMemcpyAsync(io.mix_a, fixed[0].data(), fixed[0].size() * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    if (cfg->policy_b) HIP_TRY(h, hipMemcpyAsync(io.mix_b, fixed[1].data(), fixed[1].size() * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(q_init_kernel, dim3((unsigned)((cells + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, io, cfg->q_init, cfg->alpha);
+    hipLaunchKernelGGL(q_update_kernel<1>, dim3(q_update_grid(io)), dim3(kLearnerBlock), 0, h->stream, io, 0);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // `fixed` is pageable host memory of this call
+    h->q_learners.push_back(q);
+    *out = owner.release();
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_learner_destroy(soccer_handle* h, soccer_q_learner* q) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (!q) return SOCCER_OK;
+    if (int rc = q_check(h, q, "soccer_q_learner_destroy")) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // nothing is freed under a kernel that reads it
+    h->q_learners.erase(std::find(h->q_learners.begin(), h->q_learners.end(), q));
+    delete q;
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_learner_run(soccer_handle* h, soccer_q_learner* q, int32_t n_steps) {
+    if (int rc = q_check(h, q, "soccer_q_learner_run")) return rc;
+    if (n_steps < 0) return fail(h, SOCCER_E_INVALID, "soccer_q_learner_run: n_steps must be >= 0");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    for (int32_t t = 0; t < n_steps; ++t) {
+        KernelParams P = h->P;
+        bind_tick(h, P, 1);
+        HIP_TRY(h, q_act(h, P, q->io));
+        launch_q_update(q);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_learner_update(soccer_handle* h, soccer_q_learner* q, int64_t n, const uint16_t* obs, const int8_t* act_a,
+                                       const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs) {
+    if (int rc = q_check(h, q, "soccer_q_learner_update")) return rc;
+    if (n < 0 || n > (int64_t)SOCCER_MQ_MAX_LANES) return fail(h, SOCCER_E_INVALID, "soccer_q_learner_update: n must be in 0..2^22");
+    if (n > 0 && (!obs || !act_a || !act_b || !reward || !terminated || !next_obs))
+        return fail(h, SOCCER_E_INVALID, "soccer_q_learner_update: all six transition arrays are required");
+    if (!aligned(obs, 2) || !aligned(next_obs, 2)) return fail(h, SOCCER_E_INVALID, "soccer_q_learner_update: obs / next_obs must be 2-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (n > 0)
+        hipLaunchKernelGGL(q_reduce_kernel, dim3(grid_for(h, (uint64_t)n)), dim3(kBlock), 0, h->stream, q->io, (long long)n,
+                           obs, act_a, act_b, reward, terminated, next_obs);
+    launch_q_update(q);
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_learner_read(soccer_handle* h, soccer_q_learner* q, double* Q_a, double* Q_b, uint64_t* visits,
+                                     double* alpha, uint64_t* steps) {
+    if (int rc = q_check(h, q, "soccer_q_learner_read")) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const QLearnerIO& io = q->io;
+    const size_t nS = (size_t)io.nS;
+    if (Q_a) HIP_TRY(h, hipMemcpyAsync(Q_a, io.Q[0], nS * 40, hipMemcpyDeviceToHost, h->stream));
+    if (Q_b) HIP_TRY(h, hipMemcpyAsync(Q_b, io.Q[1], nS * 40, hipMemcpyDeviceToHost, h->stream));
+    if (visits) HIP_TRY(h, hipMemcpyAsync(visits, io.visits, nS * 200, hipMemcpyDeviceToHost, h->stream));
+    if (alpha) HIP_TRY(h, hipMemcpyAsync(alpha, io.alpha + q->slot, 8, hipMemcpyDeviceToHost, h->stream));
+    if (steps) HIP_TRY(h, hipMemcpyAsync(steps, io.steps, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_learner_load(soccer_handle* h, soccer_q_learner* q, const double* Q_a, const double* Q_b, const uint64_t* visits,
+                                     const double* alpha, const uint64_t* steps) {
+    if (int rc = q_check(h, q, "soccer_q_learner_load")) return rc;
+    if (!Q_a || !Q_b) return fail(h, SOCCER_E_INVALID, "soccer_q_learner_load: Q_a / Q_b is NULL");
+    const QLearnerIO& io = q->io;
+    const size_t nS = (size_t)io.nS;
+    const double* Q[2] = {Q_a, Q_b};
+    for (int p = 0; p < 2; ++p)
+        for (size_t i = 5; i < nS * 5; ++i)
+            if (!(Q[p][i] >= -1.0 && Q[p][i] <= 1.0))
+                return fail(h, SOCCER_E_INVALID, "soccer_q_learner_load: Q_%c[%zu][%zu] is outside [-1, 1]", p ? 'b' : 'a', i / 5, i % 5);
+    if (alpha && !(*alpha >= 0.0 && *alpha <= 1.0)) return fail(h, SOCCER_E_INVALID, "soccer_q_learner_load: alpha must be in [0, 1]");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    for (int p = 0; p < 2; ++p) {
+        HIP_TRY(h, hipMemsetAsync(io.Q[p], 0, 40, h->stream));                    // Q_p[0] = 0
+        HIP_TRY(h, hipMemcpyAsync(io.Q[p] + 5, Q[p] + 5, (nS - 1) * 40, hipMemcpyHostToDevice, h->stream));
+    }
+    if (visits) HIP_TRY(h, hipMemcpyAsync(io.visits, visits, nS * 200, hipMemcpyHostToDevice, h->stream));
+    else HIP_TRY(h, hipMemsetAsync(io.visits, 0, nS * 200, h->stream));
+    if (alpha) HIP_TRY(h, hipMemcpyAsync(io.alpha + q->slot, alpha, 8, hipMemcpyHostToDevice, h->stream));
+    if (steps) HIP_TRY(h, hipMemcpyAsync(io.steps, steps, 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(q_update_kernel<1>, dim3(q_update_grid(io)), dim3(kLearnerBlock), 0, h->stream, io, q->slot);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));            // the caller's arrays are pageable host memory
     return SOCCER_OK;

@@ -479,6 +479,11 @@ class VectorSoccerEnv:
         assert self.multiagent, "minimax_q needs a two-player environment (no player with a fixed policy)"
         return self._batch.minimax_q(discount_factor, **params)
 
+    def q_learning(self, discount_factor, **params):
+        """A QLearner (SoccerBatch.q_learning) whose actors are this env's lanes: independent Q-learners for both players."""
+        assert self.multiagent, "q_learning needs a two-player environment (no player with a fixed policy)"
+        return self._batch.q_learning(discount_factor, **params)
+
     @property
     def reward_int8(self):
         """device io: player A's reward of the last step as the int8 tensor the kernel wrote (-1 / 0 / +1), no cast

@@ -64,7 +64,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_best_response and soccer_evaluate_policies were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_best_response and soccer_evaluate_policies were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -449,6 +449,65 @@ int soccer_minimax_q_read(soccer_handle* h, soccer_minimax_q* q, double* Q, doub
  * the counts, and a state without a visit gets what creation gives it — V = Q[s][0][0], uniform strategies — not the
  * solver's answer, so that read -> load on a fresh learner continues bit for bit.  alpha / steps: HOST, NULL = unchanged. */
 int soccer_minimax_q_load(soccer_handle* h, soccer_minimax_q* q, const double* Q, const uint64_t* visits,
+                          const double* alpha, const uint64_t* steps);
+/* ---- learners, independent Q (two-player handles; ordinary Q-learning for BOTH players, Littman 1994's baseline and challenger)
+ * Lives where a minimax-Q learner lives: a two-player SOCCER_F_AUTORESET handle of at most 2^22 lanes, whose lanes are its
+ * actors.  It keeps TWO float64 tables on the device, Q_a[n_states][5] over player A's actions in player A's reward and
+ * Q_b[n_states][5] over player B's in player B's OWN reward (-r, as the reference's learner-B table is), visits[n_states][25]
+ * (uint64, joint cell s * 25 + a * 5 + b), alpha and a step counter.  Derived, never state of their own:
+ *     V_p[s] = max_k Q_p[s][k],  g_p[s] = the first k that attains it,  Vq_p[s] = rint(V_p[s] * 2^40) as int64
+ * Row 0 is the terminal observation: Q_p[0] = 0 for good.
+ * How a player acts (soccer_q_learner_config::act_a / act_b):
+ *   SOCCER_QL_GREEDY   epsilon-greedy on its own table: the threshold row of (1.0 - explor) * onehot(g_p[s]) + explor / 5.0,
+ *                      by the expression of step 1 above
+ *   SOCCER_QL_UNIFORM  the NULL row table of batched_rollout, i.e. its (h * 5) >> 15 draw (NOT the thresholds of a 0.2 row,
+ *                      which differ at h = 6553)
+ *   SOCCER_QL_FIXED    the thresholds of the caller's mixed policy (policy_a / policy_b), computed once at creation
+ * Q-learning is off-policy: BOTH tables are always updated, however the players act.  So (GREEDY, UNIFORM) is Littman's QR,
+ * (GREEDY, GREEDY) his QQ, (FIXED, GREEDY) a challenger against a frozen pi_a (read Q_b) and (GREEDY, FIXED) one against a
+ * frozen pi_b (read Q_a).  One learner step, in this order:
+ *   1. the behaviour rows as above
+ *   2. act and step: batched_rollout(n_steps = 1, sample_actions = 1, mix_a, mix_b), exactly as step 2 of minimax-Q
+ *   3. reduce, INTEGER sums only:  for A, per (s, a):  c = samples, R = sum of r, SV = sum over the non-terminated samples of
+ *      Vq_a[s'];  for B, per (s, b):  c, R = sum of (-r), SV = sum of Vq_b[s']
+ *   4. update, for every (s, k) with c > 0:  m = ((double)R + discount_factor * ((double)SV * 2^-40)) / (double)c,
+ *      Q = Q + alpha * (m - Q), not contracted;  visits[joint cell] += that cell's count
+ *   5. V_p, Vq_p, g_p and the GREEDY players' threshold rows follow Q for the touched states
+ *   6. alpha = alpha * decay, steps += 1
+ * Initially Q_p[s] = q_init on the live states, so every greedy action is 0 by the first-index rule; nothing is "set, not
+ * solved": the learner's whole state is (Q_a, Q_b, visits, alpha, steps), a fixed function of (seed, parameters, number of
+ * steps).  With alpha and q_init in range and discount_factor < 1 every Q stays in [-1, 1], and the sums of 2^22 samples fit
+ * int64 as they do for minimax-Q.  Ranges, refusals, SOCCER_E_STATE during a capture, the misuse flags and the ownership of
+ * the memory are those of the soccer_minimax_q_* calls; both kinds of learner may live on one handle. */
+#define SOCCER_QL_GREEDY  0
+#define SOCCER_QL_UNIFORM 1
+#define SOCCER_QL_FIXED   2
+typedef struct soccer_q_learner soccer_q_learner;
+typedef struct soccer_q_learner_config {
+    double  discount_factor;        /* [0, 1) */
+    double  alpha;                  /* initial learning rate, [0, 1] */
+    double  decay;                  /* alpha's factor per learner step, (0, 1] */
+    double  explor;                 /* [0, 1] probability mass a GREEDY player spreads uniformly over the five actions */
+    double  q_init;                 /* [-1, 1] */
+    int32_t act_a;                  /* SOCCER_QL_* : how player A acts */
+    int32_t act_b;                  /* SOCCER_QL_* : how player B acts */
+    const double* policy_a;         /* act_a == SOCCER_QL_FIXED: HOST [n_states][5] rows >= 0 summing to 1; else NULL */
+    const double* policy_b;         /* the same for act_b */
+} soccer_q_learner_config;
+int soccer_q_learner_create(soccer_handle* h, const soccer_q_learner_config* cfg, soccer_q_learner** out);
+int soccer_q_learner_destroy(soccer_handle* h, soccer_q_learner* q);
+/* n_steps learner steps, two launches each, enqueued on the handle's stream: no synchronisation, no copy.  Consumes n_steps ticks. */
+int soccer_q_learner_run(soccer_handle* h, soccer_q_learner* q, int32_t n_steps);
+/* steps 3-6 on the caller's batch of n <= 2^22 transitions (DEVICE pointers; reward is player A's), with the checks and the
+ * misuse flags of soccer_minimax_q_update.  Consumes no tick. */
+int soccer_q_learner_update(soccer_handle* h, soccer_q_learner* q, int64_t n, const uint16_t* obs, const int8_t* act_a,
+                            const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs);
+/* HOST outputs, any may be NULL: Q_a / Q_b [n_states][5], visits[n_states][25].  Synchronises. */
+int soccer_q_learner_read(soccer_handle* h, soccer_q_learner* q, double* Q_a, double* Q_b, uint64_t* visits,
+                          double* alpha, uint64_t* steps);
+/* Resume from a checkpoint: HOST Q_a / Q_b [n_states][5] in [-1, 1] (row 0 is taken as zeros); every derived row is
+ * recomputed from them.  visits: HOST [n_states][25], or NULL: the counts are zeroed.  alpha / steps: HOST, NULL = unchanged. */
+int soccer_q_learner_load(soccer_handle* h, soccer_q_learner* q, const double* Q_a, const double* Q_b, const uint64_t* visits,
                           const double* alpha, const uint64_t* steps);
 
 /* HOST output: prob[c*3+k] = slip-combination weight c (0: no slip, 1: B slips, 2: A slips,
