@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "soccer_handle.hpp"
@@ -76,33 +77,39 @@ static int build_plan(soccer_handle* h) {
         off[(size_t)s * 5 + a + 1] = (int32_t)lists.size();
     }
     // Pmat[s][ns][a] += p and Rmat[s][a] (= 0, then += p * r) in the constructor's tuple order (:280-291):
-    // index 0 accumulates one unit of probability per goal tuple, its Rmat is the last goal tuple's (0)
-    std::vector<std::vector<double>> row((size_t)nS * 5);               // dense rows only for touched (s, a)
+    // index 0 accumulates one unit of probability per goal tuple, its Rmat is the last goal tuple's (0).
+    // A row of Pmat is kept as its touched next states only (a few dozen of nS; full rows for every (s, a) would be
+    // nS^2 * 40 bytes, 5.5 GB at 11x7); each accumulates its probabilities in tuple and entry order, as a dense row would.
+    std::vector<std::vector<std::pair<int32_t, double>>> row((size_t)nS * 5);
     std::vector<double> Rm((size_t)nS * 5, 0.0);
     for (size_t f = 0; f < T; ++f) {
         if (R.kind[f] == 0) continue;
         const int s = obs_of(f);
         for (int a = 0; a < 5; ++a) {
             const size_t key = f * 25 + (fixed_a ? policy[s] : a) * 5 + (fixed_b ? policy[s] : a);
-            std::vector<double>& r = row[(size_t)s * 5 + a];
-            if (r.empty()) r.assign(nS, 0.0);
+            std::vector<std::pair<int32_t, double>>& r = row[(size_t)s * 5 + a];
             double acc = 0.0;
             for (int k = 0; k < count[key]; ++k) {
                 const size_t e = key * kMaxOutcomes + k;
                 const double rr = flip ? -1.0 * (double)rew[e] : (double)rew[e];
-                r[obs_of((size_t)nxt[e])] += prob[e];
+                const int32_t ns = obs_of((size_t)nxt[e]);
+                auto it = std::find_if(r.begin(), r.end(), [ns](const std::pair<int32_t, double>& x) { return x.first == ns; });
+                if (it == r.end()) r.emplace_back(ns, 0.0 + prob[e]);
+                else it->second += prob[e];
                 acc = acc + prob[e] * rr;
             }
             Rm[(size_t)s * 5 + a] = acc;
         }
     }
+    // ascending next state, exact zeros dropped: the entries a scan of the dense row would emit
     std::vector<int32_t> m_off((size_t)nS * 5 + 1, 0); std::vector<PlanEntry> m_lists;
     const PlanEntry m_pad{0.0, 0, 0.0f};
     for (size_t q = 0; q < (size_t)nS * 5; ++q) {
-        for (int ns = 0; ns < nS; ++ns) if (row[q][ns] != 0.0) m_lists.push_back(PlanEntry{row[q][ns], ns, 0.0f});
+        std::sort(row[q].begin(), row[q].end());                        // next states are distinct within a row
+        for (const auto& x : row[q]) if (x.second != 0.0) m_lists.push_back(PlanEntry{x.second, x.first, 0.0f});
         while (m_lists.size() % kPlanPad) m_lists.push_back(m_pad);
         m_off[q + 1] = (int32_t)m_lists.size();
-        std::vector<double>().swap(row[q]);
+        std::vector<std::pair<int32_t, double>>().swap(row[q]);
     }
     PlanIO& io = h->plan;
     io = PlanIO{};

@@ -307,7 +307,18 @@ int soccer_enumerate_transitions(soccer_handle* h, int32_t* count, double* prob,
  * assembled from soccer_enumerate_transitions and cached on the handle until the policy changes.  One
  * single-workgroup kernel runs a whole planner; float64 throughout.  Inputs and outputs are HOST arrays
  * (V[n_states], Q[n_states*5], pi[n_states] int32); any output may be NULL.  max_sweeps bounds the total
- * number of sweeps over the state space (SOCCER_E_STATE if it is reached; the outputs hold the last iterate).
+ * number of sweeps over the state space, over all evaluations of policy iteration and modified policy iteration, whose
+ * greedy steps count as sweeps too.  A sweep that reaches it without meeting the stopping rule ends the call with
+ * SOCCER_E_STATE, the counter is still written, and the outputs hold:
+ *   value iteration             V the iterate the last sweep started from, Q and pi that sweep's (as when it converges)
+ *   policy evaluation, dense evaluation   the last iterate computed.  Dense evaluation stops after k sweeps anyway; when the
+ *                               k-th is also sweep max_sweeps and the change is still >= theta, it returns SOCCER_E_STATE too
+ *   policy iteration            V the iterate at which the evaluation in progress was cut off, Q and pi one improvement
+ *                               from that V, which is counted
+ *   modified policy iteration   cut off at a greedy step: V = max_a Q, Q and pi of that step; inside an evaluation: V that
+ *                               evaluation's last iterate, Q and pi of the greedy step it started from, the evaluation counted
+ * The state count is bounded by the workgroup's LDS (V[n_states] in float64 must fit in 150 KiB: 14x7 is the largest 7-row
+ * pitch, 13x8 is refused with SOCCER_E_INVALID "too many states").
  *
  * The list-based planners evaluate  Q[s][a] += prob * (reward + discount_factor * V[next] * (not done))  in
  * list order like the reference: values, greedy policies and iteration counts are the reference's BIT FOR BIT.
