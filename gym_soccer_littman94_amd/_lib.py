@@ -49,6 +49,17 @@ class RolloutExtra(C.Structure):
     _fields_ = [("final_obs", C.c_void_p), ("prob_code", C.c_void_p)]
 
 
+class RolloutShape(C.Structure):
+    """soccer_rollout_shape_info"""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "tail", "action_source", "slip_selection", "small_pitch", "full",
+                                         "table_placement", "parts", "chunks", "reserved_")] + \
+               [("dynamic_lds_bytes", C.c_uint64), ("lds_limit", C.c_uint64)]
+
+
+ROLLOUT_NONE, ROLLOUT_BYTE_PARALLEL, ROLLOUT_PER_LANE = 0, 1, 2
+TABLES_NONE, TABLES_LDS, TABLES_GLOBAL = 0, 1, 2
+
+
 class ScalarIO(C.Structure):
     """soccer_scalar_io"""
     _fields_ = [("row_a", C.c_int8), ("col_a", C.c_int8), ("row_b", C.c_int8), ("col_b", C.c_int8),
@@ -105,6 +116,7 @@ PROTOTYPES = {
     "soccer_set_policy": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "soccer_host_view": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "soccer_state_streams": (C.c_int, [C.c_void_p]),
+    "soccer_rollout_shape": (C.c_int, [C.c_void_p, C.POINTER(RolloutShape)]),
     "soccer_set_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 7),
     "soccer_get_state": (C.c_int, [C.c_void_p] + [C.c_void_p] * 7),
     "soccer_dims": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_int32)] * 4),

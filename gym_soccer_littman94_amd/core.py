@@ -667,6 +667,14 @@ class SoccerBatch:
             x = _lib.RolloutExtra(_ptr(final_obs), _ptr(prob_code))
             self._check(self.lib.batched_rollout_ex(self.h, C.byref(a), C.byref(x)))
 
+    def rollout_shape(self):
+        """soccer_rollout_shape: which launch shape the most recent rollout() took, as a dict of ints — kernel (0 none yet,
+        1 byte-parallel, 2 per-lane), tail, action_source (0..5), slip_selection (0..2), small_pitch, full, table_placement
+        (0 none, 1 LDS, 2 global memory), parts, chunks, dynamic_lds_bytes, lds_limit.  Diagnostics: results never depend on it."""
+        s = _lib.RolloutShape()
+        self._check(self.lib.soccer_rollout_shape(self.h, C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in s._fields_ if name != "reserved_"}
+
     def trajectory_returns(self, n_steps, reward, terminated, truncated, stride, last_return=None, episode_count=None, hist=True):
         """soccer_trajectory_returns: one pass over [n_steps][n] result trajectories (device) -> per-lane return of the most recently
         finished episode (int8[n]), per-lane finished-episode count (int32[n]) and, with hist=True (synchronises), the

@@ -152,6 +152,7 @@ struct soccer_handle {
     unsigned long long stamp_prev = 0;      // ... from this value (what the slot held when the replay was enqueued)
     unsigned long long swar_launch_lanes = kSwarLaunchLanes;   // lanes per step_kernel_swar / rollout_swar_kernel launch (SOCCER_SWAR_LAUNCH_LANES: tests of the split)
     int rollout_pref = 0;                   // SOCCER_ROLLOUT=1 (A/B runs, tests of the fallback): never the byte-parallel rollout
+    soccer_rollout_shape_info last_rollout{};   // soccer_rollout_shape: what batched_rollout_ex last launched (lds_limit is filled in on read)
     SlipF64* d_slip_f64 = nullptr;          // SLIPM == 3: nominal float64 slip thresholds (step_kernel_swar with caller-supplied uniforms)
     uint32_t* d_worklist = nullptr;         // ... and the groups it leaves to the exact walk: [n / 4] indices, the count and the
                                             // tail's statistics behind them (worklist_count)

@@ -48,6 +48,13 @@ static void launch_rollout(soccer_handle* h, const KernelParams& P, const Rollou
 
 extern "C" int batched_rollout(soccer_handle* h, const soccer_rollout_args* a) { return batched_rollout_ex(h, a, nullptr); }
 
+extern "C" int soccer_rollout_shape(const soccer_handle* h, soccer_rollout_shape_info* out) {
+    if (!h || !out) return SOCCER_E_INVALID;
+    *out = h->last_rollout;
+    out->lds_limit = h->lds_limit;
+    return SOCCER_OK;
+}
+
 extern "C" int batched_rollout_ex(soccer_handle* h, const soccer_rollout_args* a, const soccer_rollout_extra* x) {
     if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
     if (!a || a->n_steps < 1) return fail(h, SOCCER_E_INVALID, "batched_rollout: n_steps must be >= 1");
@@ -122,6 +129,10 @@ extern "C" int batched_rollout_ex(soccer_handle* h, const soccer_rollout_args* a
             // The kernel's byte offsets are 32-bit: a handle beyond kSwarLaunchLanes lanes is rolled out part by part (lanes never
             // interact), every part over the same ticks, each handed its piece of every stream; the last one publishes the tick.
             const RolloutSwar RS0 = RS; const RolloutIO io0 = io;
+            soccer_rollout_shape_info sh{};             // soccer_rollout_shape: what this chunk launches
+            sh.kernel = SOCCER_ROLLOUT_BYTE_PARALLEL; sh.tail = n4 < n_all; sh.slip_selection = sm; sh.small_pitch = h->swar_c.small ? 1 : 0;
+            sh.full = (io.final_obs || io.prob_code) ? 1 : 0; sh.dynamic_lds_bytes = smem;
+            sh.table_placement = !(dyn && (io.mix_a || io.mix_b || fixed)) ? SOCCER_TABLES_NONE : RS.lds_tables ? SOCCER_TABLES_LDS : SOCCER_TABLES_GLOBAL;
             for (unsigned long long c0 = 0; c0 < n4; c0 += h->swar_launch_lanes) {
             const unsigned long long cn = std::min<unsigned long long>(h->swar_launch_lanes, n4 - c0);
             RS = RS0; io = io0;
@@ -149,6 +160,7 @@ extern "C" int batched_rollout_ex(soccer_handle* h, const soccer_rollout_args* a
 #define LAUNCH_D(SV) do { if (dm == 0) LAUNCH_S(0, SV); else if (dm == 1) LAUNCH_S(1, SV); else if (dm == 2) LAUNCH_S(2, SV); \
                           else if (dm == 4) LAUNCH_S(4, SV); else if (dm == 5) LAUNCH_S(5, SV); else LAUNCH_S(3, SV); } while (0)
             if (sm == 0) LAUNCH_D(0); else if (sm == 1) LAUNCH_D(1); else LAUNCH_D(2);
+            sh.action_source = dm; sh.parts += 1;
 #undef LAUNCH_D
 #undef LAUNCH_S
 #undef LAUNCH_G
@@ -160,11 +172,21 @@ extern "C" int batched_rollout_ex(soccer_handle* h, const soccer_rollout_args* a
                 Q.first = n4; Q.n = n_all - n4;
                 launch_rollout<1>(h, Q, io0);           // (io0: the loop above left `io` offset to its last part; the per-lane kernel indexes by absolute lane)
             }
-        } else switch (E) {
-            case 8: launch_rollout<8>(h, P, io); break;
-            case 4: launch_rollout<4>(h, P, io); break;
-            default: launch_rollout<1>(h, P, io); break;
+            h->last_rollout = sh;
+        } else {
+            switch (E) {
+                case 8: launch_rollout<8>(h, P, io); break;
+                case 4: launch_rollout<4>(h, P, io); break;
+                default: launch_rollout<1>(h, P, io); break;
+            }
+            const bool tables = P.policy_a || P.policy_b || (io.sample_actions && (io.mix_a || io.mix_b));
+            soccer_rollout_shape_info sh{};
+            sh.kernel = SOCCER_ROLLOUT_PER_LANE; sh.action_source = (io.sample_actions || P.policy_a || P.policy_b) ? 3 : 0;
+            sh.slip_selection = h->slip ? 1 : 0; sh.full = (io.final_obs || io.prob_code) ? 1 : 0;
+            sh.table_placement = tables ? SOCCER_TABLES_GLOBAL : SOCCER_TABLES_NONE; sh.parts = 1; sh.dynamic_lds_bytes = h->smem_bytes;
+            h->last_rollout = sh;
         }
+        h->last_rollout.chunks = (a->n_steps + kChunk - 1) / kChunk;
         HIP_TRY(h, hipGetLastError());
     }
     return SOCCER_OK;

@@ -64,7 +64,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_best_response and soccer_evaluate_policies were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_best_response, soccer_evaluate_policies and soccer_rollout_shape were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -275,6 +275,46 @@ int soccer_host_view(soccer_handle* h, uint8_t** state, uint64_t* stride);
  * Results never depend on it.  The environment variable SOCCER_STATE_LAYOUT=wide, read by soccer_create,
  * forces 6 (tests and A/B runs).  0 for a NULL handle. */
 int soccer_state_streams(const soccer_handle* h);
+
+/* Which launch shape the handle's most recent batched_rollout / batched_rollout_ex call took (of a call longer than one
+ * 4096-step chunk: its last chunk; every chunk of a call takes the same shape).  Read-only diagnostics for tests and A/B runs:
+ * results never depend on any of it.  The host records it while it enqueues, so there is nothing to wait for.
+ *   kernel          SOCCER_ROLLOUT_NONE before the first rollout (every other field is then 0 except lds_limit),
+ *                   SOCCER_ROLLOUT_BYTE_PARALLEL (four lanes per thread; pitches and slips that fit the byte arithmetic) or
+ *                   SOCCER_ROLLOUT_PER_LANE (through the rule tables)
+ *   tail            1: the byte-parallel launch covered n_lanes & ~3 lanes and a per-lane launch on the same ticks the rest
+ *   action_source   where the kernel takes the actions from.  Byte-parallel: 0 both action streams, 1 both sampled uniformly,
+ *                   2 both sampled from mixed-policy tables held in LDS as one 16-byte row per state, 4 / 5 player A / B
+ *                   follows its fixed policy and the other side is streamed, 3 anything else (a table on one side only,
+ *                   tables beyond LDS, a fixed policy against a sampled side).  Per-lane: 0 both streams, 3 anything else
+ *   slip_selection  byte-parallel: 0 slip_prob == 0, 1 thresholds compared one by one, 2 by the bucket table (16.5 KB of
+ *                   static LDS).  Per-lane: 0 / 1 = slip_prob == 0 / > 0
+ *   small_pitch, full   byte-parallel: the geometry form for small pitches; the form that also writes final_obs / prob_code.
+ *                   Per-lane: 0, and whether the call asked for final_obs / prob_code
+ *   table_placement where the observation-keyed tables (mixed-policy rows, fixed policies) are read from:
+ *                   SOCCER_TABLES_NONE (the shape has none), SOCCER_TABLES_LDS (every workgroup stages them on entry) or
+ *                   SOCCER_TABLES_GLOBAL.  Byte-parallel rule: they go to LDS when, next to the 144 B of slip rows, they fit
+ *                   lds_limit minus the 16 KB + 16 B action staging area (only when an action stream is read) minus the
+ *                   static bucket table (only with slip_selection 2) — 16 B per state when both sides are sampled from
+ *                   tables, otherwise 2 x 8 B + 2 x 1 B (padded to 16) per state.  Per-lane: always global
+ *   parts           byte-parallel launches per chunk (handles beyond 2^30 lanes are rolled out part by part; every part
+ *                   stages its own tables); 1 for the per-lane kernel
+ *   chunks          launches in time: ceil(n_steps / 4096)
+ *   dynamic_lds_bytes   dynamic LDS of the (main) launch; above 48 KB the kernel's limit is raised first
+ *   lds_limit       what a workgroup of this device may be given (64 KB on CDNA3, 160 KB on gfx950); set at create */
+#define SOCCER_ROLLOUT_NONE          0
+#define SOCCER_ROLLOUT_BYTE_PARALLEL 1
+#define SOCCER_ROLLOUT_PER_LANE      2
+#define SOCCER_TABLES_NONE   0
+#define SOCCER_TABLES_LDS    1
+#define SOCCER_TABLES_GLOBAL 2
+typedef struct soccer_rollout_shape_info {
+    int32_t  kernel, tail, action_source, slip_selection, small_pitch, full, table_placement, parts, chunks;
+    int32_t  reserved_;
+    uint64_t dynamic_lds_bytes;
+    uint64_t lds_limit;
+} soccer_rollout_shape_info;
+int soccer_rollout_shape(const soccer_handle* h, soccer_rollout_shape_info* out);
 
 /* ---- state injection / readback (`env.state = tuple`, tests/test_deterministic...py:43) -- */
 /* HOST pointers of n_lanes elements; any pointer may be NULL (field left unchanged / not read).

@@ -38,6 +38,37 @@ def test_exact_walk_stats_is_declared_and_rejects_a_null_handle():
     assert parts.value == 7 and groups.value == 7
 
 
+def test_rollout_shape_is_declared_rejects_null_and_has_the_header_layout(tmp_path):
+    """soccer_rollout_shape (which launch shape the last rollout took) is part of the ABI, validates before any device work,
+    and its ctypes mirror has the size and the offsets the C compiler gives soccer_rollout_shape_info"""
+    import subprocess
+    assert "soccer_rollout_shape" in _declared_symbols()
+    lib = _lib.load()
+    sh = _lib.RolloutShape()
+    assert lib.soccer_rollout_shape(None, C.byref(sh)) == _lib.E_INVALID
+    src = tmp_path / "shape.c"
+    src.write_text("""
+#include <stdio.h>
+#include <stddef.h>
+#include "soccer_hip.h"
+int main(void) {
+    printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(soccer_rollout_shape_info), offsetof(soccer_rollout_shape_info, action_source),
+           offsetof(soccer_rollout_shape_info, table_placement), offsetof(soccer_rollout_shape_info, chunks),
+           offsetof(soccer_rollout_shape_info, dynamic_lds_bytes), offsetof(soccer_rollout_shape_info, lds_limit));
+    printf("%d %d %d %d %d %d\\n", SOCCER_ROLLOUT_NONE, SOCCER_ROLLOUT_BYTE_PARALLEL, SOCCER_ROLLOUT_PER_LANE,
+           SOCCER_TABLES_NONE, SOCCER_TABLES_LDS, SOCCER_TABLES_GLOBAL);
+    return 0;
+}
+""")
+    exe = tmp_path / "shape"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
+    S = _lib.RolloutShape
+    assert got == [C.sizeof(S), S.action_source.offset, S.table_placement.offset, S.chunks.offset, S.dynamic_lds_bytes.offset,
+                   S.lds_limit.offset, _lib.ROLLOUT_NONE, _lib.ROLLOUT_BYTE_PARALLEL, _lib.ROLLOUT_PER_LANE,
+                   _lib.TABLES_NONE, _lib.TABLES_LDS, _lib.TABLES_GLOBAL]
+
+
 def test_struct_layouts_match_header(tmp_path):
     """ctypes mirrors of the ABI structs have the size and field offsets the C compiler gives the header."""
     import subprocess

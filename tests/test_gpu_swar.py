@@ -120,46 +120,105 @@ def test_step_kernel_swar_fixed_policy(w, h, slip, fixed, full):
 _EXTRAS = [0]
 
 
-def _rollout_vs_oracle(b, o, acts, T, n, sample=False, mix=None, extras=None):
-    """extras: also ask for batched_rollout_ex's per-step final_obs / prob_code and check them; None = every other call of this
-    helper, so that both the plain and the FULL instantiations see every parametrisation family"""
-    if extras is None:
-        _EXTRAS[0] += 1; extras = bool(_EXTRAS[0] & 1)
-    A = B = None
-    if not sample:
-        A = b.alloc((T, n), np.int8).upload(acts[:, 0]); B = b.alloc((T, n), np.int8).upload(acts[:, 1])
-    obs = b.alloc((T, n), np.uint16); rew = b.alloc((T, n), np.int8); term = b.alloc((T, n), np.uint8); trunc = b.alloc((T, n), np.uint8)
-    rs = b.alloc(n, np.int32).fill(0); ec = b.alloc(n, np.int32).fill(0)
+def _oracle_rollout(o, acts, T, n, sample=False, mix=None, policy=None, fixed=None):
+    """T oracle steps with the rollout's action sources -> (what every step returned, what the run saw): actions sampled by
+    sample_actions_mixed(current observation, mix_a, mix_b), policy[current observation] on the fixed side, acts otherwise"""
+    ta, tb = mix if mix is not None else (None, None)
     lut = o.tables()[0]
     f = ((((o.row_a.astype(np.int64) * o.W + o.col_a) * o.H + o.row_b) * o.W + o.col_b) << 1) | (o.poss & 1)
     cur = lut[f]
-    da = db = None
-    if mix is not None:
-        da = b.alloc(mix[0].shape, np.uint16).upload(mix[0]); db = b.alloc(mix[1].shape, np.uint16).upload(mix[1])
-    fo = b.alloc((T, n), np.uint16).fill(0xEE) if extras else None; cd = b.alloc((T, n), np.uint8).fill(0xEE) if extras else None
-    b.rollout(T, A, B, act_stride=n, sample_actions=sample, obs=obs, reward=rew, terminated=term, truncated=trunc, out_stride=n,
-              return_sum=rs, episode_count=ec, mix_a=da, mix_b=db, final_obs=fo, prob_code=cd)
-    O, R, TE, TR = obs.download(), rew.download(), term.download(), trunc.download()
-    FO = fo.download() if extras else None; CD = cd.download() if extras else None
+    sampled = [side for side in ("player_a", "player_b") if sample and side != fixed]
+    draws = {side: np.zeros(5, np.int64) for side in sampled}
+    degenerate = np.zeros(o.nS, bool); visited = np.zeros(o.nS, bool)
+    for side, t in (("player_a", ta), ("player_b", tb)):
+        if side in sampled and t is not None:
+            degenerate |= ((t == 0) | (t == 32768)).any(axis=1)
     ret = np.zeros(n, np.int64); eps = np.zeros(n, np.int64)
+    plus = minus = 0
+    want = []
     for k in range(T):
         if sample:
-            a, bb = o.sample_actions_mixed(cur, *(mix if mix is not None else (None, None)))
+            a, bb = o.sample_actions_mixed(cur, ta, tb)
         else:
             a, bb = acts[k, 0], acts[k, 1]
+        if fixed == "player_a": a = policy[cur]
+        if fixed == "player_b": bb = policy[cur]
+        frozen = ((o.poss >> 1) & 1).astype(bool)
+        visited[cur[~frozen]] = True
+        for side, x in (("player_a", a), ("player_b", bb)):
+            if side in sampled: draws[side] += np.bincount(x[~frozen], minlength=5)
         c = o.step(a, bb)
-        np.testing.assert_array_equal(O[k], c["obs"], err_msg="obs %d" % k); np.testing.assert_array_equal(R[k], c["reward"], err_msg="reward %d" % k)
-        np.testing.assert_array_equal(TE[k], c["terminated"]); np.testing.assert_array_equal(TR[k], c["truncated"])
-        if extras:
-            np.testing.assert_array_equal(FO[k], c["final_obs"], err_msg="final_obs %d" % k)
-            np.testing.assert_array_equal(CD[k], c["prob_code"], err_msg="prob_code %d" % k)
-        frozen = ((o.poss >> 1) & 1).astype(bool) if not o.autoreset else np.zeros(n, bool)
-        ret += c["reward"]; eps += ((c["terminated"] | c["truncated"]) != 0)
+        done = ((c["terminated"] | c["truncated"]) != 0) & ~frozen      # a step on a frozen lane finishes nothing
+        ret += c["reward"]; eps += done
+        plus += int((c["reward"] == 1).sum()); minus += int((c["reward"] == -1).sum())
+        want.append(c)
         cur = c["obs"]
+    return want, dict(draws=draws, plus=plus, minus=minus, degenerate_rows=int((visited & degenerate).sum()), episodes=eps, returns=ret)
+
+
+def _rollout_vs_oracle(b, o, acts, T, n, sample=False, mix=None, extras=None, policy=None, fixed=None, precheck=None, strict=False,
+                       stride=None):
+    """One batched_rollout(_ex) of T steps against T oracle steps: every lane of every step, then the state, the per-lane
+    return sums and the histogram.  The oracle runs first, on its own (_oracle_rollout).
+    sample / mix: actions sampled in the kernel, uniformly or from the (mix_a, mix_b) threshold tables (either may be None).
+    policy / fixed: the handle plays `fixed` ("player_a" / "player_b") by policy[current observation] (b.set_policy is the
+        caller's); that side has no stream, the other one is streamed from `acts` or sampled.
+    extras: also ask for batched_rollout_ex's per-step final_obs / prob_code and check them; None = every other call of this
+        helper, so that both the plain and the FULL instantiations see every parametrisation family.
+    precheck: called with what the oracle run saw (draws per sampled side and action, episodes by sign, the visited rows
+        whose thresholds hold a 0 or a 32768, finished episodes per lane) BEFORE the device is looked at.
+    strict: also the tick, the per-lane episode counts and the misuse flags (frozen lanes stepped since the oracle was
+        made: both sides are sticky).
+    stride: elements between the rows of every [T][n] stream (default n).  The byte-parallel kernel needs rows that start on a
+        multiple of 4: a ragged lane count with stride n goes through the per-lane kernel as a whole."""
+    if extras is None:
+        _EXTRAS[0] += 1; extras = bool(_EXTRAS[0] & 1)
+    ta, tb = mix if mix is not None else (None, None)
+    want, seen = _oracle_rollout(o, acts, T, n, sample=sample, mix=mix, policy=policy, fixed=fixed)
+    ret, eps = seen["returns"], seen["episodes"]
+    if precheck is not None:
+        precheck(seen)
+    stride = n if stride is None else int(stride)
+    pad = stride - n
+
+    def rows(x):                                    # [T, n] -> [T, stride]
+        return x if not pad else np.concatenate([x, np.zeros((T, pad), x.dtype)], axis=1)
+    A = B = None
+    if not sample:
+        if fixed != "player_a": A = b.alloc((T, stride), np.int8).upload(rows(acts[:, 0]))
+        if fixed != "player_b": B = b.alloc((T, stride), np.int8).upload(rows(acts[:, 1]))
+    obs = b.alloc((T, stride), np.uint16).fill(0xEE); rew = b.alloc((T, stride), np.int8).fill(0xEE)
+    term = b.alloc((T, stride), np.uint8).fill(0xEE); trunc = b.alloc((T, stride), np.uint8).fill(0xEE)
+    rs = b.alloc(n, np.int32).fill(0); ec = b.alloc(n, np.int32).fill(0)
+    da = b.alloc(ta.shape, np.uint16).upload(ta) if ta is not None else None
+    db = b.alloc(tb.shape, np.uint16).upload(tb) if tb is not None else None
+    fo = b.alloc((T, stride), np.uint16).fill(0xEE) if extras else None; cd = b.alloc((T, stride), np.uint8).fill(0xEE) if extras else None
+    # (sampled actions: no action stride, so that no launch can take it for the output stride)
+    b.rollout(T, A, B, act_stride=0 if sample else stride, sample_actions=sample, obs=obs, reward=rew, terminated=term, truncated=trunc,
+              out_stride=stride, return_sum=rs, episode_count=ec, mix_a=da, mix_b=db, final_obs=fo, prob_code=cd)
+    O, R, TE, TR = obs.download(), rew.download(), term.download(), trunc.download()
+    FO = fo.download() if extras else None; CD = cd.download() if extras else None
+    for x in (O, R, TE, TR, FO, CD):                # nothing written between the rows
+        assert x is None or (x[:, n:].view(np.uint8) == 0xEE).all()
+    for k, c in enumerate(want):
+        np.testing.assert_array_equal(O[k, :n], c["obs"], err_msg="obs %d" % k); np.testing.assert_array_equal(R[k, :n], c["reward"], err_msg="reward %d" % k)
+        np.testing.assert_array_equal(TE[k, :n], c["terminated"], err_msg="terminated %d" % k)
+        np.testing.assert_array_equal(TR[k, :n], c["truncated"], err_msg="truncated %d" % k)
+        if extras:
+            np.testing.assert_array_equal(FO[k, :n], c["final_obs"], err_msg="final_obs %d" % k)
+            np.testing.assert_array_equal(CD[k, :n], c["prob_code"], err_msg="prob_code %d" % k)
     _state_equal(b, o)
     np.testing.assert_array_equal(rs.download(), ret)
-    np.testing.assert_array_equal(b.stats()[0], o.hist)
-    return ec.download(), eps
+    hist, misuse = b.stats()
+    np.testing.assert_array_equal(hist, o.hist)
+    got_ec = ec.download()
+    if strict:
+        np.testing.assert_array_equal(got_ec, eps)
+        assert b.tick == o.tick
+        assert misuse == (SoccerBatch.MISUSE_FROZEN if o.misuse else 0)
+    for x in (A, B, obs, rew, term, trunc, rs, ec, da, db, fo, cd):
+        if x is not None: x.free()
+    return got_ec, eps
 
 
 @pytest.mark.parametrize("w,h,slip", [(5, 4, 0.0), (7, 5, 0.0), (9, 6, 0.0), (11, 7, 0.0), (5, 4, 0.2), (11, 7, 0.3), (6, 4, 1.0), (5, 4, 0.1),
@@ -195,7 +254,8 @@ def test_rollout_swar_streams_every_lane_every_step(w, h, slip):
 @pytest.mark.parametrize("w,h,slip", [(5, 4, 0.0), (5, 4, 0.2), (11, 7, 0.0), (5, 4, 0.9)])
 def test_rollout_swar_sampled_and_mixed_policies(w, h, slip):
     """in-kernel sampling: uniform, and from [nS, 4] mixed-policy thresholds — staged in LDS on 5x4, gathered from global
-    memory on 11x7 (nS = 11 705 rows do not fit next to each other in 64 KB)"""
+    memory on 11x7 (nS = 11 705: two tables of 8-byte rows do not fit next to each other in LDS, neither in 64 KB nor in
+    gfx950's 160 KB)"""
     n, T = 8192, 100
     rng = np.random.default_rng(31)
     o = Oracle(w, h, slip, n=n, seed=8, autoreset=True)
@@ -745,8 +805,13 @@ def test_a_rollout_split_into_several_launches_is_the_same_rollout(slip, monkeyp
     rng = np.random.default_rng(13)
     b.reset(); o.reset()
     acts = rng.integers(0, 5, size=(T, 2, n), dtype=np.int8)
-    _rollout_vs_oracle(b, o, acts, T, n)
-    _rollout_vs_oracle(b, o, None, T, n, sample=True)
+    # rows n + 1 apart: with rows an odd number of elements apart the whole call would go through the per-lane kernel
+    _rollout_vs_oracle(b, o, acts, T, n, stride=n + 1)
+    sh = b.rollout_shape()
+    assert (sh["kernel"], sh["parts"], sh["tail"]) == (1, 4, 1)
+    _rollout_vs_oracle(b, o, None, T, n, sample=True, stride=n + 1)
+    sh = b.rollout_shape()
+    assert (sh["kernel"], sh["parts"], sh["tail"]) == (1, 4, 1)
     io = _IO(b, True)
     for k in range(5):
         a = rng.integers(0, 5, size=(2, n), dtype=np.int8)
