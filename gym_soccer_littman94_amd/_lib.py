@@ -187,6 +187,7 @@ PROTOTYPES = {
     "soccer_graph_begin": (C.c_int, [C.c_void_p]),
     "soccer_graph_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "soccer_graph_launch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "soccer_graph_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "soccer_graph_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 

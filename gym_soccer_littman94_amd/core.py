@@ -897,5 +897,11 @@ class SoccerBatch:
     def graph_launch(self, g, replays=1):
         self._check(self.lib.soccer_graph_launch(self.h, g, int(replays)))
 
+    def graph_info(self, g):
+        """How a capture was recorded: {"kernel_nodes", "steps_fused", "fused_launches"} (soccer_graph_info)."""
+        nodes, steps, runs = C.c_int32(), C.c_int64(), C.c_int32()
+        self._check(self.lib.soccer_graph_info(g, C.byref(nodes), C.byref(steps), C.byref(runs)))
+        return {"kernel_nodes": int(nodes.value), "steps_fused": int(steps.value), "fused_launches": int(runs.value)}
+
     def graph_destroy(self, g):
         self.lib.soccer_graph_destroy(self.h, g)

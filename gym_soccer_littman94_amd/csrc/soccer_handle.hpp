@@ -100,6 +100,18 @@ struct soccer_graph {
     uint64_t ticks = 0;       // ticks consumed by one replay
     int start_slot = 0;       // tick slot the first captured launch reads
     bool stamped = false;     // soccer_timer_start / _mark were captured: a replay writes stamp slots 0 and 1
+    int32_t kernel_nodes = 0;   // soccer_graph_info: kernel nodes the batched_* calls recorded (launch parts one by one; not the stamps, not the tick-move node)
+    int64_t steps_fused = 0;    // ... captured steps that went into multi-step launches
+    int32_t fused_launches = 0; // ... and the runs they formed
+};
+
+// Captured steps that have not been launched yet (soccer_step.hip): consecutive batched_step calls of one capture whose rows
+// are evenly spaced are one rollout, and are recorded as one when the run ends (flush_pending).  `first` is the run's first
+// step by value; the strides are fixed by the second step.
+struct PendingRun {
+    soccer_step_args first{};
+    int64_t len = 0;                        // steps in the run (0: none pending)
+    int64_t act_stride = 0, out_stride = 0; // elements between consecutive steps (len >= 2)
 };
 
 struct soccer_handle {
@@ -136,6 +148,12 @@ struct soccer_handle {
     uint64_t capture_ticks = 0;
     int capture_calls = 0;
     int capture_start_slot = 0;
+    PendingRun run;                         // captured steps not launched yet; dropped with the capture
+    bool graph_fuse = true;                 // SOCCER_GRAPH_FUSE=0 (A/B runs): every captured step is a launch of its own
+    int capture_kernels = 0;                // kernel nodes the batched_* calls of this capture recorded (note_kernel)
+    int64_t capture_steps_fused = 0; int capture_fused_launches = 0;
+    unsigned long long* d_hist_unread = nullptr;   // as large as d_hist and never read: where a fused run of a handle without
+                                            // SOCCER_F_STEP_STATS lets rollout_swar_kernel count its episodes
     int n_cu = 256;
     size_t lds_limit = 64 * 1024;           // hipDeviceProp_t::sharedMemPerBlockOptin: what a workgroup may be given (160 KB on gfx950)
     uint4* d_sub = nullptr;                 // integer slip thresholds (KernelParams::sub)
@@ -202,6 +220,9 @@ static inline void bind_tick(soccer_handle* h, KernelParams& P, uint64_t ticks) 
     else h->tick += ticks;
 }
 
+// soccer_graph_info's kernel_nodes: called next to every kernel launch of batched_step* / batched_rollout* / batched_reset
+static inline void note_kernel(soccer_handle* h) { if (h->capturing) h->capture_kernels += 1; }
+
 static inline int grid_for(const soccer_handle* h, uint64_t work_items) {
     uint64_t blocks = (work_items + kBlock - 1) / kBlock;
     if (blocks < 1) blocks = 1;
@@ -212,6 +233,14 @@ static inline int grid_for(const soccer_handle* h, uint64_t work_items) {
 // ---- what one unit needs from another ------------------------------------------------------------
 // soccer_rollout.hip: lets rollout_kernel<E, slip, lut_lds, *> of this handle's shape take `bytes` of dynamic LDS (soccer_create)
 hipError_t rollout_raise_smem_limit(const soccer_handle* h, size_t bytes);
+// soccer_rollout.hip: would a rollout with these arguments take rollout_swar_kernel (the byte-parallel arm)?
+bool rollout_takes_swar(const soccer_handle* h, const soccer_rollout_args* a, const soccer_rollout_extra* x);
+// soccer_rollout.hip: batched_rollout_ex behind its argument checks, counting episodes into `hist` (a captured run: flush_run)
+int rollout_enqueue(soccer_handle* h, const soccer_rollout_args* a, const soccer_rollout_extra* x, unsigned long long* hist);
+// soccer_step.hip: records the pending run of captured steps: one step as batched_step_ex would have, more as one rollout
+int flush_run(soccer_handle* h);
+// what every entry point that may put work on the stream during a capture calls first, so that the order of the calls is kept
+static inline int flush_pending(soccer_handle* h) { return h->run.len ? flush_run(h) : SOCCER_OK; }
 // soccer_comm.hip: destroys the handle's communicator, if it has one (the handle's destructor)
 void comm_release(soccer_handle* h);
 // soccer_learners.hip: frees the learners the caller did not destroy (the handle's destructor; the stream has drained)

@@ -132,6 +132,9 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
     while (h->hist_slots < (n + 255) / 256) h->hist_slots <<= 1;
     if (int rc = h->bufs.alloc(nullptr, h->hist_slots * kHistStride, &h->d_hist)) return rc;
     HIP_TRY(nullptr, hipMemset(h->d_hist, 0, sizeof(unsigned long long) * h->hist_slots * kHistStride));
+    // its twin for the fused runs of a capture when the handle counts no step statistics (flush_run): written, never read
+    if (int rc = h->bufs.alloc(nullptr, h->hist_slots * kHistStride, &h->d_hist_unread)) return rc;
+    HIP_TRY(nullptr, hipMemset(h->d_hist_unread, 0, sizeof(unsigned long long) * h->hist_slots * kHistStride));
     if (int rc = h->bufs.alloc_pinned(nullptr, kMappedBytes / sizeof(unsigned int), OwnedBufs::kPinnedMapped, &h->misuse_host)) return rc;
     std::memset(h->misuse_host, 0, kMappedBytes);
     HIP_TRY(nullptr, hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_misuse), h->misuse_host, 0));
@@ -186,6 +189,7 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
     if (h->swar_ok) h->swar_c = swar::make_consts(R.H, R.W, R.goal_lo, R.goal_hi, cfg->max_steps, R.n_isd, R.isd, P.autoreset != 0u);
     h->slip = cfg->slip_prob != 0.0;
     if (const char* e2 = std::getenv("SOCCER_ROLLOUT")) h->rollout_pref = std::atoi(e2);
+    if (const char* e4 = std::getenv("SOCCER_GRAPH_FUSE")) h->graph_fuse = std::atoi(e4) != 0;   // (A/B runs, tests: a launch per captured step)
     if (const char* e3 = std::getenv("SOCCER_SWAR_LAUNCH_LANES")) {
         const unsigned long long v = std::strtoull(e3, nullptr, 10) & ~3ull;
         if (v >= 4ull && v <= kSwarLaunchLanes) h->swar_launch_lanes = v;
@@ -271,6 +275,7 @@ extern "C" int batched_reset(soccer_handle* h, const uint8_t* mask, const double
     if (!aligned(u_reset, 8) || !aligned(obs, 2))
         return fail(h, SOCCER_E_INVALID, "batched_reset: u_reset must be 8-byte and obs 2-byte aligned");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (int rc = flush_pending(h)) return rc;       // captured steps before this call come first
     KernelParams P = h->P;
     bind_tick(h, P, 1);
     ResetIO io{mask, u_reset, obs};
@@ -285,6 +290,7 @@ extern "C" int batched_reset(soccer_handle* h, const uint8_t* mask, const double
                        else hipLaunchKernelGGL((reset_kernel_swar<false, true>), g, b, 0, h->stream, RS); }
         else { if (mask) hipLaunchKernelGGL((reset_kernel_swar<true, false>), g, b, 0, h->stream, RS);
                else hipLaunchKernelGGL((reset_kernel_swar<false, false>), g, b, 0, h->stream, RS); }
+        note_kernel(h);
     }
     if (n4 < P.n) {
         KernelParams Q = P;
@@ -295,6 +301,7 @@ extern "C" int batched_reset(soccer_handle* h, const uint8_t* mask, const double
                        else hipLaunchKernelGGL((reset_kernel<false, true>), dim3(grid), dim3(kBlock), h->smem_bytes, h->stream, Q, io); }
         else { if (h->lut_lds) hipLaunchKernelGGL((reset_kernel<true, false>), dim3(grid), dim3(kBlock), h->smem_bytes, h->stream, Q, io);
                else hipLaunchKernelGGL((reset_kernel<false, false>), dim3(grid), dim3(kBlock), h->smem_bytes, h->stream, Q, io); }
+        note_kernel(h);
     }
     HIP_TRY(h, hipGetLastError());
     return SOCCER_OK;
@@ -703,6 +710,7 @@ extern "C" uint32_t soccer_peek_misuse(const soccer_handle* h) {
 extern "C" int soccer_reset_stats(soccer_handle* h) {
     if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (int rc = flush_pending(h)) return rc;
     HIP_TRY(h, hipMemsetAsync(h->d_hist, 0, sizeof(unsigned long long) * h->hist_slots * kHistStride, h->stream));
     HIP_TRY(h, hipMemsetAsync(h->d_misuse, 0, 64, h->stream));
     return SOCCER_OK;
@@ -740,6 +748,7 @@ extern "C" int soccer_memcpy_d2h(soccer_handle* h, void* dst, const void* src, s
 extern "C" int soccer_memset(soccer_handle* h, void* dst, int value, size_t bytes) {
     if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (int rc = flush_pending(h)) return rc;
     HIP_TRY(h, hipMemsetAsync(dst, value, bytes, h->stream));
     return SOCCER_OK;
 }
@@ -762,6 +771,7 @@ extern "C" int soccer_stamp(soccer_handle* h, int32_t slot) {
     if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
     if (slot < 0 || slot >= SOCCER_STAMP_SLOTS) return fail(h, SOCCER_E_INVALID, "stamp slot %d out of range (0..%d)", slot, SOCCER_STAMP_SLOTS - 1);
     HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (int rc = flush_pending(h)) return rc;       // (a captured soccer_timer_start / _mark comes through here too)
     hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(64), 0, h->stream, stamp_dev(h) + kStampStride * slot);
     HIP_TRY(h, hipGetLastError());
     return SOCCER_OK;
@@ -870,13 +880,24 @@ extern "C" int soccer_graph_begin(soccer_handle* h) {
     HIP_TRY(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     h->capturing = true; h->capture_ticks = 0; h->capture_calls = 0; h->capture_stamped = false;
     h->capture_start_slot = h->tick_slot;
-
+    h->run = PendingRun{}; h->capture_kernels = 0; h->capture_steps_fused = 0; h->capture_fused_launches = 0;
     return SOCCER_OK;
 }
 
 extern "C" int soccer_graph_end(soccer_handle* h, soccer_graph** out) {
     if (!h || !out) return fail(h, SOCCER_E_INVALID, "handle/out is NULL");
     if (!h->capturing) return fail(h, SOCCER_E_STATE, "no graph capture in progress");
+    if (const int rc = flush_pending(h)) {
+        // the last run could not be recorded: the capture is abandoned (the error text is the launch's)
+        const std::string why = h->err;
+        hipGraph_t dead = nullptr;
+        h->capturing = false; h->tick_slot = h->capture_start_slot;
+        (void)hipStreamEndCapture(h->stream, &dead);
+        if (dead) (void)hipGraphDestroy(dead);
+        (void)hipGetLastError();
+        h->err = why;
+        return rc;
+    }
     if (h->capture_calls % 2 != 0) {
         // An odd number of launches leaves the tick in the other slot, and the nodes' slot pointers are baked in: one more node
         // (a one-thread kernel, ~1.5 us per replay; an even count needs none) moves it back to where a replay starts reading.
@@ -888,6 +909,7 @@ extern "C" int soccer_graph_end(soccer_handle* h, soccer_graph** out) {
     hipGraph_t graph = nullptr;
     HIP_TRY(h, hipStreamEndCapture(h->stream, &graph));
     soccer_graph* g = new soccer_graph();
+    g->kernel_nodes = h->capture_kernels; g->steps_fused = h->capture_steps_fused; g->fused_launches = h->capture_fused_launches;
     g->graph = graph; g->ticks = h->capture_ticks; g->start_slot = h->capture_start_slot; g->stamped = h->capture_stamped;
     hipError_t e = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
     if (e != hipSuccess) {
@@ -922,6 +944,14 @@ extern "C" int soccer_graph_launch(soccer_handle* h, soccer_graph* g, int32_t re
     if (h->stamp_poll) h->stamp_prev = stamp_host(h)[kStampStride];
     for (int32_t r = 0; r < replays; ++r) HIP_TRY(h, hipGraphLaunch(g->exec, h->stream));
     h->tick += g->ticks * (uint64_t)(replays > 0 ? replays : 0);
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_graph_info(const soccer_graph* g, int32_t* kernel_nodes, int64_t* steps_fused, int32_t* fused_launches) {
+    if (!g) return fail(nullptr, SOCCER_E_INVALID, "graph is NULL");
+    if (kernel_nodes) *kernel_nodes = g->kernel_nodes;
+    if (steps_fused) *steps_fused = g->steps_fused;
+    if (fused_launches) *fused_launches = g->fused_launches;
     return SOCCER_OK;
 }
 

@@ -38,6 +38,7 @@ static void launch_rollout2(soccer_handle* h, const KernelParams& P, const Rollo
         if (h->lut_lds) hipLaunchKernelGGL((rollout_kernel<E, false, true, DYN>), g, b, h->smem_bytes, h->stream, P, io);
         else hipLaunchKernelGGL((rollout_kernel<E, false, false, DYN>), g, b, h->smem_bytes, h->stream, P, io);
     }
+    note_kernel(h);
 }
 template <int E>
 static void launch_rollout(soccer_handle* h, const KernelParams& P, const RolloutIO& io) {
@@ -55,8 +56,27 @@ extern "C" int soccer_rollout_shape(const soccer_handle* h, soccer_rollout_shape
     return SOCCER_OK;
 }
 
+// dword (e = 4) or wider I/O needs every stream aligned to e of its elements and both strides multiples of e
+static bool rollout_vec_ok(const soccer_rollout_args* a, const soccer_rollout_extra* x, int e) {
+    const uint16_t* x_fin = x ? x->final_obs : nullptr; const uint8_t* x_code = x ? x->prob_code : nullptr;
+    const bool any_out = a->obs || a->reward || a->terminated || a->truncated || x_fin || x_code;
+    const bool strides = (a->sample_actions || a->act_stride % e == 0) && (!any_out || a->out_stride % e == 0);
+    return strides && aligned(a->act_a, e) && aligned(a->act_b, e) && aligned(a->reward, e) &&
+           aligned(a->terminated, e) && aligned(a->truncated, e) && aligned(a->obs, 2 * e) && aligned(x_code, e) && aligned(x_fin, 2 * e) &&
+           aligned(a->return_sum, 4 * e) && aligned(a->episode_count, 4 * e);
+}
+
+// the byte-parallel rollout: every pitch that fits the byte arithmetic, slip 0 or an exact integer slip decision
+// (a lane count that is not a multiple of 4: the byte-parallel kernel over the first n & ~3 lanes, the one to three
+// left over through the per-lane kernel on the same ticks, like batched_step's ragged tail)
+bool rollout_takes_swar(const soccer_handle* h, const soccer_rollout_args* a, const soccer_rollout_extra* x) {
+    return h->swar_ok && (!h->slip || h->slip_swar_ok) && h->P.n >= 4ull && ((h->P.lane_offset + h->P.first) & 3ull) == 0ull &&
+           rollout_vec_ok(a, x, 4) && h->rollout_pref != 1;
+}
+
 extern "C" int batched_rollout_ex(soccer_handle* h, const soccer_rollout_args* a, const soccer_rollout_extra* x) {
     if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (int rc = flush_pending(h)) return rc;       // captured steps before this call come first
     if (!a || a->n_steps < 1) return fail(h, SOCCER_E_INVALID, "batched_rollout: n_steps must be >= 1");
     if (!a->sample_actions && ((!a->act_a && !h->P.policy_a) || (!a->act_b && !h->P.policy_b)))
         return fail(h, SOCCER_E_INVALID, "batched_rollout: an action stream is required for every player without a fixed policy (or sample_actions)");
@@ -71,14 +91,14 @@ extern "C" int batched_rollout_ex(soccer_handle* h, const soccer_rollout_args* a
         !aligned(a->mix_a, 8) || !aligned(a->mix_b, 8))
         return fail(h, SOCCER_E_INVALID, "batched_rollout: misaligned obs/return_sum/episode_count/mix_*");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
+    return rollout_enqueue(h, a, x, h->P.hist);
+}
+
+int rollout_enqueue(soccer_handle* h, const soccer_rollout_args* a, const soccer_rollout_extra* x, unsigned long long* hist) {
+    uint16_t* x_fin = x ? x->final_obs : nullptr; uint8_t* x_code = x ? x->prob_code : nullptr;
     int E = h->E;
-    auto ok = [&](int e) {
-        const bool strides = (a->sample_actions || a->act_stride % e == 0) && (!any_out || a->out_stride % e == 0);
-        return strides && aligned(a->act_a, e) && aligned(a->act_b, e) && aligned(a->reward, e) &&
-               aligned(a->terminated, e) && aligned(a->truncated, e) && aligned(a->obs, 2 * e) && aligned(x_code, e) && aligned(x_fin, 2 * e) &&
-               aligned(a->return_sum, 4 * e) && aligned(a->episode_count, 4 * e);
-    };
-    while (E > 1 && !ok(E)) E = E == 4 ? 1 : E / 2;
+    while (E > 1 && !rollout_vec_ok(a, x, E)) E = E == 4 ? 1 : E / 2;
+    const bool swar_roll = rollout_takes_swar(h, a, x);
     // one launch covers at most kChunk steps (per-thread episode counters are 16 bit wide); the tick
     // sequence of consecutive launches is contiguous, so chunking does not change any result
     constexpr int kChunk = 4096;
@@ -86,17 +106,13 @@ extern "C" int batched_rollout_ex(soccer_handle* h, const soccer_rollout_args* a
     for (int s0 = 0; s0 < a->n_steps; s0 += kChunk) {
         const int ns = a->n_steps - s0 < kChunk ? a->n_steps - s0 : kChunk;
         KernelParams P = h->P;
+        P.hist = hist;
         bind_tick(h, P, (uint64_t)ns);
         const long long ao = (long long)s0 * a->act_stride, oo = (long long)s0 * a->out_stride;
         RolloutIO io{ns, a->sample_actions, a->mix_a, a->mix_b, a->act_a ? a->act_a + ao : nullptr, a->act_b ? a->act_b + ao : nullptr,
                      (long long)a->act_stride, a->obs ? a->obs + oo : nullptr, a->reward ? a->reward + oo : nullptr,
                      a->terminated ? a->terminated + oo : nullptr, a->truncated ? a->truncated + oo : nullptr,
                      (long long)a->out_stride, a->return_sum, a->episode_count, x_fin ? x_fin + oo : nullptr, x_code ? x_code + oo : nullptr};
-        // the byte-parallel rollout: every pitch that fits the byte arithmetic, slip 0 or an exact integer slip decision
-        // (a lane count that is not a multiple of 4: the byte-parallel kernel over the first n & ~3 lanes, the one to three
-        // left over through the per-lane kernel on the same ticks, like batched_step's ragged tail)
-        const bool swar_roll = h->swar_ok && (!h->slip || h->slip_swar_ok) && P.n >= 4ull && ((P.lane_offset + P.first) & 3ull) == 0ull &&
-                               ok(4) && h->rollout_pref != 1;
         const unsigned long long n_all = P.n, n4 = swar_roll ? (P.n & ~3ull) : 0ull;
         if (swar_roll) {
             P.n = n4;
@@ -160,6 +176,7 @@ extern "C" int batched_rollout_ex(soccer_handle* h, const soccer_rollout_args* a
 #define LAUNCH_D(SV) do { if (dm == 0) LAUNCH_S(0, SV); else if (dm == 1) LAUNCH_S(1, SV); else if (dm == 2) LAUNCH_S(2, SV); \
                           else if (dm == 4) LAUNCH_S(4, SV); else if (dm == 5) LAUNCH_S(5, SV); else LAUNCH_S(3, SV); } while (0)
             if (sm == 0) LAUNCH_D(0); else if (sm == 1) LAUNCH_D(1); else LAUNCH_D(2);
+            note_kernel(h);
             sh.action_source = dm; sh.parts += 1;
 #undef LAUNCH_D
 #undef LAUNCH_S
@@ -168,6 +185,7 @@ extern "C" int batched_rollout_ex(soccer_handle* h, const soccer_rollout_args* a
             }
             if (n4 < n_all) {
                 KernelParams Q = h->P;
+                Q.hist = hist;
                 Q.tick_in = P.tick_in; Q.tick_out = nullptr;      // the main launch publishes the tick
                 Q.first = n4; Q.n = n_all - n4;
                 launch_rollout<1>(h, Q, io0);           // (io0: the loop above left `io` offset to its last part; the per-lane kernel indexes by absolute lane)

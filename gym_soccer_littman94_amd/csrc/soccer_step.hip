@@ -28,6 +28,7 @@ static void launch_step3(soccer_handle* h, const KernelParams& P, const StepIO& 
     const dim3 g(grid), b(kBlock);
     if (h->slip) hipLaunchKernelGGL((step_kernel<true, EXPLICIT_U, VEC, SHARED>), g, b, 0, h->stream, P, io);
     else hipLaunchKernelGGL((step_kernel<false, EXPLICIT_U, VEC, SHARED>), g, b, 0, h->stream, P, io);
+    note_kernel(h);
 }
 static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& io, bool explicit_u, bool vec) {
     const bool shared = ((P.lane_offset + P.first) & 3ull) == 0ull;
@@ -74,11 +75,13 @@ static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& i
                          P.policy_a, P.policy_b, off(io.u_step, c0), off(io.u_reset, c0),
                          h->d_slip_f64, h->d_worklist, worklist_count(h)};
             if (P.policy_a || P.policy_b) SWAR_OUT(true); else SWAR_OUT(false);
+            note_kernel(h);
             if (expl_slip) {
                 // the groups of THIS part that were listed: the per-lane kernel, one workgroup, same tick (it publishes nothing)
                 KernelParams R = P; R.first = c0; R.n = cn; R.tick_out = nullptr;
                 StepIO jo = io; jo.worklist = h->d_worklist; jo.work_count = worklist_count(h);
                 hipLaunchKernelGGL((step_kernel<true, true, true, true>), dim3(1), dim3(kBlock), 0, h->stream, R, jo);
+                note_kernel(h);
             }
         }
 #undef SWAR_OUT
@@ -100,6 +103,7 @@ static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& i
             if (h->slip && P.slip_int == 1u) hipLaunchKernelGGL((step_kernel_hot<true, true>), gh, b, 0, h->stream, HOT_ARGS);
             else if (h->slip) hipLaunchKernelGGL(step_kernel_hot<true>, gh, b, 0, h->stream, HOT_ARGS);
             else hipLaunchKernelGGL(step_kernel_hot<false>, gh, b, 0, h->stream, HOT_ARGS);
+            note_kernel(h);
 #undef HOT_ARGS
         } else launch_step3<false, true, true>(h, P, io);
     }
@@ -107,14 +111,8 @@ static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& i
     else launch_step3<false, false, false>(h, P, io);
 }
 
-extern "C" int batched_step_ex(soccer_handle* h, const soccer_step_args* a) {
-    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
-    if (!a || (!a->act_a && !h->P.policy_a) || (!a->act_b && !h->P.policy_b))
-        return fail(h, SOCCER_E_INVALID, "batched_step: an action stream is required for every player without a fixed policy");
-    if (!aligned(a->u_step, 8) || !aligned(a->u_reset, 8) || !aligned(a->obs, 2) || !aligned(a->final_obs, 2) ||
-        !aligned(a->reward_a_f32, 4) || !aligned(a->reward_b_f32, 4))
-        return fail(h, SOCCER_E_INVALID, "batched_step: u_* must be 8-byte, reward_*_f32 4-byte and obs/final_obs 2-byte aligned");
-    HIP_TRY(h, hipSetDevice(h->cfg.device));
+// one step, one launch (two with a ragged tail); the arguments have been checked
+static int launch_one_step(soccer_handle* h, const soccer_step_args* a) {
     // dword I/O needs every byte stream 4-aligned and the uint16 streams 8-aligned; else byte I/O
     const bool vec = h->E != 1 && aligned(a->act_a, 4) && aligned(a->act_b, 4) && aligned(a->reward, 4) &&
                      aligned(a->terminated, 4) && aligned(a->truncated, 4) && aligned(a->prob_code, 4) &&
@@ -135,6 +133,109 @@ extern "C" int batched_step_ex(soccer_handle* h, const soccer_step_args* a) {
     }
     HIP_TRY(h, hipGetLastError());
     return SOCCER_OK;
+}
+
+// ---- captured steps: consecutive ones with evenly spaced rows are recorded as one rollout (include/soccer_hip.h) ----------
+// the rollout a run of `len` steps from `f` on is
+static soccer_rollout_args run_as_rollout(const soccer_step_args& f, int64_t len, int64_t act_stride, int64_t out_stride) {
+    soccer_rollout_args r{};
+    r.n_steps = (int32_t)len; r.sample_actions = 0;
+    r.act_a = f.act_a; r.act_b = f.act_b; r.act_stride = act_stride;
+    r.obs = f.obs; r.reward = f.reward; r.terminated = f.terminated; r.truncated = f.truncated; r.out_stride = out_stride;
+    return r;
+}
+
+// may this step be part of a run at all: alone it takes step_kernel_swar<0, ..> (or, with step statistics, <2, ..> for the
+// histogram only), and a run of such steps takes the byte-parallel rollout with its actions read from the two streams
+static bool step_can_fuse(const soccer_handle* h, const soccer_step_args* a) {
+    if (!h->graph_fuse || !h->own_stream || h->P.policy_a || h->P.policy_b || h->E == 1 || (h->P.n & 3ull)) return false;
+    if (a->u_step || a->u_reset || a->reward_a_f32 || a->reward_b_f32 || a->finished || a->last_return || a->prob_code || a->final_obs) return false;
+    const soccer_rollout_args r = run_as_rollout(*a, 1, (int64_t)h->P.n, (int64_t)h->P.n);
+    return rollout_takes_swar(h, &r, nullptr);
+}
+
+// Over `len` steps no result stream may touch another stream of the run: a step's results must not be what a later step of
+// the run reads or writes, because the fused launch keeps no order between lanes of different steps.  The two action streams
+// are only read and may interleave ([T][2][n] blocks do).
+static bool run_disjoint(const soccer_handle* h, const soccer_step_args& f, int64_t len, int64_t act_stride, int64_t out_stride) {
+    struct Range { uintptr_t lo, hi; bool written; };
+    const uint64_t n = h->P.n;
+    Range r[6]; int m = 0;
+    auto add = [&](const void* p, int64_t stride, size_t elem, bool written) {
+        if (!p) return;
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+        r[m++] = Range{lo, lo + (uintptr_t)(((uint64_t)(len - 1) * (uint64_t)stride + n) * elem), written};
+    };
+    add(f.act_a, act_stride, 1, false); add(f.act_b, act_stride, 1, false);
+    add(f.obs, out_stride, 2, true); add(f.reward, out_stride, 1, true);
+    add(f.terminated, out_stride, 1, true); add(f.truncated, out_stride, 1, true);
+    for (int i = 0; i < m; ++i)
+        for (int j = i + 1; j < m; ++j)
+            if ((r[i].written || r[j].written) && r[i].lo < r[j].hi && r[j].lo < r[i].hi) return false;
+    return true;
+}
+
+// does step `a` continue the pending run?  The second step of a run fixes the two strides.
+static bool run_extends(soccer_handle* h, const soccer_step_args* a) {
+    PendingRun& R = h->run;
+    const soccer_step_args& f = R.first;
+    if (R.len < 1 || R.len >= (int64_t)1 << 30) return false;
+    if (!a->obs != !f.obs || !a->reward != !f.reward || !a->terminated != !f.terminated || !a->truncated != !f.truncated) return false;
+    const int64_t n = (int64_t)h->P.n;
+    // elements from the run's first row to this step's (addresses as integers: the rows need not lie in one allocation)
+    auto rows = [](const void* p, const void* q, int64_t elem) { return (int64_t)(reinterpret_cast<intptr_t>(p) - reinterpret_cast<intptr_t>(q)) / elem; };
+    const int64_t da = rows(a->act_a, f.act_a, 1);
+    int64_t d_out = 0;
+    bool have = false, same = rows(a->act_b, f.act_b, 1) == da;
+    auto out = [&](const void* p, const void* q, int64_t elem) {
+        if (!q) return;
+        const int64_t d = rows(p, q, elem);
+        if (!have) { d_out = d; have = true; } else if (d != d_out) same = false;
+    };
+    out(a->obs, f.obs, 2); out(a->reward, f.reward, 1); out(a->terminated, f.terminated, 1); out(a->truncated, f.truncated, 1);
+    if (!same) return false;
+    int64_t as = R.act_stride, os = R.out_stride;
+    if (R.len == 1) {
+        as = da; os = have ? d_out : n;     // (no result stream: nothing is spaced by the output stride)
+        if (as < n || as % 4 != 0 || os < n || os % 4 != 0) return false;
+    } else if (da != R.len * as || (have && d_out != R.len * os)) return false;
+    if (!run_disjoint(h, f, R.len + 1, as, os)) return false;
+    R.act_stride = as; R.out_stride = os;
+    return true;
+}
+
+int flush_run(soccer_handle* h) {
+    const PendingRun R = h->run;
+    h->run = PendingRun{};
+    if (R.len < 1) return SOCCER_OK;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));     // (the caller may be soccer_graph_end or a call that has not set it yet)
+    if (R.len == 1) return launch_one_step(h, &R.first);
+    const soccer_rollout_args r = run_as_rollout(R.first, R.len, R.act_stride, R.out_stride);
+    // rollout_swar_kernel always counts finished episodes, a step only with SOCCER_F_STEP_STATS: without it the run counts
+    // into the block nobody reads; soccer_rollout_shape keeps describing the caller's own last rollout
+    const soccer_rollout_shape_info keep = h->last_rollout;
+    const int rc = rollout_enqueue(h, &r, nullptr, h->P.step_stats ? h->d_hist : h->d_hist_unread);
+    h->last_rollout = keep;
+    if (rc == SOCCER_OK) { h->capture_steps_fused += R.len; h->capture_fused_launches += 1; }
+    return rc;
+}
+
+extern "C" int batched_step_ex(soccer_handle* h, const soccer_step_args* a) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (!a || (!a->act_a && !h->P.policy_a) || (!a->act_b && !h->P.policy_b))
+        return fail(h, SOCCER_E_INVALID, "batched_step: an action stream is required for every player without a fixed policy");
+    if (!aligned(a->u_step, 8) || !aligned(a->u_reset, 8) || !aligned(a->obs, 2) || !aligned(a->final_obs, 2) ||
+        !aligned(a->reward_a_f32, 4) || !aligned(a->reward_b_f32, 4))
+        return fail(h, SOCCER_E_INVALID, "batched_step: u_* must be 8-byte, reward_*_f32 4-byte and obs/final_obs 2-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (h->capturing) {
+        // nothing is launched yet: the step joins the pending run, or ends it and starts the next one
+        const bool can = step_can_fuse(h, a);
+        if (can && h->run.len && run_extends(h, a)) { h->run.len += 1; return SOCCER_OK; }
+        if (int rc = flush_pending(h)) return rc;
+        if (can) { h->run.first = *a; h->run.len = 1; return SOCCER_OK; }
+    }
+    return launch_one_step(h, a);
 }
 
 extern "C" int batched_step(soccer_handle* h, const int8_t* act_a, const int8_t* act_b, uint16_t* obs,

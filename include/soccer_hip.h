@@ -653,11 +653,39 @@ int soccer_stamps_read(soccer_handle* h, int32_t first, int32_t count, uint64_t*
 
 /* ---- hipGraph capture of a sequence of batched_* calls ------------------------------------ */
 /* Calls between begin and end are recorded instead of executed.  Any number of batched_* calls may be recorded (the tick
- * lives in device memory in two alternating slots so that a replay advances it; a sequence with an ODD number of calls
- * gets one extra one-thread node that moves it back to the slot a replay starts from, ~1.5 us per replay). */
+ * lives in device memory in two alternating slots so that a replay advances it; a sequence with an ODD number of recorded
+ * launches gets one extra one-thread node that moves it back to the slot a replay starts from, ~1.5 us per replay).
+ *
+ * Deferred steps.  A captured sequence is declared before any of it runs, so the library may record it in any way that
+ * leaves every output, the state, the tick and the sticky flags as one launch per call would have.  During a capture
+ * batched_step / batched_step_ex check their arguments as always, but a step that qualifies is not recorded at once: it
+ * joins a pending RUN, and a run of L >= 2 steps is recorded as ONE multi-step launch, the byte-parallel kernel of
+ * batched_rollout with n_steps = L (no kernel boundary and no round trip of the resident state between the steps of the
+ * run; bit-identical results, see soccer_rollout_args).  A run of one step is recorded exactly as before.
+ *   A step qualifies when the handle created its own stream (on a caller's stream, work the caller put between two calls
+ *   would be reordered) and has no fixed policy, n_lanes is a multiple of 4, the step passes no u_step / u_reset /
+ *   reward_*_f32 / finished / last_return / prob_code / final_obs, and its streams are dword-aligned (obs: 8 bytes): alone
+ *   it would run the byte-parallel step kernel, and a rollout over its streams the byte-parallel rollout kernel.
+ *   A step extends the pending run when the same streams are NULL / non-NULL as in the run's first step and its rows
+ *   continue the run's spacing: the run's second step fixes one action stride (the same for act_a and act_b) and one
+ *   output stride in elements (the same for every non-NULL output), both >= n_lanes and multiples of 4.  Steps that pass
+ *   the same buffers again (stride 0) never form a run.  Over the run's length no result stream may overlap another stream
+ *   of the run (the two action streams are only read and may interleave, as the rows of a [T][2][n] block do).
+ *   The pending run is recorded, in call order, when a step arrives that does not extend it, when any other call that may
+ *   record work is made (batched_rollout*, batched_reset, soccer_stamp, soccer_timer_start / _mark, soccer_memset,
+ *   soccer_reset_stats) and by soccer_graph_end.
+ * Error timing: an error that only the launch can produce is returned by the call that records the run — a later step,
+ * one of the calls above or soccer_graph_end — not by the step's own call.  When soccer_graph_end fails that way the
+ * capture is abandoned.  A capture that is never ended, and soccer_destroy, drop the pending run.
+ * SOCCER_GRAPH_FUSE=0 in the environment of soccer_create turns deferral off: every captured step is a launch.
+ *
+ * soccer_graph_info reports how a capture was recorded (any pointer may be NULL): kernel_nodes, the kernel nodes the
+ * batched_* calls recorded (the parts of a split launch one by one; not the clock stamps, not the tick-move node);
+ * steps_fused, the captured steps that went into multi-step launches; fused_launches, the runs they formed. */
 int soccer_graph_begin(soccer_handle* h);
 int soccer_graph_end(soccer_handle* h, soccer_graph** out);
 int soccer_graph_launch(soccer_handle* h, soccer_graph* g, int32_t replays);
+int soccer_graph_info(const soccer_graph* g, int32_t* kernel_nodes, int64_t* steps_fused, int32_t* fused_launches);
 int soccer_graph_destroy(soccer_handle* h, soccer_graph* g);
 
 #ifdef __cplusplus
