@@ -86,8 +86,22 @@ class QLearnerConfig(C.Structure):
                 ("q_init", C.c_double), ("act_a", C.c_int32), ("act_b", C.c_int32), ("policy_a", C.c_void_p), ("policy_b", C.c_void_p)]
 
 
+class WolfPHCConfig(C.Structure):
+    """soccer_wolf_phc_config"""
+    _fields_ = [("discount_factor", C.c_double), ("alpha", C.c_double), ("decay", C.c_double), ("explor", C.c_double),
+                ("q_init", C.c_double), ("delta_win", C.c_double), ("delta_lose", C.c_double), ("delta_decay", C.c_double),
+                ("act_a", C.c_int32), ("act_b", C.c_int32), ("policy_a", C.c_void_p), ("policy_b", C.c_void_p)]
+
+
+class WolfPHCState(C.Structure):
+    """soccer_wolf_phc_state"""
+    _fields_ = [(n, C.c_void_p) for n in ("Q_a", "Q_b", "pi_a", "pi_b", "avg_a", "avg_b", "visits", "updates")] + \
+               [("alpha", C.POINTER(C.c_double)), ("dscale", C.POINTER(C.c_double)), ("steps", C.POINTER(C.c_uint64))]
+
+
 MQ_UNIFORM, MQ_SELF, MQ_FIXED = 0, 1, 2
 QL_GREEDY, QL_UNIFORM, QL_FIXED = 0, 1, 2
+PHC_LEARN, PHC_UNIFORM, PHC_FIXED = 0, 1, 2
 MQ_MAX_LANES = 1 << 22
 BR_MAX_POLICIES = 256
 MISUSE_FROZEN, MISUSE_ACTION, MISUSE_OBSERVATION = 1, 2, 4
@@ -155,6 +169,12 @@ PROTOTYPES = {
     "soccer_q_learner_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
     "soccer_q_learner_read": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 3 + [C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "soccer_q_learner_load": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 3 + [C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "soccer_wolf_phc_create": (C.c_int, [C.c_void_p, C.POINTER(WolfPHCConfig), C.POINTER(C.c_void_p)]),
+    "soccer_wolf_phc_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "soccer_wolf_phc_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "soccer_wolf_phc_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
+    "soccer_wolf_phc_read": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(WolfPHCState)]),
+    "soccer_wolf_phc_load": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(WolfPHCState)]),
     "soccer_prob_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 12)]),
     "soccer_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint64)]),
     "soccer_reset_stats": (C.c_int, [C.c_void_p]),

@@ -355,6 +355,144 @@ class QLearner:
             pass
 
 
+def wolf_phc_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
+                    delta_decay=1.0, act_a="learn", act_b="learn"):
+    """Checks the parameters of the policy hill-climbers (AssertionError, before any library call) and returns
+    (soccer_wolf_phc_config, the arrays it points into)."""
+    g, a, d, e, q0 = float(discount_factor), float(alpha), float(decay), float(explor), float(q_init)
+    dw, dl, dd = float(delta_win), float(delta_lose), float(delta_decay)
+    assert 0.0 <= g < 1.0, "discount_factor must be in [0, 1)"
+    assert 0.0 <= a <= 1.0, "alpha must be in [0, 1]"
+    assert 0.0 < d <= 1.0, "decay must be in (0, 1]"
+    assert 0.0 <= e <= 1.0, "explor must be in [0, 1]"
+    assert -1.0 <= q0 <= 1.0, "q_init must be in [-1, 1]"
+    assert 0.0 <= dw <= 1.0, "delta_win must be in [0, 1]"
+    assert 0.0 <= dl <= 1.0, "delta_lose must be in [0, 1]"
+    assert 0.0 < dd <= 1.0, "delta_decay must be in (0, 1]"
+    kinds, pols = [], []
+    for name, act in (("act_a", act_a), ("act_b", act_b)):
+        pol = None
+        if isinstance(act, str):
+            assert act in ("learn", "uniform"), "%s must be 'learn', 'uniform' or an [nS, 5] mixed policy" % name
+            kinds.append(_lib.PHC_LEARN if act == "learn" else _lib.PHC_UNIFORM)
+        else:
+            pol = np.ascontiguousarray(act, np.float64)
+            assert pol.shape == (int(nS), 5) and (pol >= 0).all() and np.allclose(pol.sum(1), 1.0), \
+                "a fixed %s must be [n_states, 5] rows summing to 1" % name
+            kinds.append(_lib.PHC_FIXED)
+        pols.append(pol)
+    return _lib.WolfPHCConfig(g, a, d, e, q0, dw, dl, dd, kinds[0], kinds[1], *[None if x is None else x.ctypes.data for x in pols]), pols
+
+
+class WolfPHCLearner:
+    """Policy hill-climbers for both players (PHC and WoLF-PHC, Bowling & Veloso 2002) on a two-player auto-reset
+    SoccerBatch: the Q-learners' two tables plus a mixed policy pi_p[nS, 5] and its running average avg_p per player on
+    the device, the batch's lanes as actors (include/soccer_hip.h, "learners, policy hill-climbing").  run() enqueues
+    and returns; read() and the properties synchronise and copy."""
+    _ROWS = ("Q_a", "Q_b", "pi_a", "pi_b", "avg_a", "avg_b")
+
+    def __init__(self, batch, discount_factor, **params):
+        cfg, keep = wolf_phc_config(batch.nS, discount_factor, **params)
+        self.batch, self.q = batch, None
+        q = C.c_void_p()
+        batch._check(batch.lib.soccer_wolf_phc_create(batch.h, C.byref(cfg), C.byref(q)))
+        del keep                                   # (create has copied the fixed policies)
+        self.q = q
+        self.nS = batch.nS
+        self.discount_factor = float(discount_factor)
+        batch._learners.add(self)
+
+    def run(self, n_steps):
+        """n_steps learner steps (every lane acts, the environment steps, both tables and the LEARN players' policies are
+        updated), enqueued."""
+        b = self.batch
+        b._check(b.lib.soccer_wolf_phc_run(b.h, self.q, int(n_steps)))
+        return self
+
+    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
+        """One learner step's reduce / update / policy step on a batch of transitions (reward is player A's): DeviceArrays
+        (or device tensors) of one length, or numpy arrays, which are copied to the device first."""
+        _learner_update(self.batch, self.batch.lib.soccer_wolf_phc_update, self.q, obs, act_a, act_b, reward, terminated, next_obs)
+        return self
+
+    def read(self):
+        """dict: Q_a / Q_b, pi_a / pi_b, avg_a / avg_b [nS, 5], V_a / V_b [nS] (the row maxima, computed here), visits[nS, 25],
+        updates[nS], alpha, dscale, steps.  The policies plug into rollout(mixed_policies=...) and planners.exploitability
+        as they are.  Synchronises."""
+        nS, b = self.nS, self.batch
+        out = {k: np.zeros((nS, 5)) for k in self._ROWS}
+        out["visits"] = np.zeros((nS, 25), np.uint64); out["updates"] = np.zeros(nS, np.uint64)
+        al, ds, st = C.c_double(), C.c_double(), C.c_uint64()
+        state = _lib.WolfPHCState(*[out[k].ctypes.data for k in self._ROWS + ("visits", "updates")],
+                                  C.pointer(al), C.pointer(ds), C.pointer(st))
+        b._check(b.lib.soccer_wolf_phc_read(b.h, self.q, C.byref(state)))
+        for p in "ab":
+            out["V_" + p] = out["Q_" + p].max(1)
+        out["alpha"], out["dscale"], out["steps"] = float(al.value), float(ds.value), int(st.value)
+        return out
+
+    def _scalar(self, name, ctype):
+        b, v = self.batch, ctype()
+        state = _lib.WolfPHCState(**{name: C.pointer(v)})
+        b._check(b.lib.soccer_wolf_phc_read(b.h, self.q, C.byref(state)))
+        return v.value
+
+    alpha = property(lambda self: float(self._scalar("alpha", C.c_double)))
+    dscale = property(lambda self: float(self._scalar("dscale", C.c_double)))
+    steps = property(lambda self: int(self._scalar("steps", C.c_uint64)))
+
+    def exploitability(self, which="pi", theta=1e-10):
+        """How badly the best possible opponent beats the pair of policies (which='pi') or of average policies
+        (which='avg') the learners hold now, at their discount: planners.exploitability.  Synchronises and copies."""
+        from . import planners
+        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
+        r = self.read()
+        return planners.exploitability(self.batch, r[which + "_a"], r[which + "_b"], theta, self.discount_factor)
+
+    def load(self, Q_a, Q_b, pi_a=None, pi_b=None, avg_a=None, avg_b=None, visits=None, updates=None, alpha=None, dscale=None,
+             steps=None):
+        """Resume from a checkpoint: everything derived is recomputed on the device.  With all of read()'s arrays and
+        scalars a fresh learner continues bit for bit.  A policy array that is None is left as it is (those of a player
+        that does not learn are ignored); without `visits` / `updates` the counts are zeroed."""
+        b = self.batch
+        rows = {"Q_a": Q_a, "Q_b": Q_b, "pi_a": pi_a, "pi_b": pi_b, "avg_a": avg_a, "avg_b": avg_b}
+        keep = {}
+        for k, x in rows.items():
+            if x is None:
+                assert not k.startswith("Q"), "Q_a / Q_b are required"
+                continue
+            x = keep[k] = np.ascontiguousarray(x, np.float64)
+            assert x.shape == (self.nS, 5), "%s must be [n_states, 5]" % k
+            if k.startswith("Q"):
+                assert (np.abs(x[1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
+        for k, x, shape in (("visits", visits, (self.nS, 25)), ("updates", updates, (self.nS,))):
+            if x is not None:
+                keep[k] = np.ascontiguousarray(x, np.uint64)
+                assert keep[k].shape == shape, "%s must be %r" % (k, list(shape))
+        assert alpha is None or 0.0 <= float(alpha) <= 1.0, "alpha must be in [0, 1]"
+        assert dscale is None or 0.0 <= float(dscale) <= 1.0, "dscale must be in [0, 1]"
+        state = _lib.WolfPHCState(**{k: x.ctypes.data for k, x in keep.items()})
+        if alpha is not None:
+            state.alpha = C.pointer(C.c_double(float(alpha)))
+        if dscale is not None:
+            state.dscale = C.pointer(C.c_double(float(dscale)))
+        if steps is not None:
+            state.steps = C.pointer(C.c_uint64(int(steps)))
+        b._check(b.lib.soccer_wolf_phc_load(b.h, self.q, C.byref(state)))
+        return self
+
+    def close(self):
+        if self.q and self.batch.h:
+            self.batch.lib.soccer_wolf_phc_destroy(self.batch.h, self.q)
+        self.q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SoccerBatch:
     """N lanes of the Littman-94 soccer game resident on one GPU.
 
@@ -375,7 +513,7 @@ class SoccerBatch:
         self.lib = _lib.load()
         self.h = None
         self._arrays = weakref.WeakSet()        # device buffers handed out by alloc(); freed with the handle
-        self._learners = weakref.WeakSet()      # minimax_q(), q_learning(): their memory goes with the handle
+        self._learners = weakref.WeakSet()      # minimax_q(), q_learning(), wolf_phc(): their memory goes with the handle
         cfg = Config(n_lanes=int(n_lanes), width=int(width), height=int(height),
                      slip_prob=float(slip_prob), max_steps=int(max_steps), device=int(device),
                      seed=int(seed) & 0xFFFFFFFFFFFFFFFF, lane_offset=int(lane_offset),
@@ -636,6 +774,13 @@ class SoccerBatch:
         """A QLearner on this batch (two players, autoreset=True, at most 2**22 lanes).  act_a / act_b: 'greedy'
         (epsilon-greedy on the player's own table), 'uniform', or a fixed [nS, 5] mixed policy.  Both tables always learn."""
         return QLearner(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
+
+    def wolf_phc(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
+                 delta_decay=1.0, act_a="learn", act_b="learn"):
+        """A WolfPHCLearner on this batch (two players, autoreset=True, at most 2**22 lanes).  act_a / act_b: 'learn'
+        (a hill-climbing mixed policy), 'uniform' or a fixed [nS, 5] mixed policy; delta_win == delta_lose is plain PHC."""
+        return WolfPHCLearner(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, delta_win=delta_win,
+                              delta_lose=delta_lose, delta_decay=delta_decay, act_a=act_a, act_b=act_b)
 
     # -- hot path -------------------------------------------------------------------------------
     def reset(self, mask=None, u_reset=None, obs=None):

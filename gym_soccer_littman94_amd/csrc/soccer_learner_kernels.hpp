@@ -1,6 +1,7 @@
 // soccer_learner_kernels.hpp — the minimax-Q learner (Littman 1994): learner_act_kernel, learner_reduce_kernel,
 // learner_update_kernel, learner_init_kernel; and the independent Q-learners of both players: q_act_kernel, q_reduce_kernel,
-// q_update_kernel, q_init_kernel (at the end: they share the act-and-step body, the reduce body and learner_thresholds).
+// q_update_kernel, q_init_kernel (they share the act-and-step body, the reduce body and learner_thresholds); and the policy
+// hill-climbers on top of those: phc_act_kernel, phc_reduce_kernel, phc_update_kernel, phc_init_kernel (at the end).
 // Included by soccer_learners.hip only: every kernel is emitted by exactly one translation unit.
 //
 // One learner step (include/soccer_hip.h, "learners") is two launches in stream order, no grid barrier between them:
@@ -343,6 +344,157 @@ __global__ __launch_bounds__(kBlock) void q_init_kernel(const QLearnerIO L, doub
     if (k < 10) L.Q[k / 5][(size_t)s * 5 + k % 5] = s ? q_init : 0.0;
     L.visits[cell] = 0ull; L.cnt[cell] = 0u; L.rsum[cell] = 0; L.sv[0][cell] = 0ll; L.sv[1][cell] = 0ll;
     if (cell == 0) { L.alpha[0] = alpha0; L.alpha[1] = alpha0; *L.steps = 0ull; }
+}
+
+// =================================================================================================
+// policy hill-climbing learners of both players (include/soccer_hip.h, "learners, policy hill-climbing")
+// =================================================================================================
+// The Q-learners with an explicit mixed policy per player.  PhcIO begins with a QLearnerIO, so the act body, the reduce body
+// and learner_accumulate are the Q-learners' own (greedy[] is not used: a LEARN player's row follows pi, not the table).
+// phc_update_kernel is q_update_kernel up to the two lanes that own a player: after the first maximum and Vq they run the
+// policy step (step 5) for a LEARN player and write pi, avg and the threshold row of the next step.  Everything there is
+// unrolled over k with the greedy index compared, never used as a subscript: the rows stay in registers.
+struct PhcIO : QLearnerIO {
+    double* pi[2];                      // [nS][5] the policies
+    double* avg[2];                     // [nS][5] their running averages
+    unsigned long long* updates;        // [nS] learner steps that touched the state
+    double* dscale;                     // [2]: two slots, as alpha
+    double delta_win, delta_lose, delta_decay;
+    int32_t learn[2];                   // the player's pi, avg and row are updated (else they are constant)
+};
+
+template <bool SLIP, bool LUT_LDS>
+__global__ __launch_bounds__(kBlock) void phc_act_kernel(const KernelParams P, const PhcIO L) {
+    learner_act<SLIP, LUT_LDS, true>(P, L);
+}
+
+// soccer_wolf_phc_update
+__global__ __launch_bounds__(kBlock) void phc_reduce_kernel(const PhcIO L, long long n, const uint16_t* obs, const int8_t* act_a,
+                                                            const int8_t* act_b, const int8_t* reward, const uint8_t* terminated,
+                                                            const uint16_t* next_obs) {
+    learner_reduce(L, n, obs, act_a, act_b, reward, terminated, next_obs);
+}
+
+// MODE 0: steps 4-6 of a learner step.  MODE 1 (creation, soccer_wolf_phc_load): Vq and the LEARN players' threshold rows are
+// recomputed from Q and pi, row 0 included; everything else is left alone.
+template <int MODE>
+__global__ __launch_bounds__(kLearnerBlock) void phc_update_kernel(const PhcIO L, int slot) {
+    __shared__ unsigned int sC[kQStates][25];
+    __shared__ int sR[kQStates][25];
+    __shared__ long long sS[2][kQStates][25];
+    __shared__ double sQ[kQStates][10];
+    __shared__ unsigned long long sN[kQStates];
+    const int st = (int)(threadIdx.x >> 5), lane = (int)(threadIdx.x & 31u);
+    const int s = (int)blockIdx.x * kQStates + st;
+    const bool live = s < L.nS && (MODE == 1 || s >= 1);        // index 0 is the terminal observation: Q_p[0] = 0 for good
+    const double alpha = L.alpha[slot], dscale = L.dscale[slot];
+    unsigned int c = 0u;
+    if (MODE == 0 && live && lane < 25) {
+        // both players' sums are read here, before anything is zeroed
+        const size_t cell = (size_t)s * 25 + lane;
+        c = L.cnt[cell];
+        sC[st][lane] = c;
+        if (c != 0u) {
+            sR[st][lane] = L.rsum[cell]; sS[0][st][lane] = L.sv[0][cell]; sS[1][st][lane] = L.sv[1][cell];
+            L.visits[cell] += (unsigned long long)c;
+            L.cnt[cell] = 0u; L.rsum[cell] = 0; L.sv[0][cell] = 0ll; L.sv[1][cell] = 0ll;
+        } else {
+            sR[st][lane] = 0; sS[0][st][lane] = 0ll; sS[1][st][lane] = 0ll;
+        }
+    }
+    // the half-wave's 25 bits of the wave's ballot: was any cell of this state touched?
+    const bool any = MODE == 1 || (((unsigned long long)__ballot(c != 0u) >> (threadIdx.x & 32u)) & 0x1ffffffull) != 0ull;
+    __syncthreads();
+    if (live && lane < 10) {
+        const int p = lane / 5, k = lane - 5 * p;                // player, own action
+        const size_t row = (size_t)s * 5 + k;
+        double q = L.Q[p][row];
+        if (MODE == 0) {
+            unsigned int cc = 0u; long long R = 0ll, SV = 0ll;
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {                        // over the other player's action
+                const int x = p ? j * 5 + k : k * 5 + j;
+                cc += sC[st][x]; R += (long long)sR[st][x]; SV += sS[p][st][x];
+            }
+            if (cc != 0u) {
+                if (p) R = -R;                                   // player B's own reward
+                const double m = ((double)R + L.gamma * ((double)SV * kVqInv)) / (double)cc;
+                q = q + alpha * (m - q);
+                L.Q[p][row] = q;
+            }
+            if (lane == 0 && any) {                              // both player lanes need the count: through LDS, one writer
+                const unsigned long long n = L.updates[s] + 1ull;
+                L.updates[s] = n;
+                sN[st] = n;
+            }
+        }
+        sQ[st][lane] = q;
+    }
+    __syncthreads();
+    if (live && any && lane < 2) {
+        const int p = lane;
+        double Q[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) Q[k] = sQ[st][p * 5 + k];
+        double v = Q[0];
+        int g = 0;
+#pragma unroll
+        for (int k = 1; k < 5; ++k)
+            if (Q[k] > v) { v = Q[k]; g = k; }                   // the first index that attains it
+        L.Vq[p][s] = (long long)rint(v * kVqScale);
+        if (L.learn[p]) {
+            double* const gpi = L.pi[p] + (size_t)s * 5;
+            double pi[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) pi[k] = gpi[k];
+            if (MODE == 0) {                                     // step 5
+                double* const gavg = L.avg[p] + (size_t)s * 5;
+                const double n = (double)sN[st];
+                double avg[5], ep = 0.0, ea = 0.0;
+#pragma unroll
+                for (int k = 0; k < 5; ++k) {
+                    avg[k] = gavg[k];
+                    avg[k] = avg[k] + (pi[k] - avg[k]) / n;
+                }
+#pragma unroll
+                for (int k = 0; k < 5; ++k) { ep = ep + pi[k] * Q[k]; ea = ea + avg[k] * Q[k]; }
+                const double d = ((ep > ea ? L.delta_win : L.delta_lose) * dscale) / 4.0;
+                double moved = 0.0;
+#pragma unroll
+                for (int k = 0; k < 5; ++k)
+                    if (k != g) {
+                        const double m = pi[k] < d ? pi[k] : d;
+                        pi[k] = pi[k] - m;
+                        moved = moved + m;
+                    }
+#pragma unroll
+                for (int k = 0; k < 5; ++k) {
+                    if (k == g) pi[k] = pi[k] + moved;
+                    gpi[k] = pi[k]; gavg[k] = avg[k];
+                }
+            }
+            learner_thresholds(pi, L.explor, (p ? L.mix_b : L.mix_a) + (size_t)s * 4);
+        }
+    }
+    if (MODE == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+        L.alpha[slot ^ 1] = alpha * L.decay; L.dscale[slot ^ 1] = dscale * L.delta_decay; *L.steps += 1ull;
+    }
+}
+
+// creation: Q_p = q_init on the live states, 0.2 rows (a FIXED player's are copied over them), dscale = 1, everything else
+// zero (phc_update_kernel<1> then derives the rows)
+__global__ __launch_bounds__(kBlock) void phc_init_kernel(const PhcIO L, double q_init, double alpha0) {
+    const int cell = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (cell >= L.nS * 25) return;
+    const int s = cell / 25, k = cell % 25;
+    if (k < 10) {
+        const size_t row = (size_t)s * 5 + k % 5;
+        L.Q[k / 5][row] = s ? q_init : 0.0;
+        L.pi[k / 5][row] = 0.2; L.avg[k / 5][row] = 0.2;
+    }
+    if (k == 0) L.updates[s] = 0ull;
+    L.visits[cell] = 0ull; L.cnt[cell] = 0u; L.rsum[cell] = 0; L.sv[0][cell] = 0ll; L.sv[1][cell] = 0ll;
+    if (cell == 0) { L.alpha[0] = alpha0; L.alpha[1] = alpha0; L.dscale[0] = 1.0; L.dscale[1] = 1.0; *L.steps = 0ull; }
 }
 
 }  // namespace soccer

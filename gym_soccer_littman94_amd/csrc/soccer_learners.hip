@@ -1,5 +1,5 @@
-// soccer_learners.hip — the minimax-Q learner: soccer_minimax_q_*, and the independent Q-learners: soccer_q_learner_*
-// (see soccer_handle.hpp).
+// soccer_learners.hip — the minimax-Q learner: soccer_minimax_q_*, the independent Q-learners: soccer_q_learner_*, and the
+// policy hill-climbers: soccer_wolf_phc_* (see soccer_handle.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,11 +31,21 @@ struct soccer_q_learner {
     int slot = 0;                       // alpha slot the NEXT update reads
 };
 
+// The policy hill-climbers of both players: the same shape.
+struct soccer_wolf_phc {
+    soccer_handle* h = nullptr;
+    PhcIO io{};
+    OwnedBufs bufs{"the WoLF-PHC learner"};
+    int slot = 0;                       // alpha / dscale slot the NEXT update reads
+};
+
 void learners_release(soccer_handle* h) {
     for (soccer_minimax_q* q : h->learners) delete q;
     h->learners.clear();
     for (soccer_q_learner* q : h->q_learners) delete q;
     h->q_learners.clear();
+    for (soccer_wolf_phc* q : h->phc_learners) delete q;
+    h->phc_learners.clear();
 }
 
 // what every entry point checks first
@@ -400,6 +410,226 @@ extern "C" int soccer_q_learner_load(soccer_handle* h, soccer_q_learner* q, cons
     if (alpha) HIP_TRY(h, hipMemcpyAsync(io.alpha + q->slot, alpha, 8, hipMemcpyHostToDevice, h->stream));
     if (steps) HIP_TRY(h, hipMemcpyAsync(io.steps, steps, 8, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(q_update_kernel<1>, dim3(q_update_grid(io)), dim3(kLearnerBlock), 0, h->stream, io, q->slot);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // the caller's arrays are pageable host memory
+    return SOCCER_OK;
+}
+
+// =================================================================================================
+// policy hill-climbers: soccer_wolf_phc_*
+// =================================================================================================
+static int phc_check(soccer_handle* h, soccer_wolf_phc* q, const char* what) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "%s during graph capture", what);
+    if (!q || std::find(h->phc_learners.begin(), h->phc_learners.end(), q) == h->phc_learners.end())
+        return fail(h, SOCCER_E_INVALID, "%s: not a learner of this handle", what);
+    return SOCCER_OK;
+}
+
+template <bool SLIP, bool LUT_LDS>
+static hipError_t launch_phc_act(soccer_handle* h, const KernelParams& P, const PhcIO& io) {
+    if (io.nS == 0)                     // soccer_wolf_phc_create: the LDS limit, as launch_act
+        return h->smem_bytes > 48 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&phc_act_kernel<SLIP, LUT_LDS>),
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_bytes) : hipSuccess;
+    hipLaunchKernelGGL((phc_act_kernel<SLIP, LUT_LDS>), dim3(grid_for(h, P.n)), dim3(kBlock), h->smem_bytes, h->stream, P, io);
+    return hipSuccess;
+}
+
+static hipError_t phc_act(soccer_handle* h, const KernelParams& P, const PhcIO& io) {
+    return h->slip ? (h->lut_lds ? launch_phc_act<true, true>(h, P, io) : launch_phc_act<true, false>(h, P, io))
+                   : (h->lut_lds ? launch_phc_act<false, true>(h, P, io) : launch_phc_act<false, false>(h, P, io));
+}
+
+static void launch_phc_update(soccer_wolf_phc* q) {
+    hipLaunchKernelGGL(phc_update_kernel<0>, dim3(q_update_grid(q->io)), dim3(kLearnerBlock), 0, q->h->stream, q->io, q->slot);
+    q->slot ^= 1;
+}
+
+static bool phc_kind(int32_t k) { return k == SOCCER_PHC_LEARN || k == SOCCER_PHC_UNIFORM || k == SOCCER_PHC_FIXED; }
+
+// rows 1.. of a checkpoint's policy array, held to what fixed_thresholds holds a fixed policy to
+static int policy_rows_check(soccer_handle* h, const char* name, const double* policy, int nS) {
+    for (int s = 1; s < nS; ++s) {
+        const double* p = policy + (size_t)s * 5;
+        double sum = 0.0;
+        for (int k = 0; k < 5; ++k) {
+            if (!(p[k] >= 0.0)) return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_load: %s[%d][%d] is negative or not a number", name, s, k);
+            sum = sum + p[k];
+        }
+        if (!(std::fabs(sum - 1.0) <= 1e-8 + 1e-5)) return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_load: %s[%d] does not sum to 1", name, s);
+    }
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_wolf_phc_create(soccer_handle* h, const soccer_wolf_phc_config* cfg, soccer_wolf_phc** out) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "soccer_wolf_phc_create during graph capture");
+    if (!cfg || !out) return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_create: cfg/out is NULL");
+    *out = nullptr;
+    if (h->P.policy_a != nullptr || h->P.policy_b != nullptr)
+        return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_create needs a two-player handle: neither side may have a fixed policy (soccer_set_policy)");
+    if (!(h->cfg.flags & SOCCER_F_AUTORESET))
+        return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_create needs a handle created with SOCCER_F_AUTORESET");
+    if (h->cfg.n_lanes > SOCCER_MQ_MAX_LANES)
+        return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_create: more than 2^22 lanes (%llu): the integer sums of a step could overflow",
+                    (unsigned long long)h->cfg.n_lanes);
+    if (!(cfg->discount_factor >= 0.0 && cfg->discount_factor < 1.0)) return fail(h, SOCCER_E_INVALID, "discount_factor must be in [0, 1)");
+    if (!(cfg->alpha >= 0.0 && cfg->alpha <= 1.0)) return fail(h, SOCCER_E_INVALID, "alpha must be in [0, 1]");
+    if (!(cfg->decay > 0.0 && cfg->decay <= 1.0)) return fail(h, SOCCER_E_INVALID, "decay must be in (0, 1]");
+    if (!(cfg->explor >= 0.0 && cfg->explor <= 1.0)) return fail(h, SOCCER_E_INVALID, "explor must be in [0, 1]");
+    if (!(cfg->q_init >= -1.0 && cfg->q_init <= 1.0)) return fail(h, SOCCER_E_INVALID, "q_init must be in [-1, 1]");
+    if (!(cfg->delta_win >= 0.0 && cfg->delta_win <= 1.0)) return fail(h, SOCCER_E_INVALID, "delta_win must be in [0, 1]");
+    if (!(cfg->delta_lose >= 0.0 && cfg->delta_lose <= 1.0)) return fail(h, SOCCER_E_INVALID, "delta_lose must be in [0, 1]");
+    if (!(cfg->delta_decay > 0.0 && cfg->delta_decay <= 1.0)) return fail(h, SOCCER_E_INVALID, "delta_decay must be in (0, 1]");
+    if (!phc_kind(cfg->act_a) || !phc_kind(cfg->act_b))
+        return fail(h, SOCCER_E_INVALID, "act_a / act_b must be SOCCER_PHC_LEARN, SOCCER_PHC_UNIFORM or SOCCER_PHC_FIXED");
+    if ((cfg->act_a == SOCCER_PHC_FIXED) != (cfg->policy_a != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_a goes with act_a == SOCCER_PHC_FIXED, and only with it");
+    if ((cfg->act_b == SOCCER_PHC_FIXED) != (cfg->policy_b != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_b goes with act_b == SOCCER_PHC_FIXED, and only with it");
+    const int nS = h->rules.nS;
+    const int32_t kinds[2] = {cfg->act_a, cfg->act_b};
+    const double* policy[2] = {cfg->policy_a, cfg->policy_b};
+    std::vector<uint16_t> fixed[2];
+    if (cfg->policy_a) if (int rc = fixed_thresholds(h, "policy_a", cfg->policy_a, nS, fixed[0])) return rc;
+    if (cfg->policy_b) if (int rc = fixed_thresholds(h, "policy_b", cfg->policy_b, nS, fixed[1])) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, phc_act(h, h->P, PhcIO{}));                   // (an empty block: the LDS limit of this handle's act kernel, nothing launched)
+    std::unique_ptr<soccer_wolf_phc> owner(new soccer_wolf_phc());
+    soccer_wolf_phc* q = owner.get();
+    q->h = h;
+    PhcIO& io = q->io;
+    const size_t cells = (size_t)nS * 25;
+    int rc = SOCCER_OK;
+    for (int p = 0; p < 2; ++p) {
+        if (!rc) rc = q->bufs.alloc(h, (size_t)nS * 5, &io.Q[p]);
+        if (!rc) rc = q->bufs.alloc(h, (size_t)nS * 5, &io.pi[p]);
+        if (!rc) rc = q->bufs.alloc(h, (size_t)nS * 5, &io.avg[p]);
+        if (!rc) rc = q->bufs.alloc(h, (size_t)nS, &io.Vq[p]);
+        if (!rc) rc = q->bufs.alloc(h, cells, &io.sv[p]);
+    }
+    if (!rc) rc = q->bufs.alloc(h, cells, &io.visits);
+    if (!rc) rc = q->bufs.alloc(h, (size_t)nS, &io.updates);
+    if (!rc) rc = q->bufs.alloc(h, cells, &io.cnt);
+    if (!rc) rc = q->bufs.alloc(h, cells, &io.rsum);
+    if (!rc && cfg->act_a != SOCCER_PHC_UNIFORM) rc = q->bufs.alloc(h, (size_t)nS * 4, &io.mix_a);
+    if (!rc && cfg->act_b != SOCCER_PHC_UNIFORM) rc = q->bufs.alloc(h, (size_t)nS * 4, &io.mix_b);
+    if (!rc) rc = q->bufs.alloc(h, 2, &io.alpha);
+    if (!rc) rc = q->bufs.alloc(h, 2, &io.dscale);
+    if (!rc) rc = q->bufs.alloc(h, 1, &io.steps);
+    if (rc) return rc;
+    io.misuse = h->d_misuse;
+    io.gamma = cfg->discount_factor; io.decay = cfg->decay; io.explor = cfg->explor;
+    io.nS = nS;
+    io.delta_win = cfg->delta_win; io.delta_lose = cfg->delta_lose; io.delta_decay = cfg->delta_decay;
+    for (int p = 0; p < 2; ++p) io.learn[p] = kinds[p] == SOCCER_PHC_LEARN ? 1 : 0;
+    hipLaunchKernelGGL(phc_init_kernel, dim3((unsigned)((cells + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, io, cfg->q_init, cfg->alpha);
+    for (int p = 0; p < 2; ++p) {
+        if (!policy[p]) continue;
+        HIP_TRY(h, hipMemcpyAsync(p ? io.mix_b : io.mix_a, fixed[p].data(), fixed[p].size() * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(io.pi[p], policy[p], (size_t)nS * 40, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(io.avg[p], policy[p], (size_t)nS * 40, hipMemcpyHostToDevice, h->stream));
+    }
+    hipLaunchKernelGGL(phc_update_kernel<1>, dim3(q_update_grid(io)), dim3(kLearnerBlock), 0, h->stream, io, 0);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // `fixed` and the policies are pageable host memory of this call
+    h->phc_learners.push_back(q);
+    *out = owner.release();
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_wolf_phc_destroy(soccer_handle* h, soccer_wolf_phc* q) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (!q) return SOCCER_OK;
+    if (int rc = phc_check(h, q, "soccer_wolf_phc_destroy")) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // nothing is freed under a kernel that reads it
+    h->phc_learners.erase(std::find(h->phc_learners.begin(), h->phc_learners.end(), q));
+    delete q;
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_wolf_phc_run(soccer_handle* h, soccer_wolf_phc* q, int32_t n_steps) {
+    if (int rc = phc_check(h, q, "soccer_wolf_phc_run")) return rc;
+    if (n_steps < 0) return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_run: n_steps must be >= 0");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    for (int32_t t = 0; t < n_steps; ++t) {
+        KernelParams P = h->P;
+        bind_tick(h, P, 1);
+        HIP_TRY(h, phc_act(h, P, q->io));
+        launch_phc_update(q);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_wolf_phc_update(soccer_handle* h, soccer_wolf_phc* q, int64_t n, const uint16_t* obs, const int8_t* act_a,
+                                      const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs) {
+    if (int rc = phc_check(h, q, "soccer_wolf_phc_update")) return rc;
+    if (n < 0 || n > (int64_t)SOCCER_MQ_MAX_LANES) return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_update: n must be in 0..2^22");
+    if (n > 0 && (!obs || !act_a || !act_b || !reward || !terminated || !next_obs))
+        return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_update: all six transition arrays are required");
+    if (!aligned(obs, 2) || !aligned(next_obs, 2)) return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_update: obs / next_obs must be 2-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (n > 0)
+        hipLaunchKernelGGL(phc_reduce_kernel, dim3(grid_for(h, (uint64_t)n)), dim3(kBlock), 0, h->stream, q->io, (long long)n,
+                           obs, act_a, act_b, reward, terminated, next_obs);
+    launch_phc_update(q);
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_wolf_phc_read(soccer_handle* h, soccer_wolf_phc* q, const soccer_wolf_phc_state* out) {
+    if (int rc = phc_check(h, q, "soccer_wolf_phc_read")) return rc;
+    if (!out) return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_read: out is NULL");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const PhcIO& io = q->io;
+    const size_t nS = (size_t)io.nS;
+    double* const rows[6] = {out->Q_a, out->Q_b, out->pi_a, out->pi_b, out->avg_a, out->avg_b};
+    const double* const from[6] = {io.Q[0], io.Q[1], io.pi[0], io.pi[1], io.avg[0], io.avg[1]};
+    for (int i = 0; i < 6; ++i)
+        if (rows[i]) HIP_TRY(h, hipMemcpyAsync(rows[i], from[i], nS * 40, hipMemcpyDeviceToHost, h->stream));
+    if (out->visits) HIP_TRY(h, hipMemcpyAsync(out->visits, io.visits, nS * 200, hipMemcpyDeviceToHost, h->stream));
+    if (out->updates) HIP_TRY(h, hipMemcpyAsync(out->updates, io.updates, nS * 8, hipMemcpyDeviceToHost, h->stream));
+    if (out->alpha) HIP_TRY(h, hipMemcpyAsync(out->alpha, io.alpha + q->slot, 8, hipMemcpyDeviceToHost, h->stream));
+    if (out->dscale) HIP_TRY(h, hipMemcpyAsync(out->dscale, io.dscale + q->slot, 8, hipMemcpyDeviceToHost, h->stream));
+    if (out->steps) HIP_TRY(h, hipMemcpyAsync(out->steps, io.steps, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_wolf_phc_load(soccer_handle* h, soccer_wolf_phc* q, const soccer_wolf_phc_state* in) {
+    if (int rc = phc_check(h, q, "soccer_wolf_phc_load")) return rc;
+    if (!in || !in->Q_a || !in->Q_b) return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_load: in / Q_a / Q_b is NULL");
+    const PhcIO& io = q->io;
+    const size_t nS = (size_t)io.nS;
+    const double* Q[2] = {in->Q_a, in->Q_b};
+    // a player that does not LEARN keeps its constant rows
+    const double* rows[4] = {io.learn[0] ? in->pi_a : nullptr, io.learn[1] ? in->pi_b : nullptr,
+                             io.learn[0] ? in->avg_a : nullptr, io.learn[1] ? in->avg_b : nullptr};
+    double* const to[4] = {io.pi[0], io.pi[1], io.avg[0], io.avg[1]};
+    static const char* const names[4] = {"pi_a", "pi_b", "avg_a", "avg_b"};
+    for (int p = 0; p < 2; ++p)
+        for (size_t i = 5; i < nS * 5; ++i)
+            if (!(Q[p][i] >= -1.0 && Q[p][i] <= 1.0))
+                return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_load: Q_%c[%zu][%zu] is outside [-1, 1]", p ? 'b' : 'a', i / 5, i % 5);
+    for (int i = 0; i < 4; ++i)
+        if (rows[i]) if (int rc = policy_rows_check(h, names[i], rows[i], io.nS)) return rc;
+    if (in->alpha && !(*in->alpha >= 0.0 && *in->alpha <= 1.0)) return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_load: alpha must be in [0, 1]");
+    if (in->dscale && !(*in->dscale >= 0.0 && *in->dscale <= 1.0)) return fail(h, SOCCER_E_INVALID, "soccer_wolf_phc_load: dscale must be in [0, 1]");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    for (int p = 0; p < 2; ++p) {
+        HIP_TRY(h, hipMemsetAsync(io.Q[p], 0, 40, h->stream));                    // Q_p[0] = 0
+        HIP_TRY(h, hipMemcpyAsync(io.Q[p] + 5, Q[p] + 5, (nS - 1) * 40, hipMemcpyHostToDevice, h->stream));
+    }
+    for (int i = 0; i < 4; ++i)                                                   // (row 0 stays what creation gave it)
+        if (rows[i]) HIP_TRY(h, hipMemcpyAsync(to[i] + 5, rows[i] + 5, (nS - 1) * 40, hipMemcpyHostToDevice, h->stream));
+    if (in->visits) HIP_TRY(h, hipMemcpyAsync(io.visits, in->visits, nS * 200, hipMemcpyHostToDevice, h->stream));
+    else HIP_TRY(h, hipMemsetAsync(io.visits, 0, nS * 200, h->stream));
+    if (in->updates) HIP_TRY(h, hipMemcpyAsync(io.updates, in->updates, nS * 8, hipMemcpyHostToDevice, h->stream));
+    else HIP_TRY(h, hipMemsetAsync(io.updates, 0, nS * 8, h->stream));
+    if (in->alpha) HIP_TRY(h, hipMemcpyAsync(io.alpha + q->slot, in->alpha, 8, hipMemcpyHostToDevice, h->stream));
+    if (in->dscale) HIP_TRY(h, hipMemcpyAsync(io.dscale + q->slot, in->dscale, 8, hipMemcpyHostToDevice, h->stream));
+    if (in->steps) HIP_TRY(h, hipMemcpyAsync(io.steps, in->steps, 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(phc_update_kernel<1>, dim3(q_update_grid(io)), dim3(kLearnerBlock), 0, h->stream, io, q->slot);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));            // the caller's arrays are pageable host memory
     return SOCCER_OK;

@@ -484,6 +484,11 @@ class VectorSoccerEnv:
         assert self.multiagent, "q_learning needs a two-player environment (no player with a fixed policy)"
         return self._batch.q_learning(discount_factor, **params)
 
+    def wolf_phc(self, discount_factor, **params):
+        """A WolfPHCLearner (SoccerBatch.wolf_phc) whose actors are this env's lanes: policy hill-climbers for both players."""
+        assert self.multiagent, "wolf_phc needs a two-player environment (no player with a fixed policy)"
+        return self._batch.wolf_phc(discount_factor, **params)
+
     @property
     def reward_int8(self):
         """device io: player A's reward of the last step as the int8 tensor the kernel wrote (-1 / 0 / +1), no cast

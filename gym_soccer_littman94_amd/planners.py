@@ -109,6 +109,31 @@ def q_learning(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2,
     return r["pi_a"], r["pi_b"], r["V_a"], r["V_b"], r["Q_a"], r["Q_b"], r["visits"]
 
 
+def wolf_phc(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
+             delta_decay=1.0, act_a="learn", act_b="learn"):
+    """PHC / WoLF-PHC (Bowling & Veloso 2002) for both players on the device: n_steps learner steps with every lane of
+    `env` acting, from the lanes' current states (lanes that were never reset are reset first).  act_a / act_b: 'learn',
+    'uniform' or a fixed [nS, 5] mixed policy; decay None: alpha falls to 1 % over the run; delta_win == delta_lose is
+    plain PHC.  Returns (pi_a[nS, 5], pi_b[nS, 5], avg_a, avg_b, Q_a[nS, 5], Q_b[nS, 5], visits[nS, 25]); the policies and
+    their averages are ready for VectorSoccerEnv.rollout(sample_actions=True, mixed_policies={...}) and for
+    exploitability; Q_b is in player B's own reward."""
+    b = _two_player_batch(env, "wolf_phc")
+    n_steps = int(n_steps)
+    assert n_steps >= 0, "n_steps must be >= 0"
+    if decay is None:
+        decay = 0.01 ** (1.0 / max(n_steps, 1))
+    learner = b.wolf_phc(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, delta_win=delta_win,
+                         delta_lose=delta_lose, delta_decay=delta_decay, act_a=act_a, act_b=act_b)
+    try:
+        if b.get_state()["needs_reset"].any():
+            (env if hasattr(env, "_batch") else b).reset()
+        learner.run(n_steps)
+        r = learner.read()
+    finally:
+        learner.close()
+    return r["pi_a"], r["pi_b"], r["avg_a"], r["avg_b"], r["Q_a"], r["Q_b"], r["visits"]
+
+
 def minimax_value_iteration(env, theta, discount_factor, max_sweeps=1000000):
     """Minimax (Shapley) value iteration of the two-player game on the device, Littman (1994)'s equilibrium values.
     Returns (pi_a[nS, 5], pi_b[nS, 5], V, Q[nS, 5, 5], iterations): player A's maximin and player B's minimax stage-game

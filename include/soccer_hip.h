@@ -64,7 +64,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_best_response, soccer_evaluate_policies and soccer_rollout_shape were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_best_response, soccer_evaluate_policies and soccer_rollout_shape were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -560,6 +560,90 @@ int soccer_q_learner_read(soccer_handle* h, soccer_q_learner* q, double* Q_a, do
  * recomputed from them.  visits: HOST [n_states][25], or NULL: the counts are zeroed.  alpha / steps: HOST, NULL = unchanged. */
 int soccer_q_learner_load(soccer_handle* h, soccer_q_learner* q, const double* Q_a, const double* Q_b, const uint64_t* visits,
                           const double* alpha, const uint64_t* steps);
+/* ---- learners, policy hill-climbing (two-player handles; PHC and WoLF-PHC, "win or learn fast", Bowling & Veloso 2002)
+ * Lives where the other two learners live: a two-player SOCCER_F_AUTORESET handle of at most 2^22 lanes, whose lanes are its
+ * actors.  Besides the Q-learners' two tables it keeps an explicit MIXED policy per player and moves it a small step towards
+ * the greedy action after every update: a small step while the policy does better than its own average, a large one while
+ * it does worse.  State, float64 unless noted:
+ *     Q_a[n_states][5], Q_b[n_states][5] (Q_b in player B's own reward), pi_a, pi_b, avg_a, avg_b [n_states][5] (the policies
+ *     and their running averages), visits[n_states][25] (uint64), updates[n_states] (uint64: the learner steps in which the
+ *     state was touched), alpha, dscale (the factor on both deltas), steps
+ * Derived, never state of their own: V_p, g_p, Vq_p as for the Q-learners, and the threshold rows.
+ * Row 0 is the terminal observation: Q_p[0] = 0 for good; row 0 of pi and avg is 0.2 at creation (a FIXED player's is the
+ * caller's) and is never read or written again.
+ * How a player acts (soccer_wolf_phc_config::act_a / act_b):
+ *   SOCCER_PHC_LEARN    it draws from the threshold row of (1.0 - explor) * pi_p[s][k] + explor / 5.0 (step 1 of minimax-Q);
+ *                       its pi and avg are updated
+ *   SOCCER_PHC_UNIFORM  the NULL row table, as SOCCER_QL_UNIFORM; pi_p = avg_p = 0.2 rows, constant
+ *   SOCCER_PHC_FIXED    the thresholds of the caller's mixed policy, computed once and checked like opponent_policy;
+ *                       pi_p = avg_p = that policy, constant
+ * One learner step, in this order:
+ *   1. the behaviour rows as above
+ *   2. act and step: batched_rollout(n_steps = 1, sample_actions = 1, mix_a, mix_b), exactly as step 2 of the Q-learners
+ *   3. reduce: the Q-learners' step 3
+ *   4. Q update: the Q-learners' step 4, for both tables whatever the modes; visits grow by the cell counts
+ *   5. policy step, for every live state s with any touched joint cell:  updates[s] += 1 (once per state, whatever the
+ *      modes), n = (double)updates[s];  then for each LEARN player, with Q = Q_p[s] AFTER step 4, every operation sequential
+ *      float64 and not contracted:
+ *        avg[k] = avg[k] + (pi[k] - avg[k]) / n                          for k = 0..4
+ *        ep = sum_k pi[k] * Q[k],  ea = sum_k avg[k] * Q[k]              each as acc = acc + p * q from 0.0 in index order,
+ *                                                                        ea with the NEW avg
+ *        d = ((ep > ea ? delta_win : delta_lose) * dscale) / 4.0
+ *        g = the first k attaining max_k Q[k]
+ *        moved = 0.0;  for k = 0..4, k != g, in index order:  m = min(pi[k], d),  pi[k] = pi[k] - m,  moved = moved + m
+ *        pi[g] = pi[g] + moved
+ *      Vq_p[s] and a LEARN player's threshold row follow
+ *   6. alpha = alpha * decay, dscale = dscale * delta_decay, steps += 1
+ * Initially Q_p = q_init on the live states, pi = avg = 0.2, updates = visits = 0, dscale = 1.0.  delta_win == delta_lose
+ * is plain PHC.  Rows of pi stay >= 0 exactly (pi[k] - min(pi[k], d) >= 0) and sum to 1 up to rounding, far inside the 1e-5
+ * that soccer_best_response's row check allows, and avg is a convex combination of such rows: what soccer_wolf_phc_read
+ * returns goes straight into soccer_best_response and into soccer_rollout_args::mix_*.  The learner's state is a fixed
+ * function of (seed, parameters, number of steps).  Ranges, refusals, SOCCER_E_STATE during a capture, the misuse flags and
+ * the ownership of the memory are those of the soccer_q_learner_* calls; all three kinds of learner may live on one handle. */
+#define SOCCER_PHC_LEARN   0
+#define SOCCER_PHC_UNIFORM 1
+#define SOCCER_PHC_FIXED   2
+typedef struct soccer_wolf_phc soccer_wolf_phc;
+typedef struct soccer_wolf_phc_config {
+    double  discount_factor;        /* [0, 1) */
+    double  alpha;                  /* initial learning rate, [0, 1] */
+    double  decay;                  /* alpha's factor per learner step, (0, 1] */
+    double  explor;                 /* [0, 1] probability mass a LEARN player spreads uniformly over the five actions */
+    double  q_init;                 /* [-1, 1] */
+    double  delta_win;              /* [0, 1] policy step while ep > ea (Bowling & Veloso: delta_lose / 4 or so) */
+    double  delta_lose;             /* [0, 1] policy step otherwise */
+    double  delta_decay;            /* dscale's factor per learner step, (0, 1] */
+    int32_t act_a;                  /* SOCCER_PHC_* : how player A acts */
+    int32_t act_b;                  /* SOCCER_PHC_* : how player B acts */
+    const double* policy_a;         /* act_a == SOCCER_PHC_FIXED: HOST [n_states][5] rows >= 0 summing to 1; else NULL */
+    const double* policy_b;         /* the same for act_b */
+} soccer_wolf_phc_config;
+/* what soccer_wolf_phc_read fills and soccer_wolf_phc_load takes: HOST pointers, any may be NULL */
+typedef struct soccer_wolf_phc_state {
+    double* Q_a; double* Q_b;       /* [n_states][5] */
+    double* pi_a; double* pi_b;     /* [n_states][5] */
+    double* avg_a; double* avg_b;   /* [n_states][5] */
+    uint64_t* visits;               /* [n_states][25] */
+    uint64_t* updates;              /* [n_states] */
+    double* alpha; double* dscale;  /* one value each */
+    uint64_t* steps;
+} soccer_wolf_phc_state;
+int soccer_wolf_phc_create(soccer_handle* h, const soccer_wolf_phc_config* cfg, soccer_wolf_phc** out);
+int soccer_wolf_phc_destroy(soccer_handle* h, soccer_wolf_phc* q);
+/* n_steps learner steps, two launches each, enqueued on the handle's stream: no synchronisation, no copy.  Consumes n_steps ticks. */
+int soccer_wolf_phc_run(soccer_handle* h, soccer_wolf_phc* q, int32_t n_steps);
+/* steps 3-6 on the caller's batch of n <= 2^22 transitions (DEVICE pointers; reward is player A's), with the checks and the
+ * misuse flags of soccer_minimax_q_update.  Consumes no tick. */
+int soccer_wolf_phc_update(soccer_handle* h, soccer_wolf_phc* q, int64_t n, const uint16_t* obs, const int8_t* act_a,
+                           const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs);
+/* Fills every array `out` points to.  Synchronises. */
+int soccer_wolf_phc_read(soccer_handle* h, soccer_wolf_phc* q, const soccer_wolf_phc_state* out);
+/* Resume from a checkpoint; nothing of `in` is written.  Q_a / Q_b are required, in [-1, 1], row 0 taken as zeros.  pi_p /
+ * avg_p of a LEARN player: rows 1.. must be >= 0 and sum to 1 as a fixed policy's must (SOCCER_E_INVALID, the message names
+ * array and state), row 0 is not read, NULL = left as it is; those of a player that does not LEARN are ignored.  visits /
+ * updates: NULL = the counts are zeroed.  alpha, dscale (both in [0, 1]) and steps: NULL = unchanged.  Every derived row is
+ * recomputed, so read -> load on a fresh learner continues bit for bit. */
+int soccer_wolf_phc_load(soccer_handle* h, soccer_wolf_phc* q, const soccer_wolf_phc_state* in);
 
 /* HOST output: prob[c*3+k] = slip-combination weight c (0: no slip, 1: B slips, 2: A slips,
  * 3: both; :211-222, evaluated left to right in float64) times outcome probability 1, 0.5, 0.25
