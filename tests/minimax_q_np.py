@@ -7,6 +7,7 @@ Also here: shapley_lists / shapley_vi, minimax value iteration on the oracle's t
 the V* a learner should approach, computed without the library."""
 import numpy as np
 
+from q_learning_np import run_learner
 from test_matrix_game_host import solve_host
 
 SCALE = 2.0 ** 40
@@ -31,6 +32,7 @@ class MinimaxQNumpy:
         self.pi_a = np.full((nS, 5), 0.2); self.pi_b = np.full((nS, 5), 0.2)
         self.visits = np.zeros((nS, 25), np.uint64)
         self.steps = 0
+        self.n_truncated = self.n_terminated = self.n_left_out = 0     # what run() met (q_learning_np.run_learner)
         self.opponent = opponent
         self.fixed = None if isinstance(opponent, str) else thresholds(opponent)
 
@@ -67,14 +69,7 @@ class MinimaxQNumpy:
 
     def run(self, orc, obs, n_steps):
         """n_steps learner steps on the oracle `orc` whose lanes currently show `obs`; returns the lanes' new observations"""
-        obs = np.asarray(obs).astype(np.uint16)
-        for _ in range(int(n_steps)):
-            ma, mb = self.tables()
-            a, b = orc.sample_actions_mixed(obs, ma, mb)
-            out = orc.step(a, b)
-            self.update(obs, a, b, out["reward"], out["terminated"], out["final_obs"])
-            obs = out["obs"]
-        return obs
+        return run_learner(self, orc, obs, n_steps)
 
     def state(self):
         return {"Q": self.Q, "V": self.V, "pi_a": self.pi_a, "pi_b": self.pi_b, "visits": self.visits,

@@ -22,6 +22,37 @@ def greedy(Q):
     return np.eye(5)[np.asarray(Q).argmax(1)]
 
 
+def observations(orc):
+    """every lane's observation from the oracle's state and tables(): lut[flat tuple], 0 where the tuple is a goal tuple
+    (kind == 2: the terminal observation).  What a lane shows after Oracle.set_state, which returns nothing."""
+    lut, kind = orc.tables()[:2]
+    W, H = orc.W, orc.H
+    f = ((((orc.row_a.astype(np.int64) * W + orc.col_a) * H + orc.row_b) * W + orc.col_b) << 1) | (orc.poss & 1)
+    return np.where(kind[f] == 2, 0, lut[f]).astype(np.uint16)
+
+
+def run_learner(q, orc, obs, n_steps):
+    """the learner step of include/soccer_hip.h on the oracle, n_steps times, for any restatement `q` with tables() and
+    update(): a lane contributes nothing if it needed reset before the step ("lanes that still need their first reset ...
+    contribute nothing") or if its current observation is 0 ("index 0 ... never a current state").  With no such lane every
+    transition goes to update() as it is.  Counts into q.n_left_out and, over the transitions it accepted, q.n_terminated and
+    q.n_truncated (the flags as the environment sets them, so one transition may count in both; a truncated transition that is
+    not terminated is the one after which the lane auto-resets and the learner still bootstraps, from final_obs)."""
+    obs = np.asarray(obs).astype(np.uint16)
+    for _ in range(int(n_steps)):
+        ma, mb = q.tables()
+        keep = (((orc.poss >> 1) & 1) == 0) & (obs != 0)
+        a, b = orc.sample_actions_mixed(obs, ma, mb)
+        out = orc.step(a, b)
+        term = out["terminated"][keep] != 0
+        q.n_left_out += int(keep.size - keep.sum())
+        q.n_terminated += int(term.sum())
+        q.n_truncated += int((out["truncated"][keep] != 0).sum())
+        q.update(obs[keep], a[keep], b[keep], out["reward"][keep], out["terminated"][keep], out["final_obs"][keep])
+        obs = out["obs"]
+    return obs
+
+
 class QLearningNumpy:
     """act_a / act_b: 'greedy' (epsilon-greedy on the player's own table), 'uniform' (the null row table) or a fixed [nS, 5]
     mixed policy.  Q_b is in player B's own reward.  Both tables are always updated."""
@@ -33,6 +64,7 @@ class QLearningNumpy:
         self.Q_b = self.Q_a.copy()
         self.visits = np.zeros((nS, 25), np.uint64)
         self.steps = 0
+        self.n_truncated = self.n_terminated = self.n_left_out = 0     # what run() met (run_learner)
         self.act = (act_a, act_b)
         self.fixed = tuple(None if isinstance(x, str) else thresholds(x) for x in self.act)
 
@@ -71,14 +103,7 @@ class QLearningNumpy:
 
     def run(self, orc, obs, n_steps):
         """n_steps learner steps on the oracle `orc` whose lanes currently show `obs`; returns the lanes' new observations"""
-        obs = np.asarray(obs).astype(np.uint16)
-        for _ in range(int(n_steps)):
-            ma, mb = self.tables()
-            a, b = orc.sample_actions_mixed(obs, ma, mb)
-            out = orc.step(a, b)
-            self.update(obs, a, b, out["reward"], out["terminated"], out["final_obs"])
-            obs = out["obs"]
-        return obs
+        return run_learner(self, orc, obs, n_steps)
 
     def state(self):
         return {"Q_a": self.Q_a, "Q_b": self.Q_b, "V_a": self.Q_a.max(1), "V_b": self.Q_b.max(1), "pi_a": greedy(self.Q_a),
