@@ -86,6 +86,12 @@ class QLearnerConfig(C.Structure):
                 ("q_init", C.c_double), ("act_a", C.c_int32), ("act_b", C.c_int32), ("policy_a", C.c_void_p), ("policy_b", C.c_void_p)]
 
 
+class QPopulationConfig(C.Structure):
+    """soccer_q_population_config"""
+    _fields_ = QLearnerConfig._fields_ + [("alpha_per_member", C.c_void_p), ("decay_per_member", C.c_void_p),
+                                          ("explor_per_member", C.c_void_p), ("discount_factor_per_member", C.c_void_p)]
+
+
 class WolfPHCConfig(C.Structure):
     """soccer_wolf_phc_config"""
     _fields_ = [("discount_factor", C.c_double), ("alpha", C.c_double), ("decay", C.c_double), ("explor", C.c_double),
@@ -175,6 +181,12 @@ PROTOTYPES = {
     "soccer_wolf_phc_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
     "soccer_wolf_phc_read": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(WolfPHCState)]),
     "soccer_wolf_phc_load": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(WolfPHCState)]),
+    "soccer_q_population_create": (C.c_int, [C.c_void_p, C.POINTER(QPopulationConfig), C.POINTER(C.c_void_p)]),
+    "soccer_q_population_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "soccer_q_population_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "soccer_q_population_update": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
+    "soccer_q_population_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.POINTER(C.c_uint64)]),
+    "soccer_q_population_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.POINTER(C.c_uint64)]),
     "soccer_prob_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 12)]),
     "soccer_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint64)]),
     "soccer_reset_stats": (C.c_int, [C.c_void_p]),

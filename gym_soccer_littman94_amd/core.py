@@ -355,6 +355,149 @@ class QLearner:
             pass
 
 
+def q_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
+    """Checks the parameters of a population of Q-learners (AssertionError, before any library call) and returns
+    (soccer_q_population_config, the arrays it points into).  discount_factor, alpha, decay and explor are scalars for every
+    member or arrays of n, one value per member."""
+    ranges = (("discount_factor", discount_factor, lambda x: (0.0 <= x) & (x < 1.0), "[0, 1)"),
+              ("alpha", alpha, lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
+              ("decay", decay, lambda x: (0.0 < x) & (x <= 1.0), "(0, 1]"),
+              ("explor", explor, lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"))
+    scalars, arrays = {}, {}
+    for name, value, ok, rng in ranges:
+        if np.ndim(value) == 0:
+            scalars[name], arrays[name] = float(value), None
+            assert ok(scalars[name]), "%s must be in %s" % (name, rng)
+        else:
+            a = np.ascontiguousarray(value, np.float64)
+            assert a.shape == (int(n),), "a per-member %s must have one value per lane (%d)" % (name, n)
+            assert ok(a).all(), "every per-member %s must be in %s" % (name, rng)
+            scalars[name], arrays[name] = float(a[0]), a
+    # (the scalar checks of q_learning_config hold for the kinds, the fixed policies and q_init)
+    base, pols = q_learning_config(nS, scalars["discount_factor"], scalars["alpha"], scalars["decay"], scalars["explor"], q_init, act_a, act_b)
+    cfg = _lib.QPopulationConfig(base.discount_factor, base.alpha, base.decay, base.explor, base.q_init, base.act_a, base.act_b,
+                                 base.policy_a, base.policy_b,
+                                 *[None if arrays[k] is None else arrays[k].ctypes.data for k in ("alpha", "decay", "explor", "discount_factor")])
+    return cfg, (pols, arrays)
+
+
+class QPopulation:
+    """A population of independent Q-learners on a two-player auto-reset SoccerBatch, a learner per lane: member i has its own
+    Q_a[nS, 5], Q_b[nS, 5] and alpha and learns from lane i alone (include/soccer_hip.h, "learners, a population of
+    independent Q-learners").  run() enqueues and returns; read() and the properties synchronise and copy.  Whole populations
+    run to gigabytes, so read(), load() and exploitability() take a range of members."""
+
+    def __init__(self, batch, discount_factor, **params):
+        cfg, keep = q_population_config(batch.n, batch.nS, discount_factor, **params)
+        self.batch, self.q = batch, None
+        q = C.c_void_p()
+        batch._check(batch.lib.soccer_q_population_create(batch.h, C.byref(cfg), C.byref(q)))
+        self.discount_factor = np.full(batch.n, cfg.discount_factor) if keep[1]["discount_factor"] is None else keep[1]["discount_factor"].copy()
+        del keep                                   # (create has copied the parameters and the fixed policies' thresholds)
+        self.q = q
+        self.n, self.nS = batch.n, batch.nS
+        batch._learners.add(self)
+
+    def run(self, n_steps):
+        """n_steps steps of every member (its lane acts, the environment steps, its two tables are updated), enqueued."""
+        b = self.batch
+        b._check(b.lib.soccer_q_population_run(b.h, self.q, int(n_steps)))
+        return self
+
+    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
+        """One step's update on n transitions, transition i for member i (reward is player A's): DeviceArrays (or device
+        tensors) of n elements, or numpy arrays, which are copied to the device first."""
+        n = self.n
+
+        def call(h, q, count, *ptrs):
+            assert count == n, "a population's update takes one transition per member (%d)" % n
+            return self.batch.lib.soccer_q_population_update(h, q, *ptrs)
+        _learner_update(self.batch, call, self.q, obs, act_a, act_b, reward, terminated, next_obs)
+        return self
+
+    def _range(self, first, count):
+        first = int(first)
+        count = self.n - first if count is None else int(count)
+        assert 0 <= first <= self.n and 0 <= count <= self.n - first, "members %d .. %d + %d are outside the population of %d" % (first, first, count, self.n)
+        return first, count
+
+    def read(self, first=0, count=None):
+        """dict for members first .. first + count - 1 (count None: to the end): Q_a / Q_b [count, nS, 5], V_a / V_b
+        [count, nS] (the row maxima), pi_a / pi_b [count, nS, 5] (one-hot of the first greedy action), alpha[count], steps.
+        Synchronises."""
+        first, count = self._range(first, count)
+        nS, b = self.nS, self.batch
+        out = {"Q_a": np.zeros((count, nS, 5)), "Q_b": np.zeros((count, nS, 5)), "alpha": np.zeros(count)}
+        st = C.c_uint64()
+        b._check(b.lib.soccer_q_population_read(b.h, self.q, first, count, *[out[k].ctypes.data for k in ("Q_a", "Q_b", "alpha")], C.byref(st)))
+        for p in "ab":
+            out["V_" + p] = out["Q_" + p].max(2)
+            out["pi_" + p] = np.eye(5)[out["Q_" + p].argmax(2)]
+        out["steps"] = int(st.value)
+        return out
+
+    @property
+    def alpha(self):
+        """every member's learning rate, [n]"""
+        b, al = self.batch, np.zeros(self.n)
+        b._check(b.lib.soccer_q_population_read(b.h, self.q, 0, self.n, None, None, al.ctypes.data, None))
+        return al
+
+    @property
+    def steps(self):
+        b, st = self.batch, C.c_uint64()
+        b._check(b.lib.soccer_q_population_read(b.h, self.q, 0, 0, None, None, None, C.byref(st)))
+        return int(st.value)
+
+    def exploitability(self, theta=1e-10, first=0, count=None):
+        """How badly the best possible opponent beats the greedy pair of each member of a range, at that member's discount:
+        the one-hot greedy policies go through SoccerBatch.best_response in batches of at most 256 members with one
+        discount.  Returns {"v_a", "v_b", "gap"}, arrays of [count, nS] (planners.exploitability's per member)."""
+        first, count = self._range(first, count)
+        b = self.batch
+        out = {k: np.zeros((count, self.nS)) for k in ("v_a", "v_b", "gap")}
+        for c0 in range(0, count, _lib.BR_MAX_POLICIES):
+            c = min(_lib.BR_MAX_POLICIES, count - c0)
+            r = self.read(first + c0, c)
+            gam = self.discount_factor[first + c0:first + c0 + c]
+            for g in np.unique(gam):                # (one solve per discount in the chunk: a batch shares its discount)
+                idx = np.flatnonzero(gam == g)
+                out["v_a"][c0 + idx] = b.best_response(r["pi_a"][idx], 0, theta, float(g))[1]
+                out["v_b"][c0 + idx] = b.best_response(r["pi_b"][idx], 1, theta, float(g))[1]
+        out["gap"] = out["v_b"] - out["v_a"]
+        return out
+
+    def load(self, Q_a=None, Q_b=None, alpha=None, steps=None, first=0):
+        """Resume members first .. first + count - 1 from a checkpoint: Q_a / Q_b [count, nS, 5] in [-1, 1] and alpha[count]
+        (count is what the arrays hold; None = unchanged), steps for the population.  With what read() gave, a fresh
+        population continues bit for bit.  A refused load changes nothing."""
+        b = self.batch
+        arrs = [None if x is None else np.ascontiguousarray(x, np.float64) for x in (Q_a, Q_b, alpha)]
+        counts = {x.shape[0] for x in arrs if x is not None and x.ndim >= 1}
+        assert len(counts) <= 1, "Q_a, Q_b and alpha must hold the same number of members"
+        first, count = self._range(first, counts.pop() if counts else 0)
+        for x in arrs[:2]:
+            if x is not None:
+                assert x.shape == (count, self.nS, 5), "Q_a / Q_b must be [count, n_states, 5]"
+                assert (np.abs(x[:, 1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
+        if arrs[2] is not None:
+            assert arrs[2].shape == (count,) and ((arrs[2] >= 0.0) & (arrs[2] <= 1.0)).all(), "alpha must be [count] values in [0, 1]"
+        st = None if steps is None else C.byref(C.c_uint64(int(steps)))
+        b._check(b.lib.soccer_q_population_load(b.h, self.q, first, count, *[None if x is None else x.ctypes.data for x in arrs], st))
+        return self
+
+    def close(self):
+        if self.q and self.batch.h:
+            self.batch.lib.soccer_q_population_destroy(self.batch.h, self.q)
+        self.q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def wolf_phc_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
                     delta_decay=1.0, act_a="learn", act_b="learn"):
     """Checks the parameters of the policy hill-climbers (AssertionError, before any library call) and returns
@@ -513,7 +656,7 @@ class SoccerBatch:
         self.lib = _lib.load()
         self.h = None
         self._arrays = weakref.WeakSet()        # device buffers handed out by alloc(); freed with the handle
-        self._learners = weakref.WeakSet()      # minimax_q(), q_learning(), wolf_phc(): their memory goes with the handle
+        self._learners = weakref.WeakSet()      # minimax_q(), q_learning(), wolf_phc(), q_population(): their memory goes with the handle
         cfg = Config(n_lanes=int(n_lanes), width=int(width), height=int(height),
                      slip_prob=float(slip_prob), max_steps=int(max_steps), device=int(device),
                      seed=int(seed) & 0xFFFFFFFFFFFFFFFF, lane_offset=int(lane_offset),
@@ -774,6 +917,12 @@ class SoccerBatch:
         """A QLearner on this batch (two players, autoreset=True, at most 2**22 lanes).  act_a / act_b: 'greedy'
         (epsilon-greedy on the player's own table), 'uniform', or a fixed [nS, 5] mixed policy.  Both tables always learn."""
         return QLearner(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
+
+    def q_population(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
+        """A QPopulation on this batch (two players, autoreset=True): a Q-learner per lane, each with its own tables.
+        discount_factor, alpha, decay and explor are scalars or arrays of one value per lane; act_a / act_b as for
+        q_learning (a fixed policy is shared by all members)."""
+        return QPopulation(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
 
     def wolf_phc(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
                  delta_decay=1.0, act_a="learn", act_b="learn"):

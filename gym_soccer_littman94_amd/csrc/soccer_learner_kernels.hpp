@@ -1,7 +1,8 @@
 // soccer_learner_kernels.hpp — the minimax-Q learner (Littman 1994): learner_act_kernel, learner_reduce_kernel,
 // learner_update_kernel, learner_init_kernel; and the independent Q-learners of both players: q_act_kernel, q_reduce_kernel,
 // q_update_kernel, q_init_kernel (they share the act-and-step body, the reduce body and learner_thresholds); and the policy
-// hill-climbers on top of those: phc_act_kernel, phc_reduce_kernel, phc_update_kernel, phc_init_kernel (at the end).
+// hill-climbers on top of those: phc_act_kernel, phc_reduce_kernel, phc_update_kernel, phc_init_kernel; and the population
+// of one-actor Q-learners, a learner per lane: pop_run_kernel, pop_update_kernel, pop_init_kernel (at the end).
 // Included by soccer_learners.hip only: every kernel is emitted by exactly one translation unit.
 //
 // One learner step (include/soccer_hip.h, "learners") is two launches in stream order, no grid barrier between them:
@@ -495,6 +496,187 @@ __global__ __launch_bounds__(kBlock) void phc_init_kernel(const PhcIO L, double 
     if (k == 0) L.updates[s] = 0ull;
     L.visits[cell] = 0ull; L.cnt[cell] = 0u; L.rsum[cell] = 0; L.sv[0][cell] = 0ll; L.sv[1][cell] = 0ll;
     if (cell == 0) { L.alpha[0] = alpha0; L.alpha[1] = alpha0; L.dscale[0] = 1.0; L.dscale[1] = 1.0; *L.steps = 0ull; }
+}
+
+// =================================================================================================
+// a population of independent Q-learners, a learner per lane (include/soccer_hip.h, "learners, a population ...")
+// =================================================================================================
+// Member i is a Q-learner whose only actor is lane i, so nothing is shared between threads: no accumulators, no atomics, no
+// second launch.  pop_run_kernel is rollout_kernel's per-lane loop (state in registers over the launch's steps) with the
+// update inside it; a thread owns lane i and member i's tables.
+// Table layout: member i's block is [nS][2][5] float64 — the row of player A and the row of player B of one state are the
+// 80 adjacent, 16-byte aligned bytes a step needs together (five 16-byte loads, one or two cache lines), and a member's
+// block is contiguous, so a range of members is one copy.
+// Per step the dependent chain is ONE row gather, at s' for the bootstrap: the row at s (for the greedy draw and the
+// update) is carried in registers — it is the previous step's s' row while the episode goes on, patched when the update
+// wrote into that very row (s' == s: every blocked move, every STAND), and loaded only after a reset.  The two moved
+// entries are stored straight away, so memory always holds what the registers do.
+// Everything is unrolled over the five actions with the action / greedy index COMPARED, never used as a subscript: the rows
+// stay in registers (0 bytes of scratch).
+struct PopIO {
+    double* Q;                          // [n][nS][2][5]
+    double* alpha;                      // [n] every member's learning rate
+    const double* decay;                // [n]
+    const double* explor;               // [n]
+    const double* gamma;                // [n]
+    const uint16_t* mix[2];             // [nS][4] a FIXED player's thresholds, shared by all members; else nullptr
+    unsigned long long* steps;
+    unsigned int* misuse;               // the handle's sticky words
+    int32_t nS;
+    int32_t n_steps;                    // pop_run_kernel: steps of this launch
+    int32_t mode[2];                    // SOCCER_QL_* of player A, player B
+};
+constexpr int kPopGreedy = 0, kPopUniform = 1;      // = SOCCER_QL_GREEDY, SOCCER_QL_UNIFORM (soccer_learners.hip asserts it)
+
+__device__ __forceinline__ void pop_load_row(const double* tab, uint32_t s, double (&row)[10]) {
+    const double2* p = reinterpret_cast<const double2*>(tab + (size_t)s * 10);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { const double2 v = p[k]; row[2 * k] = v.x; row[2 * k + 1] = v.y; }
+}
+
+// steps 3-5 of one member on its one transition: `row` = its rows at s (A's five, B's five), `nxt` = its rows at s' as they
+// were BEFORE this update.  c = 1, so the mean target is the sample's own: m = R + gamma * SV * 2^-40 on the learners' grid.
+// Moves row[a] and row[5 + b] and hands the two new values back for the store.
+__device__ __forceinline__ void pop_learn(double (&row)[10], const double (&nxt)[10], uint32_t a, uint32_t b, int32_t r,
+                                          uint32_t term, double alpha, double gamma, double& qa, double& qb) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        double v = nxt[5 * p];
+#pragma unroll
+        for (int k = 1; k < 5; ++k) v = nxt[5 * p + k] > v ? nxt[5 * p + k] : v;
+        const long long SV = term ? 0ll : (long long)rint(v * kVqScale);
+        const long long R = p ? -(long long)r : (long long)r;                   // player B's own reward
+        const double m = (double)R + gamma * ((double)SV * kVqInv);
+        const uint32_t act = p ? b : a;
+        double q = 0.0;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const double old = row[5 * p + k];
+            const double moved = old + alpha * (m - old);
+            row[5 * p + k] = (uint32_t)k == act ? moved : old;
+            q = (uint32_t)k == act ? moved : q;
+        }
+        (p ? qb : qa) = q;
+    }
+}
+
+// a player's action from its 15-bit draw h: the null row table, the shared fixed rows, or epsilon-greedy on its own row
+__device__ __forceinline__ uint32_t pop_draw(const PopIO& L, int p, const double (&row)[10], uint32_t s, double explor, uint32_t h) {
+    if (L.mode[p] == kPopUniform) return (h * 5u) >> 15;                       // wave-uniform
+    uint2 th;
+    if (L.mode[p] == kPopGreedy) {
+        double v = row[5 * p];
+        int g = 0;
+#pragma unroll
+        for (int k = 1; k < 5; ++k)
+            if (row[5 * p + k] > v) { v = row[5 * p + k]; g = k; }              // the first index that attains it
+        double pi[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) pi[k] = k == g ? 1.0 : 0.0;
+        __attribute__((aligned(8))) uint16_t t[4];
+        learner_thresholds(pi, explor, t);
+        th = *reinterpret_cast<const uint2*>(t);
+    } else {
+        th = *reinterpret_cast<const uint2*>(L.mix[p] + 4u * s);
+    }
+    return (h >= (th.x & 0xffffu)) + (h >= (th.x >> 16)) + (h >= (th.y & 0xffffu)) + (h >= (th.y >> 16));
+}
+
+template <bool SLIP, bool LUT_LDS>
+__global__ __launch_bounds__(kBlock) void pop_run_kernel(const KernelParams P, const PopIO L) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    HistAcc<false> hist; hist.init(P);
+    const Tables T = stage_tables<LUT_LDS>(P, smem);
+    const unsigned long long tick0 = *P.tick_in;
+    publish_tick(P, tick0, (unsigned long long)L.n_steps);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps += (unsigned long long)L.n_steps;
+    bool any_frozen = false;
+    for (unsigned long long g = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; g < P.n;
+         g += (unsigned long long)gridDim.x * kBlock) {
+        const unsigned long long i0 = P.first + g;                  // the lane, and the member
+        LaneVec<1> S; S.load(P, i0);
+        double* const tab = L.Q + (size_t)i0 * (size_t)L.nS * 10;
+        double alpha = L.alpha[i0];
+        const double decay = L.decay[i0], explor = L.explor[i0], gamma = L.gamma[i0];
+        uint32_t s = obs_of(T, P, S.L[0].A, S.L[0].B, S.L[0].p);
+        double row[10];
+        pop_load_row(tab, s, row);
+        int32_t ret = 0; uint32_t eps = 0u, nonzero = 0u;
+        for (int t = 0; t < L.n_steps; ++t) {
+            const unsigned long long tick = tick0 + (unsigned long long)t;
+            uint32_t words[1], awords[1];
+            lane_words<1>(P, P.lane_offset + i0, block_tick<SLIP>(tick), 0u, words);
+            lane_words<1>(P, P.lane_offset + i0, tick, 1u, awords);
+            const Draw d = draw_from_word<SLIP>(words[0], tick);
+            // two actions from one 32-bit word, 15 bits each (rollout_group)
+            const uint32_t a = pop_draw(L, 0, row, s, explor, awords[0] & 0x7fffu);
+            const uint32_t b = pop_draw(L, 1, row, s, explor, (awords[0] >> 16) & 0x7fffu);
+            StepResult R;
+            const bool frozen = lane_step<SLIP, true>(T, P, S.L[0], a, b, d, R);
+            ret += R.reward; eps += R.finished; nonzero += (uint32_t)R.reward & 1u;
+            any_frozen |= frozen;
+            // (a lane parked in a goal tuple by soccer_set_state has s = 0: never a current state)
+            const bool learn = !frozen && s != 0u;
+            const uint32_t s2 = R.final_obs, sn = R.obs;
+            double nxt[10];
+            if (learn) {
+                pop_load_row(tab, s2, nxt);                         // before the stores below: s' may be s
+                double qa, qb;
+                pop_learn(row, nxt, a, b, R.reward, R.term, alpha, gamma, qa, qb);
+                double* const at = tab + (size_t)s * 10;
+                at[a] = qa; at[5u + b] = qb;
+            }
+            if (learn && sn == s2) {                                // the episode goes on: the row at s' is the next row at s
+                if (s2 != s) {
+#pragma unroll
+                    for (int k = 0; k < 10; ++k) row[k] = nxt[k];
+                }                                                   // (s' == s: `row` already holds what the update wrote)
+            } else if (sn != s) {
+                pop_load_row(tab, sn, row);                         // after a reset
+            }
+            s = sn;
+            alpha = alpha * decay;
+        }
+        S.store(P, i0);
+        L.alpha[i0] = alpha;
+        hist.add_totals(eps, ret, nonzero);
+    }
+    if (any_frozen) P.misuse[0] = 1u;
+    hist.flush(P);
+}
+
+// soccer_q_population_update: steps 3-6 on the caller's transitions, transition i for member i
+__global__ __launch_bounds__(kBlock) void pop_update_kernel(const PopIO L, long long n, const uint16_t* obs, const int8_t* act_a,
+                                                            const int8_t* act_b, const int8_t* reward, const uint8_t* terminated,
+                                                            const uint16_t* next_obs) {
+    bool bad_act = false, bad_obs = false;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
+        const uint32_t s = obs[i], s2 = next_obs[i], a = (uint8_t)act_a[i], b = (uint8_t)act_b[i];
+        const bool ba = a > 4u || b > 4u, bo = s == 0u || s >= (uint32_t)L.nS || s2 >= (uint32_t)L.nS;
+        bad_act |= ba; bad_obs |= bo;
+        const double alpha = L.alpha[i];
+        if (!ba && !bo) {
+            double* const tab = L.Q + (size_t)i * (size_t)L.nS * 10;
+            double row[10], nxt[10], qa, qb;
+            pop_load_row(tab, s, row);
+            pop_load_row(tab, s2, nxt);
+            pop_learn(row, nxt, a, b, (int32_t)reward[i], terminated[i] != 0u ? 1u : 0u, alpha, L.gamma[i], qa, qb);
+            double* const at = tab + (size_t)s * 10;
+            at[a] = qa; at[5u + b] = qb;
+        }
+        L.alpha[i] = alpha * L.decay[i];
+    }
+    if (bad_act) L.misuse[1] = 1u;
+    if (bad_obs) L.misuse[2] = 1u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps += 1ull;
+}
+
+// creation: every member's Q_p = q_init on the live states, row 0 zero
+__global__ __launch_bounds__(kBlock) void pop_init_kernel(const PopIO L, unsigned long long n, double q_init) {
+    const unsigned long long per = (unsigned long long)L.nS * 10ull, cells = n * per;
+    for (unsigned long long c = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; c < cells; c += (unsigned long long)gridDim.x * kBlock)
+        L.Q[c] = (c % per) < 10ull ? 0.0 : q_init;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps = 0ull;
 }
 
 }  // namespace soccer

@@ -1,9 +1,11 @@
-// soccer_learners.hip — the minimax-Q learner: soccer_minimax_q_*, the independent Q-learners: soccer_q_learner_*, and the
-// policy hill-climbers: soccer_wolf_phc_* (see soccer_handle.hpp).
+// soccer_learners.hip — the minimax-Q learner: soccer_minimax_q_*, the independent Q-learners: soccer_q_learner_*, the
+// policy hill-climbers: soccer_wolf_phc_*, and the populations of one-actor Q-learners: soccer_q_population_* (see
+// soccer_handle.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <memory>
 #include <vector>
 
@@ -39,6 +41,15 @@ struct soccer_wolf_phc {
     int slot = 0;                       // alpha / dscale slot the NEXT update reads
 };
 
+// A population of Q-learners, a member per lane: the same shape; alpha lives per member in device memory, no slots.
+struct soccer_q_population {
+    soccer_handle* h = nullptr;
+    PopIO io{};
+    OwnedBufs bufs{"the population of Q-learners"};
+    unsigned long long n = 0;           // members = the handle's lanes
+    int launch_steps = 4096;            // steps per pop_run_kernel launch (SOCCER_POP_LAUNCH_STEPS)
+};
+
 void learners_release(soccer_handle* h) {
     for (soccer_minimax_q* q : h->learners) delete q;
     h->learners.clear();
@@ -46,6 +57,8 @@ void learners_release(soccer_handle* h) {
     h->q_learners.clear();
     for (soccer_wolf_phc* q : h->phc_learners) delete q;
     h->phc_learners.clear();
+    for (soccer_q_population* q : h->q_populations) delete q;
+    h->q_populations.clear();
 }
 
 // what every entry point checks first
@@ -632,5 +645,227 @@ extern "C" int soccer_wolf_phc_load(soccer_handle* h, soccer_wolf_phc* q, const 
     hipLaunchKernelGGL(phc_update_kernel<1>, dim3(q_update_grid(io)), dim3(kLearnerBlock), 0, h->stream, io, q->slot);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));            // the caller's arrays are pageable host memory
+    return SOCCER_OK;
+}
+
+// =================================================================================================
+// populations of independent Q-learners, a learner per lane: soccer_q_population_*
+// =================================================================================================
+static_assert(kPopGreedy == SOCCER_QL_GREEDY && kPopUniform == SOCCER_QL_UNIFORM, "the kernels' names of the modes");
+
+static int pop_check(soccer_handle* h, soccer_q_population* q, const char* what) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "%s during graph capture", what);
+    if (!q || std::find(h->q_populations.begin(), h->q_populations.end(), q) == h->q_populations.end())
+        return fail(h, SOCCER_E_INVALID, "%s: not a population of this handle", what);
+    return SOCCER_OK;
+}
+
+static int pop_range_check(soccer_handle* h, const soccer_q_population* q, const char* what, int64_t first, int64_t count) {
+    if (first < 0 || count < 0 || (uint64_t)first > q->n || (uint64_t)count > q->n - (uint64_t)first)
+        return fail(h, SOCCER_E_INVALID, "%s: members %lld .. %lld + %lld are outside the population of %llu", what, (long long)first,
+                    (long long)first, (long long)count, q->n);
+    return SOCCER_OK;
+}
+
+// launch == false (soccer_q_population_create): the LDS limit of this handle's run kernel, as launch_act
+template <bool SLIP, bool LUT_LDS>
+static hipError_t launch_pop_run(soccer_handle* h, const KernelParams& P, const PopIO& io, bool launch) {
+    if (!launch)
+        return h->smem_bytes > 48 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&pop_run_kernel<SLIP, LUT_LDS>),
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_bytes) : hipSuccess;
+    hipLaunchKernelGGL((pop_run_kernel<SLIP, LUT_LDS>), dim3(grid_for(h, P.n)), dim3(kBlock), h->smem_bytes, h->stream, P, io);
+    return hipSuccess;
+}
+
+static hipError_t pop_run(soccer_handle* h, const KernelParams& P, const PopIO& io, bool launch) {
+    return h->slip ? (h->lut_lds ? launch_pop_run<true, true>(h, P, io, launch) : launch_pop_run<true, false>(h, P, io, launch))
+                   : (h->lut_lds ? launch_pop_run<false, true>(h, P, io, launch) : launch_pop_run<false, false>(h, P, io, launch));
+}
+
+// a hyperparameter of every member: the caller's n values, each held to the scalar's range, or the scalar n times
+template <class Ok>
+static int pop_param(soccer_handle* h, const char* name, const char* range, const double* per_member, double scalar, size_t n, Ok ok,
+                     std::vector<double>& out) {
+    if (!per_member) {
+        if (!ok(scalar)) return fail(h, SOCCER_E_INVALID, "%s must be in %s", name, range);
+        out.assign(n, scalar);
+        return SOCCER_OK;
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (!ok(per_member[i])) return fail(h, SOCCER_E_INVALID, "%s_per_member[%zu] must be in %s", name, i, range);
+    out.assign(per_member, per_member + n);
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_population_create(soccer_handle* h, const soccer_q_population_config* cfg, soccer_q_population** out) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "soccer_q_population_create during graph capture");
+    if (!cfg || !out) return fail(h, SOCCER_E_INVALID, "soccer_q_population_create: cfg/out is NULL");
+    *out = nullptr;
+    if (h->P.policy_a != nullptr || h->P.policy_b != nullptr)
+        return fail(h, SOCCER_E_INVALID, "soccer_q_population_create needs a two-player handle: neither side may have a fixed policy (soccer_set_policy)");
+    if (!(h->cfg.flags & SOCCER_F_AUTORESET))
+        return fail(h, SOCCER_E_INVALID, "soccer_q_population_create needs a handle created with SOCCER_F_AUTORESET");
+    const size_t n = (size_t)h->cfg.n_lanes;
+    std::vector<double> par[4];         // alpha, decay, explor, discount_factor
+    if (int rc = pop_param(h, "discount_factor", "[0, 1)", cfg->discount_factor_per_member, cfg->discount_factor, n,
+                           [](double x) { return x >= 0.0 && x < 1.0; }, par[3])) return rc;
+    if (int rc = pop_param(h, "alpha", "[0, 1]", cfg->alpha_per_member, cfg->alpha, n, [](double x) { return x >= 0.0 && x <= 1.0; }, par[0])) return rc;
+    if (int rc = pop_param(h, "decay", "(0, 1]", cfg->decay_per_member, cfg->decay, n, [](double x) { return x > 0.0 && x <= 1.0; }, par[1])) return rc;
+    if (int rc = pop_param(h, "explor", "[0, 1]", cfg->explor_per_member, cfg->explor, n, [](double x) { return x >= 0.0 && x <= 1.0; }, par[2])) return rc;
+    if (!(cfg->q_init >= -1.0 && cfg->q_init <= 1.0)) return fail(h, SOCCER_E_INVALID, "q_init must be in [-1, 1]");
+    if (!ql_kind(cfg->act_a) || !ql_kind(cfg->act_b))
+        return fail(h, SOCCER_E_INVALID, "act_a / act_b must be SOCCER_QL_GREEDY, SOCCER_QL_UNIFORM or SOCCER_QL_FIXED");
+    if ((cfg->act_a == SOCCER_QL_FIXED) != (cfg->policy_a != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_a goes with act_a == SOCCER_QL_FIXED, and only with it");
+    if ((cfg->act_b == SOCCER_QL_FIXED) != (cfg->policy_b != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_b goes with act_b == SOCCER_QL_FIXED, and only with it");
+    const int nS = h->rules.nS;
+    std::vector<uint16_t> fixed[2];
+    if (cfg->policy_a) if (int rc = fixed_thresholds(h, "policy_a", cfg->policy_a, nS, fixed[0])) return rc;
+    if (cfg->policy_b) if (int rc = fixed_thresholds(h, "policy_b", cfg->policy_b, nS, fixed[1])) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, pop_run(h, h->P, PopIO{}, false));
+    std::unique_ptr<soccer_q_population> owner(new soccer_q_population());
+    soccer_q_population* q = owner.get();
+    q->h = h; q->n = n;
+    if (const char* e = std::getenv("SOCCER_POP_LAUNCH_STEPS")) {      // (tests: a launch boundary within a short run)
+        const long v = std::atol(e);
+        if (v >= 1 && v <= 4096) q->launch_steps = (int)v;
+    }
+    PopIO& io = q->io;
+    double* dpar[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint16_t* dmix[2] = {nullptr, nullptr};
+    int rc = q->bufs.alloc(h, n * (size_t)nS * 10, &io.Q);     // (a failure frees what was taken: `owner` goes, the handle is as it was)
+    for (int k = 0; k < 4; ++k) if (!rc) rc = q->bufs.alloc(h, n, &dpar[k]);
+    for (int p = 0; p < 2; ++p) if (!rc && !fixed[p].empty()) rc = q->bufs.alloc(h, (size_t)nS * 4, &dmix[p]);
+    if (!rc) rc = q->bufs.alloc(h, 1, &io.steps);
+    if (rc) return rc;
+    io.alpha = dpar[0]; io.decay = dpar[1]; io.explor = dpar[2]; io.gamma = dpar[3];
+    io.mix[0] = dmix[0]; io.mix[1] = dmix[1];
+    io.misuse = h->d_misuse;
+    io.nS = nS; io.n_steps = 0;
+    io.mode[0] = cfg->act_a; io.mode[1] = cfg->act_b;
+    for (int k = 0; k < 4; ++k) HIP_TRY(h, hipMemcpyAsync(dpar[k], par[k].data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    for (int p = 0; p < 2; ++p)
+        if (dmix[p]) HIP_TRY(h, hipMemcpyAsync(dmix[p], fixed[p].data(), fixed[p].size() * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(pop_init_kernel, dim3(grid_for(h, (uint64_t)n * (uint64_t)nS * 10)), dim3(kBlock), 0, h->stream, io, (unsigned long long)n, cfg->q_init);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // the vectors are pageable host memory of this call
+    h->q_populations.push_back(q);
+    *out = owner.release();
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_population_destroy(soccer_handle* h, soccer_q_population* q) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (!q) return SOCCER_OK;
+    if (int rc = pop_check(h, q, "soccer_q_population_destroy")) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // nothing is freed under a kernel that reads it
+    h->q_populations.erase(std::find(h->q_populations.begin(), h->q_populations.end(), q));
+    delete q;
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_population_run(soccer_handle* h, soccer_q_population* q, int32_t n_steps) {
+    if (int rc = pop_check(h, q, "soccer_q_population_run")) return rc;
+    if (n_steps < 0) return fail(h, SOCCER_E_INVALID, "soccer_q_population_run: n_steps must be >= 0");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    // the tick sequence of consecutive launches is contiguous and a member's whole state is in memory between them, so the
+    // split changes no result
+    for (int32_t t0 = 0; t0 < n_steps; t0 += q->launch_steps) {
+        KernelParams P = h->P;
+        PopIO io = q->io;
+        io.n_steps = n_steps - t0 < q->launch_steps ? n_steps - t0 : q->launch_steps;
+        bind_tick(h, P, (uint64_t)io.n_steps);
+        HIP_TRY(h, pop_run(h, P, io, true));
+    }
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_population_update(soccer_handle* h, soccer_q_population* q, const uint16_t* obs, const int8_t* act_a,
+                                          const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs) {
+    if (int rc = pop_check(h, q, "soccer_q_population_update")) return rc;
+    if (!obs || !act_a || !act_b || !reward || !terminated || !next_obs)
+        return fail(h, SOCCER_E_INVALID, "soccer_q_population_update: all six transition arrays are required");
+    if (!aligned(obs, 2) || !aligned(next_obs, 2)) return fail(h, SOCCER_E_INVALID, "soccer_q_population_update: obs / next_obs must be 2-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipLaunchKernelGGL(pop_update_kernel, dim3(grid_for(h, (uint64_t)q->n)), dim3(kBlock), 0, h->stream, q->io, (long long)q->n,
+                       obs, act_a, act_b, reward, terminated, next_obs);
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+// members per pass through the host staging block of read / load (32 MB of interleaved rows at most, one member at least)
+static size_t pop_chunk(size_t nS) { return std::max<size_t>(1, (size_t(32) << 20) / (nS * 80)); }
+
+extern "C" int soccer_q_population_read(soccer_handle* h, soccer_q_population* q, int64_t first, int64_t count, double* Q_a, double* Q_b,
+                                        double* alpha, uint64_t* steps) {
+    if (int rc = pop_check(h, q, "soccer_q_population_read")) return rc;
+    if (int rc = pop_range_check(h, q, "soccer_q_population_read", first, count)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const PopIO& io = q->io;
+    const size_t nS = (size_t)io.nS, per = nS * 10;
+    if (alpha && count) HIP_TRY(h, hipMemcpyAsync(alpha, io.alpha + first, (size_t)count * 8, hipMemcpyDeviceToHost, h->stream));
+    if (steps) HIP_TRY(h, hipMemcpyAsync(steps, io.steps, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (Q_a || Q_b) {
+        // the device keeps A's and B's row of a state side by side: through a host block, apart again here
+        const size_t chunk = pop_chunk(nS);
+        std::vector<double> stage;
+        for (size_t m0 = 0; m0 < (size_t)count; m0 += chunk) {
+            const size_t m = std::min(chunk, (size_t)count - m0);
+            stage.resize(m * per);
+            HIP_TRY(h, hipMemcpy(stage.data(), io.Q + ((size_t)first + m0) * per, m * per * 8, hipMemcpyDeviceToHost));
+            for (size_t r = 0; r < m * nS; ++r)
+                for (int k = 0; k < 5; ++k) {
+                    if (Q_a) Q_a[(m0 * nS + r) * 5 + k] = stage[r * 10 + k];
+                    if (Q_b) Q_b[(m0 * nS + r) * 5 + k] = stage[r * 10 + 5 + k];
+                }
+        }
+    }
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_population_load(soccer_handle* h, soccer_q_population* q, int64_t first, int64_t count, const double* Q_a,
+                                        const double* Q_b, const double* alpha, const uint64_t* steps) {
+    if (int rc = pop_check(h, q, "soccer_q_population_load")) return rc;
+    if (int rc = pop_range_check(h, q, "soccer_q_population_load", first, count)) return rc;
+    const PopIO& io = q->io;
+    const size_t nS = (size_t)io.nS, per = nS * 10;
+    const double* Q[2] = {Q_a, Q_b};
+    // everything is checked before anything is written
+    for (int p = 0; p < 2; ++p) {
+        if (!Q[p]) continue;
+        for (size_t i = 0; i < (size_t)count * nS * 5; ++i) {
+            if (i / 5 % nS == 0) continue;                  // row 0 is not read
+            if (!(Q[p][i] >= -1.0 && Q[p][i] <= 1.0))
+                return fail(h, SOCCER_E_INVALID, "soccer_q_population_load: Q_%c[%zu][%zu][%zu] is outside [-1, 1]", p ? 'b' : 'a',
+                            i / 5 / nS, i / 5 % nS, i % 5);
+        }
+    }
+    if (alpha)
+        for (size_t i = 0; i < (size_t)count; ++i)
+            if (!(alpha[i] >= 0.0 && alpha[i] <= 1.0)) return fail(h, SOCCER_E_INVALID, "soccer_q_population_load: alpha[%zu] must be in [0, 1]", i);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (Q_a || Q_b) {
+        const size_t chunk = pop_chunk(nS);
+        std::vector<double> stage;
+        for (size_t m0 = 0; m0 < (size_t)count; m0 += chunk) {
+            const size_t m = std::min(chunk, (size_t)count - m0);
+            double* const dev = io.Q + ((size_t)first + m0) * per;
+            stage.resize(m * per);
+            if (!Q_a || !Q_b) HIP_TRY(h, hipMemcpy(stage.data(), dev, m * per * 8, hipMemcpyDeviceToHost));   // the other player's rows stay
+            for (size_t r = 0; r < m * nS; ++r)
+                for (int p = 0; p < 2; ++p)
+                    if (Q[p])
+                        for (int k = 0; k < 5; ++k) stage[r * 10 + 5 * p + k] = r % nS == 0 ? 0.0 : Q[p][(m0 * nS + r) * 5 + k];
+            HIP_TRY(h, hipMemcpy(dev, stage.data(), m * per * 8, hipMemcpyHostToDevice));
+        }
+    }
+    if (alpha && count) HIP_TRY(h, hipMemcpy(io.alpha + first, alpha, (size_t)count * 8, hipMemcpyHostToDevice));
+    if (steps) HIP_TRY(h, hipMemcpy(io.steps, steps, 8, hipMemcpyHostToDevice));
     return SOCCER_OK;
 }

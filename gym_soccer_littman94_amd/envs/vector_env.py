@@ -484,6 +484,11 @@ class VectorSoccerEnv:
         assert self.multiagent, "q_learning needs a two-player environment (no player with a fixed policy)"
         return self._batch.q_learning(discount_factor, **params)
 
+    def q_population(self, discount_factor, **params):
+        """A QPopulation (SoccerBatch.q_population): a Q-learner per lane of this env, each with its own tables."""
+        assert self.multiagent, "q_population needs a two-player environment (no player with a fixed policy)"
+        return self._batch.q_population(discount_factor, **params)
+
     def wolf_phc(self, discount_factor, **params):
         """A WolfPHCLearner (SoccerBatch.wolf_phc) whose actors are this env's lanes: policy hill-climbers for both players."""
         assert self.multiagent, "wolf_phc needs a two-player environment (no player with a fixed policy)"

@@ -64,7 +64,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_best_response, soccer_evaluate_policies and soccer_rollout_shape were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_*, soccer_best_response, soccer_evaluate_policies and soccer_rollout_shape were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -644,6 +644,68 @@ int soccer_wolf_phc_read(soccer_handle* h, soccer_wolf_phc* q, const soccer_wolf
  * updates: NULL = the counts are zeroed.  alpha, dscale (both in [0, 1]) and steps: NULL = unchanged.  Every derived row is
  * recomputed, so read -> load on a fresh learner continues bit for bit. */
 int soccer_wolf_phc_load(soccer_handle* h, soccer_wolf_phc* q, const soccer_wolf_phc_state* in);
+/* ---- learners, a population of independent Q-learners (two-player handles; a learner per lane)
+ * The three learners above keep ONE table per handle and every lane feeds it.  A population keeps n tables: on a two-player
+ * SOCCER_F_AUTORESET handle of n lanes it has n members, and member i is exactly a soccer_q_learner whose only actor is lane
+ * i of the handle — the protocol of one learner, one stream of experience, many independent runs (seeds come from the lanes'
+ * own Philox streams, hyperparameters may differ per member).  Member i has its own float64 Q_a[n_states][5] and
+ * Q_b[n_states][5] (Q_b in player B's own reward, row 0 zero for good) and its own alpha; the population has one step counter.
+ * No visits are kept (at [n_states][25] uint64 they would be 2.5 times the tables).
+ * One step of member i is steps 1-6 of "learners, independent Q" on the single transition of lane i:
+ *   1. the behaviour rows from ITS tables at the lane's observation: SOCCER_QL_GREEDY (with its own explor), SOCCER_QL_UNIFORM
+ *      or SOCCER_QL_FIXED, with the same meanings and the same threshold expression; a FIXED player's policy is one
+ *      [n_states][5] array shared by all members
+ *   2. act and step: batched_rollout(n_steps = 1, sample_actions = 1) with that lane's rows
+ *   3.-5. with one sample c = 1, so for (s, a) in Q_a with r and for (s, b) in Q_b with -r:
+ *      m = ((double)R + discount_factor * ((double)SV * 2^-40)) / 1.0,  Q = Q + alpha * (m - Q), not contracted, where
+ *      SV = terminated ? 0 : Vq_p[s'] and Vq_p[s'] = rint(max_k Q_p[s'][k] * 2^40) is read BEFORE the step's update (it
+ *      matters when s' == s); s' = final_obs, so a truncated transition that did not terminate bootstraps from it.  The
+ *      2^-40 grid is kept although one sample does not need it: it makes a member bit for bit the learner above
+ *   6. alpha_i = alpha_i * decay_i; the step counter grows by one per step of the population
+ * A lane that still needs its first reset (SOCCER_MISUSE_FROZEN) and a lane whose current observation is 0 contribute
+ * nothing; their member's alpha still advances.  The population's state is a fixed function of (seed, parameters, number of
+ * steps): it does not depend on how run() splits its launches or on the state layout.
+ * Hyperparameters: the scalars of soccer_q_learner_config for everyone, or — where the pointer is not NULL — HOST arrays of n
+ * values, one per member, for alpha, decay, explor and discount_factor (every value in the scalar's range); q_init is scalar.
+ * Refusals, SOCCER_E_STATE during a capture, the misuse flags and the ownership of the memory are those of the
+ * soccer_q_learner_* calls (no bound on n but memory: n * n_states * 80 bytes of tables, 32 bytes of parameters per member and
+ * a shared policy's thresholds; SOCCER_E_NOMEM leaves the handle usable).  Populations and the other learners may share a handle. */
+typedef struct soccer_q_population soccer_q_population;
+typedef struct soccer_q_population_config {
+    double  discount_factor;        /* [0, 1) */
+    double  alpha;                  /* initial learning rate, [0, 1] */
+    double  decay;                  /* alpha's factor per step, (0, 1] */
+    double  explor;                 /* [0, 1] probability mass a GREEDY player spreads uniformly over the five actions */
+    double  q_init;                 /* [-1, 1] */
+    int32_t act_a;                  /* SOCCER_QL_* : how player A acts */
+    int32_t act_b;                  /* SOCCER_QL_* : how player B acts */
+    const double* policy_a;         /* act_a == SOCCER_QL_FIXED: HOST [n_states][5] rows >= 0 summing to 1; else NULL */
+    const double* policy_b;         /* the same for act_b */
+    const double* alpha_per_member;            /* HOST [n_lanes] or NULL: `alpha` for everyone */
+    const double* decay_per_member;            /* HOST [n_lanes] or NULL */
+    const double* explor_per_member;           /* HOST [n_lanes] or NULL */
+    const double* discount_factor_per_member;  /* HOST [n_lanes] or NULL */
+} soccer_q_population_config;
+int soccer_q_population_create(soccer_handle* h, const soccer_q_population_config* cfg, soccer_q_population** out);
+int soccer_q_population_destroy(soccer_handle* h, soccer_q_population* q);
+/* n_steps steps of every member in ceil(n_steps / K) launches of at most K steps each (K = 4096, the rollout's own bound; the
+ * environment variable SOCCER_POP_LAUNCH_STEPS, read at creation, overrides it: tests of the launch boundary), enqueued on the
+ * handle's stream: no synchronisation, no copy.  Consumes n_steps ticks. */
+int soccer_q_population_run(soccer_handle* h, soccer_q_population* q, int32_t n_steps);
+/* steps 3-6 on the caller's transitions: DEVICE arrays of n_lanes elements, transition i belongs to member i (reward is
+ * player A's), with the checks and the misuse flags of soccer_q_learner_update: a bad transition leaves its member's tables
+ * alone (its alpha still advances).  Consumes no tick. */
+int soccer_q_population_update(soccer_handle* h, soccer_q_population* q, const uint16_t* obs, const int8_t* act_a,
+                               const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs);
+/* Members first .. first + count - 1 (inside the population, else SOCCER_E_INVALID) to HOST arrays, any may be NULL:
+ * Q_a / Q_b [count][n_states][5], alpha[count], steps (one value).  Synchronises. */
+int soccer_q_population_read(soccer_handle* h, soccer_q_population* q, int64_t first, int64_t count, double* Q_a, double* Q_b,
+                             double* alpha, uint64_t* steps);
+/* The same range from HOST arrays, any may be NULL (= unchanged): Q_a / Q_b [count][n_states][5] in [-1, 1] (row 0 is taken
+ * as zeros), alpha[count] in [0, 1], steps.  Everything is checked before anything is written: a refused load changes
+ * nothing.  read -> load of a range on a fresh population continues bit for bit. */
+int soccer_q_population_load(soccer_handle* h, soccer_q_population* q, int64_t first, int64_t count, const double* Q_a,
+                             const double* Q_b, const double* alpha, const uint64_t* steps);
 
 /* HOST output: prob[c*3+k] = slip-combination weight c (0: no slip, 1: B slips, 2: A slips,
  * 3: both; :211-222, evaluated left to right in float64) times outcome probability 1, 0.5, 0.25
