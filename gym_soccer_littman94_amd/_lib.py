@@ -105,6 +105,19 @@ class WolfPHCState(C.Structure):
                [("alpha", C.POINTER(C.c_double)), ("dscale", C.POINTER(C.c_double)), ("steps", C.POINTER(C.c_uint64))]
 
 
+class WolfPopulationConfig(C.Structure):
+    """soccer_wolf_population_config"""
+    _fields_ = WolfPHCConfig._fields_ + [(n, C.c_void_p) for n in (
+        "policy_a_per_member", "policy_b_per_member", "alpha_per_member", "decay_per_member", "explor_per_member",
+        "discount_factor_per_member", "delta_win_per_member", "delta_lose_per_member", "delta_decay_per_member")]
+
+
+class WolfPopulationState(C.Structure):
+    """soccer_wolf_population_state"""
+    _fields_ = [(n, C.c_void_p) for n in ("Q_a", "Q_b", "pi_a", "pi_b", "avg_a", "avg_b", "updates", "alpha", "dscale")] + \
+               [("steps", C.POINTER(C.c_uint64))]
+
+
 MQ_UNIFORM, MQ_SELF, MQ_FIXED = 0, 1, 2
 QL_GREEDY, QL_UNIFORM, QL_FIXED = 0, 1, 2
 PHC_LEARN, PHC_UNIFORM, PHC_FIXED = 0, 1, 2
@@ -187,6 +200,13 @@ PROTOTYPES = {
     "soccer_q_population_update": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
     "soccer_q_population_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.POINTER(C.c_uint64)]),
     "soccer_q_population_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.POINTER(C.c_uint64)]),
+    "soccer_wolf_population_create": (C.c_int, [C.c_void_p, C.POINTER(WolfPopulationConfig), C.POINTER(C.c_void_p)]),
+    "soccer_wolf_population_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "soccer_wolf_population_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "soccer_wolf_population_update": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
+    "soccer_wolf_population_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(WolfPopulationState)]),
+    "soccer_wolf_population_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(WolfPopulationState)]),
+    "soccer_wolf_population_adopt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
     "soccer_prob_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 12)]),
     "soccer_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint64)]),
     "soccer_reset_stats": (C.c_int, [C.c_void_p]),

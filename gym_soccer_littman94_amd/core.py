@@ -636,6 +636,204 @@ class WolfPHCLearner:
             pass
 
 
+_WOLF_HYPER = (("discount_factor", lambda x: (0.0 <= x) & (x < 1.0), "[0, 1)"), ("alpha", lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
+               ("decay", lambda x: (0.0 < x) & (x <= 1.0), "(0, 1]"), ("explor", lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
+               ("delta_win", lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"), ("delta_lose", lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
+               ("delta_decay", lambda x: (0.0 < x) & (x <= 1.0), "(0, 1]"))
+
+
+def wolf_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01,
+                           delta_lose=0.04, delta_decay=1.0, act_a="learn", act_b="learn"):
+    """Checks the parameters of a population of policy hill-climbers (AssertionError, before any library call) and returns
+    (soccer_wolf_population_config, the arrays it points into).  The seven hyperparameters are scalars for every member or
+    arrays of n, one value per member; act_a / act_b: 'learn', 'uniform', one fixed [nS, 5] mixed policy for every member, or
+    [n, nS, 5], a fixed policy per member."""
+    given = dict(discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, delta_win=delta_win, delta_lose=delta_lose,
+                 delta_decay=delta_decay)
+    scalars, arrays = {}, {}
+    for name, ok, rng in _WOLF_HYPER:
+        value = given[name]
+        if np.ndim(value) == 0:
+            scalars[name], arrays[name] = float(value), None
+            assert ok(scalars[name]), "%s must be in %s" % (name, rng)
+        else:
+            a = np.ascontiguousarray(value, np.float64)
+            assert a.shape == (int(n),), "a per-member %s must have one value per lane (%d)" % (name, n)
+            assert ok(a).all(), "every per-member %s must be in %s" % (name, rng)
+            scalars[name], arrays[name] = float(a[0]), a
+    q0 = float(q_init)
+    assert -1.0 <= q0 <= 1.0, "q_init must be in [-1, 1]"
+    kinds, shared, each = [], [None, None], [None, None]
+    for p, (name, act) in enumerate((("act_a", act_a), ("act_b", act_b))):
+        if isinstance(act, str):
+            assert act in ("learn", "uniform"), "%s must be 'learn', 'uniform', an [nS, 5] or an [n, nS, 5] mixed policy" % name
+            kinds.append(_lib.PHC_LEARN if act == "learn" else _lib.PHC_UNIFORM)
+            continue
+        pol = np.ascontiguousarray(act, np.float64)
+        assert pol.shape in ((int(nS), 5), (int(n), int(nS), 5)) and (pol >= 0).all() and np.allclose(pol.sum(-1), 1.0), \
+            "a fixed %s must be [n_states, 5] or [n_lanes, n_states, 5] rows summing to 1" % name
+        (shared if pol.ndim == 2 else each)[p] = pol
+        kinds.append(_lib.PHC_FIXED)
+    ptr = lambda x: None if x is None else x.ctypes.data  # noqa: E731
+    cfg = _lib.WolfPopulationConfig(scalars["discount_factor"], scalars["alpha"], scalars["decay"], scalars["explor"], q0,
+                                    scalars["delta_win"], scalars["delta_lose"], scalars["delta_decay"], kinds[0], kinds[1],
+                                    ptr(shared[0]), ptr(shared[1]), ptr(each[0]), ptr(each[1]),
+                                    *[ptr(arrays[k]) for k in ("alpha", "decay", "explor", "discount_factor", "delta_win", "delta_lose", "delta_decay")])
+    return cfg, ((shared, each), arrays)
+
+
+class WolfPopulation:
+    """A population of policy hill-climbers (PHC / WoLF-PHC) on a two-player auto-reset SoccerBatch, a learner per lane:
+    member i has its own Q_a, Q_b, pi_a, pi_b, avg_a, avg_b [nS, 5], updates[nS], alpha and dscale and learns from lane i alone
+    (include/soccer_hip.h, "learners, a population of policy hill-climbers").  A fixed player's policy is per member.  run()
+    enqueues and returns; read() and the properties synchronise and copy.  read(), load() and exploitability() take a range
+    of members."""
+    _ROWS = ("Q_a", "Q_b", "pi_a", "pi_b", "avg_a", "avg_b")
+
+    def __init__(self, batch, discount_factor, **params):
+        cfg, keep = wolf_population_config(batch.n, batch.nS, discount_factor, **params)
+        self.batch, self.q = batch, None
+        q = C.c_void_p()
+        batch._check(batch.lib.soccer_wolf_population_create(batch.h, C.byref(cfg), C.byref(q)))
+        self.discount_factor = np.full(batch.n, cfg.discount_factor) if keep[1]["discount_factor"] is None else keep[1]["discount_factor"].copy()
+        del keep                                   # (create has copied the parameters and the fixed policies)
+        self.q = q
+        self.n, self.nS = batch.n, batch.nS
+        self.modes = (cfg.act_a, cfg.act_b)
+        batch._learners.add(self)
+
+    def run(self, n_steps):
+        """n_steps steps of every member (its lane acts, the environment steps, its tables and its LEARN players' policies
+        are updated), enqueued."""
+        b = self.batch
+        b._check(b.lib.soccer_wolf_population_run(b.h, self.q, int(n_steps)))
+        return self
+
+    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
+        """One step's update on n transitions, transition i for member i (reward is player A's): DeviceArrays (or device
+        tensors) of n elements, or numpy arrays, which are copied to the device first."""
+        n = self.n
+
+        def call(h, q, count, *ptrs):
+            assert count == n, "a population's update takes one transition per member (%d)" % n
+            return self.batch.lib.soccer_wolf_population_update(h, q, *ptrs)
+        _learner_update(self.batch, call, self.q, obs, act_a, act_b, reward, terminated, next_obs)
+        return self
+
+    def _range(self, first, count):
+        first = int(first)
+        count = self.n - first if count is None else int(count)
+        assert 0 <= first <= self.n and 0 <= count <= self.n - first, "members %d .. %d + %d are outside the population of %d" % (first, first, count, self.n)
+        return first, count
+
+    def _read(self, first, count, keys):
+        nS, b = self.nS, self.batch
+        shapes = {"updates": ((count, nS), np.uint64), "alpha": ((count,), np.float64), "dscale": ((count,), np.float64)}
+        out = {k: np.zeros(*shapes.get(k, ((count, nS, 5), np.float64))) for k in keys if k != "steps"}
+        st = C.c_uint64()
+        state = _lib.WolfPopulationState(**{k: x.ctypes.data for k, x in out.items()})
+        if "steps" in keys:
+            state.steps = C.pointer(st)
+        b._check(b.lib.soccer_wolf_population_read(b.h, self.q, first, count, C.byref(state)))
+        if "steps" in keys:
+            out["steps"] = int(st.value)
+        return out
+
+    def read(self, first=0, count=None):
+        """dict for members first .. first + count - 1 (count None: to the end): Q_a / Q_b, pi_a / pi_b, avg_a / avg_b
+        [count, nS, 5], V_a / V_b [count, nS] (the row maxima, computed here), updates[count, nS], alpha[count],
+        dscale[count], steps.  Synchronises."""
+        first, count = self._range(first, count)
+        out = self._read(first, count, self._ROWS + ("updates", "alpha", "dscale", "steps"))
+        for p in "ab":
+            out["V_" + p] = out["Q_" + p].max(2)
+        return out
+
+    alpha = property(lambda self: self._read(0, self.n, ("alpha",))["alpha"], doc="every member's learning rate, [n]")
+    dscale = property(lambda self: self._read(0, self.n, ("dscale",))["dscale"], doc="every member's factor on both deltas, [n]")
+    steps = property(lambda self: self._read(0, 0, ("steps",))["steps"])
+
+    def exploitability(self, which="pi", theta=1e-10, first=0, count=None):
+        """How badly the best possible opponent beats the pair of policies (which='pi') or of average policies (which='avg')
+        of each member of a range, at that member's discount: through SoccerBatch.best_response in batches of at most 256
+        members with one discount.  Returns {"v_a", "v_b", "gap"}, arrays of [count, nS] (planners.exploitability's per
+        member)."""
+        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
+        first, count = self._range(first, count)
+        b = self.batch
+        out = {k: np.zeros((count, self.nS)) for k in ("v_a", "v_b", "gap")}
+        for c0 in range(0, count, _lib.BR_MAX_POLICIES):
+            c = min(_lib.BR_MAX_POLICIES, count - c0)
+            r = self._read(first + c0, c, (which + "_a", which + "_b"))
+            gam = self.discount_factor[first + c0:first + c0 + c]
+            for g in np.unique(gam):                # (one solve per discount in the chunk: a batch shares its discount)
+                idx = np.flatnonzero(gam == g)
+                out["v_a"][c0 + idx] = b.best_response(r[which + "_a"][idx], 0, theta, float(g))[1]
+                out["v_b"][c0 + idx] = b.best_response(r[which + "_b"][idx], 1, theta, float(g))[1]
+        out["gap"] = out["v_b"] - out["v_a"]
+        return out
+
+    def load(self, Q_a=None, Q_b=None, pi_a=None, pi_b=None, avg_a=None, avg_b=None, updates=None, alpha=None, dscale=None, steps=None,
+             first=0):
+        """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged): the
+        six tables [count, nS, 5], updates[count, nS], alpha[count] and dscale[count], steps for the population.  With what
+        read() gave, a fresh population continues bit for bit.  A refused load changes nothing."""
+        b = self.batch
+        keep = {k: np.ascontiguousarray(x, np.float64) for k, x in zip(self._ROWS + ("alpha", "dscale"), (Q_a, Q_b, pi_a, pi_b, avg_a, avg_b, alpha, dscale))
+                if x is not None}
+        if updates is not None:
+            keep["updates"] = np.ascontiguousarray(updates, np.uint64)
+        counts = {x.shape[0] for x in keep.values() if x.ndim >= 1}
+        assert len(counts) <= 1 and all(x.ndim >= 1 for x in keep.values()), "the arrays must hold the same number of members"
+        first, count = self._range(first, counts.pop() if counts else 0)
+        for k, x in keep.items():
+            if k in self._ROWS:
+                assert x.shape == (count, self.nS, 5), "%s must be [count, n_states, 5]" % k
+                if k.startswith("Q"):
+                    assert (np.abs(x[:, 1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
+            elif k == "updates":
+                assert x.shape == (count, self.nS), "updates must be [count, n_states]"
+            else:
+                assert x.shape == (count,) and ((x >= 0.0) & (x <= 1.0)).all(), "%s must be [count] values in [0, 1]" % k
+        state = _lib.WolfPopulationState(**{k: x.ctypes.data for k, x in keep.items()})
+        if steps is not None:
+            state.steps = C.pointer(C.c_uint64(int(steps)))
+        b._check(b.lib.soccer_wolf_population_load(b.h, self.q, first, count, C.byref(state)))
+        return self
+
+    def adopt(self, player, src, src_player, which="pi"):
+        """Freeze: every member's fixed policy of `player` (0 = A, 1 = B) becomes the pi (which='pi') or avg (which='avg') of
+        `src_player` of the same member of the population `src` on this batch, on the device, enqueued."""
+        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
+        assert isinstance(src, WolfPopulation), "src must be a WolfPopulation"
+        b = self.batch
+        b._check(b.lib.soccer_wolf_population_adopt(b.h, self.q, int(player), src.q, int(src_player), 0 if which == "pi" else 1))
+        return self
+
+    def challengers(self, against, which="pi", **hyper):
+        """A second population on the same batch for the challenger protocol: its player `against` (0 = A, 1 = B) is fixed,
+        member by member, to this population's pi (or avg) of that player as it is now; its other player learns from scratch
+        with the hyperparameters given (WolfPopulation's; default discount: this population's)."""
+        assert against in (0, 1), "against must be 0 (player A is frozen) or 1 (player B)"
+        assert "act_a" not in hyper and "act_b" not in hyper, "challengers() sets act_a / act_b"
+        hyper.setdefault("discount_factor", self.discount_factor)
+        acts = ["learn", "learn"]
+        acts[against] = np.full((self.nS, 5), 0.2)          # a placeholder row table: adopt() overwrites every member's
+        c = WolfPopulation(self.batch, hyper.pop("discount_factor"), act_a=acts[0], act_b=acts[1], **hyper)
+        return c.adopt(against, self, against, which)
+
+    def close(self):
+        if self.q and self.batch.h:
+            self.batch.lib.soccer_wolf_population_destroy(self.batch.h, self.q)
+        self.q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SoccerBatch:
     """N lanes of the Littman-94 soccer game resident on one GPU.
 
@@ -929,6 +1127,14 @@ class SoccerBatch:
         """A WolfPHCLearner on this batch (two players, autoreset=True, at most 2**22 lanes).  act_a / act_b: 'learn'
         (a hill-climbing mixed policy), 'uniform' or a fixed [nS, 5] mixed policy; delta_win == delta_lose is plain PHC."""
         return WolfPHCLearner(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, delta_win=delta_win,
+                              delta_lose=delta_lose, delta_decay=delta_decay, act_a=act_a, act_b=act_b)
+
+    def wolf_population(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
+                        delta_decay=1.0, act_a="learn", act_b="learn"):
+        """A WolfPopulation on this batch (two players, autoreset=True): a PHC / WoLF-PHC learner per lane, each with its own
+        tables and policies.  The seven hyperparameters are scalars or arrays of one value per lane; act_a / act_b: 'learn',
+        'uniform', a fixed [nS, 5] mixed policy for every member or [n, nS, 5], one per member."""
+        return WolfPopulation(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, delta_win=delta_win,
                               delta_lose=delta_lose, delta_decay=delta_decay, act_a=act_a, act_b=act_b)
 
     # -- hot path -------------------------------------------------------------------------------

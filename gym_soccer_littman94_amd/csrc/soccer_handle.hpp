@@ -196,6 +196,7 @@ struct soccer_handle {
     std::vector<soccer_q_learner*> q_learners; // soccer_q_learner_create: the same for the independent Q-learners
     std::vector<soccer_wolf_phc*> phc_learners; // soccer_wolf_phc_create: the same for the policy hill-climbers
     std::vector<soccer_q_population*> q_populations; // soccer_q_population_create: the same for the populations of Q-learners
+    std::vector<soccer_wolf_population*> wolf_populations; // soccer_wolf_population_create: the same for the populations of hill-climbers
     std::string err;
 
     soccer_handle() = default;

@@ -2,7 +2,8 @@
 // learner_update_kernel, learner_init_kernel; and the independent Q-learners of both players: q_act_kernel, q_reduce_kernel,
 // q_update_kernel, q_init_kernel (they share the act-and-step body, the reduce body and learner_thresholds); and the policy
 // hill-climbers on top of those: phc_act_kernel, phc_reduce_kernel, phc_update_kernel, phc_init_kernel; and the population
-// of one-actor Q-learners, a learner per lane: pop_run_kernel, pop_update_kernel, pop_init_kernel (at the end).
+// of one-actor Q-learners, a learner per lane: pop_run_kernel, pop_update_kernel, pop_init_kernel; and the population of
+// one-actor policy hill-climbers: phc_pop_run_kernel, phc_pop_update_kernel, phc_pop_init_kernel, phc_pop_adopt_kernel (at the end).
 // Included by soccer_learners.hip only: every kernel is emitted by exactly one translation unit.
 //
 // One learner step (include/soccer_hip.h, "learners") is two launches in stream order, no grid barrier between them:
@@ -58,6 +59,9 @@ __device__ __forceinline__ void learner_accumulate(const LearnerIO& L, uint32_t 
 }
 
 // a behaviour policy's threshold row: SoccerBatch.mixed_policy_thresholds of (1.0 - explor) * pi + explor / 5.0
+// (with explor == 0.0 this is fixed_thresholds of soccer_learners.hip operation for operation: (1.0 - 0.0) * p + 0.0 / 5.0 is p
+// exactly for p >= 0, and the running sum, the floor and the clamp are the same: the populations of policy hill-climbers draw a
+// FIXED player's action from its own pi row this way and get the host-computed table's bits)
 __device__ __forceinline__ void learner_thresholds(const double (&pi)[5], double explor, uint16_t* row) {
     double c = 0.0;
     uint32_t t[4];
@@ -677,6 +681,262 @@ __global__ __launch_bounds__(kBlock) void pop_init_kernel(const PopIO L, unsigne
     for (unsigned long long c = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; c < cells; c += (unsigned long long)gridDim.x * kBlock)
         L.Q[c] = (c % per) < 10ull ? 0.0 : q_init;
     if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps = 0ull;
+}
+
+// =================================================================================================
+// a population of policy hill-climbers, a learner per lane (include/soccer_hip.h, "learners, a population of policy hill-climbers")
+// =================================================================================================
+// Member i is a soccer_wolf_phc learner whose only actor is lane i: pop_run_kernel's shape (a thread owns lane i and member i,
+// the lane and the rows of the current state in registers over the launch's steps, no atomics, no second launch) with the
+// policy step behind the Q update.  lane_words / draw_from_word / lane_step / learner_thresholds / pop_learn are the same
+// functions the other learners call.
+// Table layout: member i's block is [nS][32] float64, one 256-byte aligned row per state:
+//     0..4 Q_a   5..9 Q_b   10..14 pi_a   15..19 avg_a   20..24 pi_b   25..29 avg_b   30 updates (uint64)   31 pad
+// so everything a step needs at s is two cache lines, Q_a | Q_b and pi_p | avg_p are runs of ten values on a 16-byte
+// boundary, and a member's block is contiguous.
+// What a step carries: Q_a, Q_b, pi_a, pi_b at s (the next draw and, as the previous step's s' rows, the bootstrap), as
+// pop_run_kernel carries Q.  avg and updates at s are used only after the environment step: their loads are issued at the
+// top of the step and nothing of them lives across steps.  Everything is unrolled over the five actions with the action /
+// greedy index COMPARED, never used as a subscript: the rows stay in registers (0 bytes of scratch).
+constexpr int kPhcRow = 32;                         // float64 slots per state
+constexpr int kPhcPi = 10, kPhcAvg = 15, kPhcPlayer = 10, kPhcUpdates = 30;   // pi_p at kPhcPi + p * kPhcPlayer, avg_p at kPhcAvg + ...
+constexpr int kPhcLearn = 0, kPhcUniform = 1, kPhcFixed = 2;                   // = SOCCER_PHC_* (soccer_learners.hip asserts it)
+
+struct PhcPopIO {
+    double* tab;                        // [n][nS][32]
+    double* alpha;                      // [n] every member's learning rate
+    double* dscale;                     // [n] every member's factor on both deltas
+    const double* decay;                // [n]
+    const double* explor;               // [n]
+    const double* gamma;                // [n]
+    const double* delta_win;            // [n]
+    const double* delta_lose;           // [n]
+    const double* delta_decay;          // [n]
+    unsigned long long* steps;
+    unsigned int* misuse;               // the handle's sticky words
+    int32_t nS;
+    int32_t n_steps;                    // phc_pop_run_kernel: steps of this launch
+    int32_t mode[2];                    // SOCCER_PHC_* of player A, player B
+};
+
+__device__ __forceinline__ void phc_pop_load_q(const double* at, double (&row)[10]) {
+    const double2* p = reinterpret_cast<const double2*>(at);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { const double2 v = p[k]; row[2 * k] = v.x; row[2 * k + 1] = v.y; }
+}
+
+// pi_a | pi_b of one state's row (`at` = the row)
+__device__ __forceinline__ void phc_pop_load_pi(const double* at, double (&pi)[10]) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const double* q = at + kPhcPi + p * kPhcPlayer;
+        const double2 u = *reinterpret_cast<const double2*>(q), v = *reinterpret_cast<const double2*>(q + 2);
+        pi[5 * p] = u.x; pi[5 * p + 1] = u.y; pi[5 * p + 2] = v.x; pi[5 * p + 3] = v.y; pi[5 * p + 4] = q[4];
+    }
+}
+
+// avg_a | avg_b
+__device__ __forceinline__ void phc_pop_load_avg(const double* at, double (&avg)[10]) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const double* q = at + kPhcAvg + p * kPhcPlayer;
+        const double2 u = *reinterpret_cast<const double2*>(q + 1), v = *reinterpret_cast<const double2*>(q + 3);
+        avg[5 * p] = q[0]; avg[5 * p + 1] = u.x; avg[5 * p + 2] = u.y; avg[5 * p + 3] = v.x; avg[5 * p + 4] = v.y;
+    }
+}
+
+// step 5 of "learners, policy hill-climbing" for one player of one state, operation for operation as phc_update_kernel has
+// it: pi and avg in registers, Q = the player's row AFTER the Q update, n = (double)updates[s] after its increment
+__device__ __forceinline__ void phc_policy_step(double (&pi)[5], double (&avg)[5], const double (&Q)[5], double n, double delta_win,
+                                                double delta_lose, double dscale) {
+    double v = Q[0];
+    int g = 0;
+#pragma unroll
+    for (int k = 1; k < 5; ++k)
+        if (Q[k] > v) { v = Q[k]; g = k; }                       // the first index that attains it
+    double ep = 0.0, ea = 0.0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) avg[k] = avg[k] + (pi[k] - avg[k]) / n;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { ep = ep + pi[k] * Q[k]; ea = ea + avg[k] * Q[k]; }
+    const double d = ((ep > ea ? delta_win : delta_lose) * dscale) / 4.0;
+    double moved = 0.0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        if (k != g) {
+            const double m = pi[k] < d ? pi[k] : d;
+            pi[k] = pi[k] - m;
+            moved = moved + m;
+        }
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        if (k == g) pi[k] = pi[k] + moved;
+}
+
+// steps 3-5 of one member on its one transition.  `at` = its row at s; q / pi = Q_a | Q_b and pi_a | pi_b at s, avg and upd
+// what the row holds, nxt = Q_a | Q_b at s' as they were BEFORE this update.  Leaves the new q and pi in the caller's registers
+// and stores everything that moved.
+__device__ __forceinline__ void phc_pop_learn(const PhcPopIO& L, double* at, double (&q)[10], double (&pi)[10], double (&avg)[10],
+                                              unsigned long long upd, const double (&nxt)[10], uint32_t a, uint32_t b, int32_t r,
+                                              uint32_t term, double alpha, double gamma, double dwin, double dlose, double dscale) {
+    double qa, qb;
+    pop_learn(q, nxt, a, b, r, term, alpha, gamma, qa, qb);
+    at[a] = qa; at[5u + b] = qb;
+    upd += 1ull;
+    *reinterpret_cast<unsigned long long*>(at + kPhcUpdates) = upd;
+    const double n = (double)upd;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (L.mode[p] != kPhcLearn) continue;                   // wave-uniform
+        double P[5], A[5], Q[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { P[k] = pi[5 * p + k]; A[k] = avg[5 * p + k]; Q[k] = q[5 * p + k]; }
+        phc_policy_step(P, A, Q, n, dwin, dlose, dscale);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) pi[5 * p + k] = P[k];
+        double2* const to = reinterpret_cast<double2*>(at + kPhcPi + p * kPhcPlayer);       // pi_p | avg_p: ten values
+        to[0] = make_double2(P[0], P[1]); to[1] = make_double2(P[2], P[3]); to[2] = make_double2(P[4], A[0]);
+        to[3] = make_double2(A[1], A[2]); to[4] = make_double2(A[3], A[4]);
+    }
+}
+
+// a player's action from its 15-bit draw h: the null row table, or the thresholds of its own pi row at s — with the
+// member's explor for a LEARN player, with 0.0 for a FIXED one (learner_thresholds: the host-computed table's bits)
+__device__ __forceinline__ uint32_t phc_pop_draw(const PhcPopIO& L, int p, const double (&pi)[10], double explor, uint32_t h) {
+    if (L.mode[p] == kPhcUniform) return (h * 5u) >> 15;                      // wave-uniform
+    double row[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) row[k] = pi[5 * p + k];
+    __attribute__((aligned(8))) uint16_t t[4];
+    learner_thresholds(row, L.mode[p] == kPhcLearn ? explor : 0.0, t);
+    const uint2 th = *reinterpret_cast<const uint2*>(t);
+    return (h >= (th.x & 0xffffu)) + (h >= (th.x >> 16)) + (h >= (th.y & 0xffffu)) + (h >= (th.y >> 16));
+}
+
+template <bool SLIP, bool LUT_LDS>
+__global__ __launch_bounds__(kBlock) void phc_pop_run_kernel(const KernelParams P, const PhcPopIO L) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    HistAcc<false> hist; hist.init(P);
+    const Tables T = stage_tables<LUT_LDS>(P, smem);
+    const unsigned long long tick0 = *P.tick_in;
+    publish_tick(P, tick0, (unsigned long long)L.n_steps);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps += (unsigned long long)L.n_steps;
+    bool any_frozen = false;
+    for (unsigned long long g = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; g < P.n;
+         g += (unsigned long long)gridDim.x * kBlock) {
+        const unsigned long long i0 = P.first + g;                  // the lane, and the member
+        LaneVec<1> S; S.load(P, i0);
+        double* const tab = L.tab + (size_t)i0 * (size_t)L.nS * kPhcRow;
+        double alpha = L.alpha[i0], dscale = L.dscale[i0];
+        const double decay = L.decay[i0], explor = L.explor[i0], gamma = L.gamma[i0];
+        const double dwin = L.delta_win[i0], dlose = L.delta_lose[i0], ddecay = L.delta_decay[i0];
+        uint32_t s = obs_of(T, P, S.L[0].A, S.L[0].B, S.L[0].p);
+        double q[10], pi[10];
+        phc_pop_load_q(tab + (size_t)s * kPhcRow, q);
+        phc_pop_load_pi(tab + (size_t)s * kPhcRow, pi);
+        int32_t ret = 0; uint32_t eps = 0u, nonzero = 0u;
+        for (int t = 0; t < L.n_steps; ++t) {
+            const unsigned long long tick = tick0 + (unsigned long long)t;
+            double* const at = tab + (size_t)s * kPhcRow;
+            // used after the environment step only: issued here, dead at the end of the step
+            double avg[10];
+            phc_pop_load_avg(at, avg);
+            const unsigned long long upd = *reinterpret_cast<const unsigned long long*>(at + kPhcUpdates);
+            uint32_t words[1], awords[1];
+            lane_words<1>(P, P.lane_offset + i0, block_tick<SLIP>(tick), 0u, words);
+            lane_words<1>(P, P.lane_offset + i0, tick, 1u, awords);
+            const Draw d = draw_from_word<SLIP>(words[0], tick);
+            // two actions from one 32-bit word, 15 bits each (rollout_group)
+            const uint32_t a = phc_pop_draw(L, 0, pi, explor, awords[0] & 0x7fffu);
+            const uint32_t b = phc_pop_draw(L, 1, pi, explor, (awords[0] >> 16) & 0x7fffu);
+            StepResult R;
+            const bool frozen = lane_step<SLIP, true>(T, P, S.L[0], a, b, d, R);
+            ret += R.reward; eps += R.finished; nonzero += (uint32_t)R.reward & 1u;
+            any_frozen |= frozen;
+            // (a lane parked in a goal tuple by soccer_set_state has s = 0: never a current state)
+            const bool learn = !frozen && s != 0u;
+            const uint32_t s2 = R.final_obs, sn = R.obs;
+            double nxt[10], npi[10];
+            if (learn) {
+                phc_pop_load_q(tab + (size_t)s2 * kPhcRow, nxt);    // before the stores below: s' may be s
+                phc_pop_load_pi(tab + (size_t)s2 * kPhcRow, npi);
+                phc_pop_learn(L, at, q, pi, avg, upd, nxt, a, b, R.reward, R.term, alpha, gamma, dwin, dlose, dscale);
+            }
+            if (learn && sn == s2) {                                // the episode goes on: the rows at s' are the next rows at s
+                if (s2 != s) {
+#pragma unroll
+                    for (int k = 0; k < 10; ++k) { q[k] = nxt[k]; pi[k] = npi[k]; }
+                }                                                   // (s' == s: q and pi already hold what the update wrote)
+            } else if (sn != s) {
+                phc_pop_load_q(tab + (size_t)sn * kPhcRow, q);      // after a reset
+                phc_pop_load_pi(tab + (size_t)sn * kPhcRow, pi);
+            }
+            s = sn;
+            alpha = alpha * decay;
+            dscale = dscale * ddecay;
+        }
+        S.store(P, i0);
+        L.alpha[i0] = alpha; L.dscale[i0] = dscale;
+        hist.add_totals(eps, ret, nonzero);
+    }
+    if (any_frozen) P.misuse[0] = 1u;
+    hist.flush(P);
+}
+
+// soccer_wolf_population_update: steps 3-6 on the caller's transitions, transition i for member i
+__global__ __launch_bounds__(kBlock) void phc_pop_update_kernel(const PhcPopIO L, long long n, const uint16_t* obs, const int8_t* act_a,
+                                                                const int8_t* act_b, const int8_t* reward, const uint8_t* terminated,
+                                                                const uint16_t* next_obs) {
+    bool bad_act = false, bad_obs = false;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
+        const uint32_t s = obs[i], s2 = next_obs[i], a = (uint8_t)act_a[i], b = (uint8_t)act_b[i];
+        const bool ba = a > 4u || b > 4u, bo = s == 0u || s >= (uint32_t)L.nS || s2 >= (uint32_t)L.nS;
+        bad_act |= ba; bad_obs |= bo;
+        const double alpha = L.alpha[i], dscale = L.dscale[i];
+        if (!ba && !bo) {
+            double* const tab = L.tab + (size_t)i * (size_t)L.nS * kPhcRow;
+            double* const at = tab + (size_t)s * kPhcRow;
+            double q[10], pi[10], avg[10], nxt[10];
+            phc_pop_load_q(at, q); phc_pop_load_pi(at, pi); phc_pop_load_avg(at, avg);
+            const unsigned long long upd = *reinterpret_cast<const unsigned long long*>(at + kPhcUpdates);
+            phc_pop_load_q(tab + (size_t)s2 * kPhcRow, nxt);
+            phc_pop_learn(L, at, q, pi, avg, upd, nxt, a, b, (int32_t)reward[i], terminated[i] != 0u ? 1u : 0u, alpha, L.gamma[i],
+                          L.delta_win[i], L.delta_lose[i], dscale);
+        }
+        L.alpha[i] = alpha * L.decay[i];
+        L.dscale[i] = dscale * L.delta_decay[i];
+    }
+    if (bad_act) L.misuse[1] = 1u;
+    if (bad_obs) L.misuse[2] = 1u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps += 1ull;
+}
+
+// creation: every member's Q_p = q_init on the live states and zero in row 0, pi = avg = 0.2, updates = 0, dscale = 1
+__global__ __launch_bounds__(kBlock) void phc_pop_init_kernel(const PhcPopIO L, unsigned long long n, double q_init) {
+    const unsigned long long per = (unsigned long long)L.nS * kPhcRow, cells = n * per;
+    for (unsigned long long c = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; c < cells; c += (unsigned long long)gridDim.x * kBlock) {
+        const unsigned slot = (unsigned)(c % kPhcRow);
+        L.tab[c] = slot < 10u ? ((c % per) < (unsigned long long)kPhcRow ? 0.0 : q_init) : (slot < (unsigned)kPhcUpdates ? 0.2 : 0.0);
+        if (c < n) L.dscale[c] = 1.0;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps = 0ull;
+}
+
+// A strided row copy: for `count` members from member `first` of dst, rows of five values from src (member m of the range at
+// src + m * src_member, its state s at + s * src_row) into BOTH the pi and the avg row of dst's player (dst_slot = that
+// player's pi slot).  soccer_wolf_population_adopt: src is another population's table at the slot to copy (strides nS * 32 and
+// 32); creation: a dense [count][nS][5] staging block, or one [nS][5] policy with src_member = 0.
+__global__ __launch_bounds__(kBlock) void phc_pop_adopt_kernel(double* dst, int dst_slot, const double* src, unsigned long long src_member,
+                                                               unsigned long long src_row, unsigned long long first,
+                                                               unsigned long long count, int32_t nS) {
+    const unsigned long long rows = count * (unsigned long long)nS;
+    for (unsigned long long c = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; c < rows; c += (unsigned long long)gridDim.x * kBlock) {
+        const unsigned long long m = c / (unsigned long long)nS, s = c % (unsigned long long)nS;
+        const double* const from = src + m * src_member + s * src_row;
+        double* const to = dst + ((first + m) * (unsigned long long)nS + s) * kPhcRow + dst_slot;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { const double v = from[k]; to[k] = v; to[(kPhcAvg - kPhcPi) + k] = v; }
+    }
 }
 
 }  // namespace soccer

@@ -1,11 +1,12 @@
 // soccer_learners.hip — the minimax-Q learner: soccer_minimax_q_*, the independent Q-learners: soccer_q_learner_*, the
-// policy hill-climbers: soccer_wolf_phc_*, and the populations of one-actor Q-learners: soccer_q_population_* (see
-// soccer_handle.hpp).
+// policy hill-climbers: soccer_wolf_phc_*, the populations of one-actor Q-learners: soccer_q_population_*, and the
+// populations of one-actor policy hill-climbers: soccer_wolf_population_* (see soccer_handle.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -50,6 +51,15 @@ struct soccer_q_population {
     int launch_steps = 4096;            // steps per pop_run_kernel launch (SOCCER_POP_LAUNCH_STEPS)
 };
 
+// A population of policy hill-climbers, a member per lane: the same shape; alpha and dscale live per member in device memory.
+struct soccer_wolf_population {
+    soccer_handle* h = nullptr;
+    PhcPopIO io{};
+    OwnedBufs bufs{"the population of WoLF-PHC learners"};
+    unsigned long long n = 0;           // members = the handle's lanes
+    int launch_steps = 4096;            // steps per phc_pop_run_kernel launch (SOCCER_POP_LAUNCH_STEPS)
+};
+
 void learners_release(soccer_handle* h) {
     for (soccer_minimax_q* q : h->learners) delete q;
     h->learners.clear();
@@ -59,6 +69,8 @@ void learners_release(soccer_handle* h) {
     h->phc_learners.clear();
     for (soccer_q_population* q : h->q_populations) delete q;
     h->q_populations.clear();
+    for (soccer_wolf_population* q : h->wolf_populations) delete q;
+    h->wolf_populations.clear();
 }
 
 // what every entry point checks first
@@ -70,6 +82,8 @@ static int learner_check(soccer_handle* h, soccer_minimax_q* q, const char* what
 }
 
 // a fixed mixed policy's threshold rows, once: SoccerBatch.mixed_policy_thresholds
+// (learner_thresholds(pi, 0.0, ...) of soccer_learner_kernels.hpp is this loop operation for operation: the populations of
+// policy hill-climbers compute a FIXED player's row on the device from its pi row and get these bits — keep the two alike)
 static int fixed_thresholds(soccer_handle* h, const char* name, const double* policy, int nS, std::vector<uint16_t>& rows) {
     rows.resize((size_t)nS * 4);
     for (int s = 0; s < nS; ++s) {
@@ -867,5 +881,309 @@ extern "C" int soccer_q_population_load(soccer_handle* h, soccer_q_population* q
     }
     if (alpha && count) HIP_TRY(h, hipMemcpy(io.alpha + first, alpha, (size_t)count * 8, hipMemcpyHostToDevice));
     if (steps) HIP_TRY(h, hipMemcpy(io.steps, steps, 8, hipMemcpyHostToDevice));
+    return SOCCER_OK;
+}
+
+// =================================================================================================
+// populations of policy hill-climbers, a learner per lane: soccer_wolf_population_*
+// =================================================================================================
+static_assert(kPhcLearn == SOCCER_PHC_LEARN && kPhcUniform == SOCCER_PHC_UNIFORM && kPhcFixed == SOCCER_PHC_FIXED, "the kernels' names of the modes");
+
+static int wpop_check(soccer_handle* h, soccer_wolf_population* q, const char* what) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "%s during graph capture", what);
+    if (!q || std::find(h->wolf_populations.begin(), h->wolf_populations.end(), q) == h->wolf_populations.end())
+        return fail(h, SOCCER_E_INVALID, "%s: not a population of this handle", what);
+    return SOCCER_OK;
+}
+
+static int wpop_range_check(soccer_handle* h, const soccer_wolf_population* q, const char* what, int64_t first, int64_t count) {
+    if (first < 0 || count < 0 || (uint64_t)first > q->n || (uint64_t)count > q->n - (uint64_t)first)
+        return fail(h, SOCCER_E_INVALID, "%s: members %lld .. %lld + %lld are outside the population of %llu", what, (long long)first,
+                    (long long)first, (long long)count, q->n);
+    return SOCCER_OK;
+}
+
+// launch == false (soccer_wolf_population_create): the LDS limit of this handle's run kernel, as launch_act
+template <bool SLIP, bool LUT_LDS>
+static hipError_t launch_wpop_run(soccer_handle* h, const KernelParams& P, const PhcPopIO& io, bool launch) {
+    if (!launch)
+        return h->smem_bytes > 48 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&phc_pop_run_kernel<SLIP, LUT_LDS>),
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_bytes) : hipSuccess;
+    hipLaunchKernelGGL((phc_pop_run_kernel<SLIP, LUT_LDS>), dim3(grid_for(h, P.n)), dim3(kBlock), h->smem_bytes, h->stream, P, io);
+    return hipSuccess;
+}
+
+static hipError_t wpop_run(soccer_handle* h, const KernelParams& P, const PhcPopIO& io, bool launch) {
+    return h->slip ? (h->lut_lds ? launch_wpop_run<true, true>(h, P, io, launch) : launch_wpop_run<true, false>(h, P, io, launch))
+                   : (h->lut_lds ? launch_wpop_run<false, true>(h, P, io, launch) : launch_wpop_run<false, false>(h, P, io, launch));
+}
+
+// rows first_row.. of `members` policies [nS][5] each, held to what fixed_thresholds holds a fixed policy to
+static int wpop_rows_check(soccer_handle* h, const char* what, const char* name, const double* policy, size_t members, int nS, int first_row) {
+    for (size_t m = 0; m < members; ++m)
+        for (int s = first_row; s < nS; ++s) {
+            const double* p = policy + (m * (size_t)nS + (size_t)s) * 5;
+            double sum = 0.0;
+            for (int k = 0; k < 5; ++k) {
+                if (!(p[k] >= 0.0)) return fail(h, SOCCER_E_INVALID, "%s: %s[%zu][%d][%d] is negative or not a number", what, name, m, s, k);
+                sum = sum + p[k];
+            }
+            if (!(std::fabs(sum - 1.0) <= 1e-8 + 1e-5)) return fail(h, SOCCER_E_INVALID, "%s: %s[%zu][%d] does not sum to 1", what, name, m, s);
+        }
+    return SOCCER_OK;
+}
+
+// members per pass through the host staging block of read / load / creation (32 MB at most, one member at least)
+static size_t wpop_chunk(size_t nS) { return std::max<size_t>(1, (size_t(32) << 20) / (nS * kPhcRow * 8)); }
+
+static void launch_adopt(soccer_handle* h, double* dst, int dst_slot, const double* src, size_t src_member, size_t src_row, size_t first,
+                         size_t count, int nS) {
+    if (count)
+        hipLaunchKernelGGL(phc_pop_adopt_kernel, dim3(grid_for(h, (uint64_t)count * (uint64_t)nS)), dim3(kBlock), 0, h->stream, dst, dst_slot, src,
+                           (unsigned long long)src_member, (unsigned long long)src_row, (unsigned long long)first, (unsigned long long)count,
+                           (int32_t)nS);
+}
+
+extern "C" int soccer_wolf_population_create(soccer_handle* h, const soccer_wolf_population_config* cfg, soccer_wolf_population** out) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "soccer_wolf_population_create during graph capture");
+    if (!cfg || !out) return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_create: cfg/out is NULL");
+    *out = nullptr;
+    if (h->P.policy_a != nullptr || h->P.policy_b != nullptr)
+        return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_create needs a two-player handle: neither side may have a fixed policy (soccer_set_policy)");
+    if (!(h->cfg.flags & SOCCER_F_AUTORESET))
+        return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_create needs a handle created with SOCCER_F_AUTORESET");
+    const size_t n = (size_t)h->cfg.n_lanes;
+    const auto unit = [](double x) { return x >= 0.0 && x <= 1.0; };
+    const auto factor = [](double x) { return x > 0.0 && x <= 1.0; };
+    std::vector<double> par[7];         // alpha, decay, explor, discount_factor, delta_win, delta_lose, delta_decay
+    if (int rc = pop_param(h, "discount_factor", "[0, 1)", cfg->discount_factor_per_member, cfg->discount_factor, n,
+                           [](double x) { return x >= 0.0 && x < 1.0; }, par[3])) return rc;
+    if (int rc = pop_param(h, "alpha", "[0, 1]", cfg->alpha_per_member, cfg->alpha, n, unit, par[0])) return rc;
+    if (int rc = pop_param(h, "decay", "(0, 1]", cfg->decay_per_member, cfg->decay, n, factor, par[1])) return rc;
+    if (int rc = pop_param(h, "explor", "[0, 1]", cfg->explor_per_member, cfg->explor, n, unit, par[2])) return rc;
+    if (!(cfg->q_init >= -1.0 && cfg->q_init <= 1.0)) return fail(h, SOCCER_E_INVALID, "q_init must be in [-1, 1]");
+    if (int rc = pop_param(h, "delta_win", "[0, 1]", cfg->delta_win_per_member, cfg->delta_win, n, unit, par[4])) return rc;
+    if (int rc = pop_param(h, "delta_lose", "[0, 1]", cfg->delta_lose_per_member, cfg->delta_lose, n, unit, par[5])) return rc;
+    if (int rc = pop_param(h, "delta_decay", "(0, 1]", cfg->delta_decay_per_member, cfg->delta_decay, n, factor, par[6])) return rc;
+    if (!phc_kind(cfg->act_a) || !phc_kind(cfg->act_b))
+        return fail(h, SOCCER_E_INVALID, "act_a / act_b must be SOCCER_PHC_LEARN, SOCCER_PHC_UNIFORM or SOCCER_PHC_FIXED");
+    const int nS = h->rules.nS;
+    const int32_t kinds[2] = {cfg->act_a, cfg->act_b};
+    const double* shared[2] = {cfg->policy_a, cfg->policy_b};
+    const double* each[2] = {cfg->policy_a_per_member, cfg->policy_b_per_member};
+    static const char* const names[2][2] = {{"policy_a", "policy_a_per_member"}, {"policy_b", "policy_b_per_member"}};
+    for (int p = 0; p < 2; ++p) {
+        if ((kinds[p] == SOCCER_PHC_FIXED) != ((shared[p] != nullptr) != (each[p] != nullptr)) || (shared[p] && each[p]))
+            return fail(h, SOCCER_E_INVALID, "exactly one of %s and %s goes with act_%c == SOCCER_PHC_FIXED, and neither with another mode",
+                        names[p][0], names[p][1], p ? 'b' : 'a');
+        // (row 0 included, as fixed_thresholds checks it; a shared policy is member 0 of one)
+        if (shared[p]) if (int rc = wpop_rows_check(h, "soccer_wolf_population_create", names[p][0], shared[p], 1, nS, 0)) return rc;
+        if (each[p]) if (int rc = wpop_rows_check(h, "soccer_wolf_population_create", names[p][1], each[p], n, nS, 0)) return rc;
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, wpop_run(h, h->P, PhcPopIO{}, false));
+    std::unique_ptr<soccer_wolf_population> owner(new soccer_wolf_population());
+    soccer_wolf_population* q = owner.get();
+    q->h = h; q->n = n;
+    if (const char* e = std::getenv("SOCCER_POP_LAUNCH_STEPS")) {      // (tests: a launch boundary within a short run)
+        const long v = std::atol(e);
+        if (v >= 1 && v <= 4096) q->launch_steps = (int)v;
+    }
+    PhcPopIO& io = q->io;
+    double* dpar[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t per = (size_t)nS * kPhcRow, chunk = std::min(wpop_chunk((size_t)nS), n);
+    OwnedBufs stage_bufs{"the fixed policies of a population"};          // creation's staging block: freed when this call returns
+    double* stage = nullptr;
+    int rc = q->bufs.alloc(h, n * per, &io.tab);               // (a failure frees what was taken: `owner` goes, the handle is as it was)
+    for (int k = 0; k < 7; ++k) if (!rc) rc = q->bufs.alloc(h, n, &dpar[k]);
+    if (!rc) rc = q->bufs.alloc(h, n, &io.dscale);
+    if (!rc) rc = q->bufs.alloc(h, 1, &io.steps);
+    if (!rc && (shared[0] || shared[1] || each[0] || each[1])) rc = stage_bufs.alloc(h, chunk * (size_t)nS * 5, &stage);
+    if (rc) return rc;
+    io.alpha = dpar[0]; io.decay = dpar[1]; io.explor = dpar[2]; io.gamma = dpar[3];
+    io.delta_win = dpar[4]; io.delta_lose = dpar[5]; io.delta_decay = dpar[6];
+    io.misuse = h->d_misuse;
+    io.nS = nS; io.n_steps = 0;
+    io.mode[0] = cfg->act_a; io.mode[1] = cfg->act_b;
+    for (int k = 0; k < 7; ++k) HIP_TRY(h, hipMemcpyAsync(dpar[k], par[k].data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(phc_pop_init_kernel, dim3(grid_for(h, (uint64_t)n * (uint64_t)per)), dim3(kBlock), 0, h->stream, io, (unsigned long long)n, cfg->q_init);
+    for (int p = 0; p < 2; ++p) {
+        const int slot = kPhcPi + p * kPhcPlayer;
+        if (shared[p]) {
+            HIP_TRY(h, hipMemcpyAsync(stage, shared[p], (size_t)nS * 40, hipMemcpyHostToDevice, h->stream));
+            launch_adopt(h, io.tab, slot, stage, 0, 5, 0, n, nS);
+            HIP_TRY(h, hipStreamSynchronize(h->stream));        // the staging block is used again
+        }
+        if (each[p])
+            for (size_t m0 = 0; m0 < n; m0 += chunk) {
+                const size_t m = std::min(chunk, n - m0);
+                HIP_TRY(h, hipMemcpyAsync(stage, each[p] + m0 * (size_t)nS * 5, m * (size_t)nS * 40, hipMemcpyHostToDevice, h->stream));
+                launch_adopt(h, io.tab, slot, stage, (size_t)nS * 5, 5, m0, m, nS);
+                HIP_TRY(h, hipStreamSynchronize(h->stream));
+            }
+    }
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // the vectors are pageable host memory of this call
+    h->wolf_populations.push_back(q);
+    *out = owner.release();
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_wolf_population_destroy(soccer_handle* h, soccer_wolf_population* q) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (!q) return SOCCER_OK;
+    if (int rc = wpop_check(h, q, "soccer_wolf_population_destroy")) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // nothing is freed under a kernel that reads it
+    h->wolf_populations.erase(std::find(h->wolf_populations.begin(), h->wolf_populations.end(), q));
+    delete q;
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_wolf_population_run(soccer_handle* h, soccer_wolf_population* q, int32_t n_steps) {
+    if (int rc = wpop_check(h, q, "soccer_wolf_population_run")) return rc;
+    if (n_steps < 0) return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_run: n_steps must be >= 0");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    // (as soccer_q_population_run: contiguous ticks, a member's whole state in memory between launches)
+    for (int32_t t0 = 0; t0 < n_steps; t0 += q->launch_steps) {
+        KernelParams P = h->P;
+        PhcPopIO io = q->io;
+        io.n_steps = n_steps - t0 < q->launch_steps ? n_steps - t0 : q->launch_steps;
+        bind_tick(h, P, (uint64_t)io.n_steps);
+        HIP_TRY(h, wpop_run(h, P, io, true));
+    }
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_wolf_population_update(soccer_handle* h, soccer_wolf_population* q, const uint16_t* obs, const int8_t* act_a,
+                                             const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs) {
+    if (int rc = wpop_check(h, q, "soccer_wolf_population_update")) return rc;
+    if (!obs || !act_a || !act_b || !reward || !terminated || !next_obs)
+        return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_update: all six transition arrays are required");
+    if (!aligned(obs, 2) || !aligned(next_obs, 2)) return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_update: obs / next_obs must be 2-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipLaunchKernelGGL(phc_pop_update_kernel, dim3(grid_for(h, (uint64_t)q->n)), dim3(kBlock), 0, h->stream, q->io, (long long)q->n,
+                       obs, act_a, act_b, reward, terminated, next_obs);
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+// the slot of a state's row at which each of the six float64 arrays of soccer_wolf_population_state begins
+static const int kWpopSlots[6] = {0, 5, kPhcPi, kPhcPi + kPhcPlayer, kPhcAvg, kPhcAvg + kPhcPlayer};
+
+extern "C" int soccer_wolf_population_read(soccer_handle* h, soccer_wolf_population* q, int64_t first, int64_t count,
+                                           const soccer_wolf_population_state* out) {
+    if (int rc = wpop_check(h, q, "soccer_wolf_population_read")) return rc;
+    if (int rc = wpop_range_check(h, q, "soccer_wolf_population_read", first, count)) return rc;
+    if (!out) return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_read: out is NULL");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const PhcPopIO& io = q->io;
+    const size_t nS = (size_t)io.nS, per = nS * kPhcRow;
+    if (out->alpha && count) HIP_TRY(h, hipMemcpyAsync(out->alpha, io.alpha + first, (size_t)count * 8, hipMemcpyDeviceToHost, h->stream));
+    if (out->dscale && count) HIP_TRY(h, hipMemcpyAsync(out->dscale, io.dscale + first, (size_t)count * 8, hipMemcpyDeviceToHost, h->stream));
+    if (out->steps) HIP_TRY(h, hipMemcpyAsync(out->steps, io.steps, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    double* const rows[6] = {out->Q_a, out->Q_b, out->pi_a, out->pi_b, out->avg_a, out->avg_b};
+    bool any = out->updates != nullptr;
+    for (int i = 0; i < 6; ++i) any |= rows[i] != nullptr;
+    if (any) {
+        // the device keeps a state's values side by side: through a host block, apart again here
+        const size_t chunk = wpop_chunk(nS);
+        std::vector<double> stage;
+        for (size_t m0 = 0; m0 < (size_t)count; m0 += chunk) {
+            const size_t m = std::min(chunk, (size_t)count - m0);
+            stage.resize(m * per);
+            HIP_TRY(h, hipMemcpy(stage.data(), io.tab + ((size_t)first + m0) * per, m * per * 8, hipMemcpyDeviceToHost));
+            for (size_t r = 0; r < m * nS; ++r) {
+                const double* const from = stage.data() + r * kPhcRow;
+                for (int i = 0; i < 6; ++i)
+                    if (rows[i])
+                        for (int k = 0; k < 5; ++k) rows[i][(m0 * nS + r) * 5 + k] = from[kWpopSlots[i] + k];
+                if (out->updates) std::memcpy(&out->updates[m0 * nS + r], from + kPhcUpdates, 8);
+            }
+        }
+    }
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_wolf_population_load(soccer_handle* h, soccer_wolf_population* q, int64_t first, int64_t count,
+                                           const soccer_wolf_population_state* in) {
+    if (int rc = wpop_check(h, q, "soccer_wolf_population_load")) return rc;
+    if (int rc = wpop_range_check(h, q, "soccer_wolf_population_load", first, count)) return rc;
+    if (!in) return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_load: in is NULL");
+    const PhcPopIO& io = q->io;
+    const size_t nS = (size_t)io.nS, per = nS * kPhcRow;
+    // a UNIFORM player keeps its constant rows
+    const bool has[2] = {io.mode[0] != kPhcUniform, io.mode[1] != kPhcUniform};
+    const double* rows[6] = {in->Q_a, in->Q_b, has[0] ? in->pi_a : nullptr, has[1] ? in->pi_b : nullptr,
+                             has[0] ? in->avg_a : nullptr, has[1] ? in->avg_b : nullptr};
+    static const char* const names[6] = {"Q_a", "Q_b", "pi_a", "pi_b", "avg_a", "avg_b"};
+    // everything is checked before anything is written
+    for (int p = 0; p < 2; ++p) {
+        if (!rows[p]) continue;
+        for (size_t i = 0; i < (size_t)count * nS * 5; ++i) {
+            if (i / 5 % nS == 0) continue;                  // row 0 is not read
+            if (!(rows[p][i] >= -1.0 && rows[p][i] <= 1.0))
+                return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_load: %s[%zu][%zu][%zu] is outside [-1, 1]", names[p],
+                            i / 5 / nS, i / 5 % nS, i % 5);
+        }
+    }
+    for (int i = 2; i < 6; ++i)
+        if (rows[i]) if (int rc = wpop_rows_check(h, "soccer_wolf_population_load", names[i], rows[i], (size_t)count, io.nS, 1)) return rc;
+    const double* const scal[2] = {in->alpha, in->dscale};
+    for (int j = 0; j < 2; ++j)
+        if (scal[j])
+            for (size_t i = 0; i < (size_t)count; ++i)
+                if (!(scal[j][i] >= 0.0 && scal[j][i] <= 1.0))
+                    return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_load: %s[%zu] must be in [0, 1]", j ? "dscale" : "alpha", i);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    bool any = in->updates != nullptr;
+    for (int i = 0; i < 6; ++i) any |= rows[i] != nullptr;
+    if (any) {
+        const size_t chunk = wpop_chunk(nS);
+        std::vector<double> stage;
+        for (size_t m0 = 0; m0 < (size_t)count; m0 += chunk) {
+            const size_t m = std::min(chunk, (size_t)count - m0);
+            double* const dev = io.tab + ((size_t)first + m0) * per;
+            stage.resize(m * per);
+            HIP_TRY(h, hipMemcpy(stage.data(), dev, m * per * 8, hipMemcpyDeviceToHost));          // what is not given stays
+            for (size_t r = 0; r < m * nS; ++r) {
+                double* const to = stage.data() + r * kPhcRow;
+                const bool row0 = r % nS == 0;
+                for (int i = 0; i < 6; ++i) {
+                    if (!rows[i]) continue;
+                    if (row0 && i >= 2) continue;           // row 0 of pi and avg stays what creation gave it
+                    for (int k = 0; k < 5; ++k) to[kWpopSlots[i] + k] = row0 ? 0.0 : rows[i][(m0 * nS + r) * 5 + k];
+                }
+                if (in->updates) std::memcpy(to + kPhcUpdates, &in->updates[m0 * nS + r], 8);
+            }
+            HIP_TRY(h, hipMemcpy(dev, stage.data(), m * per * 8, hipMemcpyHostToDevice));
+        }
+    }
+    if (in->alpha && count) HIP_TRY(h, hipMemcpy(io.alpha + first, in->alpha, (size_t)count * 8, hipMemcpyHostToDevice));
+    if (in->dscale && count) HIP_TRY(h, hipMemcpy(io.dscale + first, in->dscale, (size_t)count * 8, hipMemcpyHostToDevice));
+    if (in->steps) HIP_TRY(h, hipMemcpy(io.steps, in->steps, 8, hipMemcpyHostToDevice));
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_wolf_population_adopt(soccer_handle* h, soccer_wolf_population* dst, int32_t dst_player, soccer_wolf_population* src,
+                                            int32_t src_player, int32_t which) {
+    if (int rc = wpop_check(h, dst, "soccer_wolf_population_adopt (dst)")) return rc;
+    if (int rc = wpop_check(h, src, "soccer_wolf_population_adopt (src)")) return rc;
+    if (src == dst) return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_adopt: src and dst are the same population");
+    if ((dst_player != 0 && dst_player != 1) || (src_player != 0 && src_player != 1))
+        return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_adopt: dst_player / src_player must be 0 (player A) or 1 (player B)");
+    if (which != 0 && which != 1) return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_adopt: which must be 0 (pi) or 1 (avg)");
+    if (dst->io.mode[dst_player] != kPhcFixed)
+        return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_adopt: player %c of dst is not SOCCER_PHC_FIXED", dst_player ? 'B' : 'A');
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const size_t nS = (size_t)dst->io.nS;                   // (one handle: the same pitch, the same number of members)
+    launch_adopt(h, dst->io.tab, kPhcPi + dst_player * kPhcPlayer, src->io.tab + (which ? kPhcAvg : kPhcPi) + src_player * kPhcPlayer,
+                 nS * kPhcRow, kPhcRow, 0, (size_t)dst->n, (int)nS);
+    HIP_TRY(h, hipGetLastError());
     return SOCCER_OK;
 }

@@ -494,6 +494,12 @@ class VectorSoccerEnv:
         assert self.multiagent, "wolf_phc needs a two-player environment (no player with a fixed policy)"
         return self._batch.wolf_phc(discount_factor, **params)
 
+    def wolf_population(self, discount_factor, **params):
+        """A WolfPopulation (SoccerBatch.wolf_population): a PHC / WoLF-PHC learner per lane of this env, each with its own
+        tables and policies."""
+        assert self.multiagent, "wolf_population needs a two-player environment (no player with a fixed policy)"
+        return self._batch.wolf_population(discount_factor, **params)
+
     @property
     def reward_int8(self):
         """device io: player A's reward of the last step as the int8 tensor the kernel wrote (-1 / 0 / +1), no cast

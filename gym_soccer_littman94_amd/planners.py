@@ -158,6 +158,31 @@ def wolf_phc(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q
     return r["pi_a"], r["pi_b"], r["avg_a"], r["avg_b"], r["Q_a"], r["Q_b"], r["visits"]
 
 
+def wolf_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
+                    delta_decay=1.0, act_a="learn", act_b="learn", first=0, count=None):
+    """A population of PHC / WoLF-PHC learners on the device, a learner per lane of `env`, each with its own tables,
+    policies and stream of experience: n_steps steps of every member from the lanes' current states (lanes that were never
+    reset are reset first).  The hyperparameters are scalars or arrays of one value per lane; decay None: alpha falls to
+    1 % over the run; act_a / act_b: 'learn', 'uniform', a fixed [nS, 5] policy or [n, nS, 5], one per member.  Returns, for
+    members first .. first + count - 1 (count None: to the end), (pi_a[count, nS, 5], pi_b, avg_a, avg_b, Q_a, Q_b,
+    alpha[count]); Q_b is in player B's own reward."""
+    b = _two_player_batch(env, "wolf_population")
+    n_steps = int(n_steps)
+    assert n_steps >= 0, "n_steps must be >= 0"
+    if decay is None:
+        decay = 0.01 ** (1.0 / max(n_steps, 1))
+    pop = b.wolf_population(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, delta_win=delta_win,
+                            delta_lose=delta_lose, delta_decay=delta_decay, act_a=act_a, act_b=act_b)
+    try:
+        if b.get_state()["needs_reset"].any():
+            (env if hasattr(env, "_batch") else b).reset()
+        pop.run(n_steps)
+        r = pop.read(first, count)
+    finally:
+        pop.close()
+    return r["pi_a"], r["pi_b"], r["avg_a"], r["avg_b"], r["Q_a"], r["Q_b"], r["alpha"]
+
+
 def minimax_value_iteration(env, theta, discount_factor, max_sweeps=1000000):
     """Minimax (Shapley) value iteration of the two-player game on the device, Littman (1994)'s equilibrium values.
     Returns (pi_a[nS, 5], pi_b[nS, 5], V, Q[nS, 5, 5], iterations): player A's maximin and player B's minimax stage-game

@@ -64,7 +64,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_*, soccer_best_response, soccer_evaluate_policies and soccer_rollout_shape were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_*, soccer_wolf_population_*, soccer_best_response, soccer_evaluate_policies and soccer_rollout_shape were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -706,6 +706,99 @@ int soccer_q_population_read(soccer_handle* h, soccer_q_population* q, int64_t f
  * nothing.  read -> load of a range on a fresh population continues bit for bit. */
 int soccer_q_population_load(soccer_handle* h, soccer_q_population* q, int64_t first, int64_t count, const double* Q_a,
                              const double* Q_b, const double* alpha, const uint64_t* steps);
+
+/* ---- learners, a population of policy hill-climbers (two-player handles; a PHC / WoLF-PHC learner per lane)
+ * What the population of Q-learners is to soccer_q_learner, this is to soccer_wolf_phc; nothing new is defined.  On a
+ * two-player SOCCER_F_AUTORESET handle of n lanes the population has n members, and member i is exactly a soccer_wolf_phc
+ * learner whose only actor is lane i, bit for bit: Bowling & Veloso's protocol of one learner, one stream, many trials.
+ * State of member i, float64 unless noted: Q_a, Q_b, pi_a, pi_b, avg_a, avg_b [n_states][5], updates[n_states] (uint64),
+ * alpha_i, dscale_i.  The population has one step counter.  No visits are kept, as in the population of Q-learners.
+ * Row 0 as for soccer_wolf_phc: Q_p[0] = 0 for good, row 0 of pi and avg is never read by a step.
+ * One step of member i is steps 1-6 of "learners, policy hill-climbing" on the single transition of lane i:
+ *   1. a LEARN player draws from the threshold row of (1.0 - explor_i) * pi_p[s][k] + explor_i / 5.0 of ITS pi at the lane's
+ *      observation s; a UNIFORM player from the NULL row table; a FIXED player from the thresholds of its own row pi_p[s]
+ *      with explor 0.0 — the same expression, which for explor 0.0 is the host's threshold computation of a fixed policy
+ *      operation for operation, so the action is the one the host-computed table of soccer_wolf_phc gives, bit for bit
+ *   2. act and step: batched_rollout(n_steps = 1, sample_actions = 1) with that lane's rows
+ *   3.-4. the Q update with one sample c = 1 on the 2^-40 grid, exactly as in the population of Q-learners: Vq_p[s'] is read
+ *      BEFORE the update, no bootstrap when terminated, s' = final_obs so a truncated transition bootstraps from it
+ *   5. updates[s] += 1, n = (double)updates[s]; then the policy step for each LEARN player in the exact operation order of
+ *      "learners, policy hill-climbing" with delta_win_i, delta_lose_i and dscale_i.  ep > ea is strict, so the first touch
+ *      of a state (pi == avg) is a delta_lose step
+ *   6. alpha_i = alpha_i * decay_i, dscale_i = dscale_i * delta_decay_i; the step counter grows by one per step
+ * A lane that still needs its first reset (SOCCER_MISUSE_FROZEN) and a lane whose current observation is 0 contribute
+ * nothing; their member's alpha and dscale still advance.
+ * A FIXED player's policy is PER MEMBER: it lives in that member's pi (= avg) rows, constant under run / update.  Creation
+ * takes one shared [n_states][5] policy (policy_p: copied to every member) or a HOST array [n_lanes][n_states][5]
+ * (policy_p_per_member), exactly one of the two, checked as opponent_policy is; the message names the member and the state.
+ * soccer_wolf_population_adopt writes it on the device from another population.
+ * Hyperparameters: the scalars of soccer_wolf_phc_config for everyone, or — where the pointer is not NULL — HOST arrays of n
+ * values, one per member, for alpha, decay, explor, discount_factor, delta_win, delta_lose and delta_decay (every value in
+ * the scalar's range); q_init is scalar.  The state is a fixed function of (seed, parameters, number of steps): it does not
+ * depend on how run() splits its launches or on the state layout.
+ * Refusals, SOCCER_E_STATE during a capture, the misuse flags and the ownership of the memory are those of the
+ * soccer_q_population_* calls (memory: n * n_states * 256 bytes of rows and 64 bytes of parameters per member;
+ * SOCCER_E_NOMEM leaves the handle usable).  Populations of both kinds and the three shared learners may share a handle. */
+typedef struct soccer_wolf_population soccer_wolf_population;
+typedef struct soccer_wolf_population_config {
+    double  discount_factor;        /* the fields of soccer_wolf_phc_config, in place */
+    double  alpha;
+    double  decay;
+    double  explor;
+    double  q_init;
+    double  delta_win;
+    double  delta_lose;
+    double  delta_decay;
+    int32_t act_a;                  /* SOCCER_PHC_* */
+    int32_t act_b;
+    const double* policy_a;         /* act_a == SOCCER_PHC_FIXED: HOST [n_states][5], shared by every member; else NULL */
+    const double* policy_b;
+    const double* policy_a_per_member;         /* or HOST [n_lanes][n_states][5]: a FIXED player has exactly one of the two */
+    const double* policy_b_per_member;
+    const double* alpha_per_member;            /* HOST [n_lanes] or NULL: `alpha` for everyone */
+    const double* decay_per_member;
+    const double* explor_per_member;
+    const double* discount_factor_per_member;
+    const double* delta_win_per_member;
+    const double* delta_lose_per_member;
+    const double* delta_decay_per_member;
+} soccer_wolf_population_config;
+/* what soccer_wolf_population_read fills and soccer_wolf_population_load takes for `count` members: HOST pointers, any may
+ * be NULL; soccer_wolf_phc_state with a leading dimension and without visits */
+typedef struct soccer_wolf_population_state {
+    double* Q_a; double* Q_b;       /* [count][n_states][5] */
+    double* pi_a; double* pi_b;     /* [count][n_states][5] */
+    double* avg_a; double* avg_b;   /* [count][n_states][5] */
+    uint64_t* updates;              /* [count][n_states] */
+    double* alpha; double* dscale;  /* [count] */
+    uint64_t* steps;                /* one value */
+} soccer_wolf_population_state;
+int soccer_wolf_population_create(soccer_handle* h, const soccer_wolf_population_config* cfg, soccer_wolf_population** out);
+int soccer_wolf_population_destroy(soccer_handle* h, soccer_wolf_population* q);
+/* n_steps steps of every member in ceil(n_steps / K) launches (K = 4096; SOCCER_POP_LAUNCH_STEPS, read at creation, overrides
+ * it as for soccer_q_population_run), enqueued on the handle's stream: no synchronisation, no copy.  Consumes n_steps ticks. */
+int soccer_wolf_population_run(soccer_handle* h, soccer_wolf_population* q, int32_t n_steps);
+/* steps 3-6 on the caller's transitions: DEVICE arrays of n_lanes elements, transition i belongs to member i (reward is
+ * player A's).  A bad transition leaves its member's rows alone (its alpha and dscale still advance) and sets the misuse
+ * flag.  Consumes no tick. */
+int soccer_wolf_population_update(soccer_handle* h, soccer_wolf_population* q, const uint16_t* obs, const int8_t* act_a,
+                                  const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs);
+/* Members first .. first + count - 1 (inside the population, else SOCCER_E_INVALID) into every array `out` points to.
+ * Synchronises. */
+int soccer_wolf_population_read(soccer_handle* h, soccer_wolf_population* q, int64_t first, int64_t count,
+                                const soccer_wolf_population_state* out);
+/* The same range from HOST arrays, any may be NULL (= unchanged): Q_p in [-1, 1] (row 0 is taken as zeros); pi_p / avg_p of a
+ * LEARN or FIXED player with rows 1.. >= 0 and summing to 1 as a fixed policy's must (the message names array, member and
+ * state; row 0 is not read; those of a UNIFORM player are ignored); updates; alpha and dscale in [0, 1]; steps.  Everything is
+ * checked before anything is written: a refused load changes nothing.  read -> load of a range on a fresh population
+ * continues bit for bit. */
+int soccer_wolf_population_load(soccer_handle* h, soccer_wolf_population* q, int64_t first, int64_t count,
+                                const soccer_wolf_population_state* in);
+/* The freeze of the challenger protocol: copies, member by member, on the device and in stream order, src's pi (which = 0) or
+ * avg (which = 1) of src_player (0 = A, 1 = B) into dst's pi AND avg of dst_player.  dst_player must be FIXED in dst, src != dst,
+ * both populations of this handle, else SOCCER_E_INVALID with the reason.  No host copy, no synchronisation. */
+int soccer_wolf_population_adopt(soccer_handle* h, soccer_wolf_population* dst, int32_t dst_player, soccer_wolf_population* src,
+                                 int32_t src_player, int32_t which);
 
 /* HOST output: prob[c*3+k] = slip-combination weight c (0: no slip, 1: B slips, 2: A slips,
  * 3: both; :211-222, evaluated left to right in float64) times outcome probability 1, 0.5, 0.25
