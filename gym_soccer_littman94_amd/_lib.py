@@ -118,6 +118,12 @@ class WolfPopulationState(C.Structure):
                [("steps", C.POINTER(C.c_uint64))]
 
 
+class MinimaxQPopulationConfig(C.Structure):
+    """soccer_minimax_q_population_config"""
+    _fields_ = MinimaxQConfig._fields_ + [(n, C.c_void_p) for n in (
+        "opponent_policy_per_member", "alpha_per_member", "decay_per_member", "explor_per_member", "discount_factor_per_member")]
+
+
 MQ_UNIFORM, MQ_SELF, MQ_FIXED = 0, 1, 2
 QL_GREEDY, QL_UNIFORM, QL_FIXED = 0, 1, 2
 PHC_LEARN, PHC_UNIFORM, PHC_FIXED = 0, 1, 2
@@ -207,6 +213,12 @@ PROTOTYPES = {
     "soccer_wolf_population_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(WolfPopulationState)]),
     "soccer_wolf_population_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(WolfPopulationState)]),
     "soccer_wolf_population_adopt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32]),
+    "soccer_minimax_q_population_create": (C.c_int, [C.c_void_p, C.POINTER(MinimaxQPopulationConfig), C.POINTER(C.c_void_p)]),
+    "soccer_minimax_q_population_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "soccer_minimax_q_population_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "soccer_minimax_q_population_update": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
+    "soccer_minimax_q_population_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64)]),
+    "soccer_minimax_q_population_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64)]),
     "soccer_prob_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 12)]),
     "soccer_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint64)]),
     "soccer_reset_stats": (C.c_int, [C.c_void_p]),

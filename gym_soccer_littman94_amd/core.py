@@ -834,6 +834,166 @@ class WolfPopulation:
             pass
 
 
+def minimax_q_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, opponent="uniform"):
+    """Checks the parameters of a population of minimax-Q learners (AssertionError, before any library call) and returns
+    (soccer_minimax_q_population_config, the arrays it points into).  discount_factor, alpha, decay and explor are scalars
+    for every member or arrays of n, one value per member; opponent: 'uniform', 'self', one fixed [nS, 5] mixed policy for
+    every member, or [n, nS, 5], a fixed policy per member."""
+    ranges = (("discount_factor", discount_factor, lambda x: (0.0 <= x) & (x < 1.0), "[0, 1)"),
+              ("alpha", alpha, lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
+              ("decay", decay, lambda x: (0.0 < x) & (x <= 1.0), "(0, 1]"),
+              ("explor", explor, lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"))
+    scalars, arrays = {}, {}
+    for name, value, ok, rng in ranges:
+        if np.ndim(value) == 0:
+            scalars[name], arrays[name] = float(value), None
+            assert ok(scalars[name]), "%s must be in %s" % (name, rng)
+        else:
+            a = np.ascontiguousarray(value, np.float64)
+            assert a.shape == (int(n),), "a per-member %s must have one value per lane (%d)" % (name, n)
+            assert ok(a).all(), "every per-member %s must be in %s" % (name, rng)
+            scalars[name], arrays[name] = float(a[0]), a
+    q0 = float(q_init)
+    assert -1.0 <= q0 <= 1.0, "q_init must be in [-1, 1]"
+    shared = each = None
+    if isinstance(opponent, str):
+        assert opponent in ("uniform", "self"), "opponent must be 'uniform', 'self', an [nS, 5] or an [n, nS, 5] mixed policy"
+        kind = _lib.MQ_UNIFORM if opponent == "uniform" else _lib.MQ_SELF
+    else:
+        pol = np.ascontiguousarray(opponent, np.float64)
+        assert pol.shape in ((int(nS), 5), (int(n), int(nS), 5)), "a fixed opponent must be [n_states, 5] or [n_lanes, n_states, 5] rows summing to 1"
+        bad = np.argwhere(~((pol >= 0).all(-1) & np.isclose(pol.sum(-1), 1.0)))
+        if bad.size:
+            where = "state %d" % bad[0][0] if pol.ndim == 2 else "member %d, state %d" % tuple(bad[0])
+            raise AssertionError("a fixed opponent must be [n_states, 5] or [n_lanes, n_states, 5] rows >= 0 summing to 1: %s is not" % where)
+        if pol.ndim == 2:
+            shared = pol
+        else:
+            each = pol
+        kind = _lib.MQ_FIXED
+    ptr = lambda x: None if x is None else x.ctypes.data  # noqa: E731
+    cfg = _lib.MinimaxQPopulationConfig(scalars["discount_factor"], scalars["alpha"], scalars["decay"], scalars["explor"], q0, kind, 0,
+                                        ptr(shared), ptr(each), *[ptr(arrays[k]) for k in ("alpha", "decay", "explor", "discount_factor")])
+    return cfg, ((shared, each), arrays)
+
+
+class MinimaxQPopulation:
+    """A population of minimax-Q learners (Littman 1994) on a two-player auto-reset SoccerBatch, a learner per lane: member i
+    has its own Q[nS, 5, 5], V[nS], pi_a / pi_b [nS, 5] and alpha and learns from lane i alone (include/soccer_hip.h, "learners,
+    a population of minimax-Q learners").  run() enqueues and returns; read() and the properties synchronise and copy.  Whole
+    populations run to gigabytes, so read(), load() and exploitability() take a range of members."""
+    _ROWS = ("Q", "V", "pi_a", "pi_b")
+
+    def __init__(self, batch, discount_factor, **params):
+        cfg, keep = minimax_q_population_config(batch.n, batch.nS, discount_factor, **params)
+        self.batch, self.q = batch, None
+        q = C.c_void_p()
+        batch._check(batch.lib.soccer_minimax_q_population_create(batch.h, C.byref(cfg), C.byref(q)))
+        self.discount_factor = np.full(batch.n, cfg.discount_factor) if keep[1]["discount_factor"] is None else keep[1]["discount_factor"].copy()
+        del keep                                   # (create has copied the parameters and the fixed policies' thresholds)
+        self.q = q
+        self.n, self.nS = batch.n, batch.nS
+        self.opponent = cfg.opponent
+        batch._learners.add(self)
+
+    def run(self, n_steps):
+        """n_steps steps of every member (its lane acts, the environment steps, its cell moves and its state is re-solved),
+        enqueued."""
+        b = self.batch
+        b._check(b.lib.soccer_minimax_q_population_run(b.h, self.q, int(n_steps)))
+        return self
+
+    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
+        """One step's update on n transitions, transition i for member i (reward is player A's): DeviceArrays (or device
+        tensors) of n elements, or numpy arrays, which are copied to the device first."""
+        n = self.n
+
+        def call(h, q, count, *ptrs):
+            assert count == n, "a population's update takes one transition per member (%d)" % n
+            return self.batch.lib.soccer_minimax_q_population_update(h, q, *ptrs)
+        _learner_update(self.batch, call, self.q, obs, act_a, act_b, reward, terminated, next_obs)
+        return self
+
+    def _range(self, first, count):
+        first = int(first)
+        count = self.n - first if count is None else int(count)
+        assert 0 <= first <= self.n and 0 <= count <= self.n - first, "members %d .. %d + %d are outside the population of %d" % (first, first, count, self.n)
+        return first, count
+
+    def _read(self, first, count, keys):
+        nS, b = self.nS, self.batch
+        shapes = {"Q": (count, nS, 5, 5), "V": (count, nS), "pi_a": (count, nS, 5), "pi_b": (count, nS, 5), "alpha": (count,)}
+        out = {k: np.zeros(shapes[k]) for k in keys if k != "steps"}
+        st = C.c_uint64()
+        b._check(b.lib.soccer_minimax_q_population_read(b.h, self.q, first, count,
+                                                        *[out[k].ctypes.data if k in out else None for k in self._ROWS + ("alpha",)],
+                                                        C.byref(st) if "steps" in keys else None))
+        if "steps" in keys:
+            out["steps"] = int(st.value)
+        return out
+
+    def read(self, first=0, count=None):
+        """dict for members first .. first + count - 1 (count None: to the end): Q[count, nS, 5, 5], V[count, nS], pi_a / pi_b
+        [count, nS, 5], alpha[count], steps.  Synchronises."""
+        first, count = self._range(first, count)
+        return self._read(first, count, self._ROWS + ("alpha", "steps"))
+
+    alpha = property(lambda self: self._read(0, self.n, ("alpha",))["alpha"], doc="every member's learning rate, [n]")
+    steps = property(lambda self: self._read(0, 0, ("steps",))["steps"])
+
+    def exploitability(self, theta=1e-10, first=0, count=None):
+        """How badly the best possible opponent beats the strategies pi_a and pi_b of each member of a range, at that member's
+        discount: through SoccerBatch.best_response in batches of at most 256 members with one discount.  Returns
+        {"v_a", "v_b", "gap"}, arrays of [count, nS] (planners.exploitability's per member)."""
+        first, count = self._range(first, count)
+        b = self.batch
+        out = {k: np.zeros((count, self.nS)) for k in ("v_a", "v_b", "gap")}
+        for c0 in range(0, count, _lib.BR_MAX_POLICIES):
+            c = min(_lib.BR_MAX_POLICIES, count - c0)
+            r = self._read(first + c0, c, ("pi_a", "pi_b"))
+            gam = self.discount_factor[first + c0:first + c0 + c]
+            for g in np.unique(gam):                # (one solve per discount in the chunk: a batch shares its discount)
+                idx = np.flatnonzero(gam == g)
+                out["v_a"][c0 + idx] = b.best_response(r["pi_a"][idx], 0, theta, float(g))[1]
+                out["v_b"][c0 + idx] = b.best_response(r["pi_b"][idx], 1, theta, float(g))[1]
+        out["gap"] = out["v_b"] - out["v_a"]
+        return out
+
+    def load(self, Q=None, V=None, pi_a=None, pi_b=None, alpha=None, steps=None, first=0):
+        """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged):
+        Q[count, nS, 5, 5] and V[count, nS] in [-1, 1], pi_a / pi_b [count, nS, 5], alpha[count], steps for the population.  Q
+        alone: V and the strategies of every live state of the range are re-solved on the device.  With V, pi_a and pi_b
+        they are stored as given, so with what read() gave a fresh population continues bit for bit.  A refused load changes
+        nothing."""
+        b = self.batch
+        keep = {k: np.ascontiguousarray(x, np.float64) for k, x in zip(self._ROWS + ("alpha",), (Q, V, pi_a, pi_b, alpha)) if x is not None}
+        counts = {x.shape[0] for x in keep.values() if x.ndim >= 1}
+        assert len(counts) <= 1 and all(x.ndim >= 1 for x in keep.values()), "the arrays must hold the same number of members"
+        first, count = self._range(first, counts.pop() if counts else 0)
+        shapes = {"Q": (count, self.nS, 5, 5), "V": (count, self.nS), "pi_a": (count, self.nS, 5), "pi_b": (count, self.nS, 5), "alpha": (count,)}
+        for k, x in keep.items():
+            assert x.shape == shapes[k], "%s must be %s" % (k, list(shapes[k]))
+            if k in ("Q", "V"):
+                assert (np.abs(x[:, 1:]) <= 1.0).all(), "%s must lie in [-1, 1]" % k
+            elif k == "alpha":
+                assert ((x >= 0.0) & (x <= 1.0)).all(), "alpha must be [count] values in [0, 1]"
+        st = None if steps is None else C.byref(C.c_uint64(int(steps)))
+        b._check(b.lib.soccer_minimax_q_population_load(b.h, self.q, first, count,
+                                                        *[keep[k].ctypes.data if k in keep else None for k in self._ROWS + ("alpha",)], st))
+        return self
+
+    def close(self):
+        if self.q and self.batch.h:
+            self.batch.lib.soccer_minimax_q_population_destroy(self.batch.h, self.q)
+        self.q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SoccerBatch:
     """N lanes of the Littman-94 soccer game resident on one GPU.
 
@@ -854,7 +1014,7 @@ class SoccerBatch:
         self.lib = _lib.load()
         self.h = None
         self._arrays = weakref.WeakSet()        # device buffers handed out by alloc(); freed with the handle
-        self._learners = weakref.WeakSet()      # minimax_q(), q_learning(), wolf_phc(), q_population(): their memory goes with the handle
+        self._learners = weakref.WeakSet()      # minimax_q(), q_learning(), wolf_phc() and the populations: their memory goes with the handle
         cfg = Config(n_lanes=int(n_lanes), width=int(width), height=int(height),
                      slip_prob=float(slip_prob), max_steps=int(max_steps), device=int(device),
                      seed=int(seed) & 0xFFFFFFFFFFFFFFFF, lane_offset=int(lane_offset),
@@ -1136,6 +1296,12 @@ class SoccerBatch:
         'uniform', a fixed [nS, 5] mixed policy for every member or [n, nS, 5], one per member."""
         return WolfPopulation(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, delta_win=delta_win,
                               delta_lose=delta_lose, delta_decay=delta_decay, act_a=act_a, act_b=act_b)
+
+    def minimax_q_population(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, opponent="uniform"):
+        """A MinimaxQPopulation on this batch (two players, autoreset=True): a minimax-Q learner per lane, each with its own
+        Q, V and strategies.  discount_factor, alpha, decay and explor are scalars or arrays of one value per lane; opponent:
+        'uniform', 'self', a fixed [nS, 5] mixed policy for every member or [n, nS, 5], one per member."""
+        return MinimaxQPopulation(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, opponent=opponent)
 
     # -- hot path -------------------------------------------------------------------------------
     def reset(self, mask=None, u_reset=None, obs=None):

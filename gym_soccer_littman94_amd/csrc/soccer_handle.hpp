@@ -5,7 +5,7 @@
 //   soccer_step.hip      batched_step*
 //   soccer_rollout.hip   batched_rollout*
 //   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, the matrix-game solver
-//   soccer_learners.hip  the minimax-Q learner, the independent Q-learners, the policy hill-climbers, the populations of Q-learners
+//   soccer_learners.hip  the minimax-Q learner, the independent Q-learners, the policy hill-climbers, the three kinds of populations
 //   soccer_comm.hip      the RCCL wrapper (host code only)
 //
 // Every unit carries its own code object: a kernel is instantiated, launched and given its attributes (hipFuncSetAttribute)
@@ -197,6 +197,7 @@ struct soccer_handle {
     std::vector<soccer_wolf_phc*> phc_learners; // soccer_wolf_phc_create: the same for the policy hill-climbers
     std::vector<soccer_q_population*> q_populations; // soccer_q_population_create: the same for the populations of Q-learners
     std::vector<soccer_wolf_population*> wolf_populations; // soccer_wolf_population_create: the same for the populations of hill-climbers
+    std::vector<soccer_minimax_q_population*> mq_populations; // soccer_minimax_q_population_create: the same for the populations of minimax-Q learners
     std::string err;
 
     soccer_handle() = default;

@@ -3,7 +3,9 @@
 // q_update_kernel, q_init_kernel (they share the act-and-step body, the reduce body and learner_thresholds); and the policy
 // hill-climbers on top of those: phc_act_kernel, phc_reduce_kernel, phc_update_kernel, phc_init_kernel; and the population
 // of one-actor Q-learners, a learner per lane: pop_run_kernel, pop_update_kernel, pop_init_kernel; and the population of
-// one-actor policy hill-climbers: phc_pop_run_kernel, phc_pop_update_kernel, phc_pop_init_kernel, phc_pop_adopt_kernel (at the end).
+// one-actor policy hill-climbers: phc_pop_run_kernel, phc_pop_update_kernel, phc_pop_init_kernel, phc_pop_adopt_kernel; and the
+// population of one-actor minimax-Q learners, a wave per member: mq_pop_run_kernel, mq_pop_update_kernel, mq_pop_solve_kernel,
+// mq_pop_init_kernel (at the end).
 // Included by soccer_learners.hip only: every kernel is emitted by exactly one translation unit.
 //
 // One learner step (include/soccer_hip.h, "learners") is two launches in stream order, no grid barrier between them:
@@ -937,6 +939,225 @@ __global__ __launch_bounds__(kBlock) void phc_pop_adopt_kernel(double* dst, int 
 #pragma unroll
         for (int k = 0; k < 5; ++k) { const double v = from[k]; to[k] = v; to[(kPhcAvg - kPhcPi) + k] = v; }
     }
+}
+
+// =================================================================================================
+// a population of minimax-Q learners, a learner per lane (include/soccer_hip.h, "learners, a population of minimax-Q learners")
+// =================================================================================================
+// Member i is a soccer_minimax_q learner whose only actor is lane i.  Unlike the two populations above a member is NOT a
+// thread: every learning step ends in solve_game5, whose GameWork (748 B, indexed at run time) has to live in LDS and whose
+// pivoting would diverge across the members of a wave.  A member is a WAVE, one wave per workgroup: learner_update_kernel's
+// shape (lanes 0..24 own the 25 cells, lane 0 solves from the wave's LDS slot), made persistent over the launch's steps.
+// Table layout: member i's block is [nS][36] float64, one 288-byte, 16-byte aligned row per state:
+//     0..24 Q[a * 5 + b]   25 V   26..30 pi_a   31..35 pi_b
+// so a state's row is one coalesced load by lanes 0..35 (lanes 36..63 mirror slot 35 and never store), and a member's block
+// is contiguous.  The wave holds the row at s in registers, one value per lane, as pop_run_kernel carries its row: it is the
+// previous step's s' row while the episode goes on, already the updated and re-solved row when s' == s, loaded afresh only
+// after a reset.  Everything that moved is stored straight away, so memory always holds what the registers hold and a launch
+// boundary changes nothing.
+// The environment step runs redundantly on all 64 lanes from wave-uniform inputs (the lane's state, the Philox words, the
+// strategies broadcast with v_readlane) through lane_words / draw_from_word / lane_step / learner_thresholds, the functions
+// every other learner calls; what decides a branch goes through v_readfirstlane, so the branches are scalar.  Lane 0 alone
+// stores the lane state and feeds HistAcc.  The rule tables are read from global memory (the step kernel's placement): a
+// workgroup of one wave that staged them to LDS would stage them once per member.
+// Synchronisation: lanes exchange the Q row and the solver's answer through LDS inside the step loop.  With ONE wave per
+// workgroup __syncthreads() is a wave-level barrier and cannot tie the loops of different members together; do not raise
+// kMqBlock without replacing it.
+constexpr int kMqBlock = 64;                        // one wave
+constexpr int kMqRow = 36;                          // float64 slots per state
+constexpr int kMqV = 25, kMqPiA = 26, kMqPiB = 31;
+constexpr int kMqUniform = 0, kMqSelf = 1, kMqFixed = 2;   // = SOCCER_MQ_* (soccer_learners.hip asserts it)
+
+struct MqPopIO {
+    double* tab;                        // [n][nS][36]
+    double* alpha;                      // [n] every member's learning rate
+    const double* decay;                // [n]
+    const double* explor;               // [n]
+    const double* gamma;                // [n]
+    const uint16_t* mix_b;              // SOCCER_MQ_FIXED: host-computed thresholds [nS][4] (mix_member = 0) or [n][nS][4]; else nullptr
+    unsigned long long mix_member;      // uint16 elements between two members' threshold tables
+    unsigned long long* steps;
+    unsigned int* misuse;               // the handle's sticky words
+    int32_t nS;
+    int32_t n_steps;                    // mq_pop_run_kernel: steps of this launch
+    int32_t opponent;                   // SOCCER_MQ_*
+};
+
+// the wave's LDS slot: the stage game, the solver's answer (V, pi_a, pi_b: slots 25..35 of the row) and its work memory
+struct MqPopWork {
+    double Q[25];
+    double out[kMqRow - kMqV];
+    GameWork w;
+};
+
+// slot `src` (a constant) of the row the wave holds, in every lane: two v_readlane, the result is wave-uniform
+__device__ __forceinline__ double mq_row_slot(double val, int src) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(val), src), hi = __builtin_amdgcn_readlane(__double2hiint(val), src);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ uint32_t mq_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// the action the 15-bit draw h takes from the strategy in slots first..first + 4 of the row, mixed with explor
+__device__ __forceinline__ uint32_t mq_pop_draw(double val, int first, double explor, uint32_t h) {
+    double pi[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) pi[k] = mq_row_slot(val, first + k);
+    __attribute__((aligned(8))) uint16_t t[4];
+    learner_thresholds(pi, explor, t);
+    const uint2 th = *reinterpret_cast<const uint2*>(t);
+    return (h >= (th.x & 0xffffu)) + (h >= (th.x >> 16)) + (h >= (th.y & 0xffffu)) + (h >= (th.y >> 16));
+}
+
+// step 5 for the state whose row the wave holds in `val` (`at` = that row in memory): lanes 0..24 hand Q[s] to lane 0, lane 0
+// solves, lanes 25..35 take V, pi_a, pi_b into the row and store them.  Every lane of the wave calls it.
+__device__ __forceinline__ void mq_pop_solve(double* at, double& val, int lane, MqPopWork* W) {
+    if (lane < kMqV) W->Q[lane] = val;
+    __syncthreads();
+    if (lane == 0) {
+        double v = 0.0, x[5], y[5];
+        solve_game5(W->Q, &W->w, &v, x, y);
+        W->out[0] = v;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { W->out[kMqPiA - kMqV + k] = x[k]; W->out[kMqPiB - kMqV + k] = y[k]; }
+    }
+    __syncthreads();
+    if (lane >= kMqV && lane < kMqRow) { val = W->out[lane - kMqV]; at[lane] = val; }
+}
+
+// steps 3-5 of one member on its one transition (s live, a / b in 0..4; all arguments wave-uniform but val and lane): v_next =
+// V[s'] as it was BEFORE this update.  c = 1, so the mean target is the sample's own, on the learners' grid.
+__device__ __forceinline__ void mq_pop_learn(double* at, double& val, double v_next, uint32_t a, uint32_t b, int32_t r, uint32_t term,
+                                             double alpha, double gamma, int lane, MqPopWork* W) {
+    const long long SV = term ? 0ll : (long long)rint(v_next * kVqScale);
+    const double m = (double)r + gamma * ((double)SV * kVqInv);
+    if ((uint32_t)lane == a * 5u + b) { val = val + alpha * (m - val); at[lane] = val; }
+    mq_pop_solve(at, val, lane, W);
+}
+
+template <bool SLIP>
+__global__ __launch_bounds__(kMqBlock) void mq_pop_run_kernel(const KernelParams P, const MqPopIO L) {
+    __shared__ MqPopWork W;
+    HistAcc<false> hist; hist.init(P);
+    Tables T; T.lut = P.lut; T.nc = P.next_cell; T.isd = P.isd;
+    const int lane = (int)threadIdx.x;
+    const int slot = lane < kMqRow ? lane : kMqRow - 1;
+    const unsigned long long tick0 = *P.tick_in;
+    publish_tick(P, tick0, (unsigned long long)L.n_steps);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps += (unsigned long long)L.n_steps;
+    bool any_frozen = false;
+    for (unsigned long long g = blockIdx.x; g < P.n; g += gridDim.x) {      // a wave serves members g, g + gridDim.x, ... in turn
+        const unsigned long long i0 = P.first + g;                  // the lane, and the member
+        LaneVec<1> S; S.load(P, i0);
+        double* const tab = L.tab + (size_t)i0 * (size_t)L.nS * kMqRow;
+        const uint16_t* const mix = L.mix_b ? L.mix_b + (size_t)i0 * (size_t)L.mix_member : nullptr;
+        double alpha = L.alpha[i0];
+        const double decay = L.decay[i0], explor = L.explor[i0], gamma = L.gamma[i0];
+        uint32_t s = mq_uniform(obs_of(T, P, S.L[0].A, S.L[0].B, S.L[0].p));
+        double val = tab[(size_t)s * kMqRow + slot];
+        int32_t ret = 0; uint32_t eps = 0u, nonzero = 0u;
+        for (int t = 0; t < L.n_steps; ++t) {
+            const unsigned long long tick = tick0 + (unsigned long long)t;
+            uint32_t words[1], awords[1];
+            lane_words<1>(P, P.lane_offset + i0, block_tick<SLIP>(tick), 0u, words);
+            lane_words<1>(P, P.lane_offset + i0, tick, 1u, awords);
+            const Draw d = draw_from_word<SLIP>(words[0], tick);
+            // two actions from one 32-bit word, 15 bits each (rollout_group)
+            const uint32_t ha = awords[0] & 0x7fffu, hb = (awords[0] >> 16) & 0x7fffu;
+            const uint32_t a = mq_uniform(mq_pop_draw(val, kMqPiA, explor, ha));
+            uint32_t b;
+            if (L.opponent == kMqUniform) {                         // wave-uniform
+                b = (hb * 5u) >> 15;
+            } else if (L.opponent == kMqSelf) {
+                b = mq_pop_draw(val, kMqPiB, explor, hb);
+            } else {
+                const uint2 th = *reinterpret_cast<const uint2*>(mix + 4u * s);
+                b = (hb >= (th.x & 0xffffu)) + (hb >= (th.x >> 16)) + (hb >= (th.y & 0xffffu)) + (hb >= (th.y >> 16));
+            }
+            b = mq_uniform(b);
+            StepResult R;
+            const bool frozen = mq_uniform(lane_step<SLIP, true>(T, P, S.L[0], a, b, d, R) ? 1u : 0u) != 0u;
+            ret += R.reward; eps += R.finished; nonzero += (uint32_t)R.reward & 1u;
+            any_frozen |= frozen;
+            // (a lane parked in a goal tuple by soccer_set_state has s = 0: never a current state)
+            const bool learn = !frozen && s != 0u;
+            const uint32_t s2 = mq_uniform(R.final_obs), sn = mq_uniform(R.obs);
+            double nxt = 0.0;
+            if (learn) {
+                nxt = tab[(size_t)s2 * kMqRow + slot];              // before the stores below: s' may be s
+                mq_pop_learn(tab + (size_t)s * kMqRow, val, mq_row_slot(nxt, kMqV), a, b, (int32_t)mq_uniform((uint32_t)R.reward),
+                             mq_uniform(R.term), alpha, gamma, lane, &W);
+            }
+            if (learn && sn == s2) {                                // the episode goes on: the row at s' is the next row at s
+                if (s2 != s) val = nxt;                             // (s' == s: val already holds what the update and the solve wrote)
+            } else if (sn != s) {
+                val = tab[(size_t)sn * kMqRow + slot];              // after a reset
+            }
+            s = sn;
+            alpha = alpha * decay;
+        }
+        if (lane == 0) {
+            S.store(P, i0);
+            L.alpha[i0] = alpha;
+            hist.add_totals(eps, ret, nonzero);
+        }
+    }
+    if (any_frozen && lane == 0) P.misuse[0] = 1u;
+    hist.flush(P);
+}
+
+// soccer_minimax_q_population_update: steps 3-6 on the caller's transitions, transition i for member i, a wave per member
+__global__ __launch_bounds__(kMqBlock) void mq_pop_update_kernel(const MqPopIO L, long long n, const uint16_t* obs, const int8_t* act_a,
+                                                                 const int8_t* act_b, const int8_t* reward, const uint8_t* terminated,
+                                                                 const uint16_t* next_obs) {
+    __shared__ MqPopWork W;
+    const int lane = (int)threadIdx.x;
+    const int slot = lane < kMqRow ? lane : kMqRow - 1;
+    bool bad_act = false, bad_obs = false;
+    for (long long i = blockIdx.x; i < n; i += gridDim.x) {
+        const uint32_t s = mq_uniform(obs[i]), s2 = mq_uniform(next_obs[i]);
+        const uint32_t a = mq_uniform((uint8_t)act_a[i]), b = mq_uniform((uint8_t)act_b[i]);
+        const bool ba = a > 4u || b > 4u, bo = s == 0u || s >= (uint32_t)L.nS || s2 >= (uint32_t)L.nS;
+        bad_act |= ba; bad_obs |= bo;
+        const double alpha = L.alpha[i];
+        if (!ba && !bo) {
+            double* const tab = L.tab + (size_t)i * (size_t)L.nS * kMqRow;
+            double* const at = tab + (size_t)s * kMqRow;
+            double val = at[slot];
+            const double v_next = tab[(size_t)s2 * kMqRow + kMqV];
+            mq_pop_learn(at, val, v_next, a, b, (int32_t)mq_uniform((uint32_t)(int32_t)reward[i]), terminated[i] != 0u ? 1u : 0u, alpha,
+                         L.gamma[i], lane, &W);
+        }
+        if (lane == 0) L.alpha[i] = alpha * L.decay[i];
+    }
+    if (lane == 0) {
+        if (bad_act) L.misuse[1] = 1u;
+        if (bad_obs) L.misuse[2] = 1u;
+        if (blockIdx.x == 0) *L.steps += 1ull;
+    }
+}
+
+// soccer_minimax_q_population_load with Q alone: every live state of members first .. first + count - 1 is re-solved (MODE 2
+// of learner_update_kernel), a wave per state
+__global__ __launch_bounds__(kMqBlock) void mq_pop_solve_kernel(const MqPopIO L, unsigned long long first, unsigned long long count) {
+    __shared__ MqPopWork W;
+    const int lane = (int)threadIdx.x;
+    const int slot = lane < kMqRow ? lane : kMqRow - 1;
+    const unsigned long long live = (unsigned long long)L.nS - 1ull, rows = count * live;
+    for (unsigned long long c = blockIdx.x; c < rows; c += gridDim.x) {
+        const unsigned long long m = c / live, s = 1ull + c % live;
+        double* const at = L.tab + ((first + m) * (unsigned long long)L.nS + s) * kMqRow;
+        double val = at[slot];
+        mq_pop_solve(at, val, lane, &W);
+    }
+}
+
+// creation: every member's Q = V = q_init on the live states and zero in row 0, uniform strategies (set, not solved)
+__global__ __launch_bounds__(kBlock) void mq_pop_init_kernel(const MqPopIO L, unsigned long long n, double q_init) {
+    const unsigned long long per = (unsigned long long)L.nS * kMqRow, cells = n * per;
+    for (unsigned long long c = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; c < cells; c += (unsigned long long)gridDim.x * kBlock)
+        L.tab[c] = (unsigned)(c % kMqRow) <= (unsigned)kMqV ? ((c % per) < (unsigned long long)kMqRow ? 0.0 : q_init) : 0.2;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps = 0ull;
 }
 
 }  // namespace soccer

@@ -1,6 +1,7 @@
 // soccer_learners.hip — the minimax-Q learner: soccer_minimax_q_*, the independent Q-learners: soccer_q_learner_*, the
-// policy hill-climbers: soccer_wolf_phc_*, the populations of one-actor Q-learners: soccer_q_population_*, and the
-// populations of one-actor policy hill-climbers: soccer_wolf_population_* (see soccer_handle.hpp).
+// policy hill-climbers: soccer_wolf_phc_*, the populations of one-actor Q-learners: soccer_q_population_*, the populations of
+// one-actor policy hill-climbers: soccer_wolf_population_*, and the populations of one-actor minimax-Q learners:
+// soccer_minimax_q_population_* (see soccer_handle.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,6 +61,16 @@ struct soccer_wolf_population {
     int launch_steps = 4096;            // steps per phc_pop_run_kernel launch (SOCCER_POP_LAUNCH_STEPS)
 };
 
+// A population of minimax-Q learners, a member per lane: the same shape; a member is a wave of mq_pop_run_kernel.
+struct soccer_minimax_q_population {
+    soccer_handle* h = nullptr;
+    MqPopIO io{};
+    OwnedBufs bufs{"the population of minimax-Q learners"};
+    unsigned long long n = 0;           // members = the handle's lanes
+    int launch_steps = 4096;            // steps per mq_pop_run_kernel launch (SOCCER_POP_LAUNCH_STEPS)
+    unsigned waves = 1;                 // workgroups (of one wave) per launch at most: one episode-histogram slot each
+};
+
 void learners_release(soccer_handle* h) {
     for (soccer_minimax_q* q : h->learners) delete q;
     h->learners.clear();
@@ -71,6 +82,8 @@ void learners_release(soccer_handle* h) {
     h->q_populations.clear();
     for (soccer_wolf_population* q : h->wolf_populations) delete q;
     h->wolf_populations.clear();
+    for (soccer_minimax_q_population* q : h->mq_populations) delete q;
+    h->mq_populations.clear();
 }
 
 // what every entry point checks first
@@ -1185,5 +1198,240 @@ extern "C" int soccer_wolf_population_adopt(soccer_handle* h, soccer_wolf_popula
     launch_adopt(h, dst->io.tab, kPhcPi + dst_player * kPhcPlayer, src->io.tab + (which ? kPhcAvg : kPhcPi) + src_player * kPhcPlayer,
                  nS * kPhcRow, kPhcRow, 0, (size_t)dst->n, (int)nS);
     HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+// =================================================================================================
+// populations of minimax-Q learners, a learner per lane: soccer_minimax_q_population_*
+// =================================================================================================
+static_assert(kMqUniform == SOCCER_MQ_UNIFORM && kMqSelf == SOCCER_MQ_SELF && kMqFixed == SOCCER_MQ_FIXED, "the kernels' names of the modes");
+
+static int mqpop_check(soccer_handle* h, soccer_minimax_q_population* q, const char* what) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "%s during graph capture", what);
+    if (!q || std::find(h->mq_populations.begin(), h->mq_populations.end(), q) == h->mq_populations.end())
+        return fail(h, SOCCER_E_INVALID, "%s: not a population of this handle", what);
+    return SOCCER_OK;
+}
+
+static int mqpop_range_check(soccer_handle* h, const soccer_minimax_q_population* q, const char* what, int64_t first, int64_t count) {
+    if (first < 0 || count < 0 || (uint64_t)first > q->n || (uint64_t)count > q->n - (uint64_t)first)
+        return fail(h, SOCCER_E_INVALID, "%s: members %lld .. %lld + %lld are outside the population of %llu", what, (long long)first,
+                    (long long)first, (long long)count, q->n);
+    return SOCCER_OK;
+}
+
+// workgroups of one wave for `items` members (or states): never more than the population's histogram slots allow
+static unsigned mqpop_grid(const soccer_minimax_q_population* q, uint64_t items) {
+    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(items, q->waves));
+}
+
+// members per pass through the host staging block of read / load (32 MB at most, one member at least)
+static size_t mqpop_chunk(size_t nS) { return std::max<size_t>(1, (size_t(32) << 20) / (nS * kMqRow * 8)); }
+
+extern "C" int soccer_minimax_q_population_create(soccer_handle* h, const soccer_minimax_q_population_config* cfg,
+                                                  soccer_minimax_q_population** out) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "soccer_minimax_q_population_create during graph capture");
+    if (!cfg || !out) return fail(h, SOCCER_E_INVALID, "soccer_minimax_q_population_create: cfg/out is NULL");
+    *out = nullptr;
+    if (h->P.policy_a != nullptr || h->P.policy_b != nullptr)
+        return fail(h, SOCCER_E_INVALID, "soccer_minimax_q_population_create needs a two-player handle: neither side may have a fixed policy (soccer_set_policy)");
+    if (!(h->cfg.flags & SOCCER_F_AUTORESET))
+        return fail(h, SOCCER_E_INVALID, "soccer_minimax_q_population_create needs a handle created with SOCCER_F_AUTORESET");
+    const size_t n = (size_t)h->cfg.n_lanes;
+    std::vector<double> par[4];         // alpha, decay, explor, discount_factor
+    if (int rc = pop_param(h, "discount_factor", "[0, 1)", cfg->discount_factor_per_member, cfg->discount_factor, n,
+                           [](double x) { return x >= 0.0 && x < 1.0; }, par[3])) return rc;
+    if (int rc = pop_param(h, "alpha", "[0, 1]", cfg->alpha_per_member, cfg->alpha, n, [](double x) { return x >= 0.0 && x <= 1.0; }, par[0])) return rc;
+    if (int rc = pop_param(h, "decay", "(0, 1]", cfg->decay_per_member, cfg->decay, n, [](double x) { return x > 0.0 && x <= 1.0; }, par[1])) return rc;
+    if (int rc = pop_param(h, "explor", "[0, 1]", cfg->explor_per_member, cfg->explor, n, [](double x) { return x >= 0.0 && x <= 1.0; }, par[2])) return rc;
+    if (!(cfg->q_init >= -1.0 && cfg->q_init <= 1.0)) return fail(h, SOCCER_E_INVALID, "q_init must be in [-1, 1]");
+    if (cfg->opponent != SOCCER_MQ_UNIFORM && cfg->opponent != SOCCER_MQ_SELF && cfg->opponent != SOCCER_MQ_FIXED)
+        return fail(h, SOCCER_E_INVALID, "opponent must be SOCCER_MQ_UNIFORM, SOCCER_MQ_SELF or SOCCER_MQ_FIXED");
+    const double* const shared = cfg->opponent_policy;
+    const double* const each = cfg->opponent_policy_per_member;
+    if ((cfg->opponent == SOCCER_MQ_FIXED) != ((shared != nullptr) != (each != nullptr)) || (shared && each))
+        return fail(h, SOCCER_E_INVALID, "exactly one of opponent_policy and opponent_policy_per_member goes with opponent == SOCCER_MQ_FIXED, and neither with another mode");
+    const int nS = h->rules.nS;
+    // (row 0 included, as fixed_thresholds checks it; a shared policy is member 0 of one)
+    if (shared) if (int rc = wpop_rows_check(h, "soccer_minimax_q_population_create", "opponent_policy", shared, 1, nS, 0)) return rc;
+    if (each) if (int rc = wpop_rows_check(h, "soccer_minimax_q_population_create", "opponent_policy_per_member", each, n, nS, 0)) return rc;
+    std::vector<uint16_t> fixed, one;
+    const size_t fixed_members = shared ? 1 : (each ? n : 0);
+    for (size_t m = 0; m < fixed_members; ++m) {
+        if (int rc = fixed_thresholds(h, "opponent_policy", (shared ? shared : each) + m * (size_t)nS * 5, nS, one)) return rc;
+        fixed.insert(fixed.end(), one.begin(), one.end());
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    std::unique_ptr<soccer_minimax_q_population> owner(new soccer_minimax_q_population());
+    soccer_minimax_q_population* q = owner.get();
+    q->h = h; q->n = n;
+    if (const char* e = std::getenv("SOCCER_POP_LAUNCH_STEPS")) {      // (tests: a launch boundary within a short run)
+        const long v = std::atol(e);
+        if (v >= 1 && v <= 4096) q->launch_steps = (int)v;
+    }
+    // a workgroup is one wave and owns one histogram slot: as many as the capped grids of the other kernels have waves
+    q->waves = (unsigned)std::min<uint64_t>((uint64_t)h->grid_cap * (kBlock / 64), h->hist_slots);
+    if (const char* e = std::getenv("SOCCER_MQ_POP_WAVES")) {          // (tests: a wave that serves several members in turn)
+        const long v = std::atol(e);
+        if (v >= 1 && (unsigned long)v <= q->waves) q->waves = (unsigned)v;
+    }
+    MqPopIO& io = q->io;
+    double* dpar[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint16_t* dmix = nullptr;
+    const size_t per = (size_t)nS * kMqRow;
+    int rc = q->bufs.alloc(h, n * per, &io.tab);               // (a failure frees what was taken: `owner` goes, the handle is as it was)
+    for (int k = 0; k < 4; ++k) if (!rc) rc = q->bufs.alloc(h, n, &dpar[k]);
+    if (!rc && !fixed.empty()) rc = q->bufs.alloc(h, fixed.size(), &dmix);
+    if (!rc) rc = q->bufs.alloc(h, 1, &io.steps);
+    if (rc) return rc;
+    io.alpha = dpar[0]; io.decay = dpar[1]; io.explor = dpar[2]; io.gamma = dpar[3];
+    io.mix_b = dmix; io.mix_member = each ? (unsigned long long)nS * 4ull : 0ull;
+    io.misuse = h->d_misuse;
+    io.nS = nS; io.n_steps = 0; io.opponent = cfg->opponent;
+    for (int k = 0; k < 4; ++k) HIP_TRY(h, hipMemcpyAsync(dpar[k], par[k].data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (dmix) HIP_TRY(h, hipMemcpyAsync(dmix, fixed.data(), fixed.size() * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(mq_pop_init_kernel, dim3(grid_for(h, (uint64_t)n * (uint64_t)per)), dim3(kBlock), 0, h->stream, io, (unsigned long long)n, cfg->q_init);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // the vectors are pageable host memory of this call
+    h->mq_populations.push_back(q);
+    *out = owner.release();
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_minimax_q_population_destroy(soccer_handle* h, soccer_minimax_q_population* q) {
+    if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
+    if (!q) return SOCCER_OK;
+    if (int rc = mqpop_check(h, q, "soccer_minimax_q_population_destroy")) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // nothing is freed under a kernel that reads it
+    h->mq_populations.erase(std::find(h->mq_populations.begin(), h->mq_populations.end(), q));
+    delete q;
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_minimax_q_population_run(soccer_handle* h, soccer_minimax_q_population* q, int32_t n_steps) {
+    if (int rc = mqpop_check(h, q, "soccer_minimax_q_population_run")) return rc;
+    if (n_steps < 0) return fail(h, SOCCER_E_INVALID, "soccer_minimax_q_population_run: n_steps must be >= 0");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    // (as soccer_q_population_run: contiguous ticks, a member's whole state in memory between launches)
+    for (int32_t t0 = 0; t0 < n_steps; t0 += q->launch_steps) {
+        KernelParams P = h->P;
+        MqPopIO io = q->io;
+        io.n_steps = n_steps - t0 < q->launch_steps ? n_steps - t0 : q->launch_steps;
+        bind_tick(h, P, (uint64_t)io.n_steps);
+        const dim3 grid(mqpop_grid(q, P.n));
+        if (h->slip) hipLaunchKernelGGL(mq_pop_run_kernel<true>, grid, dim3(kMqBlock), 0, h->stream, P, io);
+        else hipLaunchKernelGGL(mq_pop_run_kernel<false>, grid, dim3(kMqBlock), 0, h->stream, P, io);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_minimax_q_population_update(soccer_handle* h, soccer_minimax_q_population* q, const uint16_t* obs, const int8_t* act_a,
+                                                  const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs) {
+    if (int rc = mqpop_check(h, q, "soccer_minimax_q_population_update")) return rc;
+    if (!obs || !act_a || !act_b || !reward || !terminated || !next_obs)
+        return fail(h, SOCCER_E_INVALID, "soccer_minimax_q_population_update: all six transition arrays are required");
+    if (!aligned(obs, 2) || !aligned(next_obs, 2)) return fail(h, SOCCER_E_INVALID, "soccer_minimax_q_population_update: obs / next_obs must be 2-byte aligned");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    hipLaunchKernelGGL(mq_pop_update_kernel, dim3(mqpop_grid(q, q->n)), dim3(kMqBlock), 0, h->stream, q->io, (long long)q->n,
+                       obs, act_a, act_b, reward, terminated, next_obs);
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+// the slot of a state's row at which each of the four arrays begins, and how many values it has there
+static const int kMqSlots[4] = {0, kMqV, kMqPiA, kMqPiB};
+static const int kMqWidth[4] = {25, 1, 5, 5};
+
+extern "C" int soccer_minimax_q_population_read(soccer_handle* h, soccer_minimax_q_population* q, int64_t first, int64_t count, double* Q,
+                                                double* V, double* pi_a, double* pi_b, double* alpha, uint64_t* steps) {
+    if (int rc = mqpop_check(h, q, "soccer_minimax_q_population_read")) return rc;
+    if (int rc = mqpop_range_check(h, q, "soccer_minimax_q_population_read", first, count)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const MqPopIO& io = q->io;
+    const size_t nS = (size_t)io.nS, per = nS * kMqRow;
+    if (alpha && count) HIP_TRY(h, hipMemcpyAsync(alpha, io.alpha + first, (size_t)count * 8, hipMemcpyDeviceToHost, h->stream));
+    if (steps) HIP_TRY(h, hipMemcpyAsync(steps, io.steps, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    double* const rows[4] = {Q, V, pi_a, pi_b};
+    if (Q || V || pi_a || pi_b) {
+        // the device keeps a state's values side by side: through a host block, apart again here
+        const size_t chunk = mqpop_chunk(nS);
+        std::vector<double> stage;
+        for (size_t m0 = 0; m0 < (size_t)count; m0 += chunk) {
+            const size_t m = std::min(chunk, (size_t)count - m0);
+            stage.resize(m * per);
+            HIP_TRY(h, hipMemcpy(stage.data(), io.tab + ((size_t)first + m0) * per, m * per * 8, hipMemcpyDeviceToHost));
+            for (size_t r = 0; r < m * nS; ++r) {
+                const double* const from = stage.data() + r * kMqRow;
+                for (int i = 0; i < 4; ++i)
+                    if (rows[i])
+                        for (int k = 0; k < kMqWidth[i]; ++k) rows[i][(m0 * nS + r) * kMqWidth[i] + k] = from[kMqSlots[i] + k];
+            }
+        }
+    }
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_minimax_q_population_load(soccer_handle* h, soccer_minimax_q_population* q, int64_t first, int64_t count, const double* Q,
+                                                const double* V, const double* pi_a, const double* pi_b, const double* alpha,
+                                                const uint64_t* steps) {
+    if (int rc = mqpop_check(h, q, "soccer_minimax_q_population_load")) return rc;
+    if (int rc = mqpop_range_check(h, q, "soccer_minimax_q_population_load", first, count)) return rc;
+    const MqPopIO& io = q->io;
+    const size_t nS = (size_t)io.nS, per = nS * kMqRow;
+    const double* const rows[4] = {Q, V, pi_a, pi_b};
+    // everything is checked before anything is written
+    if (Q)
+        for (size_t i = 0; i < (size_t)count * nS * 25; ++i) {
+            if (i / 25 % nS == 0) continue;                 // row 0 is not read
+            if (!(Q[i] >= -1.0 && Q[i] <= 1.0))
+                return fail(h, SOCCER_E_INVALID, "soccer_minimax_q_population_load: Q[%zu][%zu][%zu][%zu] is outside [-1, 1]", i / 25 / nS,
+                            i / 25 % nS, i % 25 / 5, i % 5);
+        }
+    if (V)
+        for (size_t i = 0; i < (size_t)count * nS; ++i) {
+            if (i % nS == 0) continue;
+            if (!(V[i] >= -1.0 && V[i] <= 1.0))
+                return fail(h, SOCCER_E_INVALID, "soccer_minimax_q_population_load: V[%zu][%zu] is outside [-1, 1]", i / nS, i % nS);
+        }
+    if (pi_a) if (int rc = wpop_rows_check(h, "soccer_minimax_q_population_load", "pi_a", pi_a, (size_t)count, io.nS, 1)) return rc;
+    if (pi_b) if (int rc = wpop_rows_check(h, "soccer_minimax_q_population_load", "pi_b", pi_b, (size_t)count, io.nS, 1)) return rc;
+    if (alpha)
+        for (size_t i = 0; i < (size_t)count; ++i)
+            if (!(alpha[i] >= 0.0 && alpha[i] <= 1.0)) return fail(h, SOCCER_E_INVALID, "soccer_minimax_q_population_load: alpha[%zu] must be in [0, 1]", i);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (Q || V || pi_a || pi_b) {
+        const size_t chunk = mqpop_chunk(nS);
+        std::vector<double> stage;
+        for (size_t m0 = 0; m0 < (size_t)count; m0 += chunk) {
+            const size_t m = std::min(chunk, (size_t)count - m0);
+            double* const dev = io.tab + ((size_t)first + m0) * per;
+            stage.resize(m * per);
+            HIP_TRY(h, hipMemcpy(stage.data(), dev, m * per * 8, hipMemcpyDeviceToHost));          // what is not given stays
+            for (size_t r = 0; r < m * nS; ++r) {
+                double* const to = stage.data() + r * kMqRow;
+                const bool row0 = r % nS == 0;
+                for (int i = 0; i < 4; ++i) {
+                    if (!rows[i]) continue;
+                    if (row0 && i >= 2) continue;           // row 0 of the strategies stays what creation gave it
+                    for (int k = 0; k < kMqWidth[i]; ++k) to[kMqSlots[i] + k] = row0 ? 0.0 : rows[i][(m0 * nS + r) * kMqWidth[i] + k];
+                }
+            }
+            HIP_TRY(h, hipMemcpy(dev, stage.data(), m * per * 8, hipMemcpyHostToDevice));
+        }
+    }
+    if (alpha && count) HIP_TRY(h, hipMemcpy(io.alpha + first, alpha, (size_t)count * 8, hipMemcpyHostToDevice));
+    if (steps) HIP_TRY(h, hipMemcpy(io.steps, steps, 8, hipMemcpyHostToDevice));
+    if (Q && !V && !pi_a && !pi_b && count > 0 && nS > 1) {             // a table alone: V and the strategies follow it
+        hipLaunchKernelGGL(mq_pop_solve_kernel, dim3(mqpop_grid(q, (uint64_t)count * (uint64_t)(nS - 1))), dim3(kMqBlock), 0, h->stream, io,
+                           (unsigned long long)first, (unsigned long long)count);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
     return SOCCER_OK;
 }

@@ -500,6 +500,12 @@ class VectorSoccerEnv:
         assert self.multiagent, "wolf_population needs a two-player environment (no player with a fixed policy)"
         return self._batch.wolf_population(discount_factor, **params)
 
+    def minimax_q_population(self, discount_factor, **params):
+        """A MinimaxQPopulation (SoccerBatch.minimax_q_population): a minimax-Q learner per lane of this env, each with its
+        own Q, V and strategies."""
+        assert self.multiagent, "minimax_q_population needs a two-player environment (no player with a fixed policy)"
+        return self._batch.minimax_q_population(discount_factor, **params)
+
     @property
     def reward_int8(self):
         """device io: player A's reward of the last step as the int8 tensor the kernel wrote (-1 / 0 / +1), no cast

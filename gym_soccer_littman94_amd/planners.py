@@ -183,6 +183,30 @@ def wolf_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor
     return r["pi_a"], r["pi_b"], r["avg_a"], r["avg_b"], r["Q_a"], r["Q_b"], r["alpha"]
 
 
+def minimax_q_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, opponent="uniform", first=0,
+                         count=None):
+    """A population of minimax-Q learners on the device, a learner per lane of `env`, each with its own table, strategies
+    and stream of experience: n_steps steps of every member from the lanes' current states (lanes that were never reset
+    are reset first).  discount_factor, alpha, decay and explor are scalars or arrays of one value per lane; decay None:
+    alpha falls to 1 % over the run; opponent: 'uniform', 'self', a fixed [nS, 5] policy or [n, nS, 5], one per member.
+    Returns, for members first .. first + count - 1 (count None: to the end), (pi_a[count, nS, 5], pi_b, V[count, nS],
+    Q[count, nS, 5, 5], alpha[count])."""
+    b = _two_player_batch(env, "minimax_q_population")
+    n_steps = int(n_steps)
+    assert n_steps >= 0, "n_steps must be >= 0"
+    if decay is None:
+        decay = 0.01 ** (1.0 / max(n_steps, 1))
+    pop = b.minimax_q_population(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, opponent=opponent)
+    try:
+        if b.get_state()["needs_reset"].any():
+            (env if hasattr(env, "_batch") else b).reset()
+        pop.run(n_steps)
+        r = pop.read(first, count)
+    finally:
+        pop.close()
+    return r["pi_a"], r["pi_b"], r["V"], r["Q"], r["alpha"]
+
+
 def minimax_value_iteration(env, theta, discount_factor, max_sweeps=1000000):
     """Minimax (Shapley) value iteration of the two-player game on the device, Littman (1994)'s equilibrium values.
     Returns (pi_a[nS, 5], pi_b[nS, 5], V, Q[nS, 5, 5], iterations): player A's maximin and player B's minimax stage-game

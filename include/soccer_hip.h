@@ -64,7 +64,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_*, soccer_wolf_population_*, soccer_best_response, soccer_evaluate_policies and soccer_rollout_shape were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_*, soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies and soccer_rollout_shape were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -799,6 +799,82 @@ int soccer_wolf_population_load(soccer_handle* h, soccer_wolf_population* q, int
  * both populations of this handle, else SOCCER_E_INVALID with the reason.  No host copy, no synchronisation. */
 int soccer_wolf_population_adopt(soccer_handle* h, soccer_wolf_population* dst, int32_t dst_player, soccer_wolf_population* src,
                                  int32_t src_player, int32_t which);
+
+/* ---- learners, a population of minimax-Q learners (two-player handles; a minimax-Q learner per lane)
+ * What the two populations above are to soccer_q_learner and soccer_wolf_phc, this is to soccer_minimax_q; nothing new is
+ * defined.  On a two-player SOCCER_F_AUTORESET handle of n lanes the population has n members, and member i is exactly a
+ * soccer_minimax_q learner whose only actor is lane i, bit for bit: Littman's protocol of one learner, one stream of experience,
+ * many runs.  State of member i, all float64: Q[n_states][5][5], V[n_states], pi_a / pi_b [n_states][5], alpha_i.  The
+ * population has one step counter.  No visits are kept, as in the other populations.
+ * Row 0 is the terminal observation: Q[0] = V[0] = 0 for good.  Creation gives Q = V = q_init on the live states and uniform
+ * strategies, SET, NOT SOLVED: a state's strategies are first solved when the state is first updated, so pi_a and pi_b are
+ * state kept in memory and cannot be recomputed from Q.
+ * One step of member i is steps 1-6 of "learners (minimax-Q)" on the single transition of lane i:
+ *   1. player A draws from the threshold row of (1.0 - explor_i) * pi_a[s][k] + explor_i / 5.0 of ITS pi_a at the lane's
+ *      observation s (the expression of step 1 there); player B by `opponent`: SOCCER_MQ_UNIFORM the NULL row table,
+ *      (h * 5) >> 15; SOCCER_MQ_SELF the same expression on its pi_b[s]; SOCCER_MQ_FIXED the host-computed thresholds of a
+ *      fixed mixed policy, one [n_states][5] array shared by all members (opponent_policy) or one per member
+ *      (opponent_policy_per_member, [n_lanes][n_states][5]): exactly one of the two, checked as opponent_policy of
+ *      soccer_minimax_q_config is; the message names the member and the state
+ *   2. act and step: batched_rollout(n_steps = 1, sample_actions = 1) with that lane's rows — the same tick and Philox
+ *      words, auto-reset, episode histogram and misuse flags as for the other populations
+ *   3.-4. with one sample c = 1, on the cell (s, a, b):  m = (double)r + discount_factor_i * ((double)SV * 2^-40) where
+ *      SV = terminated ? 0 : rint(V[s'] * 2^40),  Q = Q + alpha_i * (m - Q), not contracted.  V[s'] is read BEFORE the step's
+ *      re-solve (it matters when s' == s); s' = final_obs, so a truncated transition that did not terminate bootstraps from
+ *      it.  The 2^-40 grid is kept so that a member is bit for bit the shared learner with one lane
+ *   5. re-solve: (V[s], pi_a[s], pi_b[s]) = solve(Q[s]) (csrc/soccer_games.hpp), that one state, on every learning step
+ *   6. alpha_i = alpha_i * decay_i; the step counter grows by one per step of the population
+ * A lane that still needs its first reset (SOCCER_MISUSE_FROZEN) and a lane whose current observation is 0 contribute
+ * nothing; their member's alpha still advances.  The population's state is a fixed function of (seed, parameters, number of
+ * steps): it does not depend on how run() splits its launches, on the launch geometry or on the state layout.
+ * Hyperparameters: the scalars of soccer_minimax_q_config for everyone, or — where the pointer is not NULL — HOST arrays of n
+ * values, one per member, for alpha, decay, explor and discount_factor (every value in the scalar's range); q_init is scalar.
+ * Refusals, SOCCER_E_STATE during a capture, the misuse flags and the ownership of the memory are those of the
+ * soccer_q_population_* calls (memory: n * n_states * 288 bytes of rows, 32 bytes of parameters per member and 8 * n_states
+ * bytes of thresholds per fixed policy; SOCCER_E_NOMEM leaves the handle usable).  Populations of all three kinds and the
+ * three shared learners may share a handle. */
+typedef struct soccer_minimax_q_population soccer_minimax_q_population;
+typedef struct soccer_minimax_q_population_config {
+    double  discount_factor;        /* the fields of soccer_minimax_q_config, in place */
+    double  alpha;
+    double  decay;
+    double  explor;
+    double  q_init;
+    int32_t opponent;               /* SOCCER_MQ_* : how player B acts */
+    int32_t reserved_;              /* 0 */
+    const double* opponent_policy;             /* SOCCER_MQ_FIXED: HOST [n_states][5], shared by every member; else NULL */
+    const double* opponent_policy_per_member;  /* or HOST [n_lanes][n_states][5]: SOCCER_MQ_FIXED has exactly one of the two */
+    const double* alpha_per_member;            /* HOST [n_lanes] or NULL: `alpha` for everyone */
+    const double* decay_per_member;
+    const double* explor_per_member;
+    const double* discount_factor_per_member;
+} soccer_minimax_q_population_config;
+int soccer_minimax_q_population_create(soccer_handle* h, const soccer_minimax_q_population_config* cfg, soccer_minimax_q_population** out);
+int soccer_minimax_q_population_destroy(soccer_handle* h, soccer_minimax_q_population* q);
+/* n_steps steps of every member in ceil(n_steps / K) launches (K = 4096; SOCCER_POP_LAUNCH_STEPS, read at creation and accepted
+ * in 1..4096, overrides it as for soccer_q_population_run), enqueued on the handle's stream: no synchronisation, no copy.
+ * Consumes n_steps ticks.  A launch has min(n, W) workgroups of one wave, a wave per member; beyond W members (W = the waves
+ * of the other kernels' largest grid, 8 192 on an MI355X) a wave serves several members in turn.  A test hook: the
+ * environment variable SOCCER_MQ_POP_WAVES, read at creation and accepted in 1..W, lowers W (tests of a wave that serves
+ * several members); it changes no result, and update() and load()'s re-solve use the same bound. */
+int soccer_minimax_q_population_run(soccer_handle* h, soccer_minimax_q_population* q, int32_t n_steps);
+/* steps 3-6 on the caller's transitions: DEVICE arrays of n_lanes elements, transition i belongs to member i (reward is
+ * player A's), with the checks and the misuse flags of soccer_q_population_update: a bad transition leaves its member alone
+ * (its alpha still advances).  Consumes no tick. */
+int soccer_minimax_q_population_update(soccer_handle* h, soccer_minimax_q_population* q, const uint16_t* obs, const int8_t* act_a,
+                                       const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs);
+/* Members first .. first + count - 1 (inside the population, else SOCCER_E_INVALID) to HOST arrays, any may be NULL:
+ * Q[count][n_states][5][5], V[count][n_states], pi_a / pi_b [count][n_states][5], alpha[count], steps (one value).  Synchronises. */
+int soccer_minimax_q_population_read(soccer_handle* h, soccer_minimax_q_population* q, int64_t first, int64_t count, double* Q, double* V,
+                                     double* pi_a, double* pi_b, double* alpha, uint64_t* steps);
+/* The same range from HOST arrays, any may be NULL (= unchanged): Q and V in [-1, 1] (row 0 is taken as zeros); pi_a / pi_b with
+ * rows 1.. >= 0 and summing to 1 as a fixed policy's must (the message names array, member and state; row 0 is not read and
+ * stays what creation gave it); alpha[count] in [0, 1]; steps.  Everything is checked before anything is written: a refused
+ * load changes nothing.  Q given with NONE of V, pi_a, pi_b: every live state of the range is re-solved on the device from
+ * the new Q.  Otherwise whatever is given is stored as it is and nothing is solved — V or a strategy without Q included — so
+ * read -> load of a range on a fresh or a running population continues bit for bit, states never updated included. */
+int soccer_minimax_q_population_load(soccer_handle* h, soccer_minimax_q_population* q, int64_t first, int64_t count, const double* Q,
+                                     const double* V, const double* pi_a, const double* pi_b, const double* alpha, const uint64_t* steps);
 
 /* HOST output: prob[c*3+k] = slip-combination weight c (0: no slip, 1: B slips, 2: A slips,
  * 3: both; :211-222, evaluated left to right in float64) times outcome probability 1, 0.5, 0.25
