@@ -129,6 +129,7 @@ QL_GREEDY, QL_UNIFORM, QL_FIXED = 0, 1, 2
 PHC_LEARN, PHC_UNIFORM, PHC_FIXED = 0, 1, 2
 MQ_MAX_LANES = 1 << 22
 BR_MAX_POLICIES = 256
+CROSS_MAX_POLICIES = 1024
 MISUSE_FROZEN, MISUSE_ACTION, MISUSE_OBSERVATION = 1, 2, 4
 STAGE_ACT_A, STAGE_ACT_B, STAGE_U_STEP, STAGE_U_RESET, STAGE_MASK = 1, 2, 4, 8, 16
 COMM_ID_BYTES = 128
@@ -182,6 +183,8 @@ PROTOTYPES = {
                              + [C.c_void_p] * 4),
     "soccer_evaluate_policies": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32,
                                            C.c_void_p, C.c_void_p]),
+    "soccer_cross_play": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "soccer_minimax_q_create": (C.c_int, [C.c_void_p, C.POINTER(MinimaxQConfig), C.POINTER(C.c_void_p)]),
     "soccer_minimax_q_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "soccer_minimax_q_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),

@@ -381,6 +381,26 @@ def q_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e
     return cfg, (pols, arrays)
 
 
+def _population_cross_play(pop, read, key_a, key_b, theta, first, count, discount_factor):
+    """Members first .. first + count - 1 of a population against one another (SoccerBatch.cross_play): player A's policies
+    read(first, count)[key_a] meet the same members' player-B policies [key_b], read in chunks of at most 256 members."""
+    first, count = pop._range(first, count)
+    assert 1 <= count <= _lib.CROSS_MAX_POLICIES, "cross_play takes 1 .. %d members, not %d" % (_lib.CROSS_MAX_POLICIES, count)
+    gam = pop.discount_factor[first:first + count]
+    if discount_factor is None:
+        other = np.flatnonzero(gam != gam[0])
+        if other.size:
+            raise ValueError("members %d and %d have different discounts (%r and %r): pass discount_factor" % (
+                first, first + other[0], float(gam[0]), float(gam[other[0]])))
+        discount_factor = float(gam[0])
+    pa = np.zeros((count, pop.nS, 5)); pb = np.zeros((count, pop.nS, 5))
+    for c0 in range(0, count, _lib.BR_MAX_POLICIES):
+        c = min(_lib.BR_MAX_POLICIES, count - c0)
+        r = read(first + c0, c)
+        pa[c0:c0 + c] = r[key_a]; pb[c0:c0 + c] = r[key_b]
+    return pop.batch.cross_play(pa, pb, theta, float(discount_factor))
+
+
 class QPopulation:
     """A population of independent Q-learners on a two-player auto-reset SoccerBatch, a learner per lane: member i has its own
     Q_a[nS, 5], Q_b[nS, 5] and alpha and learns from lane i alone (include/soccer_hip.h, "learners, a population of
@@ -466,6 +486,12 @@ class QPopulation:
                 out["v_b"][c0 + idx] = b.best_response(r["pi_b"][idx], 1, theta, float(g))[1]
         out["gap"] = out["v_b"] - out["v_a"]
         return out
+
+    def cross_play(self, theta=1e-10, first=0, count=None, discount_factor=None):
+        """What each member's player A scores against each member's player B: (payoff[count, count], iterations) of
+        SoccerBatch.cross_play on the one-hot greedy policies of members first .. first + count - 1 (at most 1024).
+        discount_factor None: the range's common discount, ValueError if the members differ."""
+        return _population_cross_play(self, self.read, "pi_a", "pi_b", theta, first, count, discount_factor)
 
     def load(self, Q_a=None, Q_b=None, alpha=None, steps=None, first=0):
         """Resume members first .. first + count - 1 from a checkpoint: Q_a / Q_b [count, nS, 5] in [-1, 1] and alpha[count]
@@ -773,6 +799,14 @@ class WolfPopulation:
         out["gap"] = out["v_b"] - out["v_a"]
         return out
 
+    def cross_play(self, which="pi", theta=1e-10, first=0, count=None, discount_factor=None):
+        """What each member's player A scores against each member's player B: (payoff[count, count], iterations) of
+        SoccerBatch.cross_play on the policies (which='pi') or the average policies (which='avg') of members first ..
+        first + count - 1 (at most 1024).  discount_factor None: the range's common discount, ValueError if the members differ."""
+        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
+        return _population_cross_play(self, lambda f, c: self._read(f, c, (which + "_a", which + "_b")), which + "_a", which + "_b",
+                                      theta, first, count, discount_factor)
+
     def load(self, Q_a=None, Q_b=None, pi_a=None, pi_b=None, avg_a=None, avg_b=None, updates=None, alpha=None, dscale=None, steps=None,
              first=0):
         """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged): the
@@ -958,6 +992,13 @@ class MinimaxQPopulation:
                 out["v_b"][c0 + idx] = b.best_response(r["pi_b"][idx], 1, theta, float(g))[1]
         out["gap"] = out["v_b"] - out["v_a"]
         return out
+
+    def cross_play(self, theta=1e-10, first=0, count=None, discount_factor=None):
+        """What each member's player A scores against each member's player B: (payoff[count, count], iterations) of
+        SoccerBatch.cross_play on the strategies pi_a and pi_b of members first .. first + count - 1 (at most 1024).
+        discount_factor None: the range's common discount, ValueError if the members differ."""
+        return _population_cross_play(self, lambda f, c: self._read(f, c, ("pi_a", "pi_b")), "pi_a", "pi_b", theta, first, count,
+                                      discount_factor)
 
     def load(self, Q=None, V=None, pi_a=None, pi_b=None, alpha=None, steps=None, first=0):
         """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged):
@@ -1264,6 +1305,29 @@ class SoccerBatch:
         code = self.lib.soccer_evaluate_policies(self.h, n, a.ctypes.data, b.ctypes.data, float(theta), float(discount_factor),
                                                  int(max_sweeps), V.ctypes.data, it.ctypes.data)
         return self._response_result(code, (V, it), ba or bb)
+
+    def cross_play(self, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000, pairs_per_pass=0, values=False):
+        """The payoff matrix of two sets of mixed policies: payoff[i, j] is player A's value at kick-off (the mean of V over the
+        initial states) when pi_a[i] meets pi_b[j], each pair iterated exactly like evaluate_policies on that pair alone.
+        pi_a is [n_a, nS, 5], pi_b [n_b, nS, 5], up to 1024 policies each (a single [nS, 5] policy is a batch of one).
+        Returns (payoff[n_a, n_b], iterations[n_a, n_b]), and with values=True also V[n_a, n_b, nS].  pairs_per_pass: how many
+        pairs are solved together on the device (0: the library chooses; else a multiple of 64) — no result depends on it.
+        RuntimeError if max_sweeps is reached (its .results holds the tuple, iterations == max_sweeps marks the open pairs)."""
+        a, _ = self._policies(pi_a, "pi_a")
+        b, _ = self._policies(pi_b, "pi_b")
+        na, nb = a.shape[0], b.shape[0]
+        payoff = np.zeros((na, nb)); it = np.zeros((na, nb), np.int32)
+        V = np.zeros((na, nb, self.nS)) if values else None
+        code = self.lib.soccer_cross_play(self.h, na, a.ctypes.data, nb, b.ctypes.data, float(theta), float(discount_factor),
+                                          int(max_sweeps), int(pairs_per_pass), payoff.ctypes.data,
+                                          V.ctypes.data if values else None, it.ctypes.data)
+        out = (payoff, it.astype(np.int64)) + ((V,) if values else ())
+        try:
+            self._check(code)
+        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
+            e.results = out
+            raise
+        return out
 
     # -- learners -------------------------------------------------------------------------------
     def minimax_q(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, opponent="uniform"):

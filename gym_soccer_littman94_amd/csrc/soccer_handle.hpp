@@ -4,7 +4,7 @@
 //   soccer_hip.hip       create / destroy, seed / tick, reset, state, staging, one-environment calls, statistics, timers, graphs
 //   soccer_step.hip      batched_step*
 //   soccer_rollout.hip   batched_rollout*
-//   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, the matrix-game solver
+//   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, cross-play, the matrix-game solver
 //   soccer_learners.hip  the minimax-Q learner, the independent Q-learners, the policy hill-climbers, the three kinds of populations
 //   soccer_comm.hip      the RCCL wrapper (host code only)
 //
@@ -192,6 +192,18 @@ struct soccer_handle {
     unsigned long long* br_words = nullptr; // [br_cap][kMinimaxBatch + 1] per-policy, per-sweep max |V_k - V_{k-1}| (bits)
     int br_cap = 0; bool br_pairs = false;
     OwnedBufs br_bufs{"the best-response solver"};
+    // soccer_cross_play: the policies of a call and one pass's buffers ([..][cx_stride], the pass's pairs along the fastest
+    // axis), allocated on first use and again when a call needs more of either, see cross_buffers
+    double* cx_pol = nullptr;               // [cx_policies][nS][5] player A's policies, then player B's
+    double* cx_V[2] = {nullptr, nullptr};   // [nS][cx_stride] V double-buffered across sweeps
+    unsigned long long* cx_words = nullptr; // [kMinimaxBatch + 1][cx_stride] per-sweep, per-pair max |V_k - V_{k-1}| (bits)
+    int32_t* cx_done = nullptr;             // [cx_stride] each pair's stopping sweep
+    int32_t* cx_iter = nullptr;             // [cx_stride] ... as it is returned (max_sweeps for an open pair)
+    double* cx_payoff = nullptr;            // [cx_stride]
+    int32_t* cx_open = nullptr;             // the number of open pairs after a batch
+    double* cx_values = nullptr;            // [cx_stride][nS] V of the pass in the caller's order (cx_has_values: allocated)
+    int cx_policies = 0, cx_stride = 0; bool cx_has_values = false;
+    OwnedBufs cx_bufs{"the cross-play solver"};
     std::vector<soccer_minimax_q*> learners; // soccer_minimax_q_create: the learners that were not destroyed (freed with the handle)
     std::vector<soccer_q_learner*> q_learners; // soccer_q_learner_create: the same for the independent Q-learners
     std::vector<soccer_wolf_phc*> phc_learners; // soccer_wolf_phc_create: the same for the policy hill-climbers

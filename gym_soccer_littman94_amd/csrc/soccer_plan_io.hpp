@@ -55,4 +55,41 @@ struct ResponseIO {
     int32_t word_stride;
 };
 
+// the payoff matrix of n_a x n_b mixed policies (soccer_cross_play): evaluations like kEvalPair's, transposed — a lane owns a
+// pair, V and the words are laid out [..][stride] with the pass's pairs along the fastest axis
+struct CrossIO {
+    const int32_t* offset; const PlanEntry* list;   // MinimaxIO's lists
+    const double* x;                 // [n_a][nS][5] player A's policies, row 0 of each zeroed
+    const double* y;                 // [n_b][nS][5] player B's
+    const double* V;                 // [nS][stride] V_{k-1}
+    double* V_out;                   // [nS][stride] V_k
+    unsigned long long* delta;       // [stride] this sweep's word of every pair of the pass
+    const unsigned long long* prev;  // [stride] the previous sweep's
+    double gamma, theta;
+    int32_t nS, n_b;
+    int32_t stride, pairs;           // pairs of the pass, and that number rounded up to whole waves
+    int32_t first, last;             // matrix index i * n_b + j of the pass's pair 0, and of the matrix's last pair
+};
+
+// between two batches of sweeps (cross_batch_kernel): each pair's stopping sweep from the batch's words, the words reset
+struct CrossBatchIO {
+    unsigned long long* words;       // [n_words][stride]; row 0 is the sweep before the batch's first
+    int32_t* done_at;                // [stride] the pair's stopping sweep, 0 while it is open
+    int32_t* open;                   // the kernel adds the number of pairs still open
+    double theta;
+    int32_t stride, pairs, n_words;
+    int32_t k0, nb;                  // the batch's first sweep and its length; nb == 0: before the first batch
+};
+
+// after the last batch (cross_finish_kernel, cross_values_kernel): every pair from the V buffer of its own parity
+struct CrossFinishIO {
+    const double* V[2];              // [nS][stride] each
+    const int32_t* done_at;          // [stride]
+    double* payoff;                  // [stride] the mean of V over the initial states
+    int32_t* iterations;             // [stride]
+    double* values;                  // [pairs][nS] (cross_values_kernel only)
+    int32_t isd[4];                  // the initial states' observation indices in ISD order
+    int32_t n_isd, nS, stride, pairs, max_sweeps;
+};
+
 }  // namespace soccer

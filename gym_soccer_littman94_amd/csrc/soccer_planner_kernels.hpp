@@ -1,4 +1,4 @@
-// soccer_planner_kernels.hpp — enumerate_kernel (the transition table), planner_kernel, the minimax kernels, response_sweep_kernel, games_kernel.
+// soccer_planner_kernels.hpp — enumerate_kernel (the transition table), planner_kernel, the minimax kernels, response_sweep_kernel, the cross-play kernels, games_kernel.
 // Included by soccer_planners.hip only: every kernel is emitted by exactly one translation unit.
 #pragma once
 #include "soccer_kernels.hpp"
@@ -388,6 +388,123 @@ __global__ __launch_bounds__(kMinimaxBlock) void response_sweep_kernel(const Res
     __syncthreads();
     unsigned long long* word = IO.delta + pol * (size_t)IO.word_stride;
     if (threadIdx.x == 0 && s_max > *reinterpret_cast<volatile unsigned long long*>(word)) atomicMax(word, s_max);
+}
+
+// =================================================================================================
+// the payoff matrix of n_a x n_b mixed policies (soccer_cross_play)
+// =================================================================================================
+// Pair (i, j) is kEvalPair's iteration on (x_i, y_j), the same sums in the same order, by minimax_sweep_kernel's scheme (a
+// launch per sweep, V double-buffered, a word per pair and sweep) — with the work transposed: a lane owns a pair and a wave
+// owns (state, 64 consecutive pairs of the pass).  The state is wave-uniform, so the list offsets and entries sit at
+// wave-uniform addresses (scalar loads, one fetch per wave), and with V laid out [nS][stride] the 64 lanes' V[next] are one
+// contiguous 512-byte load.  Padding entries are accumulated like any other.  The waves of a workgroup share their 64 pairs
+// and take consecutive states; a pair whose previous word is below theta (and a lane past the end of a ragged pass) writes
+// neither V nor its word, and the workgroup returns at once when that holds for all 64.
+constexpr int kCrossBlock = 256;
+constexpr int kCrossWaves = kCrossBlock / 64;
+
+__global__ __launch_bounds__(kCrossBlock) void cross_sweep_kernel(const CrossIO IO) {
+    __shared__ unsigned long long sD[kCrossWaves][64];
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int p = (int)blockIdx.y * 64 + lane;
+    const bool live = p < IO.pairs && !(__longlong_as_double((long long)IO.prev[p]) < IO.theta);
+    if (__ballot(live) == 0ull) return;                                 // the same in every wave: they share the 64 pairs
+    const int s = (int)blockIdx.x * kCrossWaves + wave;                 // wave-uniform, and so is every list index below
+    const size_t stride = (size_t)IO.stride;
+    unsigned long long d = 0ull;
+    if (s < IO.nS) {
+        const int g = min(IO.first + p, IO.last);                       // (a lane past the end reads the last pair's rows)
+        const int i = g / IO.n_b, j = g - i * IO.n_b;
+        const double* xr = IO.x + ((size_t)i * IO.nS + s) * 5;
+        const double* yr = IO.y + ((size_t)j * IO.nS + s) * 5;
+        const double* Vp = IO.V + p;
+        double v = 0.0;
+#pragma unroll 1
+        for (int a = 0; a < 5; ++a) {
+            const double xa = xr[a];                                    // (asked for before the lists that hide its latency)
+            double inner = 0.0;
+#pragma unroll 1
+            for (int b = 0; b < 5; ++b) {
+                const double yb = yr[b];
+                const int key = s * 25 + a * 5 + b;
+                const int end = IO.offset[key + 1];
+                double q = 0.0;                                         // minimax_list_q's expression
+                for (int e = IO.offset[key]; e < end; e += kPlanPad) {
+                    PlanEntry x[kPlanPad];
+                    double vn[kPlanPad];
+#pragma unroll
+                    for (int t = 0; t < kPlanPad; ++t) x[t] = IO.list[e + t];
+#pragma unroll
+                    for (int t = 0; t < kPlanPad; ++t) vn[t] = Vp[(size_t)(x[t].next_done & 0x7fffffff) * stride];
+#pragma unroll
+                    for (int t = 0; t < kPlanPad; ++t) {
+                        const double cont = (IO.gamma * vn[t]) * (x[t].next_done < 0 ? 0.0 : 1.0);
+                        q = q + x[t].prob * ((double)x[t].reward + cont);
+                    }
+                }
+                inner = inner + yb * q;
+            }
+            v = v + xa * inner;
+        }
+        if (live) {
+            IO.V_out[(size_t)s * stride + p] = v;
+            d = (unsigned long long)__double_as_longlong(fabs(v - Vp[(size_t)s * stride]));
+        }
+    }
+    sD[wave][lane] = d;
+    __syncthreads();
+    if (wave == 0 && live) {
+#pragma unroll
+        for (int w = 1; w < kCrossWaves; ++w) d = max(d, sD[w][lane]);
+        // a non-atomic look first: the word only grows
+        if (d > *reinterpret_cast<volatile unsigned long long*>(IO.delta + p)) atomicMax(IO.delta + p, d);
+    }
+}
+
+// a thread per pair of the pass, between two batches of sweeps: the first sweep of the batch whose word is below theta is
+// the pair's stopping sweep; row 0 takes the batch's last word (a pair that has stopped keeps a word below theta), the
+// other rows are cleared for the next batch
+__global__ __launch_bounds__(kCrossBlock) void cross_batch_kernel(const CrossBatchIO IO) {
+    const int p = (int)blockIdx.x * kCrossBlock + (int)threadIdx.x;
+    if (p >= IO.pairs) return;
+    int done = IO.nb ? IO.done_at[p] : 0;
+    for (int j = 1; j <= IO.nb; ++j)
+        if (!done && __longlong_as_double((long long)IO.words[(size_t)j * IO.stride + p]) < IO.theta) done = IO.k0 + j - 1;
+    IO.done_at[p] = done;
+    IO.words[p] = IO.nb ? IO.words[(size_t)IO.nb * IO.stride + p] : (unsigned long long)__double_as_longlong(__builtin_huge_val());
+    for (int j = 1; j < IO.n_words; ++j) IO.words[(size_t)j * IO.stride + p] = 0ull;
+    if (!done) atomicAdd(IO.open, 1);
+}
+
+// a thread per pair: the sweep count (max_sweeps for an open pair) and player A's value at kick-off, from the buffer of the
+// pair's own parity
+__global__ __launch_bounds__(kCrossBlock) void cross_finish_kernel(const CrossFinishIO IO) {
+    const int p = (int)blockIdx.x * kCrossBlock + (int)threadIdx.x;
+    if (p >= IO.pairs) return;
+    const int k = IO.done_at[p] ? IO.done_at[p] : IO.max_sweeps;
+    const double* V = IO.V[k & 1] + p;
+    double sum = 0.0;
+    for (int i = 0; i < IO.n_isd; ++i) sum = sum + V[(size_t)IO.isd[i] * IO.stride];
+    IO.payoff[p] = sum / (double)IO.n_isd;
+    IO.iterations[p] = k;
+}
+
+// V[nS][stride] -> values[pair][nS] through a 64 x 64 tile in LDS, both sides coalesced
+__global__ __launch_bounds__(kCrossBlock) void cross_values_kernel(const CrossFinishIO IO) {
+    __shared__ double tile[64][65];
+    const int col = (int)(threadIdx.x & 63u), row0 = (int)(threadIdx.x >> 6);
+    const int p0 = (int)blockIdx.x * 64, s0 = (int)blockIdx.y * 64;
+    {
+        const int p = p0 + col;
+        const int k = p < IO.pairs ? (IO.done_at[p] ? IO.done_at[p] : IO.max_sweeps) : 0;
+        const double* V = IO.V[k & 1] + p;
+        for (int r = row0; r < 64; r += kCrossWaves)
+            if (p < IO.pairs && s0 + r < IO.nS) tile[r][col] = V[(size_t)(s0 + r) * IO.stride];
+    }
+    __syncthreads();
+    for (int r = row0; r < 64; r += kCrossWaves)
+        if (p0 + r < IO.pairs && s0 + col < IO.nS) IO.values[(size_t)(p0 + r) * IO.nS + s0 + col] = tile[col][r];
 }
 
 // the two-player lists assembled on the device from enumerate_kernel's output (build_minimax): a thread per (state, joint

@@ -1,4 +1,4 @@
-// soccer_planners.hip — the transition table, the single-agent planners, minimax value iteration, best responses to mixed policies and the matrix-game solver (see soccer_handle.hpp).
+// soccer_planners.hip — the transition table, the single-agent planners, minimax value iteration, best responses to mixed policies, cross-play and the matrix-game solver (see soccer_handle.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -520,4 +520,107 @@ extern "C" int soccer_evaluate_policies(soccer_handle* h, int32_t n_pairs, const
                                         double discount_factor, int32_t max_sweeps, double* V, int32_t* iterations) {
     return response_solve(h, "soccer_evaluate_policies", kEvalPair, n_pairs, pi_a, pi_b, theta, discount_factor, max_sweeps,
                           V, nullptr, nullptr, iterations);
+}
+
+// ------------------------------------------------------------------------------------------------
+// cross-play: player A's value of every pair (pi_a[i], pi_b[j]) of two sets of mixed policies.  Each pair is
+// soccer_evaluate_policies' iteration, solved to the bits it has alone; the work is laid out the other way round (a lane owns
+// a pair, cross_sweep_kernel), the policies are uploaded once, a matrix larger than a pass is solved pass after pass over the
+// same buffers, and the stopping sweeps are found on the device: a batch of sweeps costs the host one 4-byte read.
+static int cross_buffers(soccer_handle* h, int policies, int stride, bool values) {
+    if (policies <= h->cx_policies && stride <= h->cx_stride && (!values || h->cx_has_values)) return SOCCER_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    policies = std::max(policies, h->cx_policies); stride = std::max(stride, h->cx_stride); values = values || h->cx_has_values;
+    h->cx_bufs.clear();
+    h->cx_policies = 0; h->cx_stride = 0; h->cx_has_values = false;
+    const size_t nS = (size_t)h->mm.nS, cells = nS * (size_t)stride;
+    int rc = h->cx_bufs.alloc(h, (size_t)policies * nS * 5, &h->cx_pol);
+    if (!rc) rc = h->cx_bufs.alloc(h, cells, &h->cx_V[0]);
+    if (!rc) rc = h->cx_bufs.alloc(h, cells, &h->cx_V[1]);
+    if (!rc) rc = h->cx_bufs.alloc(h, (size_t)stride * (kMinimaxBatch + 1), &h->cx_words);
+    if (!rc) rc = h->cx_bufs.alloc(h, (size_t)stride, &h->cx_done);
+    if (!rc) rc = h->cx_bufs.alloc(h, (size_t)stride, &h->cx_iter);
+    if (!rc) rc = h->cx_bufs.alloc(h, (size_t)stride, &h->cx_payoff);
+    if (!rc) rc = h->cx_bufs.alloc(h, (size_t)1, &h->cx_open);
+    if (!rc && values) rc = h->cx_bufs.alloc(h, cells, &h->cx_values);
+    if (rc) { h->cx_bufs.clear(); return rc; }
+    h->cx_policies = policies; h->cx_stride = stride; h->cx_has_values = values;
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_cross_play(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t n_b, const double* pi_b, double theta,
+                                 double discount_factor, int32_t max_sweeps, int32_t pairs_per_pass, double* payoff, double* V,
+                                 int32_t* iterations) {
+    const char* what = "soccer_cross_play";
+    if (int rc = minimax_check(h, what, discount_factor)) return rc;
+    if (n_a < 1 || n_a > SOCCER_CROSS_MAX_POLICIES || n_b < 1 || n_b > SOCCER_CROSS_MAX_POLICIES)
+        return fail(h, SOCCER_E_INVALID, "%s: the number of policies of each player must be 1 .. %d, not %d and %d", what,
+                    SOCCER_CROSS_MAX_POLICIES, n_a, n_b);
+    if (max_sweeps < 1) return fail(h, SOCCER_E_INVALID, "max_sweeps must be >= 1");
+    if (!(theta >= 0.0)) return fail(h, SOCCER_E_INVALID, "theta must be >= 0");
+    if (pairs_per_pass < 0 || pairs_per_pass % 64)
+        return fail(h, SOCCER_E_INVALID, "%s: pairs_per_pass must be 0 (the library chooses) or a positive multiple of 64, not %d", what, pairs_per_pass);
+    if (int rc = response_rows(h, what, "pi_a", n_a, pi_a)) return rc;
+    if (int rc = response_rows(h, what, "pi_b", n_b, pi_b)) return rc;
+    if (int rc = minimax_prepare(h)) return rc;
+    const int nS = h->mm.nS;
+    const int total = n_a * n_b, total64 = (total + 63) / 64 * 64;
+    // the library's choice: the two V buffers of a pass, 2 * nS * pairs * 8 bytes, stay at or under 1 GiB
+    int per_pass = pairs_per_pass ? pairs_per_pass : std::max(64, (int)(((size_t)1 << 30) / ((size_t)16 * nS) / 64 * 64));
+    per_pass = std::min(per_pass, total64);
+    if (int rc = cross_buffers(h, n_a + n_b, per_pass, V != nullptr)) return rc;
+    const int stride = h->cx_stride;                                    // (what an earlier, larger pass left: no result depends on it)
+    double* d_x = h->cx_pol; double* d_y = h->cx_pol + (size_t)n_a * nS * 5;
+    if (int rc = response_upload(h, d_x, pi_a, n_a)) return rc;
+    if (int rc = response_upload(h, d_y, pi_b, n_b)) return rc;
+    constexpr int kWords = kMinimaxBatch + 1;
+    CrossIO io{};
+    io.offset = h->mm.offset; io.list = h->mm.list; io.x = d_x; io.y = d_y; io.gamma = discount_factor; io.theta = theta;
+    io.nS = nS; io.n_b = n_b; io.stride = stride; io.last = total - 1;
+    CrossBatchIO bio{};
+    bio.words = h->cx_words; bio.done_at = h->cx_done; bio.open = h->cx_open; bio.theta = theta; bio.stride = stride; bio.n_words = kWords;
+    CrossFinishIO fio{};
+    fio.V[0] = h->cx_V[0]; fio.V[1] = h->cx_V[1]; fio.done_at = h->cx_done; fio.payoff = h->cx_payoff; fio.iterations = h->cx_iter;
+    fio.values = h->cx_values; fio.n_isd = h->rules.n_isd; fio.nS = nS; fio.stride = stride; fio.max_sweeps = max_sweeps;
+    for (int i = 0; i < h->rules.n_isd; ++i) fio.isd[i] = (int32_t)h->rules.isd_obs[i];
+    int64_t open_total = 0;
+    for (int first = 0; first < total; first += per_pass) {
+        const int pairs = std::min(per_pass, total - first);
+        const unsigned pair_blocks = (unsigned)((pairs + kCrossBlock - 1) / kCrossBlock);
+        io.first = first; io.pairs = pairs; bio.pairs = pairs; fio.pairs = pairs;
+        HIP_TRY(h, hipMemsetAsync(h->cx_V[0], 0, (size_t)nS * stride * 8, h->stream));      // V_0 = 0
+        HIP_TRY(h, hipMemsetAsync(h->cx_V[1], 0, (size_t)nS * stride * 8, h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->cx_open, 0, sizeof(int32_t), h->stream));
+        bio.k0 = 0; bio.nb = 0;
+        hipLaunchKernelGGL(cross_batch_kernel, dim3(pair_blocks), dim3(kCrossBlock), 0, h->stream, bio);
+        const dim3 grid((unsigned)((nS + kCrossWaves - 1) / kCrossWaves), (unsigned)((pairs + 63) / 64));
+        int32_t k0 = 1, open = pairs;                                                          // k0: first sweep of the batch
+        while (k0 <= max_sweeps && open) {
+            const int nb = (int)std::min<int64_t>(kMinimaxBatch, (int64_t)max_sweeps - k0 + 1);
+            for (int j = 1; j <= nb; ++j) {
+                const int32_t k = k0 + j - 1;
+                io.V = h->cx_V[(k - 1) & 1]; io.V_out = h->cx_V[k & 1];
+                io.delta = h->cx_words + (size_t)j * stride; io.prev = h->cx_words + (size_t)(j - 1) * stride;
+                hipLaunchKernelGGL(cross_sweep_kernel, grid, dim3(kCrossBlock), 0, h->stream, io);
+            }
+            HIP_TRY(h, hipMemsetAsync(h->cx_open, 0, sizeof(int32_t), h->stream));
+            bio.k0 = k0; bio.nb = nb;
+            hipLaunchKernelGGL(cross_batch_kernel, dim3(pair_blocks), dim3(kCrossBlock), 0, h->stream, bio);
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipMemcpyAsync(&open, h->cx_open, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            k0 += nb;
+        }
+        open_total += open;
+        hipLaunchKernelGGL(cross_finish_kernel, dim3(pair_blocks), dim3(kCrossBlock), 0, h->stream, fio);
+        if (V) hipLaunchKernelGGL(cross_values_kernel, dim3((unsigned)((pairs + 63) / 64), (unsigned)((nS + 63) / 64)), dim3(kCrossBlock), 0, h->stream, fio);
+        HIP_TRY(h, hipGetLastError());
+        if (payoff) HIP_TRY(h, hipMemcpyAsync(payoff + first, h->cx_payoff, (size_t)pairs * 8, hipMemcpyDeviceToHost, h->stream));
+        if (iterations) HIP_TRY(h, hipMemcpyAsync(iterations + first, h->cx_iter, (size_t)pairs * 4, hipMemcpyDeviceToHost, h->stream));
+        if (V) HIP_TRY(h, hipMemcpyAsync(V + (size_t)first * nS, h->cx_values, (size_t)pairs * nS * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    if (open_total) return fail(h, SOCCER_E_STATE, "%s: %lld of %d pairs had not converged after max_sweeps = %d sweeps", what,
+                                (long long)open_total, total, max_sweeps);
+    return SOCCER_OK;
 }

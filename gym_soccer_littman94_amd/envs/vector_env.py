@@ -506,6 +506,11 @@ class VectorSoccerEnv:
         assert self.multiagent, "minimax_q_population needs a two-player environment (no player with a fixed policy)"
         return self._batch.minimax_q_population(discount_factor, **params)
 
+    def cross_play(self, pi_a, pi_b, theta, discount_factor, **params):
+        """The payoff matrix of two sets of mixed policies (SoccerBatch.cross_play): consumes no tick, leaves the lanes alone."""
+        assert self.multiagent, "cross_play needs a two-player environment (no player with a fixed policy)"
+        return self._batch.cross_play(pi_a, pi_b, theta, discount_factor, **params)
+
     @property
     def reward_int8(self):
         """device io: player A's reward of the last step as the int8 tensor the kernel wrote (-1 / 0 / +1), no cast

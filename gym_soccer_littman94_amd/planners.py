@@ -242,3 +242,16 @@ def exploitability(env, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000):
     br_b, v_a, _, k_a = b.best_response(pi_a, 0, theta, discount_factor, max_sweeps=max_sweeps)
     br_a, v_b, _, k_b = b.best_response(pi_b, 1, theta, discount_factor, max_sweeps=max_sweeps)
     return {"v_a": v_a, "v_b": v_b, "gap": v_b - v_a, "br_a": br_a, "br_b": br_b, "iterations": (k_a, k_b)}
+
+
+def cross_play(env, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000):
+    """The cross-play (tournament) matrix of two sets of mixed policies, on the device (include/soccer_hip.h, "cross-play"):
+    pi_a is [n_a, nS, 5], pi_b [n_b, nS, 5].  Returns a dict, everything player A's value at kick-off:
+      payoff      [n_a, n_b], pi_a[i] against pi_b[j]
+      iterations  [n_a, n_b], the sweeps of each pair's solve
+      row_min     [n_a] each A policy against its worst opponent in the set,  col_max  [n_b] likewise each B policy
+      bounds      (row_min.max(), col_max.min()): the pure maximin and minimax, which bracket the meta-game's value"""
+    payoff, it = _two_player_batch(env, "cross_play").cross_play(pi_a, pi_b, theta, discount_factor, max_sweeps=max_sweeps)
+    row_min, col_max = payoff.min(1), payoff.max(0)
+    return {"payoff": payoff, "iterations": it, "row_min": row_min, "col_max": col_max,
+            "bounds": (float(row_min.max()), float(col_max.min()))}

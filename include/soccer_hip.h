@@ -64,7 +64,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_*, soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies and soccer_rollout_shape were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_*, soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies, soccer_cross_play and soccer_rollout_shape were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -441,6 +441,27 @@ int soccer_best_response(soccer_handle* h, int32_t player, int32_t n_policies, c
                          double* V, double* Qr, int32_t* br, int32_t* iterations);
 int soccer_evaluate_policies(soccer_handle* h, int32_t n_pairs, const double* pi_a, const double* pi_b,
                              double theta, double discount_factor, int32_t max_sweeps, double* V, int32_t* iterations);
+/* ---- cross-play: the payoff matrix of n_a x n_b mixed policies (two-player handles) -----------------------------------
+ * What does policy i of player A score against policy j of player B, for all i and j?  Pair (i, j) is exactly
+ * soccer_evaluate_policies on (pi_a[i], pi_b[j]) solved alone: V_0 = 0, the same sequential float64 sums in the same
+ * order, its own stopping sweep k_ij — V[i][j] and iterations[i][j] are the bits and the count that call returns.
+ * payoff[i][j] is player A's value at kick-off: the sum of V[i][j][obs] over the handle's initial states in ISD order,
+ * from 0.0, divided by n_isd (soccer_dims, soccer_get_tables).
+ * pi_a is HOST [n_a][n_states][5], pi_b HOST [n_b][n_states][5]; payoff and iterations are HOST [n_a][n_b], V is HOST
+ * [n_a][n_b][n_states]; any of the three may be NULL, and only what is asked for is formed and copied.  Row 0 of a policy
+ * is not read and counts as zeros; the row check is soccer_evaluate_policies' on the n_a + n_b policies.  n_a and n_b are
+ * 1 .. SOCCER_CROSS_MAX_POLICIES, discount_factor in [0, 1], theta >= 0, max_sweeps >= 1.  The policies are uploaded once
+ * per call, (n_a + n_b) * n_states * 40 bytes, and nothing per pair.
+ * pairs_per_pass is the number of pairs solved together on the device: 0 lets the library choose (as many as keep the two
+ * V buffers of a pass, 2 * n_states * pairs * 8 bytes, at or under 1 GiB), otherwise a positive multiple of 64
+ * (SOCCER_E_INVALID if not).  A matrix with more pairs is solved pass after pass; no result depends on this value.
+ * SOCCER_E_STATE when some pair has not converged after max_sweeps: iterations == max_sweeps marks those, whose outputs
+ * hold the last iterate, and the other pairs are complete.  Like the calls above this one consumes no tick, leaves the
+ * lanes alone and returns SOCCER_E_STATE during a graph capture. */
+#define SOCCER_CROSS_MAX_POLICIES 1024
+int soccer_cross_play(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t n_b, const double* pi_b,
+                      double theta, double discount_factor, int32_t max_sweeps, int32_t pairs_per_pass,
+                      double* payoff, double* V, int32_t* iterations);
 /* ---- learners (two-player handles; minimax-Q, Littman 1994) ------------------------------------------------------
  * A learner lives on a two-player SOCCER_F_AUTORESET handle of at most 2^22 lanes and keeps ONE shared table
  * Q[n_states][5][5] (float64) on the device, with V[n_states] = val(Q[s]) and the stage-game strategies
