@@ -50,6 +50,7 @@ struct soccer_q_population {
     OwnedBufs bufs{"the population of Q-learners"};
     unsigned long long n = 0;           // members = the handle's lanes
     int launch_steps = 4096;            // steps per pop_run_kernel launch (SOCCER_POP_LAUNCH_STEPS)
+    int grid_blocks = 0;                // workgroups per run / update launch at most (SOCCER_POP_GRID_BLOCKS); 0: the handle's cap alone
 };
 
 // A population of policy hill-climbers, a member per lane: the same shape; alpha and dscale live per member in device memory.
@@ -59,6 +60,7 @@ struct soccer_wolf_population {
     OwnedBufs bufs{"the population of WoLF-PHC learners"};
     unsigned long long n = 0;           // members = the handle's lanes
     int launch_steps = 4096;            // steps per phc_pop_run_kernel launch (SOCCER_POP_LAUNCH_STEPS)
+    int grid_blocks = 0;                // workgroups per run / update launch at most (SOCCER_POP_GRID_BLOCKS); 0: the handle's cap alone
 };
 
 // A population of minimax-Q learners, a member per lane: the same shape; a member is a wave of mq_pop_run_kernel.
@@ -695,19 +697,35 @@ static int pop_range_check(soccer_handle* h, const soccer_q_population* q, const
     return SOCCER_OK;
 }
 
+// SOCCER_POP_GRID_BLOCKS, read at creation (tests: a grid-stride loop over members that wraps on a small population, as
+// SOCCER_MQ_POP_WAVES does for the minimax-Q population): 1 .. the handle's grid_cap, ignored otherwise
+static int pop_grid_blocks_env(const soccer_handle* h) {
+    if (const char* e = std::getenv("SOCCER_POP_GRID_BLOCKS")) {
+        const long v = std::atol(e);
+        if (v >= 1 && v <= (long)h->grid_cap) return (int)v;
+    }
+    return 0;
+}
+
+// the grid of a population's run / update launch: grid_for, under the population's own cap where it has one
+static int pop_grid(const soccer_handle* h, int grid_blocks, uint64_t members) {
+    const int g = grid_for(h, members);
+    return grid_blocks > 0 && g > grid_blocks ? grid_blocks : g;
+}
+
 // launch == false (soccer_q_population_create): the LDS limit of this handle's run kernel, as launch_act
 template <bool SLIP, bool LUT_LDS>
-static hipError_t launch_pop_run(soccer_handle* h, const KernelParams& P, const PopIO& io, bool launch) {
+static hipError_t launch_pop_run(soccer_handle* h, const KernelParams& P, const PopIO& io, bool launch, int grid_blocks) {
     if (!launch)
         return h->smem_bytes > 48 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&pop_run_kernel<SLIP, LUT_LDS>),
                                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_bytes) : hipSuccess;
-    hipLaunchKernelGGL((pop_run_kernel<SLIP, LUT_LDS>), dim3(grid_for(h, P.n)), dim3(kBlock), h->smem_bytes, h->stream, P, io);
+    hipLaunchKernelGGL((pop_run_kernel<SLIP, LUT_LDS>), dim3(pop_grid(h, grid_blocks, P.n)), dim3(kBlock), h->smem_bytes, h->stream, P, io);
     return hipSuccess;
 }
 
-static hipError_t pop_run(soccer_handle* h, const KernelParams& P, const PopIO& io, bool launch) {
-    return h->slip ? (h->lut_lds ? launch_pop_run<true, true>(h, P, io, launch) : launch_pop_run<true, false>(h, P, io, launch))
-                   : (h->lut_lds ? launch_pop_run<false, true>(h, P, io, launch) : launch_pop_run<false, false>(h, P, io, launch));
+static hipError_t pop_run(soccer_handle* h, const KernelParams& P, const PopIO& io, bool launch, int grid_blocks = 0) {
+    return h->slip ? (h->lut_lds ? launch_pop_run<true, true>(h, P, io, launch, grid_blocks) : launch_pop_run<true, false>(h, P, io, launch, grid_blocks))
+                   : (h->lut_lds ? launch_pop_run<false, true>(h, P, io, launch, grid_blocks) : launch_pop_run<false, false>(h, P, io, launch, grid_blocks));
 }
 
 // a hyperparameter of every member: the caller's n values, each held to the scalar's range, or the scalar n times
@@ -759,6 +777,7 @@ extern "C" int soccer_q_population_create(soccer_handle* h, const soccer_q_popul
         const long v = std::atol(e);
         if (v >= 1 && v <= 4096) q->launch_steps = (int)v;
     }
+    q->grid_blocks = pop_grid_blocks_env(h);
     PopIO& io = q->io;
     double* dpar[4] = {nullptr, nullptr, nullptr, nullptr};
     uint16_t* dmix[2] = {nullptr, nullptr};
@@ -805,7 +824,7 @@ extern "C" int soccer_q_population_run(soccer_handle* h, soccer_q_population* q,
         PopIO io = q->io;
         io.n_steps = n_steps - t0 < q->launch_steps ? n_steps - t0 : q->launch_steps;
         bind_tick(h, P, (uint64_t)io.n_steps);
-        HIP_TRY(h, pop_run(h, P, io, true));
+        HIP_TRY(h, pop_run(h, P, io, true, q->grid_blocks));
     }
     HIP_TRY(h, hipGetLastError());
     return SOCCER_OK;
@@ -818,7 +837,7 @@ extern "C" int soccer_q_population_update(soccer_handle* h, soccer_q_population*
         return fail(h, SOCCER_E_INVALID, "soccer_q_population_update: all six transition arrays are required");
     if (!aligned(obs, 2) || !aligned(next_obs, 2)) return fail(h, SOCCER_E_INVALID, "soccer_q_population_update: obs / next_obs must be 2-byte aligned");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipLaunchKernelGGL(pop_update_kernel, dim3(grid_for(h, (uint64_t)q->n)), dim3(kBlock), 0, h->stream, q->io, (long long)q->n,
+    hipLaunchKernelGGL(pop_update_kernel, dim3(pop_grid(h, q->grid_blocks, (uint64_t)q->n)), dim3(kBlock), 0, h->stream, q->io, (long long)q->n,
                        obs, act_a, act_b, reward, terminated, next_obs);
     HIP_TRY(h, hipGetLastError());
     return SOCCER_OK;
@@ -919,17 +938,17 @@ static int wpop_range_check(soccer_handle* h, const soccer_wolf_population* q, c
 
 // launch == false (soccer_wolf_population_create): the LDS limit of this handle's run kernel, as launch_act
 template <bool SLIP, bool LUT_LDS>
-static hipError_t launch_wpop_run(soccer_handle* h, const KernelParams& P, const PhcPopIO& io, bool launch) {
+static hipError_t launch_wpop_run(soccer_handle* h, const KernelParams& P, const PhcPopIO& io, bool launch, int grid_blocks) {
     if (!launch)
         return h->smem_bytes > 48 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&phc_pop_run_kernel<SLIP, LUT_LDS>),
                                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_bytes) : hipSuccess;
-    hipLaunchKernelGGL((phc_pop_run_kernel<SLIP, LUT_LDS>), dim3(grid_for(h, P.n)), dim3(kBlock), h->smem_bytes, h->stream, P, io);
+    hipLaunchKernelGGL((phc_pop_run_kernel<SLIP, LUT_LDS>), dim3(pop_grid(h, grid_blocks, P.n)), dim3(kBlock), h->smem_bytes, h->stream, P, io);
     return hipSuccess;
 }
 
-static hipError_t wpop_run(soccer_handle* h, const KernelParams& P, const PhcPopIO& io, bool launch) {
-    return h->slip ? (h->lut_lds ? launch_wpop_run<true, true>(h, P, io, launch) : launch_wpop_run<true, false>(h, P, io, launch))
-                   : (h->lut_lds ? launch_wpop_run<false, true>(h, P, io, launch) : launch_wpop_run<false, false>(h, P, io, launch));
+static hipError_t wpop_run(soccer_handle* h, const KernelParams& P, const PhcPopIO& io, bool launch, int grid_blocks = 0) {
+    return h->slip ? (h->lut_lds ? launch_wpop_run<true, true>(h, P, io, launch, grid_blocks) : launch_wpop_run<true, false>(h, P, io, launch, grid_blocks))
+                   : (h->lut_lds ? launch_wpop_run<false, true>(h, P, io, launch, grid_blocks) : launch_wpop_run<false, false>(h, P, io, launch, grid_blocks));
 }
 
 // rows first_row.. of `members` policies [nS][5] each, held to what fixed_thresholds holds a fixed policy to
@@ -1004,6 +1023,7 @@ extern "C" int soccer_wolf_population_create(soccer_handle* h, const soccer_wolf
         const long v = std::atol(e);
         if (v >= 1 && v <= 4096) q->launch_steps = (int)v;
     }
+    q->grid_blocks = pop_grid_blocks_env(h);
     PhcPopIO& io = q->io;
     double* dpar[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const size_t per = (size_t)nS * kPhcRow, chunk = std::min(wpop_chunk((size_t)nS), n);
@@ -1065,7 +1085,7 @@ extern "C" int soccer_wolf_population_run(soccer_handle* h, soccer_wolf_populati
         PhcPopIO io = q->io;
         io.n_steps = n_steps - t0 < q->launch_steps ? n_steps - t0 : q->launch_steps;
         bind_tick(h, P, (uint64_t)io.n_steps);
-        HIP_TRY(h, wpop_run(h, P, io, true));
+        HIP_TRY(h, wpop_run(h, P, io, true, q->grid_blocks));
     }
     HIP_TRY(h, hipGetLastError());
     return SOCCER_OK;
@@ -1078,7 +1098,7 @@ extern "C" int soccer_wolf_population_update(soccer_handle* h, soccer_wolf_popul
         return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_update: all six transition arrays are required");
     if (!aligned(obs, 2) || !aligned(next_obs, 2)) return fail(h, SOCCER_E_INVALID, "soccer_wolf_population_update: obs / next_obs must be 2-byte aligned");
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    hipLaunchKernelGGL(phc_pop_update_kernel, dim3(grid_for(h, (uint64_t)q->n)), dim3(kBlock), 0, h->stream, q->io, (long long)q->n,
+    hipLaunchKernelGGL(phc_pop_update_kernel, dim3(pop_grid(h, q->grid_blocks, (uint64_t)q->n)), dim3(kBlock), 0, h->stream, q->io, (long long)q->n,
                        obs, act_a, act_b, reward, terminated, next_obs);
     HIP_TRY(h, hipGetLastError());
     return SOCCER_OK;

@@ -711,7 +711,9 @@ int soccer_q_population_create(soccer_handle* h, const soccer_q_population_confi
 int soccer_q_population_destroy(soccer_handle* h, soccer_q_population* q);
 /* n_steps steps of every member in ceil(n_steps / K) launches of at most K steps each (K = 4096, the rollout's own bound; the
  * environment variable SOCCER_POP_LAUNCH_STEPS, read at creation, overrides it: tests of the launch boundary), enqueued on the
- * handle's stream: no synchronisation, no copy.  Consumes n_steps ticks. */
+ * handle's stream: no synchronisation, no copy.  Consumes n_steps ticks.  A second test hook: SOCCER_POP_GRID_BLOCKS, read at
+ * creation and accepted in 1..the handle's grid cap, caps the workgroups of this population's run and update launches (tests
+ * of a thread that serves several members in turn); it changes no result. */
 int soccer_q_population_run(soccer_handle* h, soccer_q_population* q, int32_t n_steps);
 /* steps 3-6 on the caller's transitions: DEVICE arrays of n_lanes elements, transition i belongs to member i (reward is
  * player A's), with the checks and the misuse flags of soccer_q_learner_update: a bad transition leaves its member's tables
@@ -797,7 +799,8 @@ typedef struct soccer_wolf_population_state {
 int soccer_wolf_population_create(soccer_handle* h, const soccer_wolf_population_config* cfg, soccer_wolf_population** out);
 int soccer_wolf_population_destroy(soccer_handle* h, soccer_wolf_population* q);
 /* n_steps steps of every member in ceil(n_steps / K) launches (K = 4096; SOCCER_POP_LAUNCH_STEPS, read at creation, overrides
- * it as for soccer_q_population_run), enqueued on the handle's stream: no synchronisation, no copy.  Consumes n_steps ticks. */
+ * it as for soccer_q_population_run), enqueued on the handle's stream: no synchronisation, no copy.  Consumes n_steps ticks.
+ * SOCCER_POP_GRID_BLOCKS caps the grid of run and update launches as for soccer_q_population_run. */
 int soccer_wolf_population_run(soccer_handle* h, soccer_wolf_population* q, int32_t n_steps);
 /* steps 3-6 on the caller's transitions: DEVICE arrays of n_lanes elements, transition i belongs to member i (reward is
  * player A's).  A bad transition leaves its member's rows alone (its alpha and dscale still advance) and sets the misuse

@@ -77,7 +77,8 @@ def a_goal_tuple(orc):
 
 def special_state(c, orc):
     """the arguments of set_state (the oracle's and the handle's alike) that turn the lanes of a freshly reset oracle into the
-    case's mix, and masks of who is what; None for a case of plain lanes"""
+    case's mix, and masks of who is what; None for a case of plain lanes.  'frozen tail': every fifth of the last c["tail"] lanes
+    (259 where the case names none) is frozen."""
     kind = c.get("special")
     if kind is None:
         return None, {}
@@ -86,7 +87,7 @@ def special_state(c, orc):
               poss=(orc.poss & 1).astype(np.uint8), t=orc.t.copy(), needs_reset=((orc.poss >> 1) & 1).astype(np.uint8))
     frozen = np.zeros(n, bool); parked = np.zeros(n, bool); late = np.zeros(n, bool)
     if kind == "frozen tail":
-        frozen[n - 259::5] = True
+        frozen[n - c.get("tail", 259)::5] = True
     else:
         frozen[::5] = True
         rest = np.flatnonzero(~frozen)
