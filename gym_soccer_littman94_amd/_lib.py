@@ -118,6 +118,11 @@ class WolfPopulationState(C.Structure):
                [("steps", C.POINTER(C.c_uint64))]
 
 
+class MetaGameResult(C.Structure):
+    """soccer_meta_game_result: host pointers, any may be NULL"""
+    _fields_ = [(n, C.c_void_p) for n in ("value", "x", "y", "lo", "hi", "pivots", "status")]
+
+
 class MinimaxQPopulationConfig(C.Structure):
     """soccer_minimax_q_population_config"""
     _fields_ = MinimaxQConfig._fields_ + [(n, C.c_void_p) for n in (
@@ -130,6 +135,7 @@ PHC_LEARN, PHC_UNIFORM, PHC_FIXED = 0, 1, 2
 MQ_MAX_LANES = 1 << 22
 BR_MAX_POLICIES = 256
 CROSS_MAX_POLICIES = 1024
+META_MAX_POLICIES = 1024
 MISUSE_FROZEN, MISUSE_ACTION, MISUSE_OBSERVATION = 1, 2, 4
 STAGE_ACT_A, STAGE_ACT_B, STAGE_U_STEP, STAGE_U_RESET, STAGE_MASK = 1, 2, 4, 8, 16
 COMM_ID_BYTES = 128
@@ -185,6 +191,8 @@ PROTOTYPES = {
                                            C.c_void_p, C.c_void_p]),
     "soccer_cross_play": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "soccer_solve_meta_games": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                          C.POINTER(MetaGameResult)]),
     "soccer_minimax_q_create": (C.c_int, [C.c_void_p, C.POINTER(MinimaxQConfig), C.POINTER(C.c_void_p)]),
     "soccer_minimax_q_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "soccer_minimax_q_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),

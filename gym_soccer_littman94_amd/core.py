@@ -401,6 +401,24 @@ def _population_cross_play(pop, read, key_a, key_b, theta, first, count, discoun
     return pop.batch.cross_play(pa, pb, theta, float(discount_factor))
 
 
+def meta_lds_bytes(n_a, n_b):
+    """The LDS a workgroup of the meta-game's LDS kernel takes for an n_a x n_b game (include/soccer_hip.h, "the meta-game"):
+    path=1 of solve_meta_game needs this to be at most the device's limit, 163 840 bytes on gfx950."""
+    stride = (n_a + n_b + 2) | 1
+    return 128 + 8 * ((n_a + 2) * stride + n_a + 1) + 4 * n_a
+
+
+def _meta_of_cross_play(batch, payoff, iterations, max_pivots):
+    """cross-play's dict (planners.cross_play) plus the solved meta-game and what mixing buys player A"""
+    row_min, col_max = payoff.min(1), payoff.max(0)
+    out = {"payoff": payoff, "iterations": iterations, "row_min": row_min, "col_max": col_max,
+           "bounds": (float(row_min.max()), float(col_max.min()))}
+    m = batch.solve_meta_game(payoff, max_pivots=max_pivots)
+    out.update({k: m[k] for k in ("x", "y", "value", "lo", "hi", "status")})
+    out["gain"] = out["lo"] - out["bounds"][0]
+    return out
+
+
 class QPopulation:
     """A population of independent Q-learners on a two-player auto-reset SoccerBatch, a learner per lane: member i has its own
     Q_a[nS, 5], Q_b[nS, 5] and alpha and learns from lane i alone (include/soccer_hip.h, "learners, a population of
@@ -492,6 +510,11 @@ class QPopulation:
         SoccerBatch.cross_play on the one-hot greedy policies of members first .. first + count - 1 (at most 1024).
         discount_factor None: the range's common discount, ValueError if the members differ."""
         return _population_cross_play(self, self.read, "pi_a", "pi_b", theta, first, count, discount_factor)
+
+    def meta_game(self, theta=1e-10, first=0, count=None, discount_factor=None, max_pivots=None):
+        """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
+        opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
+        return _meta_of_cross_play(self.batch, *self.cross_play(theta, first, count, discount_factor), max_pivots)
 
     def load(self, Q_a=None, Q_b=None, alpha=None, steps=None, first=0):
         """Resume members first .. first + count - 1 from a checkpoint: Q_a / Q_b [count, nS, 5] in [-1, 1] and alpha[count]
@@ -807,6 +830,11 @@ class WolfPopulation:
         return _population_cross_play(self, lambda f, c: self._read(f, c, (which + "_a", which + "_b")), which + "_a", which + "_b",
                                       theta, first, count, discount_factor)
 
+    def meta_game(self, which="pi", theta=1e-10, first=0, count=None, discount_factor=None, max_pivots=None):
+        """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
+        opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
+        return _meta_of_cross_play(self.batch, *self.cross_play(which, theta, first, count, discount_factor), max_pivots)
+
     def load(self, Q_a=None, Q_b=None, pi_a=None, pi_b=None, avg_a=None, avg_b=None, updates=None, alpha=None, dscale=None, steps=None,
              first=0):
         """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged): the
@@ -999,6 +1027,11 @@ class MinimaxQPopulation:
         discount_factor None: the range's common discount, ValueError if the members differ."""
         return _population_cross_play(self, lambda f, c: self._read(f, c, ("pi_a", "pi_b")), "pi_a", "pi_b", theta, first, count,
                                       discount_factor)
+
+    def meta_game(self, theta=1e-10, first=0, count=None, discount_factor=None, max_pivots=None):
+        """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
+        opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
+        return _meta_of_cross_play(self.batch, *self.cross_play(theta, first, count, discount_factor), max_pivots)
 
     def load(self, Q=None, V=None, pi_a=None, pi_b=None, alpha=None, steps=None, first=0):
         """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged):
@@ -1325,6 +1358,39 @@ class SoccerBatch:
         try:
             self._check(code)
         except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
+            e.results = out
+            raise
+        return out
+
+    def solve_meta_game(self, payoff, max_pivots=None, path=0, pivots_per_sync=0):
+        """The maximin mixtures of zero-sum matrix games of any shape up to 1024 a side (include/soccer_hip.h, "the meta-game"):
+        payoff is [n_a, n_b] or [g, n_a, n_b], the row player's (the maximiser's) payoffs, for instance cross_play's matrix.
+        Returns a dict (a [g, ..] input: arrays with a leading g): x[n_a] and y[n_b] the two mixtures, lo = min_j (x @ payoff)_j
+        what x guarantees, hi = max_i (payoff @ y)_i what y concedes at most, value their midpoint, gap = hi - lo, pivots,
+        status (1 saddle point, 0 gap <= 1e-10 * max(1, max|payoff|), 2 finished but wider, 3 stopped at max_pivots) and
+        certified = status <= 1.  lo <= the game's value <= hi holds whatever the status.  max_pivots None: 100 * (n_a + n_b).
+        path: 0 the library chooses, 1 the LDS kernel (AssertionError if the game does not fit, meta_lds_bytes), 2 the global
+        kernels; pivots_per_sync: 0 the library chooses — no result depends on either.
+        RuntimeError if a game stopped at max_pivots (its .results holds the dict: the last basis and its valid bracket)."""
+        A = np.ascontiguousarray(payoff, np.float64)
+        assert A.ndim in (2, 3), "payoff must be [n_a, n_b] or [g, n_a, n_b]"
+        single = A.ndim == 2
+        g = 1 if single else A.shape[0]
+        n_a, n_b = A.shape[-2:]
+        if max_pivots is None:
+            max_pivots = 100 * (n_a + n_b)
+        out = {"value": np.zeros(g), "x": np.zeros((g, n_a)), "y": np.zeros((g, n_b)), "lo": np.zeros(g), "hi": np.zeros(g),
+               "pivots": np.zeros(g, np.int32), "status": np.zeros(g, np.int32)}
+        res = _lib.MetaGameResult(**{k: v.ctypes.data for k, v in out.items()})
+        code = self.lib.soccer_solve_meta_games(self.h, g, n_a, n_b, A.ctypes.data, int(max_pivots), int(path), int(pivots_per_sync),
+                                                C.byref(res))
+        out["gap"] = out["hi"] - out["lo"]
+        out["certified"] = out["status"] <= 1
+        if single:
+            out = {k: v[0] for k, v in out.items()}
+        try:
+            self._check(code)
+        except RuntimeError as e:               # a game stopped at the cap (or a capture): what was reached goes with the exception
             e.results = out
             raise
         return out

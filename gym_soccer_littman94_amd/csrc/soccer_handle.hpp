@@ -5,6 +5,7 @@
 //   soccer_step.hip      batched_step*
 //   soccer_rollout.hip   batched_rollout*
 //   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, cross-play, the matrix-game solver
+//   soccer_metagame.hip  soccer_solve_meta_games: the maximin mixtures of n_a x n_b matrix games
 //   soccer_learners.hip  the minimax-Q learner, the independent Q-learners, the policy hill-climbers, the three kinds of populations
 //   soccer_comm.hip      the RCCL wrapper (host code only)
 //
@@ -204,6 +205,16 @@ struct soccer_handle {
     double* cx_values = nullptr;            // [cx_stride][nS] V of the pass in the caller's order (cx_has_values: allocated)
     int cx_policies = 0, cx_stride = 0; bool cx_has_values = false;
     OwnedBufs cx_bufs{"the cross-play solver"};
+    // soccer_solve_meta_games: one pass's buffers, allocated on first use and again when a pass needs more of any, see meta_buffers
+    double* mg_A = nullptr;                 // [games][n_a][n_b] the caller's matrices
+    double* mg_T = nullptr;                 // [games][n_a + 1][stride] the tableaux (the global path only)
+    double* mg_x = nullptr; double* mg_y = nullptr;   // [games][n_a], [games][n_b]
+    double* mg_fcol = nullptr; double* mg_prow = nullptr;   // [games][n_a + 1], [games][stride] the side buffers of a pivot
+    int32_t* mg_basis = nullptr;            // [games][n_a]
+    double* mg_scal = nullptr;              // [4][games] value, lo, hi, max |A|
+    int32_t* mg_int = nullptr;              // [games][kMetaRec] the records, then [games] pivots, [games] status, the open count
+    size_t mg_need[5] = {0, 0, 0, 0, 0};    // what the buffers hold, in meta_need's order
+    OwnedBufs mg_bufs{"the meta-game solver"};
     std::vector<soccer_minimax_q*> learners; // soccer_minimax_q_create: the learners that were not destroyed (freed with the handle)
     std::vector<soccer_q_learner*> q_learners; // soccer_q_learner_create: the same for the independent Q-learners
     std::vector<soccer_wolf_phc*> phc_learners; // soccer_wolf_phc_create: the same for the policy hill-climbers

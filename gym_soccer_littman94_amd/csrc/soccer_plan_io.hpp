@@ -92,4 +92,31 @@ struct CrossFinishIO {
     int32_t n_isd, nS, stride, pairs, max_sweeps;
 };
 
+// a pass of n_a x n_b zero-sum matrix games (soccer_solve_meta_games): the record of a game, and what every kernel of
+// soccer_metagame_kernels.hpp is given
+constexpr int kMetaRec = 8;
+enum MetaRecWord : int {
+    kMetaClosed = 0,                 // 0 while the game pivots, 1 once it has stopped
+    kMetaStatus = 1,                 // 1 saddle point, 3 stopped at the cap, -1 finished (0 or 2 once the bracket is known)
+    kMetaPivots = 2,
+    kMetaCol = 3, kMetaRow = 4,      // the pivot the next update applies
+    kMetaIStar = 5, kMetaJStar = 6,  // the saddle point
+};
+struct MetaIO {
+    const double* A;                 // [games][n_a][n_b] the caller's matrices
+    double* T;                       // [games][rows][stride] the tableaux (the global path; the LDS path keeps them in LDS)
+    double* prow;                    // [games][stride] the scaled pivot row
+    double* fcol;                    // [games][rows] the pivot column before the update: every row's factor
+    int32_t* basis;                  // [games][n_a]
+    int32_t* rec;                    // [games][kMetaRec]
+    double* amax;                    // [games] max |A|
+    double* x; double* y;            // [games][n_a], [games][n_b]
+    double* value; double* lo; double* hi;          // [games]
+    int32_t* pivots; int32_t* status;               // [games]
+    int32_t* open;                   // meta_count_kernel adds the games still pivoting
+    int32_t n_a, n_b;
+    int32_t rows, cols, stride;      // n_a + 1, n_a + n_b + 2, cols rounded up to an odd number
+    int32_t max_pivots, games;
+};
+
 }  // namespace soccer

@@ -511,6 +511,11 @@ class VectorSoccerEnv:
         assert self.multiagent, "cross_play needs a two-player environment (no player with a fixed policy)"
         return self._batch.cross_play(pi_a, pi_b, theta, discount_factor, **params)
 
+    def solve_meta_game(self, payoff, **params):
+        """The maximin mixtures of zero-sum matrix games, cross_play's for instance (SoccerBatch.solve_meta_game): nothing to do
+        with the pitch, so any environment will do; consumes no tick, leaves the lanes alone."""
+        return self._batch.solve_meta_game(payoff, **params)
+
     @property
     def reward_int8(self):
         """device io: player A's reward of the last step as the int8 tensor the kernel wrote (-1 / 0 / +1), no cast

@@ -255,3 +255,17 @@ def cross_play(env, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000):
     row_min, col_max = payoff.min(1), payoff.max(0)
     return {"payoff": payoff, "iterations": it, "row_min": row_min, "col_max": col_max,
             "bounds": (float(row_min.max()), float(col_max.min()))}
+
+
+def meta_game(env, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000, max_pivots=None):
+    """cross_play followed by the solve of its meta-game, both on the device (include/soccer_hip.h, "the meta-game"): which
+    mixture of player A's policies can a rational mixture of player B's not beat?  Returns cross_play's dict plus
+      x [n_a], y [n_b]  the maximin mixture of A's policies and the minimax mixture of B's
+      lo, hi, value     what x guarantees, what y concedes at most (lo <= the meta-game's value <= hi), their midpoint
+      status            1 saddle point, 0 hi - lo <= 1e-10 * max(1, max|payoff|), 2 finished but wider
+      gain              lo - bounds[0]: what mixing buys player A over the best single policy
+    max_pivots None: 100 * (n_a + n_b); RuntimeError if the solve stops there."""
+    from .core import _meta_of_cross_play
+    batch = _two_player_batch(env, "meta_game")
+    payoff, it = batch.cross_play(pi_a, pi_b, theta, discount_factor, max_sweeps=max_sweeps)
+    return _meta_of_cross_play(batch, payoff, it, max_pivots)

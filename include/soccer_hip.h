@@ -64,7 +64,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_*, soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies, soccer_cross_play and soccer_rollout_shape were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_*, soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies, soccer_cross_play, soccer_solve_meta_games and soccer_rollout_shape were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -462,6 +462,61 @@ int soccer_evaluate_policies(soccer_handle* h, int32_t n_pairs, const double* pi
 int soccer_cross_play(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t n_b, const double* pi_b,
                       double theta, double discount_factor, int32_t max_sweeps, int32_t pairs_per_pass,
                       double* payoff, double* V, int32_t* iterations);
+/* ---- the meta-game: maximin mixtures of n_a x n_b zero-sum matrix games (any handle) ------------------------------------
+ * Which mixture of the rows of a payoff matrix (soccer_cross_play's, or any other) can a rational opponent not beat?
+ * A is HOST [n_games][n_a][n_b], the row player's (the maximiser's) payoffs.  Per game, in float64, nothing contracted
+ * (a product and the sum that takes it are two roundings), every reduction with an index tie-break, so that no bit
+ * depends on how the work is spread over threads:
+ *  1. Saddle point.  rmin[i] = min_j A[i][j], cmax[j] = max_i A[i][j].  If max_i rmin == min_j cmax: i* is the first row
+ *     attaining it, j* the first column, x = e_i*, y = e_j*, value = lo = hi = A[i*][j*] bit for bit, status 1, 0 pivots.
+ *  2. Tableau.  lo_A = min A, range = max A - lo_A (> 0 here).  n_a + 1 rows, n_b + n_a + 2 columns: the structural
+ *     columns T[i][j] = (A[i][j] - lo_A) / range + 1.0, the slack identity, the right-hand side R = 1.0, and a SHADOW
+ *     right-hand side S[i] = 1.0 + (i + 1) * 2^-26 (exact); the objective row is -1.0 under the structural columns and
+ *     0.0 elsewhere; basis[i] = n_b + i.
+ *  3. Pivot.  c = the column among the first n_a + n_b with the smallest objective entry, lowest index on ties
+ *     (Dantzig); the game is finished unless that entry is < -1e-12; if pivots == max_pivots, stop with status 3; r =
+ *     among the rows with T[i][c] > 1e-12 the one with the smallest T[i][R] / T[i][c], ties (equal quotients) to the
+ *     smallest T[i][S] / T[i][c], then to the lowest i (no such row: impossible for a positive matrix, kept as a guard:
+ *     stop with status 3).  row' = T[r][.] / T[r][c] with row'[c] =
+ *     1.0; every other row, the objective included, becomes T[i][j] - T[i][c] * row'[j] over all columns, R and S too,
+ *     with T[i][c] = 0.0 afterwards — no row is skipped because its factor is 0, which fixes the signs of zeros;
+ *     basis[r] = c.
+ *  4. Strategies.  y[j] = max(T[r][R], 0) where basis[r] == j, else 0; x[i] = max(T[objective][n_b + i], 0); each divided
+ *     by its sequential sum in index order from 0.0; a sum that is not positive gives the uniform strategy.
+ *  5. Bracket, on the caller's A.  lo = min_j sum_i x[i] * A[i][j], hi = max_i sum_j A[i][j] * y[j], the sums sequential
+ *     from 0.0 in index order (acc = acc + p * q); value = 0.5 * (lo + hi); with eps = 1e-10 * max(1, max|A|) a finished
+ *     game has status 0 when hi - lo <= eps, else status 2.
+ * The shadow column only breaks the ratio test's ties (all-ones right-hand sides with tied or duplicated policies are
+ * heavily degenerate): the quotients of the true column R come first, because a ratio test on the shadow column alone
+ * lets entries of R go negative by the size of the perturbation, and the clipped strategies then certify a bracket that
+ * wide.  The strategies are read from R.  The rule is no proof against cycling: max_pivots and status 3 are.  The contract is the certificate: lo <= the game's value <= hi holds for whatever x and y come out (a
+ * tableau updated tens of thousands of times drifts: there is no reinversion), and the status says whether the bracket is
+ * as narrow as eps.
+ * n_a and n_b are 1 .. SOCCER_META_MAX_POLICIES, n_games >= 0 (0 returns SOCCER_OK at once), max_pivots >= 1.  A NaN or
+ * infinite entry is SOCCER_E_INVALID, found on the host before anything is uploaded; the message names the game, the row
+ * and the column.  path: 0 the library chooses, 1 the LDS kernel (a workgroup per game, the tableau in LDS, one launch;
+ * SOCCER_E_INVALID "does not fit" unless 128 + 8 * ((n_a + 2) * stride + n_a + 1) + 4 * n_a bytes, stride = (n_a + n_b + 2)
+ * rounded up to an odd number, are at most the LDS a workgroup may be given: 163 840 bytes on gfx950, so 99 x 99 fits
+ * and 100 x 100 does not), 2 the global kernels (the tableaux in device memory, two launches per pivot).
+ * pivots_per_sync >= 0: how many pivots the global path enqueues before it reads back how many games are still open (0:
+ * the library chooses).  Games are solved in passes whose matrices and tableaux stay at or under 1 GiB.  Game g of a
+ * batch returns the bits it returns alone, and no result depends on path or pivots_per_sync.
+ * SOCCER_E_STATE when some game stopped at max_pivots (status 3): its outputs hold the strategies of the last basis and
+ * their (valid) bracket, and the other games are complete.  Like soccer_solve_matrix_games the call has nothing to do with
+ * the pitch: any handle will do, it consumes no tick, leaves the lanes alone and returns SOCCER_E_STATE during a graph
+ * capture.  A NULL `out` asks for nothing. */
+#define SOCCER_META_MAX_POLICIES 1024
+typedef struct soccer_meta_game_result {   /* HOST pointers, any may be NULL */
+    double*  value;    /* [n_games]            midpoint of the bracket */
+    double*  x;        /* [n_games][n_a]       row player's (the maximiser's) mixture */
+    double*  y;        /* [n_games][n_b]       column player's mixture */
+    double*  lo;       /* [n_games]            min_j (x^T A)_j : what x guarantees */
+    double*  hi;       /* [n_games]            max_i (A y)_i   : what y concedes at most */
+    int32_t* pivots;   /* [n_games] */
+    int32_t* status;   /* [n_games]  1 saddle point, 0 finished and hi - lo <= eps, 2 finished but wider, 3 stopped at max_pivots */
+} soccer_meta_game_result;
+int soccer_solve_meta_games(soccer_handle* h, int64_t n_games, int32_t n_a, int32_t n_b, const double* A /* HOST [n_games][n_a][n_b] */,
+                            int32_t max_pivots, int32_t path, int32_t pivots_per_sync, const soccer_meta_game_result* out);
 /* ---- learners (two-player handles; minimax-Q, Littman 1994) ------------------------------------------------------
  * A learner lives on a two-player SOCCER_F_AUTORESET handle of at most 2^22 lanes and keeps ONE shared table
  * Q[n_states][5][5] (float64) on the device, with V[n_states] = val(Q[s]) and the stage-game strategies
