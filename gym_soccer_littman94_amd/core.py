@@ -1371,6 +1371,7 @@ class SoccerBatch:
         certified = status <= 1.  lo <= the game's value <= hi holds whatever the status.  max_pivots None: 100 * (n_a + n_b).
         path: 0 the library chooses, 1 the LDS kernel (AssertionError if the game does not fit, meta_lds_bytes), 2 the global
         kernels; pivots_per_sync: 0 the library chooses — no result depends on either.
+        AssertionError for an entry that is not finite and for a game whose max - min is not finite (1e308 and -1e308).
         RuntimeError if a game stopped at max_pivots (its .results holds the dict: the last basis and its valid bracket)."""
         A = np.ascontiguousarray(payoff, np.float64)
         assert A.ndim in (2, 3), "payoff must be [n_a, n_b] or [g, n_a, n_b]"

@@ -62,10 +62,18 @@ extern "C" int soccer_solve_meta_games(soccer_handle* h, int64_t n_games, int32_
     if (n_games == 0) return SOCCER_OK;
     if (!A) return fail(h, SOCCER_E_INVALID, "A is NULL");
     const size_t cells = (size_t)n_a * n_b;
-    for (int64_t g = 0; g < n_games; ++g)
-        for (size_t k = 0; k < cells; ++k)
-            if (!std::isfinite(A[(size_t)g * cells + k]))
+    for (int64_t g = 0; g < n_games; ++g) {
+        const double* a = A + (size_t)g * cells;
+        double lo_a = a[0], hi_a = a[0];
+        for (size_t k = 0; k < cells; ++k) {
+            if (!std::isfinite(a[k]))
                 return fail(h, SOCCER_E_INVALID, "%s: A[game %lld][row %d][column %d] is not finite", what, (long long)g, (int)(k / n_b), (int)(k % n_b));
+            lo_a = a[k] < lo_a ? a[k] : lo_a;
+            hi_a = a[k] > hi_a ? a[k] : hi_a;
+        }
+        if (!std::isfinite(hi_a - lo_a))                                // the tableau would divide by it
+            return fail(h, SOCCER_E_INVALID, "%s: A[game %lld]: max A - min A is not finite (%g - %g)", what, (long long)g, hi_a, lo_a);
+    }
     const size_t lds = meta_lds_bytes(n_a, n_b);
     const bool fits = lds <= h->lds_limit;
     if (path == 1 && !fits)

@@ -494,7 +494,9 @@ int soccer_cross_play(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t
  * as narrow as eps.
  * n_a and n_b are 1 .. SOCCER_META_MAX_POLICIES, n_games >= 0 (0 returns SOCCER_OK at once), max_pivots >= 1.  A NaN or
  * infinite entry is SOCCER_E_INVALID, found on the host before anything is uploaded; the message names the game, the row
- * and the column.  path: 0 the library chooses, 1 the LDS kernel (a workgroup per game, the tableau in LDS, one launch;
+ * and the column.  A game whose max A - min A is not finite (finite entries further apart than DBL_MAX, such as 1e308 and
+ * -1e308: step 2 would divide by it) is SOCCER_E_INVALID as well, saddle point or not, found in the same loop; the
+ * message names the game.  Entries of +-8e307 are accepted.  path: 0 the library chooses, 1 the LDS kernel (a workgroup per game, the tableau in LDS, one launch;
  * SOCCER_E_INVALID "does not fit" unless 128 + 8 * ((n_a + 2) * stride + n_a + 1) + 4 * n_a bytes, stride = (n_a + n_b + 2)
  * rounded up to an odd number, are at most the LDS a workgroup may be given: 163 840 bytes on gfx950, so 99 x 99 fits
  * and 100 x 100 does not), 2 the global kernels (the tableaux in device memory, two launches per pivot).

@@ -1,7 +1,9 @@
 """Where there is no GPU: soccer_solve_meta_games is part of the C ABI and checks its handle first, and the numpy restatement
 of its definition (tests/meta_game_np.py), which tests/test_gpu_meta_game.py pins the device to bit for bit, solves games:
 known ones exactly, 5 x 5 ones like the host build of soccer_games.hpp, larger ones like scipy's HiGHS, and under a pivot cap
-it stops where it is told with a bracket that still holds."""
+it stops where it is told with a bracket that still holds.  The edges (mg.EDGE_SHAPES: shapes at the kernels' thread and tile
+boundaries, tie-heavy games, games with closed-form values, numeric edges) finish, reach the ties they are there for, bracket
+their known values and scale exactly by powers of two; a range that overflows is refused.  None of that needs scipy."""
 import ctypes as C
 import os
 import re
@@ -157,3 +159,103 @@ def test_the_pivot_cap():
     r = mg.solve(A, need)
     assert r["status"] == 0 and r["pivots"] == need
     assert all(np.array_equal(r[k], full[k]) for k in ("x", "y", "value", "lo", "hi"))
+
+
+# ---- the edges: what tests/test_gpu_meta_game_edges.py holds the device to, checked here for what it computes -------------
+_edge = {}
+
+
+def edge_ref(name):
+    if name not in _edge:
+        _edge[name] = mg.solve(mg.edge(name))
+    return _edge[name]
+
+
+def test_the_edge_list_holds_what_it_is_there_for():
+    """the boundary shapes by their strides and rows, the fit rule as the list assumes it, and the families' sizes"""
+    shapes = {name: mg.edge(name).shape for name, _, _ in mg.EDGE_SHAPES}
+    assert len(shapes) == len(mg.EDGE_SHAPES), "a name twice"
+    stride = {name: (a + b + 2) | 1 for name, (a, b) in shapes.items()}
+    assert stride["15x238"] == 255 and stride["16x238"] == 257 and stride["127x127"] == 257 and stride["128x128"] == 259
+    assert stride["17x494"] == stride["494x17"] == 513
+    for n in (255, 256, 257):
+        assert shapes["%dx2" % n] == (n, 2) and shapes["2x%d" % n] == (2, n)
+    assert shapes["257x257-integer"] == (257, 257) and shapes["1024x2"] == (1024, 2) and shapes["3x1024"] == (3, 1024)
+    assert shapes["1x1024"] == (1, 1024) and shapes["1024x1"] == (1024, 1)
+    assert mg.lds_bytes(2, 1024) == 33088 and mg.lds_bytes(3, 1024) == 41332
+    LIMIT = 163840
+    fit = {name for name, (a, b) in shapes.items() if mg.lds_bytes(a, b) <= LIMIT}
+    for name in ("15x238", "16x238", "2x255", "2x256", "2x257", "17x494", "2x1024", "3x1024", "1x1024", "identity-99", "cyclic-99"):
+        assert name in fit, name
+    for name in ("127x127", "128x128", "255x2", "256x2", "257x2", "257x257-integer", "494x17", "1024x2", "1024x3", "1024x1",
+                 "identity-100", "cyclic-101", "block-5x20"):
+        assert name not in fit, name
+    for n in (3, 64, 99, 100, 257):
+        assert shapes["identity-%d" % n] == (n, n)
+    for n in (5, 63, 99, 101, 255):
+        A = mg.edge("cyclic-%d" % n)
+        assert A.shape == (n, n) and np.array_equal(A, -A.T) and (np.abs(A).sum(1) == n - 1).all()
+    for n in (99, 255):
+        A = mg.edge("shuffled-cyclic-%d" % n)
+        assert A.shape == (n, n) and (np.abs(A).sum(1) == n - 1).all() and (A.sum(0) == 0).all() and (A.sum(1) == 0).all()
+    assert shapes["diagonal-40"] == (40, 40) and shapes["block-6x10"] == (60, 60) and shapes["block-5x20"] == (100, 100)
+    for m, seed in ((6, 100), (5, 127)):
+        assert np.abs(mg.block_base(m, seed)).max() <= 2 and mg.solve(mg.block_base(m, seed))["pivots"] > 0
+
+
+@pytest.mark.parametrize("name", [s[0] for s in mg.EDGE_SHAPES])
+def test_an_edge_game_finishes_with_mixtures_and_brackets_its_known_value(name):
+    A = mg.edge(name)
+    r = edge_ref(name)
+    known = mg.known_value(name)
+    print("%s: %d pivots, %d ties, status %d, lo %r, hi %r, known %r" % (name, r["pivots"], r["ties"], r["status"], r["lo"], r["hi"], known))
+    assert r["status"] in (0, 1)
+    assert (r["x"] >= 0).all() and (r["y"] >= 0).all() and abs(r["x"].sum() - 1) <= 1e-12 and abs(r["y"].sum() - 1) <= 1e-12
+    kind = next(s[1] for s in mg.EDGE_SHAPES if s[0] == name)
+    if kind == "cyclic":
+        assert r["ties"] >= A.shape[0] // 2 - 2
+    if kind == "block":
+        assert r["ties"] == r["pivots"] > 0
+    if name == "257x257-integer":
+        assert r["ties"] > 0
+    # in cyclic and block games the shadow quotient orders the tied rows as their indices do; these are the games in which it
+    # decides against the index, within a wave and across waves: a reduction that dropped or mixed up the middle key differs
+    if name in ("128x128", "257x257-integer", "shuffled-cyclic-99", "shuffled-cyclic-255"):
+        assert r["decided"] > r["across"] > 0 and r["ties"] >= r["decided"]
+    if known is not None:
+        m = mg.value_margin(A)
+        assert r["lo"] - m <= known[0] and known[1] <= r["hi"] + m
+    else:
+        assert kind not in ("identity", "cyclic", "shuffled-cyclic", "diagonal", "block")
+
+
+def test_the_saddle_point_of_minus_zeros_returns_minus_zero():
+    r = edge_ref("minus-zeros")
+    assert r["status"] == 1 and r["pivots"] == 0
+    for k in ("value", "lo", "hi"):
+        assert r[k] == 0.0 and np.signbit(r[k]), k
+
+
+@pytest.mark.parametrize("k", mg.SCALES)
+def test_a_power_of_two_scales_the_bracket_and_nothing_else(k):
+    """(A - min A) / range is the same tableau to the bit, so are the pivots and the mixtures; lo and hi are sums of products
+    with A and scale exactly; both branches of eps = 1e-10 * max(1, max|A|) are taken"""
+    one, r = edge_ref("7x9"), edge_ref("7x9*2^%d" % k)
+    assert np.array_equal(mg.edge("7x9*2^%d" % k), np.ldexp(mg.edge("7x9"), k)) and one["pivots"] > 0
+    assert r["pivots"] == one["pivots"] and r["status"] == one["status"] == 0
+    assert np.array_equal(r["x"], one["x"]) and np.array_equal(r["y"], one["y"])
+    assert r["lo"] == np.ldexp(one["lo"], k) and r["hi"] == np.ldexp(one["hi"], k)
+    assert (mg.eps_of(mg.edge("7x9*2^%d" % k)) == 1e-10) == (k < 0)
+
+
+def test_a_range_that_overflows_is_refused():
+    """finite entries whose max - min is inf would put inf / inf = NaN into the tableau; the largest range that works stays"""
+    assert np.isfinite(mg.OVERFLOWING).all()
+    with pytest.raises(ValueError, match="max A - min A is not finite"):
+        mg.solve(mg.OVERFLOWING)
+    with pytest.raises(ValueError, match="max A - min A is not finite"):
+        mg.solve(np.array([[1e308, -1e308]]))                           # a saddle point, refused all the same
+    with pytest.raises(ValueError, match="max A - min A is not finite"):
+        mg.solve_batch(np.stack([np.eye(2), mg.OVERFLOWING, np.eye(2)]))
+    r = edge_ref("8e307")
+    assert r["pivots"] == 2 and r["status"] == 0
