@@ -1287,11 +1287,18 @@ class SoccerBatch:
 
     def minimax_value_iteration(self, theta, discount_factor, max_sweeps=1000000):
         """Minimax value iteration from V = 0 until max|V_k - V_{k-1}| < theta: (pi_a[nS, 5], pi_b[nS, 5], V_k,
-        Q_k[nS, 5, 5], k), with V_k = val(Q_k) and the strategies those of Q_k.  RuntimeError if max_sweeps is reached."""
+        Q_k[nS, 5, 5], k), with V_k = val(Q_k) and the strategies those of Q_k.  RuntimeError if max_sweeps is reached (its
+        .results holds the tuple of sweep max_sweeps, which the library has copied out before it fails; a RuntimeError for
+        another reason, such as a graph capture, carries a .results too, which then means nothing)."""
         pa, pb, V, Q = self._minimax_out()
         it = C.c_int32()
-        self._check(self.lib.soccer_minimax_value_iteration(self.h, float(theta), float(discount_factor), int(max_sweeps),
-                                                            V.ctypes.data, Q.ctypes.data, pa.ctypes.data, pb.ctypes.data, C.byref(it)))
+        code = self.lib.soccer_minimax_value_iteration(self.h, float(theta), float(discount_factor), int(max_sweeps),
+                                                       V.ctypes.data, Q.ctypes.data, pa.ctypes.data, pb.ctypes.data, C.byref(it))
+        try:
+            self._check(code)
+        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
+            e.results = (pa, pb, V, Q, int(it.value))
+            raise
         return pa, pb, V, Q, int(it.value)
 
     # -- best responses to mixed policies (two-player handles) ----------------------------------------

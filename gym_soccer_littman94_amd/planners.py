@@ -210,7 +210,8 @@ def minimax_q_population(env, n_steps, discount_factor, alpha=1.0, decay=None, e
 def minimax_value_iteration(env, theta, discount_factor, max_sweeps=1000000):
     """Minimax (Shapley) value iteration of the two-player game on the device, Littman (1994)'s equilibrium values.
     Returns (pi_a[nS, 5], pi_b[nS, 5], V, Q[nS, 5, 5], iterations): player A's maximin and player B's minimax stage-game
-    strategies, ready for VectorSoccerEnv.rollout(sample_actions=True, mixed_policies={...})."""
+    strategies, ready for VectorSoccerEnv.rollout(sample_actions=True, mixed_policies={...}).  RuntimeError if max_sweeps is
+    reached: the handle's exception passes through, its .results holding the tuple of sweep max_sweeps."""
     from .core import SoccerBatch
     if isinstance(env, SoccerBatch):
         b = env

@@ -44,7 +44,7 @@ def sets(w, h, slip, n_a, n_b):
     return policy_set(w, h, slip, n_a, 31), policy_set(w, h, slip, n_b, 32)
 
 
-def pairwise(b, A, B, max_sweeps=1000000):
+def pairwise(b, A, B, max_sweeps=1000000, theta=THETA, gamma=GAMMA):
     """the same matrix through evaluate_policies, 256 pairs a call: (payoff, iterations, V)"""
     na, nb = len(A), len(B)
     ii, jj = np.divmod(np.arange(na * nb), nb)
@@ -52,7 +52,7 @@ def pairwise(b, A, B, max_sweeps=1000000):
     for c in range(0, na * nb, 256):
         s = slice(c, c + 256)
         try:
-            V[s], it[s] = b.evaluate_policies(A[ii[s]], B[jj[s]], THETA, GAMMA, max_sweeps=max_sweeps)
+            V[s], it[s] = b.evaluate_policies(A[ii[s]], B[jj[s]], theta, gamma, max_sweeps=max_sweeps)
         except RuntimeError as e:
             V[s], it[s] = e.results
     starts = kickoff_states(b)
