@@ -135,6 +135,7 @@ PHC_LEARN, PHC_UNIFORM, PHC_FIXED = 0, 1, 2
 MQ_MAX_LANES = 1 << 22
 BR_MAX_POLICIES = 256
 CROSS_MAX_POLICIES = 1024
+LEAGUE_MAX_POLICIES = 1024
 META_MAX_POLICIES = 1024
 MISUSE_FROZEN, MISUSE_ACTION, MISUSE_OBSERVATION = 1, 2, 4
 STAGE_ACT_A, STAGE_ACT_B, STAGE_U_STEP, STAGE_U_RESET, STAGE_MASK = 1, 2, 4, 8, 16
@@ -217,6 +218,10 @@ PROTOTYPES = {
     "soccer_q_population_update": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
     "soccer_q_population_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.POINTER(C.c_uint64)]),
     "soccer_q_population_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 3 + [C.POINTER(C.c_uint64)]),
+    "soccer_q_population_create_league": (C.c_int, [C.c_void_p, C.POINTER(QPopulationConfig), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(C.c_void_p)]),
+    "soccer_q_population_league_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "soccer_q_population_league_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "soccer_wolf_population_create": (C.c_int, [C.c_void_p, C.POINTER(WolfPopulationConfig), C.POINTER(C.c_void_p)]),
     "soccer_wolf_population_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "soccer_wolf_population_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),

@@ -355,10 +355,39 @@ class QLearner:
             pass
 
 
-def q_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
+def league_config(nS, act_a, act_b, league_policies, league_weights):
+    """Checks a league (AssertionError, before any library call): exactly one of act_a / act_b is "league", and then
+    league_policies is [K, nS, 5] rows summing to 1 and league_weights [K] values >= 0 summing to 1, K in 1 .. 1024.
+    Returns None without a league, else (player, K, policies, weights) with the arrays contiguous float64."""
+    sides = [isinstance(a, str) and a == "league" for a in (act_a, act_b)]
+    if not any(sides):
+        assert league_policies is None and league_weights is None, "league_policies / league_weights go with act_a or act_b = 'league'"
+        return None
+    assert not all(sides), "exactly one player may be a league, not both"
+    assert league_policies is not None and league_weights is not None, "a league needs league_policies [K, n_states, 5] and league_weights [K]"
+    pol = np.ascontiguousarray(league_policies, np.float64)
+    w = np.ascontiguousarray(league_weights, np.float64)
+    assert pol.ndim == 3 and pol.shape[1:] == (int(nS), 5), "league_policies must be [K, n_states, 5]"
+    K = pol.shape[0]
+    assert 1 <= K <= _lib.LEAGUE_MAX_POLICIES, "a league holds 1 .. %d policies, not %d" % (_lib.LEAGUE_MAX_POLICIES, K)
+    assert w.shape == (K,), "league_weights must hold one weight per league policy (%d)" % K
+    bad = np.flatnonzero(~(np.isfinite(w) & (w >= 0)))
+    assert bad.size == 0, "league_weights[%d] is negative or not a finite number" % (bad[0] if bad.size else -1)
+    assert np.allclose(w.sum(), 1.0), "league_weights does not sum to 1"
+    rows = (pol >= 0).all(2) & np.isclose(pol.sum(2), 1.0)
+    bad = np.argwhere(~rows)
+    assert bad.size == 0, "league_policies[%d][%d] is not a row >= 0 summing to 1" % (tuple(bad[0]) if bad.size else (-1, -1))
+    return sides.index(True), K, pol, w
+
+
+def q_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy",
+                        league=None):
     """Checks the parameters of a population of Q-learners (AssertionError, before any library call) and returns
     (soccer_q_population_config, the arrays it points into).  discount_factor, alpha, decay and explor are scalars for every
-    member or arrays of n, one value per member."""
+    member or arrays of n, one value per member.  league: league_config's tuple, or None; its player is SOCCER_QL_FIXED
+    with a NULL policy in the config."""
+    if league is not None:                      # (the other checks see a placeholder for the league's player)
+        act_a, act_b = ("uniform", act_b) if league[0] == 0 else (act_a, "uniform")
     ranges = (("discount_factor", discount_factor, lambda x: (0.0 <= x) & (x < 1.0), "[0, 1)"),
               ("alpha", alpha, lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
               ("decay", decay, lambda x: (0.0 < x) & (x <= 1.0), "(0, 1]"),
@@ -378,6 +407,8 @@ def q_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e
     cfg = _lib.QPopulationConfig(base.discount_factor, base.alpha, base.decay, base.explor, base.q_init, base.act_a, base.act_b,
                                  base.policy_a, base.policy_b,
                                  *[None if arrays[k] is None else arrays[k].ctypes.data for k in ("alpha", "decay", "explor", "discount_factor")])
+    if league is not None:
+        setattr(cfg, "act_b" if league[0] else "act_a", _lib.QL_FIXED)
     return cfg, (pols, arrays)
 
 
@@ -425,11 +456,17 @@ class QPopulation:
     independent Q-learners").  run() enqueues and returns; read() and the properties synchronise and copy.  Whole populations
     run to gigabytes, so read(), load() and exploitability() take a range of members."""
 
-    def __init__(self, batch, discount_factor, **params):
-        cfg, keep = q_population_config(batch.n, batch.nS, discount_factor, **params)
+    def __init__(self, batch, discount_factor, league_policies=None, league_weights=None, **params):
+        lg = league_config(batch.nS, params.get("act_a", "greedy"), params.get("act_b", "greedy"), league_policies, league_weights)
+        cfg, keep = q_population_config(batch.n, batch.nS, discount_factor, league=lg, **params)
         self.batch, self.q = batch, None
+        self.league, self.n_policies = (None, 0) if lg is None else lg[:2]      # the league's player (0 = A, 1 = B) and its K
         q = C.c_void_p()
-        batch._check(batch.lib.soccer_q_population_create(batch.h, C.byref(cfg), C.byref(q)))
+        if lg is None:
+            batch._check(batch.lib.soccer_q_population_create(batch.h, C.byref(cfg), C.byref(q)))
+        else:
+            batch._check(batch.lib.soccer_q_population_create_league(batch.h, C.byref(cfg), lg[0], lg[1], lg[2].ctypes.data, lg[3].ctypes.data,
+                                                                     C.byref(q)))
         self.discount_factor = np.full(batch.n, cfg.discount_factor) if keep[1]["discount_factor"] is None else keep[1]["discount_factor"].copy()
         del keep                                   # (create has copied the parameters and the fixed policies' thresholds)
         self.q = q
@@ -515,6 +552,25 @@ class QPopulation:
         """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
         opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
         return _meta_of_cross_play(self.batch, *self.cross_play(theta, first, count, discount_factor), max_pivots)
+
+    def picks(self, first=0, count=None):
+        """A league population's picks, int32[count]: the league policy each member's lane follows until its episode ends,
+        -1 where the next step draws one.  Synchronises.  AssertionError on a population without a league."""
+        first, count = self._range(first, count)
+        b, out = self.batch, np.zeros(count, np.int32)
+        b._check(b.lib.soccer_q_population_league_read(b.h, self.q, first, count, out.ctypes.data))
+        return out
+
+    def load_picks(self, picks, first=0):
+        """Resume the picks of members first .. first + len(picks) - 1: values in -1 .. K - 1, -1 forces a draw at the next
+        step.  With read() + picks() a fresh population continues bit for bit via load() + load_picks(), mid-episode
+        included.  A refused load changes nothing."""
+        p = np.ascontiguousarray(picks, np.int32)
+        assert p.ndim == 1, "picks must be a vector, one value per member"
+        first, count = self._range(first, p.shape[0])
+        b = self.batch
+        b._check(b.lib.soccer_q_population_league_load(b.h, self.q, first, count, p.ctypes.data))
+        return self
 
     def load(self, Q_a=None, Q_b=None, alpha=None, steps=None, first=0):
         """Resume members first .. first + count - 1 from a checkpoint: Q_a / Q_b [count, nS, 5] in [-1, 1] and alpha[count]
@@ -1414,11 +1470,15 @@ class SoccerBatch:
         (epsilon-greedy on the player's own table), 'uniform', or a fixed [nS, 5] mixed policy.  Both tables always learn."""
         return QLearner(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
 
-    def q_population(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
+    def q_population(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy",
+                     league_policies=None, league_weights=None):
         """A QPopulation on this batch (two players, autoreset=True): a Q-learner per lane, each with its own tables.
         discount_factor, alpha, decay and explor are scalars or arrays of one value per lane; act_a / act_b as for
-        q_learning (a fixed policy is shared by all members)."""
-        return QPopulation(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
+        q_learning (a fixed policy is shared by all members), or — one of them — "league": that player draws one of
+        league_policies [K, nS, 5] with probability league_weights [K] at every kick-off and plays it to the end of the
+        episode (include/soccer_hip.h, "learners, a league opponent for the population of Q-learners")."""
+        return QPopulation(self, discount_factor, league_policies=league_policies, league_weights=league_weights, alpha=alpha, decay=decay,
+                           explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
 
     def wolf_phc(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
                  delta_decay=1.0, act_a="learn", act_b="learn"):

@@ -2,7 +2,8 @@
 // learner_update_kernel, learner_init_kernel; and the independent Q-learners of both players: q_act_kernel, q_reduce_kernel,
 // q_update_kernel, q_init_kernel (they share the act-and-step body, the reduce body and learner_thresholds); and the policy
 // hill-climbers on top of those: phc_act_kernel, phc_reduce_kernel, phc_update_kernel, phc_init_kernel; and the population
-// of one-actor Q-learners, a learner per lane: pop_run_kernel, pop_update_kernel, pop_init_kernel; and the population of
+// of one-actor Q-learners, a learner per lane: pop_run_kernel, pop_league_run_kernel (against a league opponent),
+// pop_update_kernel, pop_init_kernel; and the population of
 // one-actor policy hill-climbers: phc_pop_run_kernel, phc_pop_update_kernel, phc_pop_init_kernel, phc_pop_adopt_kernel; and the
 // population of one-actor minimax-Q learners, a wave per member: mq_pop_run_kernel, mq_pop_update_kernel, mq_pop_solve_kernel,
 // mq_pop_init_kernel (at the end).
@@ -22,6 +23,7 @@
 // Integer sums make the result independent of the order in which lanes arrive (float atomics would not be).
 #pragma once
 #include "soccer_kernels.hpp"
+#include "soccer_league.hpp"
 
 namespace soccer {
 
@@ -645,6 +647,102 @@ __global__ __launch_bounds__(kBlock) void pop_run_kernel(const KernelParams P, c
         }
         S.store(P, i0);
         L.alpha[i0] = alpha;
+        hist.add_totals(eps, ret, nonzero);
+    }
+    if (any_frozen) P.misuse[0] = 1u;
+    hist.flush(P);
+}
+
+// ---- a league opponent (include/soccer_hip.h, "learners, a league opponent for the population of Q-learners") ----------
+// pop_run_kernel with one word more per member: `pick`, the league policy its lane's league player follows until the
+// episode ends.  pick lives in a register over the launch (loaded once, stored once, like alpha).  The league player's
+// threshold row is one 8-byte load at (pick, s) from the [K][nS][4] table; the other player draws through pop_draw as in
+// pop_run_kernel.  A pick is drawn only under pick < 0 — the Philox block of purpose 1 at counter 2^62 + tick and the
+// bisection of the cumulative table T (soccer_league.hpp) sit inside that branch.  T stays in global memory: a lane probes
+// it at its own index (a vector load, not a scalar one), at most ten dependent loads of an 8 KB table that lives in L2
+// once per EPISODE of a lane, against one row gather per STEP; staging it in LDS would cost every workgroup K - 1 loads
+// and a barrier per launch to save those.  Unmeasured.
+struct PopLeagueIO {
+    const uint16_t* thr;                // [K][nS][4] the league policies' thresholds
+    const uint64_t* T;                  // [K - 1] the weights' cumulative thresholds, never decreasing, <= 2^32
+    int32_t* pick;                      // [n] -1: draw at the next step
+    int32_t K;
+    int32_t player;                     // 0: player A is the league, 1: player B
+};
+
+__device__ __forceinline__ uint32_t league_draw(const PopLeagueIO& G, int32_t nS, int32_t pick, uint32_t s, uint32_t h) {
+    // (K * nS * 4 <= 2^10 * 2^16 * 4: the index fits 32 bits)
+    const uint2 th = *reinterpret_cast<const uint2*>(G.thr + 4u * ((uint32_t)pick * (uint32_t)nS + s));
+    return (h >= (th.x & 0xffffu)) + (h >= (th.x >> 16)) + (h >= (th.y & 0xffffu)) + (h >= (th.y >> 16));
+}
+
+template <bool SLIP, bool LUT_LDS>
+__global__ __launch_bounds__(kBlock) void pop_league_run_kernel(const KernelParams P, const PopIO L, const PopLeagueIO G) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    HistAcc<false> hist; hist.init(P);
+    const Tables T = stage_tables<LUT_LDS>(P, smem);
+    const unsigned long long tick0 = *P.tick_in;
+    publish_tick(P, tick0, (unsigned long long)L.n_steps);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps += (unsigned long long)L.n_steps;
+    bool any_frozen = false;
+    for (unsigned long long g = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; g < P.n;
+         g += (unsigned long long)gridDim.x * kBlock) {
+        const unsigned long long i0 = P.first + g;                  // the lane, and the member
+        LaneVec<1> S; S.load(P, i0);
+        double* const tab = L.Q + (size_t)i0 * (size_t)L.nS * 10;
+        double alpha = L.alpha[i0];
+        const double decay = L.decay[i0], explor = L.explor[i0], gamma = L.gamma[i0];
+        int32_t pick = G.pick[i0];
+        uint32_t s = obs_of(T, P, S.L[0].A, S.L[0].B, S.L[0].p);
+        double row[10];
+        pop_load_row(tab, s, row);
+        int32_t ret = 0; uint32_t eps = 0u, nonzero = 0u;
+        for (int t = 0; t < L.n_steps; ++t) {
+            const unsigned long long tick = tick0 + (unsigned long long)t;
+            uint32_t words[1], awords[1];
+            lane_words<1>(P, P.lane_offset + i0, block_tick<SLIP>(tick), 0u, words);
+            lane_words<1>(P, P.lane_offset + i0, tick, 1u, awords);
+            const Draw d = draw_from_word<SLIP>(words[0], tick);
+            if (__builtin_expect(pick < 0, 0)) {                                         // kick-off: frozen and parked lanes draw too
+                uint32_t lw[1];
+                lane_words<1>(P, P.lane_offset + i0, (1ull << 62) + tick, 1u, lw);
+                pick = league_pick(G.T, G.K - 1, lw[0]);
+            }
+            const uint32_t ha = awords[0] & 0x7fffu, hb = (awords[0] >> 16) & 0x7fffu;
+            // (one branch on the league's player, not a select per action: with selects the slip-0 instantiations kept a
+            // dead 68-byte frame — a scalar tuple the allocator planned to spill and then reloaded from the kernel arguments)
+            uint32_t a, b;
+            if (G.player == 0) { a = league_draw(G, L.nS, pick, s, ha); b = pop_draw(L, 1, row, s, explor, hb); }   // (wave-uniform)
+            else { a = pop_draw(L, 0, row, s, explor, ha); b = league_draw(G, L.nS, pick, s, hb); }
+            StepResult R;
+            const bool frozen = lane_step<SLIP, true>(T, P, S.L[0], a, b, d, R);
+            ret += R.reward; eps += R.finished; nonzero += (uint32_t)R.reward & 1u;
+            any_frozen |= frozen;
+            pick = R.finished ? -1 : pick;                          // the next episode draws again
+            const bool learn = !frozen && s != 0u;
+            const uint32_t s2 = R.final_obs, sn = R.obs;
+            double nxt[10];
+            if (learn) {
+                pop_load_row(tab, s2, nxt);                         // before the stores below: s' may be s
+                double qa, qb;
+                pop_learn(row, nxt, a, b, R.reward, R.term, alpha, gamma, qa, qb);
+                double* const at = tab + (size_t)s * 10;
+                at[a] = qa; at[5u + b] = qb;
+            }
+            if (learn && sn == s2) {                                // the episode goes on: the row at s' is the next row at s
+                if (s2 != s) {
+#pragma unroll
+                    for (int k = 0; k < 10; ++k) row[k] = nxt[k];
+                }
+            } else if (sn != s) {
+                pop_load_row(tab, sn, row);                         // after a reset
+            }
+            s = sn;
+            alpha = alpha * decay;
+        }
+        S.store(P, i0);
+        L.alpha[i0] = alpha;
+        G.pick[i0] = pick;
         hist.add_totals(eps, ret, nonzero);
     }
     if (any_frozen) P.misuse[0] = 1u;

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -51,6 +52,7 @@ struct soccer_q_population {
     unsigned long long n = 0;           // members = the handle's lanes
     int launch_steps = 4096;            // steps per pop_run_kernel launch (SOCCER_POP_LAUNCH_STEPS)
     int grid_blocks = 0;                // workgroups per run / update launch at most (SOCCER_POP_GRID_BLOCKS); 0: the handle's cap alone
+    PopLeagueIO league{};               // K == 0: no league; else pop_league_run_kernel runs it
 };
 
 // A population of policy hill-climbers, a member per lane: the same shape; alpha and dscale live per member in device memory.
@@ -728,6 +730,21 @@ static hipError_t pop_run(soccer_handle* h, const KernelParams& P, const PopIO& 
                    : (h->lut_lds ? launch_pop_run<false, true>(h, P, io, launch, grid_blocks) : launch_pop_run<false, false>(h, P, io, launch, grid_blocks));
 }
 
+// the same for a population with a league opponent
+template <bool SLIP, bool LUT_LDS>
+static hipError_t launch_pop_league_run(soccer_handle* h, const KernelParams& P, const PopIO& io, const PopLeagueIO& lg, bool launch, int grid_blocks) {
+    if (!launch)
+        return h->smem_bytes > 48 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&pop_league_run_kernel<SLIP, LUT_LDS>),
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_bytes) : hipSuccess;
+    hipLaunchKernelGGL((pop_league_run_kernel<SLIP, LUT_LDS>), dim3(pop_grid(h, grid_blocks, P.n)), dim3(kBlock), h->smem_bytes, h->stream, P, io, lg);
+    return hipSuccess;
+}
+
+static hipError_t pop_league_run(soccer_handle* h, const KernelParams& P, const PopIO& io, const PopLeagueIO& lg, bool launch, int grid_blocks = 0) {
+    return h->slip ? (h->lut_lds ? launch_pop_league_run<true, true>(h, P, io, lg, launch, grid_blocks) : launch_pop_league_run<true, false>(h, P, io, lg, launch, grid_blocks))
+                   : (h->lut_lds ? launch_pop_league_run<false, true>(h, P, io, lg, launch, grid_blocks) : launch_pop_league_run<false, false>(h, P, io, lg, launch, grid_blocks));
+}
+
 // a hyperparameter of every member: the caller's n values, each held to the scalar's range, or the scalar n times
 template <class Ok>
 static int pop_param(soccer_handle* h, const char* name, const char* range, const double* per_member, double scalar, size_t n, Ok ok,
@@ -743,15 +760,24 @@ static int pop_param(soccer_handle* h, const char* name, const char* range, cons
     return SOCCER_OK;
 }
 
-extern "C" int soccer_q_population_create(soccer_handle* h, const soccer_q_population_config* cfg, soccer_q_population** out) {
+// what soccer_q_population_create_league adds to a creation: the league's player, its K policies and their weights (HOST)
+struct PopLeagueSpec {
+    int32_t player, K;
+    const double* policies;             // [K][nS][5]
+    const double* weights;              // [K]
+};
+
+// both creations; `what` names the entry point in the messages, lg == nullptr: no league
+static int pop_create(soccer_handle* h, const soccer_q_population_config* cfg, const PopLeagueSpec* lg, const char* what,
+                      soccer_q_population** out) {
     if (!h) return fail(nullptr, SOCCER_E_INVALID, "handle is NULL");
-    if (h->capturing) return fail(h, SOCCER_E_STATE, "soccer_q_population_create during graph capture");
-    if (!cfg || !out) return fail(h, SOCCER_E_INVALID, "soccer_q_population_create: cfg/out is NULL");
+    if (h->capturing) return fail(h, SOCCER_E_STATE, "%s during graph capture", what);
+    if (!cfg || !out) return fail(h, SOCCER_E_INVALID, "%s: cfg/out is NULL", what);
     *out = nullptr;
     if (h->P.policy_a != nullptr || h->P.policy_b != nullptr)
-        return fail(h, SOCCER_E_INVALID, "soccer_q_population_create needs a two-player handle: neither side may have a fixed policy (soccer_set_policy)");
+        return fail(h, SOCCER_E_INVALID, "%s needs a two-player handle: neither side may have a fixed policy (soccer_set_policy)", what);
     if (!(h->cfg.flags & SOCCER_F_AUTORESET))
-        return fail(h, SOCCER_E_INVALID, "soccer_q_population_create needs a handle created with SOCCER_F_AUTORESET");
+        return fail(h, SOCCER_E_INVALID, "%s needs a handle created with SOCCER_F_AUTORESET", what);
     const size_t n = (size_t)h->cfg.n_lanes;
     std::vector<double> par[4];         // alpha, decay, explor, discount_factor
     if (int rc = pop_param(h, "discount_factor", "[0, 1)", cfg->discount_factor_per_member, cfg->discount_factor, n,
@@ -762,14 +788,42 @@ extern "C" int soccer_q_population_create(soccer_handle* h, const soccer_q_popul
     if (!(cfg->q_init >= -1.0 && cfg->q_init <= 1.0)) return fail(h, SOCCER_E_INVALID, "q_init must be in [-1, 1]");
     if (!ql_kind(cfg->act_a) || !ql_kind(cfg->act_b))
         return fail(h, SOCCER_E_INVALID, "act_a / act_b must be SOCCER_QL_GREEDY, SOCCER_QL_UNIFORM or SOCCER_QL_FIXED");
-    if ((cfg->act_a == SOCCER_QL_FIXED) != (cfg->policy_a != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_a goes with act_a == SOCCER_QL_FIXED, and only with it");
-    if ((cfg->act_b == SOCCER_QL_FIXED) != (cfg->policy_b != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_b goes with act_b == SOCCER_QL_FIXED, and only with it");
     const int nS = h->rules.nS;
+    // the league player is SOCCER_QL_FIXED with a NULL policy: its rows come from the league
+    const bool league_a = lg && lg->player == 0, league_b = lg && lg->player == 1;
+    if (lg) {
+        if (!league_a && !league_b) return fail(h, SOCCER_E_INVALID, "%s: league_player must be 0 (player A) or 1 (player B)", what);
+        if ((league_a ? cfg->act_a : cfg->act_b) != SOCCER_QL_FIXED || (league_a ? cfg->policy_a : cfg->policy_b) != nullptr)
+            return fail(h, SOCCER_E_INVALID, "%s: the league player must be SOCCER_QL_FIXED with a NULL policy (act_%c / policy_%c)", what,
+                        league_a ? 'a' : 'b', league_a ? 'a' : 'b');
+        if (lg->K < 1 || lg->K > SOCCER_LEAGUE_MAX_POLICIES)
+            return fail(h, SOCCER_E_INVALID, "%s: n_policies must be in 1 .. %d, not %d", what, SOCCER_LEAGUE_MAX_POLICIES, (int)lg->K);
+        if (!lg->policies || !lg->weights) return fail(h, SOCCER_E_INVALID, "%s: policies / weights is NULL", what);
+    }
+    if (!league_a && (cfg->act_a == SOCCER_QL_FIXED) != (cfg->policy_a != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_a goes with act_a == SOCCER_QL_FIXED, and only with it");
+    if (!league_b && (cfg->act_b == SOCCER_QL_FIXED) != (cfg->policy_b != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_b goes with act_b == SOCCER_QL_FIXED, and only with it");
     std::vector<uint16_t> fixed[2];
     if (cfg->policy_a) if (int rc = fixed_thresholds(h, "policy_a", cfg->policy_a, nS, fixed[0])) return rc;
     if (cfg->policy_b) if (int rc = fixed_thresholds(h, "policy_b", cfg->policy_b, nS, fixed[1])) return rc;
+    std::vector<uint16_t> league_thr;   // [K][nS][4]
+    std::vector<uint64_t> league_T;     // [K - 1]
+    if (lg) {
+        const int bad = league_check_weights(lg->weights, lg->K);
+        if (bad >= 0 && bad < lg->K) return fail(h, SOCCER_E_INVALID, "weights[%d] is negative or not a finite number", bad);
+        if (bad == lg->K) return fail(h, SOCCER_E_INVALID, "weights does not sum to 1");
+        league_thr.reserve((size_t)lg->K * (size_t)nS * 4);
+        std::vector<uint16_t> one;
+        char name[48];
+        for (int k = 0; k < lg->K; ++k) {
+            std::snprintf(name, sizeof name, "policies[%d]", k);
+            if (int rc = fixed_thresholds(h, name, lg->policies + (size_t)k * (size_t)nS * 5, nS, one)) return rc;
+            league_thr.insert(league_thr.end(), one.begin(), one.end());
+        }
+        league_T.assign((size_t)std::max(lg->K - 1, 1), 0);        // (K == 1: one unread entry, so that no pointer is NULL)
+        league_thresholds(lg->weights, lg->K, league_T.data());
+    }
     HIP_TRY(h, hipSetDevice(h->cfg.device));
-    HIP_TRY(h, pop_run(h, h->P, PopIO{}, false));
+    HIP_TRY(h, lg ? pop_league_run(h, h->P, PopIO{}, PopLeagueIO{}, false) : pop_run(h, h->P, PopIO{}, false));
     std::unique_ptr<soccer_q_population> owner(new soccer_q_population());
     soccer_q_population* q = owner.get();
     q->h = h; q->n = n;
@@ -785,6 +839,12 @@ extern "C" int soccer_q_population_create(soccer_handle* h, const soccer_q_popul
     for (int k = 0; k < 4; ++k) if (!rc) rc = q->bufs.alloc(h, n, &dpar[k]);
     for (int p = 0; p < 2; ++p) if (!rc && !fixed[p].empty()) rc = q->bufs.alloc(h, (size_t)nS * 4, &dmix[p]);
     if (!rc) rc = q->bufs.alloc(h, 1, &io.steps);
+    uint16_t* dthr = nullptr; uint64_t* dT = nullptr; int32_t* dpick = nullptr;
+    if (lg) {
+        if (!rc) rc = q->bufs.alloc(h, league_thr.size(), &dthr);
+        if (!rc) rc = q->bufs.alloc(h, league_T.size(), &dT);
+        if (!rc) rc = q->bufs.alloc(h, n, &dpick);
+    }
     if (rc) return rc;
     io.alpha = dpar[0]; io.decay = dpar[1]; io.explor = dpar[2]; io.gamma = dpar[3];
     io.mix[0] = dmix[0]; io.mix[1] = dmix[1];
@@ -794,11 +854,56 @@ extern "C" int soccer_q_population_create(soccer_handle* h, const soccer_q_popul
     for (int k = 0; k < 4; ++k) HIP_TRY(h, hipMemcpyAsync(dpar[k], par[k].data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     for (int p = 0; p < 2; ++p)
         if (dmix[p]) HIP_TRY(h, hipMemcpyAsync(dmix[p], fixed[p].data(), fixed[p].size() * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    if (lg) {
+        q->league = PopLeagueIO{dthr, dT, dpick, lg->K, lg->player};
+        HIP_TRY(h, hipMemcpyAsync(dthr, league_thr.data(), league_thr.size() * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(dT, league_T.data(), league_T.size() * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemsetAsync(dpick, 0xff, n * sizeof(int32_t), h->stream));         // every pick -1
+    }
     hipLaunchKernelGGL(pop_init_kernel, dim3(grid_for(h, (uint64_t)n * (uint64_t)nS * 10)), dim3(kBlock), 0, h->stream, io, (unsigned long long)n, cfg->q_init);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));            // the vectors are pageable host memory of this call
     h->q_populations.push_back(q);
     *out = owner.release();
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_population_create(soccer_handle* h, const soccer_q_population_config* cfg, soccer_q_population** out) {
+    return pop_create(h, cfg, nullptr, "soccer_q_population_create", out);
+}
+
+extern "C" int soccer_q_population_create_league(soccer_handle* h, const soccer_q_population_config* cfg, int32_t league_player,
+                                                 int32_t n_policies, const double* policies, const double* weights,
+                                                 soccer_q_population** out) {
+    const PopLeagueSpec lg{league_player, n_policies, policies, weights};
+    return pop_create(h, cfg, &lg, "soccer_q_population_create_league", out);
+}
+
+static int pop_league_check(soccer_handle* h, soccer_q_population* q, const char* what, int64_t first, int64_t count) {
+    if (int rc = pop_check(h, q, what)) return rc;
+    if (q->league.K == 0) return fail(h, SOCCER_E_INVALID, "%s: this population has no league (soccer_q_population_create_league)", what);
+    return pop_range_check(h, q, what, first, count);
+}
+
+extern "C" int soccer_q_population_league_read(soccer_handle* h, soccer_q_population* q, int64_t first, int64_t count, int32_t* pick) {
+    if (int rc = pop_league_check(h, q, "soccer_q_population_league_read", first, count)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    if (pick && count) HIP_TRY(h, hipMemcpyAsync(pick, q->league.pick + first, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_q_population_league_load(soccer_handle* h, soccer_q_population* q, int64_t first, int64_t count, const int32_t* pick) {
+    if (int rc = pop_league_check(h, q, "soccer_q_population_league_load", first, count)) return rc;
+    if (!pick && count) return fail(h, SOCCER_E_INVALID, "soccer_q_population_league_load: pick is NULL");
+    // everything is checked before anything is written: the kernel uses a pick as an index
+    for (int64_t i = 0; i < count; ++i)
+        if (pick[i] < -1 || pick[i] >= q->league.K)
+            return fail(h, SOCCER_E_INVALID, "soccer_q_population_league_load: pick[%lld] = %d is outside -1 .. %d", (long long)i, (int)pick[i],
+                        (int)q->league.K - 1);
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (count) HIP_TRY(h, hipMemcpy(q->league.pick + first, pick, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice));
     return SOCCER_OK;
 }
 
@@ -819,12 +924,15 @@ extern "C" int soccer_q_population_run(soccer_handle* h, soccer_q_population* q,
     HIP_TRY(h, hipSetDevice(h->cfg.device));
     // the tick sequence of consecutive launches is contiguous and a member's whole state is in memory between them, so the
     // split changes no result
+    // (a league's kick-off draws take the blocks of counter 2^62 + tick: below 2^62 a tick's own blocks are never met)
+    if (q->league.K != 0 && (h->tick >= (1ull << 62) || (uint64_t)n_steps > (1ull << 62) - h->tick))
+        return fail(h, SOCCER_E_INVALID, "soccer_q_population_run: a league population's run may not cross tick 2^62");
     for (int32_t t0 = 0; t0 < n_steps; t0 += q->launch_steps) {
         KernelParams P = h->P;
         PopIO io = q->io;
         io.n_steps = n_steps - t0 < q->launch_steps ? n_steps - t0 : q->launch_steps;
         bind_tick(h, P, (uint64_t)io.n_steps);
-        HIP_TRY(h, pop_run(h, P, io, true, q->grid_blocks));
+        HIP_TRY(h, q->league.K != 0 ? pop_league_run(h, P, io, q->league, true, q->grid_blocks) : pop_run(h, P, io, true, q->grid_blocks));
     }
     HIP_TRY(h, hipGetLastError());
     return SOCCER_OK;

@@ -110,11 +110,12 @@ def q_learning(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2,
 
 
 def q_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy",
-                 first=0, count=None):
+                 first=0, count=None, league_policies=None, league_weights=None):
     """A population of independent Q-learners on the device, a learner per lane of `env`, each with its own tables and its
     own stream of experience: n_steps steps of every member from the lanes' current states (lanes that were never reset
     are reset first).  discount_factor, alpha, decay and explor are scalars or arrays of one value per lane; decay None:
-    alpha falls to 1 % over the run.  Returns, for members first .. first + count - 1 (count None: to the end),
+    alpha falls to 1 % over the run.  act_a or act_b may be "league" with league_policies [K, nS, 5] and league_weights [K]
+    (SoccerBatch.q_population).  Returns, for members first .. first + count - 1 (count None: to the end),
     (pi_a[count, nS, 5], pi_b, V_a[count, nS], V_b, Q_a[count, nS, 5], Q_b, alpha[count]); Q_b and V_b are in player B's
     own reward."""
     b = _two_player_batch(env, "q_population")
@@ -122,7 +123,8 @@ def q_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.
     assert n_steps >= 0, "n_steps must be >= 0"
     if decay is None:
         decay = 0.01 ** (1.0 / max(n_steps, 1))
-    pop = b.q_population(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
+    pop = b.q_population(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b,
+                         league_policies=league_policies, league_weights=league_weights)
     try:
         if b.get_state()["needs_reset"].any():
             (env if hasattr(env, "_batch") else b).reset()
@@ -270,3 +272,107 @@ def meta_game(env, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000, max_p
     batch = _two_player_batch(env, "meta_game")
     payoff, it = batch.cross_play(pi_a, pi_b, theta, discount_factor, max_sweeps=max_sweeps)
     return _meta_of_cross_play(batch, payoff, it, max_pivots)
+
+
+PSRO_MAX_POLICIES = 1024        # what cross_play, solve_meta_game and a league take a side
+
+
+def _weighted(P, w):
+    """sum_j w[j] * P[:, j], sequentially in ascending j in float64"""
+    u = np.zeros(P.shape[0])
+    for j in range(P.shape[1]):
+        u = u + float(w[j]) * P[:, j]
+    return u
+
+
+def psro(env, iterations, n_steps, discount_factor, theta=1e-10, pi_a0=None, pi_b0=None, **q_hyper):
+    """Policy-space response oracles (double oracle with learned responses) on the device, built from cross_play, the
+    meta-game and league challengers.  `env` is a two-player autoreset env whose n lanes are the challengers.  The policy
+    sets start as pi_a0 / pi_b0 ([nS, 5] or [k, nS, 5]; None: the uniform policy).  Per iteration:
+      1. the payoff matrix of the sets Pi_A x Pi_B is extended by the new row and the new column alone (every pair has the
+         bits it has alone, so the matrix equals a full cross_play(Pi_A, Pi_B) bit for bit)
+      2. solve_meta_game gives x, y, lo, hi, status
+      3. a fresh population with act_a="greedy" against the league (Pi_B, y) runs n_steps, then a fresh one with
+         act_b="greedy" against the league (Pi_A, x); q_hyper (alpha, decay, explor, q_init) goes to both, decay None:
+         alpha falls to 1 % over the run
+      4. every member's one-hot greedy policy is scored exactly: u_a[i] = sum_j y_j * cross_play(candidate_i, Pi_B[j]),
+         summed in ascending j; u_b[i] likewise with x.  A's pick is the first argmax of u_a, B's the first argmin of u_b
+      5. A's pick joins Pi_A only if u_a[pick] > hi, B's joins Pi_B only if u_b[pick] < lo; a set stops growing at 1024
+    Returns a dict: pi_a, pi_b (the final sets), payoff and iterations (their matrix and its sweep counts), and per
+    iteration the lists x, y, lo, hi, status, chosen_a, chosen_b, added_a, added_b, br_a = u_a[chosen_a], br_b, gap =
+    br_a - br_b, with u_a, u_b as [iterations, n] arrays.
+    gap is a LOWER estimate of the NashConv of the mixture pair (x, y) in the full game: the challengers are learners, not
+    exact best responses.  The exact best response to a kick-off mixture is a partially observed problem (the responder
+    does not see which policy was drawn) and is out of scope here."""
+    b = _two_player_batch(env, "psro")
+    iterations, n_steps = int(iterations), int(n_steps)
+    assert iterations >= 0 and n_steps >= 0, "iterations and n_steps must be >= 0"
+    nS, n = b.nS, b.n
+    gamma = float(discount_factor)
+    hyper = dict(q_hyper)
+    if hyper.get("decay") is None:
+        hyper["decay"] = 0.01 ** (1.0 / max(n_steps, 1))
+    assert not {"act_a", "act_b", "league_policies", "league_weights"} & set(hyper), "psro sets the players of its challengers itself"
+
+    def seed(pi, name):
+        if pi is None:
+            return np.full((1, nS, 5), 0.2)
+        pi = np.array(pi, np.float64)
+        pi = pi[None] if pi.ndim == 2 else pi
+        assert pi.ndim == 3 and pi.shape[1:] == (nS, 5) and 1 <= pi.shape[0] <= PSRO_MAX_POLICIES, "%s must be [n_states, 5] or [k, n_states, 5]" % name
+        return pi
+    Pa, Pb = seed(pi_a0, "pi_a0"), seed(pi_b0, "pi_b0")
+    payoff, sweeps = b.cross_play(Pa, Pb, theta, gamma)
+    out = {k: [] for k in ("x", "y", "lo", "hi", "status", "chosen_a", "chosen_b", "added_a", "added_b", "br_a", "br_b", "gap")}
+    U = {0: [], 1: []}
+
+    def challengers(learner, league, weights):
+        """[n, nS, 5]: the greedy policies `learner` (0 = A, 1 = B) has learned against the league after n_steps"""
+        acts = {"act_a": "greedy", "act_b": "league"} if learner == 0 else {"act_a": "league", "act_b": "greedy"}
+        pop = b.q_population(gamma, league_policies=league, league_weights=weights, **acts, **hyper)
+        try:
+            if b.get_state()["needs_reset"].any():
+                (env if hasattr(env, "_batch") else b).reset()
+            pop.run(n_steps)
+            cand = np.zeros((n, nS, 5))
+            for c0 in range(0, n, 256):
+                c = min(256, n - c0)
+                cand[c0:c0 + c] = pop.read(c0, c)["pi_b" if learner else "pi_a"]
+        finally:
+            pop.close()
+        return cand
+
+    def score(cand, learner, others, weights):
+        u = np.zeros(n)
+        for c0 in range(0, n, PSRO_MAX_POLICIES):
+            c = cand[c0:c0 + PSRO_MAX_POLICIES]
+            P = b.cross_play(c, others, theta, gamma)[0] if learner == 0 else b.cross_play(others, c, theta, gamma)[0].T
+            u[c0:c0 + c.shape[0]] = _weighted(P, weights)
+        return u
+
+    for _ in range(iterations):
+        m = b.solve_meta_game(payoff)
+        x, y, lo, hi = m["x"].copy(), m["y"].copy(), float(m["lo"]), float(m["hi"])
+        cand_a = challengers(0, Pb, y)
+        cand_b = challengers(1, Pa, x)
+        u_a, u_b = score(cand_a, 0, Pb, y), score(cand_b, 1, Pa, x)
+        ia, ib = int(np.argmax(u_a)), int(np.argmin(u_b))
+        add_a = bool(u_a[ia] > hi) and Pa.shape[0] < PSRO_MAX_POLICIES
+        add_b = bool(u_b[ib] < lo) and Pb.shape[0] < PSRO_MAX_POLICIES
+        for k, v in (("x", x), ("y", y), ("lo", lo), ("hi", hi), ("status", int(m["status"])), ("chosen_a", ia), ("chosen_b", ib),
+                     ("added_a", add_a), ("added_b", add_b), ("br_a", float(u_a[ia])), ("br_b", float(u_b[ib])),
+                     ("gap", float(u_a[ia]) - float(u_b[ib]))):
+            out[k].append(v)
+        U[0].append(u_a); U[1].append(u_b)
+        # the new column against the old rows, then the new row against every column
+        if add_b:
+            col, col_it = b.cross_play(Pa, cand_b[ib], theta, gamma)
+            Pb = np.concatenate([Pb, cand_b[ib][None]])
+            payoff, sweeps = np.concatenate([payoff, col], 1), np.concatenate([sweeps, col_it], 1)
+        if add_a:
+            row, row_it = b.cross_play(cand_a[ia], Pb, theta, gamma)
+            Pa = np.concatenate([Pa, cand_a[ia][None]])
+            payoff, sweeps = np.concatenate([payoff, row], 0), np.concatenate([sweeps, row_it], 0)
+    out.update({"pi_a": Pa, "pi_b": Pb, "payoff": payoff, "iterations": sweeps,
+                "u_a": np.array(U[0]).reshape(iterations, n), "u_b": np.array(U[1]).reshape(iterations, n)})
+    return out

@@ -34,6 +34,9 @@
  *       g = lane_offset + i,  q = g >> 2,  key = (seed & 0xffffffff, seed >> 32)
  *       block(c, purpose) = philox4x32_10(counter = (q & 0xffffffff, q >> 32, c & 0xffffffff, (c >> 32) | purpose << 31), key)
  *   (purpose 0: step/reset, 1: in-kernel action sampling; k < 2^63) and lane g owns word w = block[g & 3].
+ *   One more block, for the populations with a league opponent alone: block(2^62 + k, 1), the kick-off draw of a league
+ *   policy at tick k (same quad, same word rule).  While k < 2^62 it is no block that a step, a reset or an action draw
+ *   of any tick takes, so it collides with nothing; soccer_q_population_run refuses a league run that would cross 2^62.
  *   A uniform is always u = (m + 1/2) * 2^-b for a b-bit integer m — never 0, never on a dyadic threshold:
  *     slip_prob > 0   one block per tick, block(k, 0):
  *         step uniform   u = ((w >> 2) + 1/2) * 2^-30      (30 bits)
@@ -64,7 +67,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_*, soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies, soccer_cross_play, soccer_solve_meta_games and soccer_rollout_shape were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_* (soccer_q_population_create_league and soccer_q_population_league_* among them), soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies, soccer_cross_play, soccer_solve_meta_games and soccer_rollout_shape were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -786,6 +789,46 @@ int soccer_q_population_read(soccer_handle* h, soccer_q_population* q, int64_t f
  * nothing.  read -> load of a range on a fresh population continues bit for bit. */
 int soccer_q_population_load(soccer_handle* h, soccer_q_population* q, int64_t first, int64_t count, const double* Q_a,
                              const double* Q_b, const double* alpha, const uint64_t* steps);
+/* ---- learners, a league opponent for the population of Q-learners
+ * A FIXED player of a population follows ONE policy.  A league player follows a MIXTURE over K policies in the sense of a
+ * meta-game (soccer_solve_meta_games): "draw policy j with probability w_j at kick-off and play it to the end of the
+ * episode" — not the state-wise average sum_j w_j * pi_j, which is another policy.  It is the opponent of policy-space
+ * response oracles (PSRO, double oracle), fictitious self-play and league training.
+ * A league is K <= SOCCER_LEAGUE_MAX_POLICIES mixed policies [K][n_states][5], one weight vector w[K] shared by all members
+ * and the player (0 = A, 1 = B) that plays them.  In the config that player is SOCCER_QL_FIXED with a NULL policy pointer;
+ * the other player is anything a population allows.  Member i gains one word of state, pick_i in {-1, 0 .. K - 1}, -1 at
+ * creation.  One step of member i at tick t is steps 1-6 of the population with one addition before step 1 and one after
+ * the environment step:
+ *   0. if pick_i == -1 (whether or not the lane is frozen or parked at observation 0), a pick is drawn from W, the lane's
+ *      word of block(2^62 + t, 1) (global lane g = lane_offset + i, word g & 3):
+ *          pick_i = #{k < K - 1 : W >= T_k},   T_k = min(2^32, floor(c_k * 2^32)) as an integer,
+ *          c_k = w_0 + .. + w_k, summed sequentially in float64
+ *      (how the count is found is no part of the definition: the kernel bisects the never decreasing T)
+ *   1. the league player's row is the threshold row of policies[pick_i][s], computed on the host at creation by the fixed
+ *      policies' own threshold expression; the other player's row as before
+ *   2.-6. as before; and after the environment step, if the lane's episode finished (terminated or truncated: the
+ *      auto-reset happened), pick_i = -1
+ * So a policy of weight zero is never picked (T_k = T_{k-1}); with a trailing zero weight the last policy is unreachable
+ * whenever c_{K-2} >= 1; the pick survives launch boundaries; soccer_q_population_update never touches it; a frozen lane
+ * draws once, at its first run step, and keeps that pick.  A batched_reset by the CALLER does not redraw it either: the
+ * lane's new episode goes on with the pick of the one the caller cut short (load -1 to redraw).
+ * Checks, SOCCER_E_INVALID with the reason: the weights as a policy row is — finite, >= 0 (the message names the index),
+ * |sum - 1| <= 1e-8 + 1e-5; every policy as policy_a / policy_b are (the message names policy and state); K < 1,
+ * K > SOCCER_LEAGUE_MAX_POLICIES; a league player that is not FIXED-with-NULL.  Every other soccer_q_population_* call
+ * works on a league population unchanged (run, update, read, load, destroy, SOCCER_POP_LAUNCH_STEPS,
+ * SOCCER_POP_GRID_BLOCKS); the league calls on a population without one return SOCCER_E_INVALID.  Memory: K * n_states * 8
+ * bytes of thresholds, 8 * (K - 1) bytes of T and 4 bytes per member.  Not offered: per-member weights, new weights for
+ * a live population, leagues in the other two populations, per-(member, policy) tallies. */
+#define SOCCER_LEAGUE_MAX_POLICIES 1024
+int soccer_q_population_create_league(soccer_handle* h, const soccer_q_population_config* cfg, int32_t league_player,
+                                      int32_t n_policies, const double* policies /* HOST [K][n_states][5] */,
+                                      const double* weights /* HOST [K] */, soccer_q_population** out);
+/* Members first .. first + count - 1 to HOST pick[count].  Synchronises. */
+int soccer_q_population_league_read(soccer_handle* h, soccer_q_population* q, int64_t first, int64_t count, int32_t* pick);
+/* The same range from HOST pick[count], every value in -1 .. K - 1, checked before anything is written: a refused load
+ * changes nothing.  read + league_read -> load + league_load on a fresh population continues bit for bit, mid-episode
+ * included. */
+int soccer_q_population_league_load(soccer_handle* h, soccer_q_population* q, int64_t first, int64_t count, const int32_t* pick);
 
 /* ---- learners, a population of policy hill-climbers (two-player handles; a PHC / WoLF-PHC learner per lane)
  * What the population of Q-learners is to soccer_q_learner, this is to soccer_wolf_phc; nothing new is defined.  On a
