@@ -137,27 +137,90 @@ def _learner_update(b, call, q, obs, act_a, act_b, reward, terminated, next_obs)
                 a.free()
 
 
-class MinimaxQLearner:
-    """A minimax-Q learner (Littman 1994) on a two-player auto-reset SoccerBatch: one shared Q[nS, 5, 5] on the device,
-    the batch's lanes as actors (include/soccer_hip.h, "learners").  run() enqueues and returns; the properties
-    synchronise and copy."""
+class _Learner:
+    """What the six wrappers of a C learner share: they keep the batch and the learner, run() and close().  _C is the prefix
+    of the kind's C entry points: _C + "_create", "_run", "_destroy"."""
+    _C = None
 
-    def __init__(self, batch, discount_factor, **params):
-        cfg, keep = minimax_q_config(batch.nS, discount_factor, **params)
+    def _create(self, batch, cfg, *league):
+        """the C learner of a config, whose arrays the caller keeps alive until this returns (create copies what it needs);
+        league: what soccer_q_population_create_league takes between the config and the result"""
         self.batch, self.q = batch, None
         q = C.c_void_p()
-        batch._check(batch.lib.soccer_minimax_q_create(batch.h, C.byref(cfg), C.byref(q)))
-        del keep                                   # (create has copied the opponent's thresholds)
-        self.q = q
-        self.nS = batch.nS
-        self.discount_factor = float(discount_factor)
+        create = getattr(batch.lib, self._C + ("_create_league" if league else "_create"))
+        batch._check(create(batch.h, C.byref(cfg), *league, C.byref(q)))
+        self.q, self.nS = q, batch.nS
         batch._learners.add(self)
 
     def run(self, n_steps):
-        """n_steps learner steps (every lane acts, the environment steps, Q / V / pi are updated), enqueued."""
+        """n_steps learner steps (every lane acts, the environment steps, the kind's tables and policies are updated; a
+        population: every member's, from its lane), enqueued."""
         b = self.batch
-        b._check(b.lib.soccer_minimax_q_run(b.h, self.q, int(n_steps)))
+        b._check(getattr(b.lib, self._C + "_run")(b.h, self.q, int(n_steps)))
         return self
+
+    def close(self):
+        if self.q and self.batch.h:
+            getattr(self.batch.lib, self._C + "_destroy")(self.batch.h, self.q)
+        self.q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Population(_Learner):
+    """What the three populations share: a member per lane with its own discount, ranges of members, update()."""
+
+    def _create(self, batch, cfg, per_member, *league):
+        """per_member: the config function's arrays of per-member hyperparameters (None: the scalar for every member)"""
+        super()._create(batch, cfg, *league)
+        self.n = batch.n
+        gam = per_member["discount_factor"]
+        self.discount_factor = np.full(batch.n, cfg.discount_factor) if gam is None else gam.copy()
+
+    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
+        """One step's update on n transitions, transition i for member i (reward is player A's): DeviceArrays (or device
+        tensors) of n elements, or numpy arrays, which are copied to the device first."""
+        n = self.n
+
+        def call(h, q, count, *ptrs):
+            assert count == n, "a population's update takes one transition per member (%d)" % n
+            return getattr(self.batch.lib, self._C + "_update")(h, q, *ptrs)
+        _learner_update(self.batch, call, self.q, obs, act_a, act_b, reward, terminated, next_obs)
+        return self
+
+    def _range(self, first, count):
+        first = int(first)
+        count = self.n - first if count is None else int(count)
+        assert 0 <= first <= self.n and 0 <= count <= self.n - first, "members %d .. %d + %d are outside the population of %d" % (first, first, count, self.n)
+        return first, count
+
+    def cross_play(self, theta=1e-10, first=0, count=None, discount_factor=None):
+        """What each member's player A scores against each member's player B: (payoff[count, count], iterations) of
+        SoccerBatch.cross_play on pi_a and pi_b (Q-learners: the one-hot greedy policies) of members first ..
+        first + count - 1 (at most 1024).  discount_factor None: the range's common discount, ValueError if the members differ."""
+        return _population_cross_play(self, self._policies, "pi_a", "pi_b", theta, first, count, discount_factor)
+
+    def meta_game(self, theta=1e-10, first=0, count=None, discount_factor=None, max_pivots=None):
+        """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
+        opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
+        return _meta_of_cross_play(self.batch, *self.cross_play(theta, first, count, discount_factor), max_pivots)
+
+
+class MinimaxQLearner(_Learner):
+    """A minimax-Q learner (Littman 1994) on a two-player auto-reset SoccerBatch: one shared Q[nS, 5, 5] on the device,
+    the batch's lanes as actors (include/soccer_hip.h, "learners").  run() enqueues and returns; the properties
+    synchronise and copy."""
+    _C = "soccer_minimax_q"
+
+    def __init__(self, batch, discount_factor, **params):
+        cfg, keep = minimax_q_config(batch.nS, discount_factor, **params)
+        self._create(batch, cfg)
+        del keep                                   # (create has copied the opponent's thresholds)
+        self.discount_factor = float(discount_factor)
 
     def update(self, obs, act_a, act_b, reward, terminated, next_obs):
         """One learner step's reduce / update / re-solve on a batch of transitions: DeviceArrays (or device tensors) of one
@@ -225,17 +288,6 @@ class MinimaxQLearner:
         b._check(b.lib.soccer_minimax_q_load(b.h, self.q, Q.ctypes.data, None if v is None else v.ctypes.data, al, st))
         return self
 
-    def close(self):
-        if self.q and self.batch.h:
-            self.batch.lib.soccer_minimax_q_destroy(self.batch.h, self.q)
-        self.q = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def q_learning_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
     """Checks the parameters of the independent Q-learners (AssertionError, before any library call) and returns
@@ -261,28 +313,18 @@ def q_learning_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), e
     return _lib.QLearnerConfig(g, a, d, e, q0, kinds[0], kinds[1], *[None if x is None else x.ctypes.data for x in pols]), pols
 
 
-class QLearner:
+class QLearner(_Learner):
     """Independent Q-learners for both players (Littman 1994's baseline and challenger) on a two-player auto-reset
     SoccerBatch: Q_a[nS, 5] and Q_b[nS, 5] (player B's in its own reward) on the device, the batch's lanes as actors
     (include/soccer_hip.h, "learners, independent Q").  run() enqueues and returns; read() and the properties synchronise
     and copy."""
+    _C = "soccer_q_learner"
 
     def __init__(self, batch, discount_factor, **params):
         cfg, keep = q_learning_config(batch.nS, discount_factor, **params)
-        self.batch, self.q = batch, None
-        q = C.c_void_p()
-        batch._check(batch.lib.soccer_q_learner_create(batch.h, C.byref(cfg), C.byref(q)))
+        self._create(batch, cfg)
         del keep                                   # (create has copied the fixed policies' thresholds)
-        self.q = q
-        self.nS = batch.nS
         self.discount_factor = float(discount_factor)
-        batch._learners.add(self)
-
-    def run(self, n_steps):
-        """n_steps learner steps (every lane acts, the environment steps, both tables are updated), enqueued."""
-        b = self.batch
-        b._check(b.lib.soccer_q_learner_run(b.h, self.q, int(n_steps)))
-        return self
 
     def update(self, obs, act_a, act_b, reward, terminated, next_obs):
         """One learner step's reduce / update on a batch of transitions (reward is player A's): DeviceArrays (or device
@@ -342,17 +384,6 @@ class QLearner:
         st = None if steps is None else C.byref(C.c_uint64(int(steps)))
         b._check(b.lib.soccer_q_learner_load(b.h, self.q, Q[0].ctypes.data, Q[1].ctypes.data, None if v is None else v.ctypes.data, al, st))
         return self
-
-    def close(self):
-        if self.q and self.batch.h:
-            self.batch.lib.soccer_q_learner_destroy(self.batch.h, self.q)
-        self.q = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def league_config(nS, act_a, act_b, league_policies, league_weights):
@@ -450,51 +481,22 @@ def _meta_of_cross_play(batch, payoff, iterations, max_pivots):
     return out
 
 
-class QPopulation:
+class QPopulation(_Population):
     """A population of independent Q-learners on a two-player auto-reset SoccerBatch, a learner per lane: member i has its own
     Q_a[nS, 5], Q_b[nS, 5] and alpha and learns from lane i alone (include/soccer_hip.h, "learners, a population of
     independent Q-learners").  run() enqueues and returns; read() and the properties synchronise and copy.  Whole populations
     run to gigabytes, so read(), load() and exploitability() take a range of members."""
+    _C = "soccer_q_population"
 
     def __init__(self, batch, discount_factor, league_policies=None, league_weights=None, **params):
         lg = league_config(batch.nS, params.get("act_a", "greedy"), params.get("act_b", "greedy"), league_policies, league_weights)
         cfg, keep = q_population_config(batch.n, batch.nS, discount_factor, league=lg, **params)
-        self.batch, self.q = batch, None
         self.league, self.n_policies = (None, 0) if lg is None else lg[:2]      # the league's player (0 = A, 1 = B) and its K
-        q = C.c_void_p()
-        if lg is None:
-            batch._check(batch.lib.soccer_q_population_create(batch.h, C.byref(cfg), C.byref(q)))
-        else:
-            batch._check(batch.lib.soccer_q_population_create_league(batch.h, C.byref(cfg), lg[0], lg[1], lg[2].ctypes.data, lg[3].ctypes.data,
-                                                                     C.byref(q)))
-        self.discount_factor = np.full(batch.n, cfg.discount_factor) if keep[1]["discount_factor"] is None else keep[1]["discount_factor"].copy()
+        self._create(batch, cfg, keep[1], *(() if lg is None else (lg[0], lg[1], lg[2].ctypes.data, lg[3].ctypes.data)))
         del keep                                   # (create has copied the parameters and the fixed policies' thresholds)
-        self.q = q
-        self.n, self.nS = batch.n, batch.nS
-        batch._learners.add(self)
 
-    def run(self, n_steps):
-        """n_steps steps of every member (its lane acts, the environment steps, its two tables are updated), enqueued."""
-        b = self.batch
-        b._check(b.lib.soccer_q_population_run(b.h, self.q, int(n_steps)))
-        return self
-
-    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
-        """One step's update on n transitions, transition i for member i (reward is player A's): DeviceArrays (or device
-        tensors) of n elements, or numpy arrays, which are copied to the device first."""
-        n = self.n
-
-        def call(h, q, count, *ptrs):
-            assert count == n, "a population's update takes one transition per member (%d)" % n
-            return self.batch.lib.soccer_q_population_update(h, q, *ptrs)
-        _learner_update(self.batch, call, self.q, obs, act_a, act_b, reward, terminated, next_obs)
-        return self
-
-    def _range(self, first, count):
-        first = int(first)
-        count = self.n - first if count is None else int(count)
-        assert 0 <= first <= self.n and 0 <= count <= self.n - first, "members %d .. %d + %d are outside the population of %d" % (first, first, count, self.n)
-        return first, count
+    def _policies(self, first, count):
+        return self.read(first, count)
 
     def read(self, first=0, count=None):
         """dict for members first .. first + count - 1 (count None: to the end): Q_a / Q_b [count, nS, 5], V_a / V_b
@@ -542,17 +544,6 @@ class QPopulation:
         out["gap"] = out["v_b"] - out["v_a"]
         return out
 
-    def cross_play(self, theta=1e-10, first=0, count=None, discount_factor=None):
-        """What each member's player A scores against each member's player B: (payoff[count, count], iterations) of
-        SoccerBatch.cross_play on the one-hot greedy policies of members first .. first + count - 1 (at most 1024).
-        discount_factor None: the range's common discount, ValueError if the members differ."""
-        return _population_cross_play(self, self.read, "pi_a", "pi_b", theta, first, count, discount_factor)
-
-    def meta_game(self, theta=1e-10, first=0, count=None, discount_factor=None, max_pivots=None):
-        """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
-        opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
-        return _meta_of_cross_play(self.batch, *self.cross_play(theta, first, count, discount_factor), max_pivots)
-
     def picks(self, first=0, count=None):
         """A league population's picks, int32[count]: the league policy each member's lane follows until its episode ends,
         -1 where the next step draws one.  Synchronises.  AssertionError on a population without a league."""
@@ -591,17 +582,6 @@ class QPopulation:
         b._check(b.lib.soccer_q_population_load(b.h, self.q, first, count, *[None if x is None else x.ctypes.data for x in arrs], st))
         return self
 
-    def close(self):
-        if self.q and self.batch.h:
-            self.batch.lib.soccer_q_population_destroy(self.batch.h, self.q)
-        self.q = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def wolf_phc_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
                     delta_decay=1.0, act_a="learn", act_b="learn"):
@@ -632,30 +612,19 @@ def wolf_phc_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), exp
     return _lib.WolfPHCConfig(g, a, d, e, q0, dw, dl, dd, kinds[0], kinds[1], *[None if x is None else x.ctypes.data for x in pols]), pols
 
 
-class WolfPHCLearner:
+class WolfPHCLearner(_Learner):
     """Policy hill-climbers for both players (PHC and WoLF-PHC, Bowling & Veloso 2002) on a two-player auto-reset
     SoccerBatch: the Q-learners' two tables plus a mixed policy pi_p[nS, 5] and its running average avg_p per player on
     the device, the batch's lanes as actors (include/soccer_hip.h, "learners, policy hill-climbing").  run() enqueues
     and returns; read() and the properties synchronise and copy."""
+    _C = "soccer_wolf_phc"
     _ROWS = ("Q_a", "Q_b", "pi_a", "pi_b", "avg_a", "avg_b")
 
     def __init__(self, batch, discount_factor, **params):
         cfg, keep = wolf_phc_config(batch.nS, discount_factor, **params)
-        self.batch, self.q = batch, None
-        q = C.c_void_p()
-        batch._check(batch.lib.soccer_wolf_phc_create(batch.h, C.byref(cfg), C.byref(q)))
+        self._create(batch, cfg)
         del keep                                   # (create has copied the fixed policies)
-        self.q = q
-        self.nS = batch.nS
         self.discount_factor = float(discount_factor)
-        batch._learners.add(self)
-
-    def run(self, n_steps):
-        """n_steps learner steps (every lane acts, the environment steps, both tables and the LEARN players' policies are
-        updated), enqueued."""
-        b = self.batch
-        b._check(b.lib.soccer_wolf_phc_run(b.h, self.q, int(n_steps)))
-        return self
 
     def update(self, obs, act_a, act_b, reward, terminated, next_obs):
         """One learner step's reduce / update / policy step on a batch of transitions (reward is player A's): DeviceArrays
@@ -729,17 +698,6 @@ class WolfPHCLearner:
         b._check(b.lib.soccer_wolf_phc_load(b.h, self.q, C.byref(state)))
         return self
 
-    def close(self):
-        if self.q and self.batch.h:
-            self.batch.lib.soccer_wolf_phc_destroy(self.batch.h, self.q)
-        self.q = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 _WOLF_HYPER = (("discount_factor", lambda x: (0.0 <= x) & (x < 1.0), "[0, 1)"), ("alpha", lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
                ("decay", lambda x: (0.0 < x) & (x <= 1.0), "(0, 1]"), ("explor", lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
@@ -787,49 +745,20 @@ def wolf_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 /
     return cfg, ((shared, each), arrays)
 
 
-class WolfPopulation:
+class WolfPopulation(_Population):
     """A population of policy hill-climbers (PHC / WoLF-PHC) on a two-player auto-reset SoccerBatch, a learner per lane:
     member i has its own Q_a, Q_b, pi_a, pi_b, avg_a, avg_b [nS, 5], updates[nS], alpha and dscale and learns from lane i alone
     (include/soccer_hip.h, "learners, a population of policy hill-climbers").  A fixed player's policy is per member.  run()
     enqueues and returns; read() and the properties synchronise and copy.  read(), load() and exploitability() take a range
     of members."""
+    _C = "soccer_wolf_population"
     _ROWS = ("Q_a", "Q_b", "pi_a", "pi_b", "avg_a", "avg_b")
 
     def __init__(self, batch, discount_factor, **params):
         cfg, keep = wolf_population_config(batch.n, batch.nS, discount_factor, **params)
-        self.batch, self.q = batch, None
-        q = C.c_void_p()
-        batch._check(batch.lib.soccer_wolf_population_create(batch.h, C.byref(cfg), C.byref(q)))
-        self.discount_factor = np.full(batch.n, cfg.discount_factor) if keep[1]["discount_factor"] is None else keep[1]["discount_factor"].copy()
+        self._create(batch, cfg, keep[1])
         del keep                                   # (create has copied the parameters and the fixed policies)
-        self.q = q
-        self.n, self.nS = batch.n, batch.nS
         self.modes = (cfg.act_a, cfg.act_b)
-        batch._learners.add(self)
-
-    def run(self, n_steps):
-        """n_steps steps of every member (its lane acts, the environment steps, its tables and its LEARN players' policies
-        are updated), enqueued."""
-        b = self.batch
-        b._check(b.lib.soccer_wolf_population_run(b.h, self.q, int(n_steps)))
-        return self
-
-    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
-        """One step's update on n transitions, transition i for member i (reward is player A's): DeviceArrays (or device
-        tensors) of n elements, or numpy arrays, which are copied to the device first."""
-        n = self.n
-
-        def call(h, q, count, *ptrs):
-            assert count == n, "a population's update takes one transition per member (%d)" % n
-            return self.batch.lib.soccer_wolf_population_update(h, q, *ptrs)
-        _learner_update(self.batch, call, self.q, obs, act_a, act_b, reward, terminated, next_obs)
-        return self
-
-    def _range(self, first, count):
-        first = int(first)
-        count = self.n - first if count is None else int(count)
-        assert 0 <= first <= self.n and 0 <= count <= self.n - first, "members %d .. %d + %d are outside the population of %d" % (first, first, count, self.n)
-        return first, count
 
     def _read(self, first, count, keys):
         nS, b = self.nS, self.batch
@@ -940,17 +869,6 @@ class WolfPopulation:
         c = WolfPopulation(self.batch, hyper.pop("discount_factor"), act_a=acts[0], act_b=acts[1], **hyper)
         return c.adopt(against, self, against, which)
 
-    def close(self):
-        if self.q and self.batch.h:
-            self.batch.lib.soccer_wolf_population_destroy(self.batch.h, self.q)
-        self.q = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def minimax_q_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, opponent="uniform"):
     """Checks the parameters of a population of minimax-Q learners (AssertionError, before any library call) and returns
@@ -995,48 +913,22 @@ def minimax_q_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 **
     return cfg, ((shared, each), arrays)
 
 
-class MinimaxQPopulation:
+class MinimaxQPopulation(_Population):
     """A population of minimax-Q learners (Littman 1994) on a two-player auto-reset SoccerBatch, a learner per lane: member i
     has its own Q[nS, 5, 5], V[nS], pi_a / pi_b [nS, 5] and alpha and learns from lane i alone (include/soccer_hip.h, "learners,
     a population of minimax-Q learners").  run() enqueues and returns; read() and the properties synchronise and copy.  Whole
     populations run to gigabytes, so read(), load() and exploitability() take a range of members."""
+    _C = "soccer_minimax_q_population"
     _ROWS = ("Q", "V", "pi_a", "pi_b")
 
     def __init__(self, batch, discount_factor, **params):
         cfg, keep = minimax_q_population_config(batch.n, batch.nS, discount_factor, **params)
-        self.batch, self.q = batch, None
-        q = C.c_void_p()
-        batch._check(batch.lib.soccer_minimax_q_population_create(batch.h, C.byref(cfg), C.byref(q)))
-        self.discount_factor = np.full(batch.n, cfg.discount_factor) if keep[1]["discount_factor"] is None else keep[1]["discount_factor"].copy()
+        self._create(batch, cfg, keep[1])
         del keep                                   # (create has copied the parameters and the fixed policies' thresholds)
-        self.q = q
-        self.n, self.nS = batch.n, batch.nS
         self.opponent = cfg.opponent
-        batch._learners.add(self)
 
-    def run(self, n_steps):
-        """n_steps steps of every member (its lane acts, the environment steps, its cell moves and its state is re-solved),
-        enqueued."""
-        b = self.batch
-        b._check(b.lib.soccer_minimax_q_population_run(b.h, self.q, int(n_steps)))
-        return self
-
-    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
-        """One step's update on n transitions, transition i for member i (reward is player A's): DeviceArrays (or device
-        tensors) of n elements, or numpy arrays, which are copied to the device first."""
-        n = self.n
-
-        def call(h, q, count, *ptrs):
-            assert count == n, "a population's update takes one transition per member (%d)" % n
-            return self.batch.lib.soccer_minimax_q_population_update(h, q, *ptrs)
-        _learner_update(self.batch, call, self.q, obs, act_a, act_b, reward, terminated, next_obs)
-        return self
-
-    def _range(self, first, count):
-        first = int(first)
-        count = self.n - first if count is None else int(count)
-        assert 0 <= first <= self.n and 0 <= count <= self.n - first, "members %d .. %d + %d are outside the population of %d" % (first, first, count, self.n)
-        return first, count
+    def _policies(self, first, count):
+        return self._read(first, count, ("pi_a", "pi_b"))
 
     def _read(self, first, count, keys):
         nS, b = self.nS, self.batch
@@ -1077,18 +969,6 @@ class MinimaxQPopulation:
         out["gap"] = out["v_b"] - out["v_a"]
         return out
 
-    def cross_play(self, theta=1e-10, first=0, count=None, discount_factor=None):
-        """What each member's player A scores against each member's player B: (payoff[count, count], iterations) of
-        SoccerBatch.cross_play on the strategies pi_a and pi_b of members first .. first + count - 1 (at most 1024).
-        discount_factor None: the range's common discount, ValueError if the members differ."""
-        return _population_cross_play(self, lambda f, c: self._read(f, c, ("pi_a", "pi_b")), "pi_a", "pi_b", theta, first, count,
-                                      discount_factor)
-
-    def meta_game(self, theta=1e-10, first=0, count=None, discount_factor=None, max_pivots=None):
-        """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
-        opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
-        return _meta_of_cross_play(self.batch, *self.cross_play(theta, first, count, discount_factor), max_pivots)
-
     def load(self, Q=None, V=None, pi_a=None, pi_b=None, alpha=None, steps=None, first=0):
         """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged):
         Q[count, nS, 5, 5] and V[count, nS] in [-1, 1], pi_a / pi_b [count, nS, 5], alpha[count], steps for the population.  Q
@@ -1111,17 +991,6 @@ class MinimaxQPopulation:
         b._check(b.lib.soccer_minimax_q_population_load(b.h, self.q, first, count,
                                                         *[keep[k].ctypes.data if k in keep else None for k in self._ROWS + ("alpha",)], st))
         return self
-
-    def close(self):
-        if self.q and self.batch.h:
-            self.batch.lib.soccer_minimax_q_population_destroy(self.batch.h, self.q)
-        self.q = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class SoccerBatch:

@@ -6,7 +6,7 @@
 //   soccer_rollout.hip   batched_rollout*
 //   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, cross-play, the matrix-game solver
 //   soccer_metagame.hip  soccer_solve_meta_games: the maximin mixtures of n_a x n_b matrix games
-//   soccer_learners.hip  the minimax-Q learner, the independent Q-learners, the policy hill-climbers, the three kinds of populations
+//   soccer_learners.hip  the six kinds of learners on one host skeleton: minimax-Q, independent Q, WoLF-PHC, and a population of each
 //   soccer_comm.hip      the RCCL wrapper (host code only)
 //
 // Every unit carries its own code object: a kernel is instantiated, launched and given its attributes (hipFuncSetAttribute)
@@ -115,6 +115,8 @@ struct PendingRun {
     int64_t act_stride = 0, out_stride = 0; // elements between consecutive steps (len >= 2)
 };
 
+struct Learner;                             // soccer_learners.hip: what the six kinds of learners have in common
+
 struct soccer_handle {
     soccer_config cfg{};
     Rules rules;
@@ -215,12 +217,8 @@ struct soccer_handle {
     int32_t* mg_int = nullptr;              // [games][kMetaRec] the records, then [games] pivots, [games] status, the open count
     size_t mg_need[5] = {0, 0, 0, 0, 0};    // what the buffers hold, in meta_need's order
     OwnedBufs mg_bufs{"the meta-game solver"};
-    std::vector<soccer_minimax_q*> learners; // soccer_minimax_q_create: the learners that were not destroyed (freed with the handle)
-    std::vector<soccer_q_learner*> q_learners; // soccer_q_learner_create: the same for the independent Q-learners
-    std::vector<soccer_wolf_phc*> phc_learners; // soccer_wolf_phc_create: the same for the policy hill-climbers
-    std::vector<soccer_q_population*> q_populations; // soccer_q_population_create: the same for the populations of Q-learners
-    std::vector<soccer_wolf_population*> wolf_populations; // soccer_wolf_population_create: the same for the populations of hill-climbers
-    std::vector<soccer_minimax_q_population*> mq_populations; // soccer_minimax_q_population_create: the same for the populations of minimax-Q learners
+    std::vector<Learner*> learners;         // soccer_*_create of soccer_learners.hip: the learners and populations of every kind that
+                                            // were not destroyed (freed with the handle, learners_release)
     std::string err;
 
     soccer_handle() = default;
