@@ -121,7 +121,9 @@ RUN_CASES = [(2, 259, 1, "greedy", 5, 4, 0.0, 0),
              (5, 67, 0, "fixed", 7, 5, 0.3, 0),
              (5, 1, 1, "greedy", 5, 4, 0.0, 3),
              (2, 259, 0, "uniform", 5, 4, 0.2, 0),
-             (1024, 3, 1, "fixed", 7, 5, 0.3, 1)]
+             (1024, 3, 1, "fixed", 7, 5, 0.3, 1),
+             # 12x14 at the slip of the populations' G: pop_league_run_kernel with the observation table in global memory
+             (5, 17, 1, "greedy", 12, 14, 0.2, 0)]
 
 
 @pytest.mark.parametrize("case", RUN_CASES, ids=lambda c: "K%d-n%d-p%d-%s-%dx%d-s%s-off%d" % c)

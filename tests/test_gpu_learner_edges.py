@@ -1,7 +1,7 @@
 """-m gpu: the three on-device learners (minimax-Q, the independent Q-learners, WoLF-PHC) against their numpy restatements, bit
 for bit, away from the corner their own suites test in: episodes that truncate (T, C), frozen, goal-parked and nearly-out-of-time
 lanes in one launch (S), grid-stride loops that wrap in run() and update() (W, U), the integer sums at their stated worst case
-(U), act kernels with more than 48 KB of dynamic LDS (L) and a lane offset that carries lane ids across 2^32 (O).  The cases are
+(U), act kernels with more than 48 KB of dynamic LDS (L), act kernels whose observation table stays in global memory (G) and a lane offset that carries lane ids across 2^32 (O).  The cases are
 defined in tests/test_learner_edges_np.py, which also shows without a GPU that each reaches its path.  No tolerances."""
 import os
 import sys
@@ -206,6 +206,24 @@ def test_act_kernels_with_more_than_48_kb_of_lds(host, learner):
     sh = b.rollout_shape()
     assert sh["kernel"] == _lib.ROLLOUT_PER_LANE and sh["dynamic_lds_bytes"] > 48 * 1024
     assert sh["dynamic_lds_bytes"] > (o.W * o.H) ** 2 * 4      # the observation table is staged in it
+    b.close()
+
+
+# ---- G: the observation table in global memory ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("learner", LEARNERS)
+def test_act_kernels_with_the_observation_table_in_global_memory(host, learner):
+    """12x14: learner_act_kernel / q_act_kernel / phc_act_kernel with LUT_LDS = false, which stage the move table alone"""
+    c = CASES["G"]
+    o, ref = reference(learner, "G", host)[:2]
+    assert ref.n_terminated > 0 and ref.n_truncated > 0
+    b, q = device_run(learner, c, [c["T"]])
+    assert b.nS == 56113
+    assert_equals_reference(learner, b, q, o, ref)
+    rew = b.alloc(c["n"] + 8, np.int8)
+    b.rollout(1, sample_actions=True, reward=rew.ptr + 1, out_stride=c["n"] + 4)     # as in L: what the act kernels are launched with
+    sh = b.rollout_shape()
+    assert sh["kernel"] == _lib.ROLLOUT_PER_LANE and 0 < sh["dynamic_lds_bytes"] < (o.W * o.H) ** 2 * 4
+    assert sh["dynamic_lds_bytes"] == (2 * o.W * o.H * 5 + 16) * 4
     b.close()
 
 

@@ -34,6 +34,8 @@ CASES = {
     "S uint8 end of t": dict(w=5, h=4, slip=0.2, n=4096 + 3, max_steps=250, T=12, special="mixed"),
     "L": dict(w=5, h=16, slip=0.2, n=8192 + 3, max_steps=100, T=30),
     "O": dict(w=5, h=4, slip=0.2, n=4096 + 3, max_steps=6, T=20, lane_offset=2 ** 32 - 4096),
+    # the pitch, slip and max_steps of the populations' G (tests/test_population_edges_np.py): the observation table does not fit LDS
+    "G": dict(w=12, h=14, slip=0.2, n=4096 + 3, max_steps=7, T=16),
 }
 # the same handle as O at offset 0: what O must differ from
 CASES["O at offset 0"] = dict(CASES["O"], lane_offset=0)
@@ -202,6 +204,17 @@ def test_case_L_terminates_on_the_tall_pitch(host, learner):
     o, ref = reference(learner, "L", host)[:2]
     assert o.nS == 12641 and (o.W * o.H) ** 2 * 4 == 50176 > 48 * 1024       # the observation table alone
     assert ref.n_terminated > 0 and ref.n_left_out == 0
+
+
+@pytest.mark.parametrize("learner", LEARNERS)
+def test_case_G_terminates_and_truncates_where_the_table_leaves_lds(host, learner):
+    c = CASES["G"]
+    o, ref = reference(learner, "G", host)[:2]
+    table, moves = (o.W * o.H) ** 2 * 4, (2 * o.W * o.H * 5 + 16) * 4
+    assert o.nS == 56113 and table == 153664 and table + moves > 150 * 1024 > moves          # soccer_create's line
+    print("%s: %d truncated, %d terminated of %d transitions" % (learner, ref.n_truncated, ref.n_terminated, c["n"] * c["T"]))
+    assert ref.n_truncated >= c["n"] and ref.n_terminated >= 100 and ref.n_left_out == 0
+    assert int(ref.visits.sum()) == c["n"] * c["T"] and (o.hist > 0).all()
 
 
 @pytest.mark.parametrize("learner", LEARNERS)

@@ -2,8 +2,8 @@
 col_b, t) on the CPU, EXHAUSTIVELY: the round trip of every field value in every byte position with its neighbours untouched,
 and a step taken through packed dwords against the step through the six-stream swar::Group and against the oracle, over the
 enumeration tests/test_swar_host.py uses (every reachable tuple x 25 joint actions x 4 outcome draws x 4 reset draws) on the
-two pitches the packed layout is timed on, 5x4 and 11x7.  tests/host/state_pack_host.cpp compiles the header for the host, so
-this is the code the kernels run.  SWAR_HOST_SANITIZE=1 builds it with UndefinedBehaviorSanitizer."""
+two pitches the packed layout is timed on, 5x4 and 11x7, and on 14x8, the corner of the layout (row 7, column 15, H * W = 128).
+tests/host/state_pack_host.cpp compiles the header for the host, so this is the code the kernels run.  SWAR_HOST_SANITIZE=1 builds it with UndefinedBehaviorSanitizer."""
 import ctypes as C
 import os
 import subprocess
@@ -95,7 +95,7 @@ def _against_oracle(got, exp):
         np.testing.assert_array_equal(got["state"][k], exp["state"][k], err_msg=name)
 
 
-@pytest.mark.parametrize("w,h", [(5, 4), (11, 7)])
+@pytest.mark.parametrize("w,h", [(5, 4), (11, 7), (14, 8)])
 @pytest.mark.parametrize("autoreset", [True, False])
 def test_general_step_through_packed_dwords(host, w, h, autoreset):
     """live and goal tuples, frozen lanes, timesteps around the truncation: Out and next state of the packed walk equal the
@@ -110,7 +110,7 @@ def test_general_step_through_packed_dwords(host, w, h, autoreset):
             _against_oracle(_step_both_ways(host, w, h, autoreset, True, full, geo0, st, t, need, aa, ab, words), exp)
 
 
-@pytest.mark.parametrize("w,h", [(5, 4), (11, 7)])
+@pytest.mark.parametrize("w,h", [(5, 4), (11, 7), (14, 8)])
 def test_steady_state_step_through_packed_dwords(host, w, h):
     """the instantiation without the frozen-lane / goal-tuple code, on every live tuple"""
     rng = np.random.default_rng(w * 100 + h + 1)

@@ -1,7 +1,8 @@
 """The byte-parallel step of the hot kernels (csrc/soccer_swar.hpp: four lanes per dword, no rule tables) against the
 oracle, on the CPU, EXHAUSTIVELY: every reachable tuple (live and goal) x 25 joint actions x 4 outcome draws x 4 reset
 draws, at timesteps around the truncation, frozen and not, with and without auto-reset, on every pitch the reference
-parametrises (tests/test_general.py:5-11) — 5x4 ... 11x7.  The header compiles for the host with the four GPU builtins
+parametrises (tests/test_general.py:5-11) — 5x4 ... 11x7 — and on the pitches at the edges of the byte arithmetic itself
+(PITCHES below).  The header compiles for the host with the four GPU builtins
 it uses restated in C++ (tests/host/swar_host.cpp), so this is the code the kernels run.  The oracle itself is pinned
 to the reference by tests/test_oracle_golden.py."""
 import ctypes as C
@@ -113,7 +114,11 @@ def _compare(got, exp, need, full):
     assert not got["bad"].any()
 
 
-PITCHES = [(5, 4), (6, 4), (7, 5), (9, 6), (11, 7)]
+# the reference's pitches, then the byte arithmetic's own extremes (tests/large_pitch_cases.py): 6x6 the last pitch on the byte
+# tables and 6x7 its first arithmetic neighbour, 14x8 with row 7, column 15 and H * W = 128, 15x4 and 30x4 (columns 16 .. 31),
+# 5x9 and 5x18 (rows 8 .. 17).  Nothing is thinned: every tuple, action pair and draw on each of them.
+PITCHES = [(5, 4), (6, 4), (7, 5), (9, 6), (11, 7), (6, 6), (6, 7), (14, 8), (15, 4), (30, 4), (5, 9), (5, 18)]
+SMALL = [(w, h) for w, h in PITCHES if h + 2 <= 8 and w + 2 <= 8]        # Consts::small: these take the byte tables unless told otherwise
 
 
 @pytest.fixture(params=["tables", "arithmetic"])
@@ -128,7 +133,7 @@ def geometry(request, host):
 @pytest.mark.parametrize("w,h", PITCHES)
 @pytest.mark.parametrize("autoreset", [True, False])
 def test_general_step_every_tuple_action_and_draw(host, geometry, w, h, autoreset):
-    if geometry == "arithmetic" and (w, h) not in ((5, 4), (6, 4)):
+    if geometry == "arithmetic" and (w, h) not in SMALL:
         pytest.skip("already arithmetic")
     rng = np.random.default_rng(w * 100 + h)
     o = Oracle(w, h, 0.0, n=1)
@@ -144,7 +149,7 @@ def test_general_step_every_tuple_action_and_draw(host, geometry, w, h, autorese
 
 @pytest.mark.parametrize("w,h", PITCHES)
 def test_steady_state_step_every_live_tuple_action_and_draw(host, geometry, w, h):
-    if geometry == "arithmetic" and (w, h) not in ((5, 4), (6, 4)):
+    if geometry == "arithmetic" and (w, h) not in SMALL:
         pytest.skip("already arithmetic")
     """the instantiation of an auto-resetting handle whose lanes have all been reset: no frozen / goal-tuple code"""
     rng = np.random.default_rng(w * 100 + h + 1)
