@@ -129,6 +129,11 @@ class MinimaxQPopulationConfig(C.Structure):
         "opponent_policy_per_member", "alpha_per_member", "decay_per_member", "explor_per_member", "discount_factor_per_member")]
 
 
+class OMPopulationConfig(C.Structure):
+    """soccer_om_population_config"""
+    _fields_ = QPopulationConfig._fields_
+
+
 MQ_UNIFORM, MQ_SELF, MQ_FIXED = 0, 1, 2
 QL_GREEDY, QL_UNIFORM, QL_FIXED = 0, 1, 2
 PHC_LEARN, PHC_UNIFORM, PHC_FIXED = 0, 1, 2
@@ -235,6 +240,12 @@ PROTOTYPES = {
     "soccer_minimax_q_population_update": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
     "soccer_minimax_q_population_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64)]),
     "soccer_minimax_q_population_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64)]),
+    "soccer_om_population_create": (C.c_int, [C.c_void_p, C.POINTER(OMPopulationConfig), C.POINTER(C.c_void_p)]),
+    "soccer_om_population_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "soccer_om_population_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "soccer_om_population_update": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
+    "soccer_om_population_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64)]),
+    "soccer_om_population_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64)]),
     "soccer_prob_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 12)]),
     "soccer_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint64)]),
     "soccer_reset_stats": (C.c_int, [C.c_void_p]),

@@ -583,6 +583,139 @@ class QPopulation(_Population):
         return self
 
 
+def om_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
+    """Checks the parameters of a population of opponent-modelling Q-learners (AssertionError, before any library call) and
+    returns (soccer_om_population_config, the arrays it points into): q_population_config's checks and layout, no league."""
+    cfg, keep = q_population_config(n, nS, discount_factor, alpha, decay, explor, q_init, act_a, act_b)
+    return _lib.OMPopulationConfig.from_buffer_copy(cfg), keep
+
+
+def om_derive(Q, counts):
+    """The derived values of an opponent-modelling Q-learner by the definition's expression (include/soccer_hip.h, "learners, a
+    population of opponent-modelling Q-learners"), operation for operation, so they equal the device's: Q [..., 5, 5] (own
+    action, other's action) and counts [..., 5] (uint64) -> (V [...], g [...])."""
+    Q = np.asarray(Q, np.float64); counts = np.asarray(counts, np.uint64)
+    n = counts.sum(-1, dtype=np.uint64)
+    w = np.where((n > 0)[..., None], counts.astype(np.float64), 1.0)
+    N = np.where(n > 0, n.astype(np.float64), 5.0)
+    W = w[..., None, 0] * Q[..., 0]
+    for k in range(1, 5):
+        W = W + w[..., None, k] * Q[..., k]
+    g = W.argmax(-1)                                # the first index that attains the maximum
+    V = np.minimum(1.0, np.maximum(-1.0, np.take_along_axis(W, g[..., None], -1)[..., 0] / N))
+    return V, g
+
+
+def om_model(counts):
+    """Counts [..., 5] of a player's actions as a mixed policy: the frequencies, 0.2 where nothing was seen; renormalised in
+    float64 so that a row whose quotients sum an ulp off 1 is a policy row to the library."""
+    c = np.asarray(counts, np.uint64).astype(np.float64)
+    n = c.sum(-1, keepdims=True)
+    m = np.where(n > 0, c / np.where(n > 0, n, 1.0), 0.2)
+    return m / m.sum(-1, keepdims=True)
+
+
+class OpponentModelPopulation(_Population):
+    """A population of opponent-modelling Q-learners (joint-action learners; fictitious play in self-play) on a two-player
+    auto-reset SoccerBatch, a learner per lane: member i has, per player, a joint-action table Q[nS, 5, 5] over (own action,
+    the other's action) in that player's own reward and the counts C[nS, 5] of the other player's actions, and its alpha, and
+    learns from lane i alone (include/soccer_hip.h, "learners, a population of opponent-modelling Q-learners").  A player
+    answers the other's empirical frequencies greedily.  run() enqueues and returns; read() and the properties synchronise and
+    copy.  read(), load() and exploitability() take a range of members (a member is 390 KB on 5x4)."""
+    _C = "soccer_om_population"
+    _WHICH = {"greedy": ("pi_a", "pi_b"), "model": ("model_a", "model_b")}
+
+    def __init__(self, batch, discount_factor, **params):
+        cfg, keep = om_population_config(batch.n, batch.nS, discount_factor, **params)
+        self._create(batch, cfg, keep[1])
+        del keep                                   # (create has copied the parameters and the fixed policies' thresholds)
+
+    def _read(self, first, count, keys):
+        """the library's arrays alone: any of Q_a, Q_b, C_a, C_b, alpha, steps"""
+        nS, b = self.nS, self.batch
+        shapes = {"Q_a": ((count, nS, 5, 5), np.float64), "Q_b": ((count, nS, 5, 5), np.float64), "C_a": ((count, nS, 5), np.uint64),
+                  "C_b": ((count, nS, 5), np.uint64), "alpha": ((count,), np.float64)}
+        out = {k: np.zeros(*shapes[k]) for k in keys if k != "steps"}
+        st = C.c_uint64()
+        b._check(b.lib.soccer_om_population_read(b.h, self.q, first, count, *[out[k].ctypes.data if k in out else None for k in shapes],
+                                                 C.byref(st) if "steps" in keys else None))
+        if "steps" in keys:
+            out["steps"] = int(st.value)
+        return out
+
+    def read(self, first=0, count=None):
+        """dict for members first .. first + count - 1 (count None: to the end): Q_a / Q_b [count, nS, 5, 5], C_a / C_b
+        [count, nS, 5] (uint64), alpha[count], steps; and, computed here by the definition's expression, V_a / V_b [count, nS]
+        and pi_a / pi_b [count, nS, 5] (one-hot of g); and model_a = C_b as frequencies (what B has seen A play; 0.2 where
+        nothing was seen), model_b = C_a likewise.  Synchronises."""
+        first, count = self._range(first, count)
+        out = self._read(first, count, ("Q_a", "Q_b", "C_a", "C_b", "alpha", "steps"))
+        for p, other in (("a", "b"), ("b", "a")):
+            out["V_" + p], g = om_derive(out["Q_" + p], out["C_" + p])
+            out["pi_" + p] = np.eye(5)[g]
+            out["model_" + p] = om_model(out["C_" + other])
+        return out
+
+    alpha = property(lambda self: self._read(0, self.n, ("alpha",))["alpha"], doc="every member's learning rate, [n]")
+    steps = property(lambda self: self._read(0, 0, ("steps",))["steps"])
+
+    def exploitability(self, which="greedy", theta=1e-10, first=0, count=None):
+        """How badly the best possible opponent beats the pair of greedy policies (which='greedy') or the pair of models
+        (which='model': model_a, what B has seen A play, with model_b) of each member of a range, at that member's discount:
+        through SoccerBatch.best_response in batches of at most 256 members with one discount.  Returns {"v_a", "v_b", "gap"},
+        arrays of [count, nS] (planners.exploitability's per member)."""
+        assert which in self._WHICH, "which must be 'greedy' or 'model'"
+        ka, kb = self._WHICH[which]
+        first, count = self._range(first, count)
+        b = self.batch
+        out = {k: np.zeros((count, self.nS)) for k in ("v_a", "v_b", "gap")}
+        for c0 in range(0, count, _lib.BR_MAX_POLICIES):
+            c = min(_lib.BR_MAX_POLICIES, count - c0)
+            r = self.read(first + c0, c)
+            gam = self.discount_factor[first + c0:first + c0 + c]
+            for g in np.unique(gam):                # (one solve per discount in the chunk: a batch shares its discount)
+                idx = np.flatnonzero(gam == g)
+                out["v_a"][c0 + idx] = b.best_response(r[ka][idx], 0, theta, float(g))[1]
+                out["v_b"][c0 + idx] = b.best_response(r[kb][idx], 1, theta, float(g))[1]
+        out["gap"] = out["v_b"] - out["v_a"]
+        return out
+
+    def cross_play(self, which="greedy", theta=1e-10, first=0, count=None, discount_factor=None):
+        """What each member's player A scores against each member's player B: (payoff[count, count], iterations) of
+        SoccerBatch.cross_play on the greedy policies (which='greedy') or the models (which='model') of members first ..
+        first + count - 1 (at most 1024).  discount_factor None: the range's common discount, ValueError if the members differ."""
+        assert which in self._WHICH, "which must be 'greedy' or 'model'"
+        return _population_cross_play(self, self.read, *self._WHICH[which], theta, first, count, discount_factor)
+
+    def meta_game(self, which="greedy", theta=1e-10, first=0, count=None, discount_factor=None, max_pivots=None):
+        """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
+        opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
+        return _meta_of_cross_play(self.batch, *self.cross_play(which, theta, first, count, discount_factor), max_pivots)
+
+    def load(self, Q_a=None, Q_b=None, C_a=None, C_b=None, alpha=None, steps=None, first=0):
+        """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged): Q_a /
+        Q_b [count, nS, 5, 5] in [-1, 1], C_a / C_b [count, nS, 5] counts, alpha[count], steps for the population.  V and the
+        greedy actions follow on the device.  With what read() gave, a fresh population continues bit for bit.  A refused
+        load changes nothing."""
+        b = self.batch
+        arrs = [None if x is None else np.ascontiguousarray(x, dt) for x, dt in
+                zip((Q_a, Q_b, C_a, C_b, alpha), (np.float64, np.float64, np.uint64, np.uint64, np.float64))]
+        counts = {x.shape[0] for x in arrs if x is not None and x.ndim >= 1}
+        assert len(counts) <= 1, "Q_a, Q_b, C_a, C_b and alpha must hold the same number of members"
+        first, count = self._range(first, counts.pop() if counts else 0)
+        for x in arrs[:2]:
+            if x is not None:
+                assert x.shape == (count, self.nS, 5, 5), "Q_a / Q_b must be [count, n_states, 5, 5]"
+                assert (np.abs(x[:, 1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
+        for x in arrs[2:4]:
+            assert x is None or x.shape == (count, self.nS, 5), "C_a / C_b must be [count, n_states, 5]"
+        if arrs[4] is not None:
+            assert arrs[4].shape == (count,) and ((arrs[4] >= 0.0) & (arrs[4] <= 1.0)).all(), "alpha must be [count] values in [0, 1]"
+        st = None if steps is None else C.byref(C.c_uint64(int(steps)))
+        b._check(b.lib.soccer_om_population_load(b.h, self.q, first, count, *[None if x is None else x.ctypes.data for x in arrs], st))
+        return self
+
+
 def wolf_phc_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
                     delta_decay=1.0, act_a="learn", act_b="learn"):
     """Checks the parameters of the policy hill-climbers (AssertionError, before any library call) and returns
@@ -1348,6 +1481,13 @@ class SoccerBatch:
         episode (include/soccer_hip.h, "learners, a league opponent for the population of Q-learners")."""
         return QPopulation(self, discount_factor, league_policies=league_policies, league_weights=league_weights, alpha=alpha, decay=decay,
                            explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
+
+    def om_population(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
+        """An OpponentModelPopulation on this batch (two players, autoreset=True): an opponent-modelling Q-learner per lane,
+        each with its own joint-action tables and counts of the other player's actions.  discount_factor, alpha, decay and
+        explor are scalars or arrays of one value per lane; act_a / act_b as for q_learning: 'greedy' answers the other
+        player's empirical frequencies (a fixed policy is shared by all members)."""
+        return OpponentModelPopulation(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
 
     def wolf_phc(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
                  delta_decay=1.0, act_a="learn", act_b="learn"):

@@ -6,7 +6,8 @@
 //   soccer_rollout.hip   batched_rollout*
 //   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, cross-play, the matrix-game solver
 //   soccer_metagame.hip  soccer_solve_meta_games: the maximin mixtures of n_a x n_b matrix games
-//   soccer_learners.hip  the six kinds of learners on one host skeleton: minimax-Q, independent Q, WoLF-PHC, and a population of each
+//   soccer_learners.hip  the seven kinds of learners on one host skeleton: minimax-Q, independent Q, WoLF-PHC, a population of each, and a
+//                        population of opponent-modelling Q-learners
 //   soccer_comm.hip      the RCCL wrapper (host code only)
 //
 // Every unit carries its own code object: a kernel is instantiated, launched and given its attributes (hipFuncSetAttribute)
@@ -115,7 +116,7 @@ struct PendingRun {
     int64_t act_stride = 0, out_stride = 0; // elements between consecutive steps (len >= 2)
 };
 
-struct Learner;                             // soccer_learners.hip: what the six kinds of learners have in common
+struct Learner;                             // soccer_learners.hip: what the seven kinds of learners have in common
 
 struct soccer_handle {
     soccer_config cfg{};

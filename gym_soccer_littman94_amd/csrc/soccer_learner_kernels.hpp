@@ -6,7 +6,8 @@
 // pop_update_kernel, pop_init_kernel; and the population of
 // one-actor policy hill-climbers: phc_pop_run_kernel, phc_pop_update_kernel, phc_pop_init_kernel, phc_pop_adopt_kernel; and the
 // population of one-actor minimax-Q learners, a wave per member: mq_pop_run_kernel, mq_pop_update_kernel, mq_pop_solve_kernel,
-// mq_pop_init_kernel (at the end).
+// mq_pop_init_kernel; and the population of one-actor opponent-modelling Q-learners: om_pop_run_kernel, om_pop_update_kernel,
+// om_pop_init_kernel, om_pop_derive_kernel (at the end).
 // Included by soccer_learners.hip only: every kernel is emitted by exactly one translation unit.
 //
 // One learner step (include/soccer_hip.h, "learners") is two launches in stream order, no grid barrier between them:
@@ -1256,6 +1257,253 @@ __global__ __launch_bounds__(kBlock) void mq_pop_init_kernel(const MqPopIO L, un
     for (unsigned long long c = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; c < cells; c += (unsigned long long)gridDim.x * kBlock)
         L.tab[c] = (unsigned)(c % kMqRow) <= (unsigned)kMqV ? ((c % per) < (unsigned long long)kMqRow ? 0.0 : q_init) : 0.2;
     if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps = 0ull;
+}
+
+// =================================================================================================
+// a population of opponent-modelling Q-learners, a learner per lane (include/soccer_hip.h, "learners, a population of
+// opponent-modelling Q-learners")
+// =================================================================================================
+// pop_run_kernel's shape: a thread owns lane i and member i, nothing is shared between threads, no atomics, no second launch.
+// Its argument block is PopIO with Q = the members' rows.
+// Table layout: member i's block is [nS][2][32] 8-byte slots — player A's 256-byte row, then player B's, are the 512
+// adjacent, 256-byte aligned bytes a step needs at s.  Per player:
+//     0..24 Q[own * 5 + other] (float64)   25..29 C[other] (uint64)   30 V (float64)   31 g (uint64)
+// so (V, g) is one 16-byte load, and a member's block is contiguous: a range of members is one copy.
+// V and g are kept in the row (derived by om_derive, the one function every kernel here calls, and stored whenever Q or C
+// of the row moved) so that a step's dependent chain is short: acting needs g_p[s] alone, carried in a register — it is
+// what the (V, g) load at s' of the previous step brought while the episode goes on, what om_learn just derived when
+// s' == s, and loaded only after a reset; the bootstrap needs V_p[s'] alone, that one 16-byte load per player.  The full
+// row at s (25 Q + 5 C) is needed only to derive again after the update: its address is known at the top of the step, so
+// player A's row is asked for before the environment step; player B's row is loaded when A's is done, so that one player's
+// 30 values are live at a time.  The cell, the count and (V, g) are stored straight away: memory always holds what the
+// registers hold, a launch boundary changes nothing, and a thread's later load at s' == s sees its own store.
+// Actions and cells are COMPARED, never used as subscripts of the register rows (pop_learn's rule): 0 bytes of scratch.
+constexpr int kOmPlayer = 32;                       // slots per player and state
+constexpr int kOmRow = 2 * kOmPlayer;               // slots per state
+constexpr int kOmC = 25, kOmV = 30;                 // a player's counts; its (V, g) pair
+
+struct OmRow {
+    double Q[25];                       // [own][other]
+    unsigned long long C[5];            // [other]
+};
+
+__device__ __forceinline__ void om_load_row(const double* at, OmRow& row) {
+    const double2* p = reinterpret_cast<const double2*>(at);
+    double v[30];
+#pragma unroll
+    for (int k = 0; k < 15; ++k) { const double2 x = p[k]; v[2 * k] = x.x; v[2 * k + 1] = x.y; }
+#pragma unroll
+    for (int k = 0; k < 25; ++k) row.Q[k] = v[k];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) row.C[k] = (unsigned long long)__double_as_longlong(v[kOmC + k]);
+}
+
+// THE derived values of one (player, state): the greedy answer g to the empirical frequencies of the other player's
+// actions, and its value V (the header's expression, operation for operation; the build does not contract)
+__device__ __forceinline__ void om_derive(const OmRow& row, double& V, uint32_t& g) {
+    const unsigned long long n = row.C[0] + row.C[1] + row.C[2] + row.C[3] + row.C[4];
+    double w[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) w[k] = n > 0ull ? (double)row.C[k] : 1.0;
+    const double N = n > 0ull ? (double)n : 5.0;
+    double best = 0.0;
+    g = 0u;
+#pragma unroll
+    for (int a = 0; a < 5; ++a) {
+        double W = w[0] * row.Q[5 * a];
+#pragma unroll
+        for (int k = 1; k < 5; ++k) W = W + w[k] * row.Q[5 * a + k];
+        if (a == 0 || W > best) { best = W; g = (uint32_t)a; }              // the first index that attains it
+    }
+    const double v = best / N;
+    V = v < -1.0 ? -1.0 : (v > 1.0 ? 1.0 : v);
+}
+
+__device__ __forceinline__ void om_store_derived(double* at, double V, uint32_t g) {
+    *reinterpret_cast<double2*>(at + kOmV) = make_double2(V, __longlong_as_double((long long)g));
+}
+
+// the (V, g) pair of one player's row
+__device__ __forceinline__ void om_load_derived(const double* at, double& V, uint32_t& g) {
+    const double2 x = *reinterpret_cast<const double2*>(at + kOmV);
+    V = x.x; g = (uint32_t)__double_as_longlong(x.y);
+}
+
+// steps 4-5 of one player of one member on its one transition: `at` = the player's row at s in memory, `row` = that row in
+// registers, own / other = the two actions as this player sees them, r = its own reward, v_next = its V[s'] as it was BEFORE
+// this update.  Moves and stores the cell, the count and (V, g); hands the new g back.
+__device__ __forceinline__ void om_learn(double* at, OmRow& row, uint32_t own, uint32_t other, int32_t r, uint32_t term, double v_next,
+                                         double alpha, double gamma, uint32_t& g) {
+    const long long SV = term ? 0ll : (long long)rint(v_next * kVqScale);
+    const double m = (double)r + gamma * ((double)SV * kVqInv);
+    const uint32_t cell = own * 5u + other;
+    double old = row.Q[0];
+#pragma unroll
+    for (int k = 1; k < 25; ++k) old = (uint32_t)k == cell ? row.Q[k] : old;
+    const double moved = old + alpha * (m - old);
+#pragma unroll
+    for (int k = 0; k < 25; ++k) row.Q[k] = (uint32_t)k == cell ? moved : row.Q[k];
+    unsigned long long c = 0ull;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        row.C[k] += (uint32_t)k == other ? 1ull : 0ull;
+        c = (uint32_t)k == other ? row.C[k] : c;
+    }
+    at[cell] = moved;
+    reinterpret_cast<unsigned long long*>(at)[kOmC + other] = c;
+    double V;
+    om_derive(row, V, g);
+    om_store_derived(at, V, g);
+}
+
+// a player's action from its 15-bit draw h: the null row table, the shared fixed rows, or epsilon-greedy on onehot(g)
+__device__ __forceinline__ uint32_t om_pop_draw(const PopIO& L, int p, uint32_t g, uint32_t s, double explor, uint32_t h) {
+    if (L.mode[p] == kPopUniform) return (h * 5u) >> 15;                       // wave-uniform
+    uint2 th;
+    if (L.mode[p] == kPopGreedy) {
+        double pi[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) pi[k] = (uint32_t)k == g ? 1.0 : 0.0;
+        __attribute__((aligned(8))) uint16_t t[4];
+        learner_thresholds(pi, explor, t);
+        th = *reinterpret_cast<const uint2*>(t);
+    } else {
+        th = *reinterpret_cast<const uint2*>(L.mix[p] + 4u * s);
+    }
+    return (h >= (th.x & 0xffffu)) + (h >= (th.x >> 16)) + (h >= (th.y & 0xffffu)) + (h >= (th.y >> 16));
+}
+
+template <bool SLIP, bool LUT_LDS>
+__global__ __launch_bounds__(kBlock) void om_pop_run_kernel(const KernelParams P, const PopIO L) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    HistAcc<false> hist; hist.init(P);
+    const Tables T = stage_tables<LUT_LDS>(P, smem);
+    const unsigned long long tick0 = *P.tick_in;
+    publish_tick(P, tick0, (unsigned long long)L.n_steps);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps += (unsigned long long)L.n_steps;
+    bool any_frozen = false;
+    for (unsigned long long g = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; g < P.n;
+         g += (unsigned long long)gridDim.x * kBlock) {
+        const unsigned long long i0 = P.first + g;                  // the lane, and the member
+        LaneVec<1> S; S.load(P, i0);
+        double* const tab = L.Q + (size_t)i0 * (size_t)L.nS * kOmRow;
+        double alpha = L.alpha[i0];
+        const double decay = L.decay[i0], explor = L.explor[i0], gamma = L.gamma[i0];
+        uint32_t s = obs_of(T, P, S.L[0].A, S.L[0].B, S.L[0].p);
+        double unused;
+        uint32_t ga, gb;                                            // g_A[s], g_B[s]
+        om_load_derived(tab + (size_t)s * kOmRow, unused, ga);
+        om_load_derived(tab + (size_t)s * kOmRow + kOmPlayer, unused, gb);
+        int32_t ret = 0; uint32_t eps = 0u, nonzero = 0u;
+        for (int t = 0; t < L.n_steps; ++t) {
+            const unsigned long long tick = tick0 + (unsigned long long)t;
+            double* const at = tab + (size_t)s * kOmRow;
+            OmRow row;
+            om_load_row(at, row);                                   // player A's row at s: wanted only after the step
+            uint32_t words[1], awords[1];
+            lane_words<1>(P, P.lane_offset + i0, block_tick<SLIP>(tick), 0u, words);
+            lane_words<1>(P, P.lane_offset + i0, tick, 1u, awords);
+            const Draw d = draw_from_word<SLIP>(words[0], tick);
+            // two actions from one 32-bit word, 15 bits each (rollout_group)
+            const uint32_t a = om_pop_draw(L, 0, ga, s, explor, awords[0] & 0x7fffu);
+            const uint32_t b = om_pop_draw(L, 1, gb, s, explor, (awords[0] >> 16) & 0x7fffu);
+            StepResult R;
+            const bool frozen = lane_step<SLIP, true>(T, P, S.L[0], a, b, d, R);
+            ret += R.reward; eps += R.finished; nonzero += (uint32_t)R.reward & 1u;
+            any_frozen |= frozen;
+            // (a lane parked in a goal tuple by soccer_set_state has s = 0: never a current state)
+            const bool learn = !frozen && s != 0u;
+            const uint32_t s2 = R.final_obs, sn = R.obs;
+            uint32_t ga2 = 0u, gb2 = 0u;
+            if (learn) {
+                double va2, vb2;                                    // before the stores below: s' may be s
+                om_load_derived(tab + (size_t)s2 * kOmRow, va2, ga2);
+                om_load_derived(tab + (size_t)s2 * kOmRow + kOmPlayer, vb2, gb2);
+                om_learn(at, row, a, b, R.reward, R.term, va2, alpha, gamma, ga);
+                om_load_row(at + kOmPlayer, row);
+                om_learn(at + kOmPlayer, row, b, a, -R.reward, R.term, vb2, alpha, gamma, gb);
+            }                                                       // (ga, gb are g at s as the update left it)
+            if (sn != s) {
+                if (learn && sn == s2) {                            // the episode goes on: the pair at s' is the next pair at s
+                    ga = ga2; gb = gb2;
+                } else {                                            // after a reset
+                    om_load_derived(tab + (size_t)sn * kOmRow, unused, ga);
+                    om_load_derived(tab + (size_t)sn * kOmRow + kOmPlayer, unused, gb);
+                }
+            }
+            s = sn;
+            alpha = alpha * decay;
+        }
+        S.store(P, i0);
+        L.alpha[i0] = alpha;
+        hist.add_totals(eps, ret, nonzero);
+    }
+    if (any_frozen) P.misuse[0] = 1u;
+    hist.flush(P);
+}
+
+// soccer_om_population_update: steps 3-6 on the caller's transitions, transition i for member i
+__global__ __launch_bounds__(kBlock) void om_pop_update_kernel(const PopIO L, long long n, const uint16_t* obs, const int8_t* act_a,
+                                                               const int8_t* act_b, const int8_t* reward, const uint8_t* terminated,
+                                                               const uint16_t* next_obs) {
+    bool bad_act = false, bad_obs = false;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
+        const uint32_t s = obs[i], s2 = next_obs[i], a = (uint8_t)act_a[i], b = (uint8_t)act_b[i];
+        const bool ba = a > 4u || b > 4u, bo = s == 0u || s >= (uint32_t)L.nS || s2 >= (uint32_t)L.nS;
+        bad_act |= ba; bad_obs |= bo;
+        const double alpha = L.alpha[i];
+        if (!ba && !bo) {
+            double* const tab = L.Q + (size_t)i * (size_t)L.nS * kOmRow;
+            double* const at = tab + (size_t)s * kOmRow;
+            const uint32_t term = terminated[i] != 0u ? 1u : 0u;
+            const int32_t r = (int32_t)reward[i];
+            double va2, vb2;                                        // before the stores below: s' may be s
+            uint32_t g;
+            om_load_derived(tab + (size_t)s2 * kOmRow, va2, g);
+            om_load_derived(tab + (size_t)s2 * kOmRow + kOmPlayer, vb2, g);
+            OmRow row;
+            om_load_row(at, row);
+            om_learn(at, row, a, b, r, term, va2, alpha, L.gamma[i], g);
+            om_load_row(at + kOmPlayer, row);
+            om_learn(at + kOmPlayer, row, b, a, -r, term, vb2, alpha, L.gamma[i], g);
+        }
+        L.alpha[i] = alpha * L.decay[i];
+    }
+    if (bad_act) L.misuse[1] = 1u;
+    if (bad_obs) L.misuse[2] = 1u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps += 1ull;
+}
+
+// creation: every member's Q_p = q_init on the live states, row 0 and every count zero, (V, g) derived; a thread per
+// (member, state, player) row
+__global__ __launch_bounds__(kBlock) void om_pop_init_kernel(const PopIO L, unsigned long long n, double q_init) {
+    const unsigned long long rows = n * (unsigned long long)L.nS * 2ull;
+    for (unsigned long long c = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; c < rows; c += (unsigned long long)gridDim.x * kBlock) {
+        double* const at = L.Q + c * kOmPlayer;
+        const double q = (c / 2ull) % (unsigned long long)L.nS == 0ull ? 0.0 : q_init;
+        OmRow row;
+#pragma unroll
+        for (int k = 0; k < 25; ++k) { row.Q[k] = q; at[k] = q; }
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { row.C[k] = 0ull; reinterpret_cast<unsigned long long*>(at)[kOmC + k] = 0ull; }
+        double V; uint32_t g;
+        om_derive(row, V, g);
+        om_store_derived(at, V, g);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps = 0ull;
+}
+
+// soccer_om_population_load: (V, g) of every row of members first .. first + count - 1 follow what was loaded
+__global__ __launch_bounds__(kBlock) void om_pop_derive_kernel(const PopIO L, unsigned long long first, unsigned long long count) {
+    const unsigned long long per = (unsigned long long)L.nS * 2ull, rows = count * per;
+    for (unsigned long long c = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; c < rows; c += (unsigned long long)gridDim.x * kBlock) {
+        double* const at = L.Q + (first * per + c) * kOmPlayer;
+        OmRow row;
+        om_load_row(at, row);
+        double V; uint32_t g;
+        om_derive(row, V, g);
+        om_store_derived(at, V, g);
+    }
 }
 
 }  // namespace soccer

@@ -1,6 +1,7 @@
-// soccer_learners.hip — the six kinds of learners (see soccer_handle.hpp): the minimax-Q learner soccer_minimax_q_*, the
+// soccer_learners.hip — the seven kinds of learners (see soccer_handle.hpp): the minimax-Q learner soccer_minimax_q_*, the
 // independent Q-learners soccer_q_learner_*, the policy hill-climbers soccer_wolf_phc_*, and the populations of one-actor
-// learners, a member per lane: soccer_q_population_*, soccer_wolf_population_*, soccer_minimax_q_population_*.
+// learners, a member per lane: soccer_q_population_*, soccer_wolf_population_*, soccer_minimax_q_population_*,
+// soccer_om_population_*.
 //
 // What the kinds share comes first and is written once: the registry of live learners with its checks and destroy, the
 // kernel-shape dispatch, the prologue and the hyperparameter checks of a creation, the messages of a refused table
@@ -99,6 +100,14 @@ struct soccer_minimax_q_population : Population {
     MqPopIO io{};
     unsigned waves = 1;                 // workgroups (of one wave) per launch at most: one episode-histogram slot each
     explicit soccer_minimax_q_population(soccer_handle* handle) : Population(handle, kKind, "the population of minimax-Q learners") {}
+};
+
+// a member is a thread of om_pop_run_kernel; io.Q is the members' rows [n][nS][kOmRow]
+struct soccer_om_population : Population {
+    static constexpr int kKind = 6;
+    PopIO io{};
+    int grid_blocks = 0;                // as soccer_q_population's
+    explicit soccer_om_population(soccer_handle* handle) : Population(handle, kKind, "the population of opponent-modelling Q-learners") {}
 };
 #pragma GCC visibility pop
 
@@ -1237,6 +1246,115 @@ extern "C" int soccer_minimax_q_population_load(soccer_handle* h, soccer_minimax
     if (steps) HIP_TRY(h, hipMemcpy(io.steps, steps, 8, hipMemcpyHostToDevice));
     if (Q && !V && !pi_a && !pi_b && count > 0 && nS > 1) {             // a table alone: V and the strategies follow it
         hipLaunchKernelGGL(mq_pop_solve_kernel, dim3(mqpop_grid(q, (uint64_t)count * (uint64_t)(nS - 1))), dim3(kMqBlock), 0, h->stream, io,
+                           (unsigned long long)first, (unsigned long long)count);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    return SOCCER_OK;
+}
+
+// ---- populations of opponent-modelling Q-learners: soccer_om_population_* --------------------------
+// the parts of a member's rows as the caller sees them: Q_a, Q_b [nS][25], C_a, C_b [nS][5]
+template <class V>
+static void om_parts(V* Q_a, V* Q_b, V* C_a, V* C_b, RowPart<V> (&parts)[4]) {
+    parts[0] = {Q_a, 0, 25, kRow0Zero}; parts[1] = {Q_b, kOmPlayer, 25, kRow0Zero};
+    parts[2] = {C_a, kOmC, 5, kRow0Zero}; parts[3] = {C_b, kOmPlayer + kOmC, 5, kRow0Zero};
+}
+
+extern "C" int soccer_om_population_create(soccer_handle* h, const soccer_om_population_config* cfg, soccer_om_population** out) {
+    if (int rc = create_check(h, cfg, out, "soccer_om_population_create")) return rc;
+    const size_t n = (size_t)h->cfg.n_lanes;
+    std::vector<double> par[4];         // alpha, decay, explor, discount_factor
+    if (int rc = pop_params(h, cfg, n, par)) return rc;
+    if (!ql_kind(cfg->act_a) || !ql_kind(cfg->act_b))
+        return fail(h, SOCCER_E_INVALID, "act_a / act_b must be SOCCER_QL_GREEDY, SOCCER_QL_UNIFORM or SOCCER_QL_FIXED");
+    if ((cfg->act_a == SOCCER_QL_FIXED) != (cfg->policy_a != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_a goes with act_a == SOCCER_QL_FIXED, and only with it");
+    if ((cfg->act_b == SOCCER_QL_FIXED) != (cfg->policy_b != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_b goes with act_b == SOCCER_QL_FIXED, and only with it");
+    const int nS = h->rules.nS;
+    std::vector<uint16_t> fixed[2];
+    if (cfg->policy_a) if (int rc = thresholds(h, "policy_a", cfg->policy_a, nS, fixed[0])) return rc;
+    if (cfg->policy_b) if (int rc = thresholds(h, "policy_b", cfg->policy_b, nS, fixed[1])) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, with_shape(h, [&](auto slip, auto lds) { return raise_lds_limit(h, om_pop_run_kernel<slip, lds>); }));
+    std::unique_ptr<soccer_om_population> owner(new soccer_om_population(h));
+    soccer_om_population* q = owner.get();
+    q->grid_blocks = (int)env_in("SOCCER_POP_GRID_BLOCKS", 1, h->grid_cap, 0);
+    PopIO& io = q->io;
+    double* dpar[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint16_t* dmix[2] = {nullptr, nullptr};
+    int rc = q->bufs.alloc(h, n * (size_t)nS * kOmRow, &io.Q);  // (a failure frees what was taken: `owner` goes, the handle is as it was)
+    for (int k = 0; k < 4; ++k) if (!rc) rc = q->bufs.alloc(h, n, &dpar[k]);
+    for (int p = 0; p < 2; ++p) if (!rc && !fixed[p].empty()) rc = q->bufs.alloc(h, (size_t)nS * 4, &dmix[p]);
+    if (!rc) rc = q->bufs.alloc(h, 1, &io.steps);
+    if (rc) return rc;
+    io.alpha = dpar[0]; io.decay = dpar[1]; io.explor = dpar[2]; io.gamma = dpar[3];
+    io.mix[0] = dmix[0]; io.mix[1] = dmix[1];
+    io.misuse = h->d_misuse;
+    io.nS = nS; io.n_steps = 0;
+    io.mode[0] = cfg->act_a; io.mode[1] = cfg->act_b;
+    for (int k = 0; k < 4; ++k) HIP_TRY(h, hipMemcpyAsync(dpar[k], par[k].data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    for (int p = 0; p < 2; ++p)
+        if (dmix[p]) HIP_TRY(h, hipMemcpyAsync(dmix[p], fixed[p].data(), fixed[p].size() * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(om_pop_init_kernel, dim3(grid_for(h, (uint64_t)n * (uint64_t)nS * 2)), dim3(kBlock), 0, h->stream, io, (unsigned long long)n, cfg->q_init);
+    return created(owner, out);
+}
+
+extern "C" int soccer_om_population_destroy(soccer_handle* h, soccer_om_population* q) { return destroy(h, q, "soccer_om_population_destroy"); }
+
+extern "C" int soccer_om_population_run(soccer_handle* h, soccer_om_population* q, int32_t n_steps) {
+    if (int rc = run_check(h, q, n_steps, "soccer_om_population_run")) return rc;
+    return pop_run(h, q, n_steps, [&](const KernelParams& P, const PopIO& io) {
+        return with_shape(h, [&](auto slip, auto lds) {
+            hipLaunchKernelGGL((om_pop_run_kernel<slip, lds>), dim3(pop_grid(h, q->grid_blocks, P.n)), dim3(kBlock), h->smem_bytes, h->stream, P, io);
+            return hipSuccess;
+        });
+    });
+}
+
+extern "C" int soccer_om_population_update(soccer_handle* h, soccer_om_population* q, const uint16_t* obs, const int8_t* act_a,
+                                           const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs) {
+    if (int rc = pop_update_check(h, q, "soccer_om_population_update", obs, act_a, act_b, reward, terminated, next_obs)) return rc;
+    hipLaunchKernelGGL(om_pop_update_kernel, dim3(pop_grid(h, q->grid_blocks, (uint64_t)q->n)), dim3(kBlock), 0, h->stream, q->io, (long long)q->n,
+                       obs, act_a, act_b, reward, terminated, next_obs);
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_om_population_read(soccer_handle* h, soccer_om_population* q, int64_t first, int64_t count, double* Q_a, double* Q_b,
+                                         uint64_t* C_a, uint64_t* C_b, double* alpha, uint64_t* steps) {
+    if (int rc = check(h, q, "soccer_om_population_read")) return rc;
+    if (int rc = range_check(h, q, "soccer_om_population_read", first, count)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const PopIO& io = q->io;
+    if (alpha && count) HIP_TRY(h, hipMemcpyAsync(alpha, io.alpha + first, (size_t)count * 8, hipMemcpyDeviceToHost, h->stream));
+    if (steps) HIP_TRY(h, hipMemcpyAsync(steps, io.steps, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    RowPart<void> parts[4];
+    om_parts<void>(Q_a, Q_b, C_a, C_b, parts);
+    return pop_rows_read(h, PopTable{io.Q, (size_t)io.nS, kOmRow}, first, count, parts);
+}
+
+extern "C" int soccer_om_population_load(soccer_handle* h, soccer_om_population* q, int64_t first, int64_t count, const double* Q_a,
+                                         const double* Q_b, const uint64_t* C_a, const uint64_t* C_b, const double* alpha,
+                                         const uint64_t* steps) {
+    static const char* const what = "soccer_om_population_load";
+    if (int rc = check(h, q, what)) return rc;
+    if (int rc = range_check(h, q, what, first, count)) return rc;
+    const PopIO& io = q->io;
+    const size_t nS = (size_t)io.nS;
+    // everything is checked before anything is written
+    if (Q_a && count) if (int rc = bounds_check(h, what, "Q_a", Q_a, (size_t)count, nS, 25)) return rc;
+    if (Q_b && count) if (int rc = bounds_check(h, what, "Q_b", Q_b, (size_t)count, nS, 25)) return rc;
+    if (alpha) if (int rc = unit_check(h, what, "alpha", alpha, (size_t)count)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    RowPart<const void> parts[4];
+    om_parts<const void>(Q_a, Q_b, C_a, C_b, parts);
+    if (int rc = pop_rows_load(h, PopTable{io.Q, nS, kOmRow}, first, count, parts)) return rc;
+    if (alpha && count) HIP_TRY(h, hipMemcpy(io.alpha + first, alpha, (size_t)count * 8, hipMemcpyHostToDevice));
+    if (steps) HIP_TRY(h, hipMemcpy(io.steps, steps, 8, hipMemcpyHostToDevice));
+    if ((Q_a || Q_b || C_a || C_b) && count > 0) {                      // V and g of the range follow what was loaded
+        hipLaunchKernelGGL(om_pop_derive_kernel, dim3(grid_for(h, (uint64_t)count * (uint64_t)nS * 2)), dim3(kBlock), 0, h->stream, io,
                            (unsigned long long)first, (unsigned long long)count);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipStreamSynchronize(h->stream));

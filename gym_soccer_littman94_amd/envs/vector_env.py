@@ -489,6 +489,12 @@ class VectorSoccerEnv:
         assert self.multiagent, "q_population needs a two-player environment (no player with a fixed policy)"
         return self._batch.q_population(discount_factor, **params)
 
+    def om_population(self, discount_factor, **params):
+        """An OpponentModelPopulation (SoccerBatch.om_population): an opponent-modelling Q-learner per lane of this env, each
+        with its own joint-action tables and counts."""
+        assert self.multiagent, "om_population needs a two-player environment (no player with a fixed policy)"
+        return self._batch.om_population(discount_factor, **params)
+
     def wolf_phc(self, discount_factor, **params):
         """A WolfPHCLearner (SoccerBatch.wolf_phc) whose actors are this env's lanes: policy hill-climbers for both players."""
         assert self.multiagent, "wolf_phc needs a two-player environment (no player with a fixed policy)"

@@ -135,6 +135,31 @@ def q_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.
     return r["pi_a"], r["pi_b"], r["V_a"], r["V_b"], r["Q_a"], r["Q_b"], r["alpha"]
 
 
+def om_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy",
+                  first=0, count=None):
+    """A population of opponent-modelling Q-learners on the device, a learner per lane of `env`, each with its own
+    joint-action tables, its own counts of the other player's actions and its own stream of experience: n_steps steps of
+    every member from the lanes' current states (lanes that were never reset are reset first).  discount_factor, alpha,
+    decay and explor are scalars or arrays of one value per lane; decay None: alpha falls to 1 % over the run.  Returns, for
+    members first .. first + count - 1 (count None: to the end), (pi_a[count, nS, 5], pi_b, V_a[count, nS], V_b,
+    Q_a[count, nS, 5, 5], Q_b, alpha[count]): the greedy answers to the modelled opponent and their values; Q_b and V_b are
+    in player B's own reward."""
+    b = _two_player_batch(env, "om_population")
+    n_steps = int(n_steps)
+    assert n_steps >= 0, "n_steps must be >= 0"
+    if decay is None:
+        decay = 0.01 ** (1.0 / max(n_steps, 1))
+    pop = b.om_population(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
+    try:
+        if b.get_state()["needs_reset"].any():
+            (env if hasattr(env, "_batch") else b).reset()
+        pop.run(n_steps)
+        r = pop.read(first, count)
+    finally:
+        pop.close()
+    return r["pi_a"], r["pi_b"], r["V_a"], r["V_b"], r["Q_a"], r["Q_b"], r["alpha"]
+
+
 def wolf_phc(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
              delta_decay=1.0, act_a="learn", act_b="learn"):
     """PHC / WoLF-PHC (Bowling & Veloso 2002) for both players on the device: n_steps learner steps with every lane of

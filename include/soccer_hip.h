@@ -1000,6 +1000,90 @@ int soccer_minimax_q_population_read(soccer_handle* h, soccer_minimax_q_populati
 int soccer_minimax_q_population_load(soccer_handle* h, soccer_minimax_q_population* q, int64_t first, int64_t count, const double* Q,
                                      const double* V, const double* pi_a, const double* pi_b, const double* alpha, const uint64_t* steps);
 
+/* ---- learners, a population of opponent-modelling Q-learners (two-player handles; a learner per lane)
+ * The learner that SEES the other player's action and models it: opponent-modelling Q-learning (Uther & Veloso 1997, on this
+ * game), the joint-action learner of Claus & Boutilier (1998); in self-play, fictitious play in a Markov game.  It learns a
+ * joint-action table like minimax-Q but solves no stage game: it best-responds to the EMPIRICAL frequencies of the other
+ * player's actions in the state.  On a two-player SOCCER_F_AUTORESET handle of n lanes the population has n members, member i
+ * fed by lane i alone.  Per member and per player p in {A, B}:
+ *     Q_p[n_states][5][5]  float64, index [s][own action][other's action], in p's OWN reward (B's is -r); row 0, the terminal
+ *                          observation, is zero for good
+ *     C_p[n_states][5]     uint64, how often the OTHER player was seen to take each action at s; row 0 stays zero
+ * and the member's alpha; the population has one step counter.  Derived, never state of their own, for (p, s) — one device
+ * function computes them for run, update, creation and load:
+ *     n   = C[0] + C[1] + C[2] + C[3] + C[4]                                   (uint64)
+ *     w_k = n > 0 ? (double)C[k] : 1.0,   N = n > 0 ? (double)n : 5.0          (nothing seen yet: a uniform belief)
+ *     W[a] = ((((w_0 * Q[a][0] + w_1 * Q[a][1]) + w_2 * Q[a][2]) + w_3 * Q[a][3]) + w_4 * Q[a][4])
+ *            every product and every sum rounded on its own (not contracted), in this order
+ *     g   = the first a that attains max_a W[a]
+ *     V   = min(1.0, max(-1.0, W[g] / N))
+ *     Vq  = rint(V * 2^40) as int64, the learners' grid
+ * The clamp is what makes "Q stays in [-1, 1]" provable whatever the counts: while n < 2^53 rounding is monotone and
+ * |W[g]| <= N, but counts beyond that (a load takes them as given) round one by one, and the rounded weights may sum to more
+ * than the rounded n — C = (2^53 + 3, 2, 0, 0, 0) with a row of ones gives W[g] / N > 1; with |V| <= 1 a target m = r + discount_factor * V has |m| <= 1 (r is not 0 only where the transition
+ * terminated and nothing is bootstrapped), and Q + alpha * (m - Q) stays between Q and m as for the other learners.
+ * How a player acts: SOCCER_QL_GREEDY, epsilon-greedy on onehot(g_p[s]) with the member's explor; SOCCER_QL_UNIFORM, the NULL
+ * row table, (h * 5) >> 15; SOCCER_QL_FIXED, one [n_states][5] policy shared by all members, its thresholds computed once on
+ * the host — the meanings and the threshold expression of "learners, independent Q".  BOTH players' tables and counts are
+ * always updated, however they act.  One step of member i on its lane's single transition (s, a, b, r, terminated,
+ * s' = final_obs), in the order of "learners, a population of independent Q-learners":
+ *   1. the behaviour rows from ITS tables at s
+ *   2. act and step: batched_rollout(n_steps = 1, sample_actions = 1) with that lane's rows — the same tick and Philox words,
+ *      auto-reset, episode histogram and misuse flags as for the other populations
+ *   3. SV_p = terminated ? 0 : Vq_p[s'] for both players, read BEFORE anything moves (it matters when s' == s: every blocked
+ *      move, every STAND)
+ *   4. for A at cell (a, b):  m = (double)r + discount_factor_i * ((double)SV_A * 2^-40),  Q = Q + alpha_i * (m - Q), not
+ *      contracted, then C_A[s][b] += 1;  for B at cell (b, a) the same with -r and SV_B, then C_B[s][a] += 1
+ *   5. V, g (and Vq) of (A, s) and (B, s) follow by the function above
+ *   6. alpha_i = alpha_i * decay_i; the step counter grows by one per step of the population
+ * A lane that still needs its first reset (SOCCER_MISUSE_FROZEN) and a lane whose current observation is 0 contribute
+ * nothing; their member's alpha still advances.  Initially Q = q_init on the live states and C = 0, so g = 0 everywhere by
+ * the first-index rule.  The population's state is (Q_a, Q_b, C_a, C_b, alpha, steps), a fixed function of (seed,
+ * parameters, number of steps): it does not depend on how run() splits its launches, on the grid or on the state layout.
+ * Hyperparameters: those of soccer_q_population_config, with the same ranges and the same per-member HOST arrays.
+ * Refusals, SOCCER_E_STATE during a capture, the misuse flags and the ownership of the memory are those of the
+ * soccer_q_population_* calls (memory: n * n_states * 512 bytes of rows — 390 KB per member on 5x4 —, 32 bytes of parameters
+ * per member and a shared policy's thresholds; SOCCER_E_NOMEM leaves the handle usable).  Populations of all kinds and the
+ * three shared learners may share a handle.  Not offered: a league opponent, decayed or windowed counts, a shared-table
+ * form. */
+typedef struct soccer_om_population soccer_om_population;
+typedef struct soccer_om_population_config {
+    double  discount_factor;        /* the fields of soccer_q_population_config, in place */
+    double  alpha;
+    double  decay;
+    double  explor;
+    double  q_init;
+    int32_t act_a;                  /* SOCCER_QL_* : how player A acts */
+    int32_t act_b;                  /* SOCCER_QL_* : how player B acts */
+    const double* policy_a;         /* act_a == SOCCER_QL_FIXED: HOST [n_states][5] rows >= 0 summing to 1; else NULL */
+    const double* policy_b;         /* the same for act_b */
+    const double* alpha_per_member;            /* HOST [n_lanes] or NULL: `alpha` for everyone */
+    const double* decay_per_member;
+    const double* explor_per_member;
+    const double* discount_factor_per_member;
+} soccer_om_population_config;
+int soccer_om_population_create(soccer_handle* h, const soccer_om_population_config* cfg, soccer_om_population** out);
+int soccer_om_population_destroy(soccer_handle* h, soccer_om_population* q);
+/* n_steps steps of every member in ceil(n_steps / K) launches of at most K = 4096 steps each, enqueued on the handle's stream:
+ * no synchronisation, no copy.  Consumes n_steps ticks.  The test hooks SOCCER_POP_LAUNCH_STEPS and SOCCER_POP_GRID_BLOCKS are
+ * read at creation as for soccer_q_population_run; they change no result. */
+int soccer_om_population_run(soccer_handle* h, soccer_om_population* q, int32_t n_steps);
+/* steps 3-6 on the caller's transitions: DEVICE arrays of n_lanes elements, transition i belongs to member i (reward is
+ * player A's), with the checks and the misuse flags of soccer_q_population_update: a bad transition leaves its member's
+ * tables and counts alone (its alpha still advances).  Consumes no tick. */
+int soccer_om_population_update(soccer_handle* h, soccer_om_population* q, const uint16_t* obs, const int8_t* act_a,
+                                const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs);
+/* Members first .. first + count - 1 (inside the population, else SOCCER_E_INVALID) to HOST arrays, any may be NULL:
+ * Q_a / Q_b [count][n_states][5][5], C_a / C_b [count][n_states][5] uint64, alpha[count], steps (one value).  Synchronises. */
+int soccer_om_population_read(soccer_handle* h, soccer_om_population* q, int64_t first, int64_t count, double* Q_a, double* Q_b,
+                              uint64_t* C_a, uint64_t* C_b, double* alpha, uint64_t* steps);
+/* The same range from HOST arrays, any may be NULL (= unchanged): Q_a / Q_b in [-1, 1], C_a / C_b taken as given (row 0
+ * of all four is taken as zeros), alpha[count] in [0, 1], steps.  Everything is checked before anything is written: a refused load changes
+ * nothing.  Every derived value of the range is recomputed on the device by the function above, so read -> load of a range
+ * on a fresh population continues bit for bit. */
+int soccer_om_population_load(soccer_handle* h, soccer_om_population* q, int64_t first, int64_t count, const double* Q_a,
+                              const double* Q_b, const uint64_t* C_a, const uint64_t* C_b, const double* alpha, const uint64_t* steps);
+
 /* HOST output: prob[c*3+k] = slip-combination weight c (0: no slip, 1: B slips, 2: A slips,
  * 3: both; :211-222, evaluated left to right in float64) times outcome probability 1, 0.5, 0.25
  * (k = 0,1,2; :326-360).  prob_code values index this table (:241). */
