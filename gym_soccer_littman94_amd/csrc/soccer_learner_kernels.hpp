@@ -81,6 +81,25 @@ __device__ __forceinline__ void learner_thresholds(const double (&pi)[5], double
     *reinterpret_cast<uint2*>(row) = make_uint2(t[0] | (t[1] << 16), t[2] | (t[3] << 16));
 }
 
+// the action a 15-bit draw h takes from a threshold row: the number of thresholds <= the draw.  (pop_draw and om_pop_draw, whose
+// row comes from one of two places, write the sum out: through this function their run kernels sum in another order.)
+__device__ __forceinline__ uint32_t thresholds_not_above(uint2 th, uint32_t h) {
+    return (h >= (th.x & 0xffffu)) + (h >= (th.x >> 16)) + (h >= (th.y & 0xffffu)) + (h >= (th.y >> 16));
+}
+
+// One lane's randomness for the step at `tick`: the environment's draw, and two action draws from one 32-bit word, 15 bits
+// each (rollout_group).  (The four run kernels whose member is a thread write these lines out: through this function their
+// slip-0 instantiations place two scalar instructions elsewhere, and there an instruction order has measured 1 %: DESIGN §1.)
+struct StepDraws { Draw d; uint32_t ha, hb; };
+
+template <bool SLIP>
+__device__ __forceinline__ StepDraws step_draws(const KernelParams& P, unsigned long long i0, unsigned long long tick) {
+    uint32_t words[1], awords[1];
+    lane_words<1>(P, P.lane_offset + i0, block_tick<SLIP>(tick), 0u, words);
+    lane_words<1>(P, P.lane_offset + i0, tick, 1u, awords);
+    return StepDraws{draw_from_word<SLIP>(words[0], tick), awords[0] & 0x7fffu, (awords[0] >> 16) & 0x7fffu};
+}
+
 // what a state's row of everything derived from Q[s] becomes: V, Vq, the strategies, the threshold rows
 __device__ __forceinline__ void learner_publish(const LearnerIO& L, int s, double v, const double (&x)[5], const double (&y)[5]) {
     L.V[s] = v;
@@ -109,24 +128,13 @@ __device__ __forceinline__ void learner_act(const KernelParams P, const IO L) {
         const unsigned long long i0 = P.first + g;
         LaneVec<1> S; S.load(P, i0);
         const uint32_t s_now = obs_of(T, P, S.L[0].A, S.L[0].B, S.L[0].p);
-        uint32_t words[1], awords[1];
-        lane_words<1>(P, P.lane_offset + i0, block_tick<SLIP>(tick), 0u, words);
-        lane_words<1>(P, P.lane_offset + i0, tick, 1u, awords);
-        const Draw d = draw_from_word<SLIP>(words[0], tick);
-        // two actions from one 32-bit word, 15 bits each (rollout_group): the number of thresholds <= the draw
-        const uint32_t ha = awords[0] & 0x7fffu, hb = (awords[0] >> 16) & 0x7fffu;
-        uint32_t a, b = (hb * 5u) >> 15;
-        if (NULL_A) a = (ha * 5u) >> 15;
-        if (!NULL_A || L.mix_a) {
-            const uint2 th = *reinterpret_cast<const uint2*>(L.mix_a + 4u * s_now);
-            a = (ha >= (th.x & 0xffffu)) + (ha >= (th.x >> 16)) + (ha >= (th.y & 0xffffu)) + (ha >= (th.y >> 16));
-        }
-        if (L.mix_b) {
-            const uint2 th = *reinterpret_cast<const uint2*>(L.mix_b + 4u * s_now);
-            b = (hb >= (th.x & 0xffffu)) + (hb >= (th.x >> 16)) + (hb >= (th.y & 0xffffu)) + (hb >= (th.y >> 16));
-        }
+        const StepDraws w = step_draws<SLIP>(P, i0, tick);
+        uint32_t a, b = (w.hb * 5u) >> 15;
+        if (NULL_A) a = (w.ha * 5u) >> 15;
+        if (!NULL_A || L.mix_a) a = thresholds_not_above(*reinterpret_cast<const uint2*>(L.mix_a + 4u * s_now), w.ha);
+        if (L.mix_b) b = thresholds_not_above(*reinterpret_cast<const uint2*>(L.mix_b + 4u * s_now), w.hb);
         StepResult R;
-        const bool frozen = lane_step<SLIP, true>(T, P, S.L[0], a, b, d, R);
+        const bool frozen = lane_step<SLIP, true>(T, P, S.L[0], a, b, w.d, R);
         S.store(P, i0);
         hist.add_totals(R.finished, R.reward, (uint32_t)R.reward & 1u);
         any_frozen |= frozen;
@@ -673,8 +681,7 @@ struct PopLeagueIO {
 
 __device__ __forceinline__ uint32_t league_draw(const PopLeagueIO& G, int32_t nS, int32_t pick, uint32_t s, uint32_t h) {
     // (K * nS * 4 <= 2^10 * 2^16 * 4: the index fits 32 bits)
-    const uint2 th = *reinterpret_cast<const uint2*>(G.thr + 4u * ((uint32_t)pick * (uint32_t)nS + s));
-    return (h >= (th.x & 0xffffu)) + (h >= (th.x >> 16)) + (h >= (th.y & 0xffffu)) + (h >= (th.y >> 16));
+    return thresholds_not_above(*reinterpret_cast<const uint2*>(G.thr + 4u * ((uint32_t)pick * (uint32_t)nS + s)), h);
 }
 
 template <bool SLIP, bool LUT_LDS>
@@ -910,8 +917,7 @@ __device__ __forceinline__ uint32_t phc_pop_draw(const PhcPopIO& L, int p, const
     for (int k = 0; k < 5; ++k) row[k] = pi[5 * p + k];
     __attribute__((aligned(8))) uint16_t t[4];
     learner_thresholds(row, L.mode[p] == kPhcLearn ? explor : 0.0, t);
-    const uint2 th = *reinterpret_cast<const uint2*>(t);
-    return (h >= (th.x & 0xffffu)) + (h >= (th.x >> 16)) + (h >= (th.y & 0xffffu)) + (h >= (th.y >> 16));
+    return thresholds_not_above(*reinterpret_cast<const uint2*>(t), h);
 }
 
 template <bool SLIP, bool LUT_LDS>
@@ -1104,8 +1110,7 @@ __device__ __forceinline__ uint32_t mq_pop_draw(double val, int first, double ex
     for (int k = 0; k < 5; ++k) pi[k] = mq_row_slot(val, first + k);
     __attribute__((aligned(8))) uint16_t t[4];
     learner_thresholds(pi, explor, t);
-    const uint2 th = *reinterpret_cast<const uint2*>(t);
-    return (h >= (th.x & 0xffffu)) + (h >= (th.x >> 16)) + (h >= (th.y & 0xffffu)) + (h >= (th.y >> 16));
+    return thresholds_not_above(*reinterpret_cast<const uint2*>(t), h);
 }
 
 // step 5 for the state whose row the wave holds in `val` (`at` = that row in memory): lanes 0..24 hand Q[s] to lane 0, lane 0
@@ -1157,25 +1162,19 @@ __global__ __launch_bounds__(kMqBlock) void mq_pop_run_kernel(const KernelParams
         int32_t ret = 0; uint32_t eps = 0u, nonzero = 0u;
         for (int t = 0; t < L.n_steps; ++t) {
             const unsigned long long tick = tick0 + (unsigned long long)t;
-            uint32_t words[1], awords[1];
-            lane_words<1>(P, P.lane_offset + i0, block_tick<SLIP>(tick), 0u, words);
-            lane_words<1>(P, P.lane_offset + i0, tick, 1u, awords);
-            const Draw d = draw_from_word<SLIP>(words[0], tick);
-            // two actions from one 32-bit word, 15 bits each (rollout_group)
-            const uint32_t ha = awords[0] & 0x7fffu, hb = (awords[0] >> 16) & 0x7fffu;
-            const uint32_t a = mq_uniform(mq_pop_draw(val, kMqPiA, explor, ha));
+            const StepDraws w = step_draws<SLIP>(P, i0, tick);
+            const uint32_t a = mq_uniform(mq_pop_draw(val, kMqPiA, explor, w.ha));
             uint32_t b;
             if (L.opponent == kMqUniform) {                         // wave-uniform
-                b = (hb * 5u) >> 15;
+                b = (w.hb * 5u) >> 15;
             } else if (L.opponent == kMqSelf) {
-                b = mq_pop_draw(val, kMqPiB, explor, hb);
+                b = mq_pop_draw(val, kMqPiB, explor, w.hb);
             } else {
-                const uint2 th = *reinterpret_cast<const uint2*>(mix + 4u * s);
-                b = (hb >= (th.x & 0xffffu)) + (hb >= (th.x >> 16)) + (hb >= (th.y & 0xffffu)) + (hb >= (th.y >> 16));
+                b = thresholds_not_above(*reinterpret_cast<const uint2*>(mix + 4u * s), w.hb);
             }
             b = mq_uniform(b);
             StepResult R;
-            const bool frozen = mq_uniform(lane_step<SLIP, true>(T, P, S.L[0], a, b, d, R) ? 1u : 0u) != 0u;
+            const bool frozen = mq_uniform(lane_step<SLIP, true>(T, P, S.L[0], a, b, w.d, R) ? 1u : 0u) != 0u;
             ret += R.reward; eps += R.finished; nonzero += (uint32_t)R.reward & 1u;
             any_frozen |= frozen;
             // (a lane parked in a goal tuple by soccer_set_state has s = 0: never a current state)

@@ -18,6 +18,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from league_np import QLeagueNumpy, assert_league_equal, league_pick, league_thresholds  # noqa: E402
 from philox_np import lane_words  # noqa: E402
 from q_population_np import assert_population_equal  # noqa: E402
+from test_population_edges_np import CASES as EDGE_CASES, G0_LEAGUE_PLAYER, KW as EDGE_KW, g0_league, reference_g0  # noqa: E402
+
+G0 = EDGE_CASES["G0"]
 
 pytestmark = pytest.mark.gpu
 
@@ -143,6 +146,24 @@ def test_run_equals_the_restatement_bit_for_bit(case):
     assert (ref.max_live if n > 1 else len(ref.seen)) >= 2
     part = q.picks(n // 2, 1)
     assert part.shape == (1,) and part[0] == ref.pick[n // 2]
+    b.close()
+
+
+def test_run_on_12x14_without_slip_equals_the_restatement_bit_for_bit():
+    """case G0 of tests/test_population_edges_np.py, which shows without a GPU that it terminates, truncates, meets s' == s
+    and holds two picks at once: pop_league_run_kernel<SLIP = false, LUT_LDS = false>"""
+    c = G0
+    o, ref = reference_g0("league")
+    assert (c["w"], c["h"], c["slip"]) == (12, 14, 0.0) and RUN_KW == EDGE_KW["q"]
+    b, q = device(3, c["n"], G0_LEAGUE_PLAYER, "greedy", c["w"], c["h"], c["slip"], 0, c["max_steps"], league=g0_league(o.nS))
+    q.run(c["T"])
+    assert_league_equal(read_all(q), ref.state())
+    assert_state_equal(b, o)
+    assert b.tick == o.tick == c["T"] + 1
+    hist, misuse = b.stats()
+    np.testing.assert_array_equal(hist, o.hist)
+    assert misuse == 0 and q.steps == c["T"]
+    assert ref.n_redraws > 0 and ref.n_truncated_only > 0 and ref.n_terminated > 0 and ref.n_same > 0 and ref.max_live >= 2
     b.close()
 
 

@@ -20,6 +20,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from large_pitch_cases import CASES as PITCHES  # noqa: E402
 from om_population_np import OMPopulationNumpy, assert_om_population_equal, derive  # noqa: E402
 from test_om_population_np import BOUND, LEARN  # noqa: E402
+from test_population_edges_np import CASES as EDGE_CASES, KW as EDGE_KW, reference_g0  # noqa: E402
+
+G0 = EDGE_CASES["G0"]
 
 pytestmark = pytest.mark.gpu
 
@@ -169,6 +172,24 @@ def test_run_equals_the_restatement_bit_for_bit(w, h, slip, act_a, act_b, n, max
     part = q.read(n // 2, 1)                       # a range is the slice
     assert part["Q_a"].tobytes() == ref.Q_a[n // 2:n // 2 + 1].tobytes() and part["alpha"][0] == ref.alpha[n // 2]
     assert part["C_b"].tobytes() == ref.C_b[n // 2:n // 2 + 1].tobytes()
+    b.close()
+
+
+def test_run_on_12x14_without_slip_equals_the_restatement_bit_for_bit():
+    """case G0 of tests/test_population_edges_np.py, which shows without a GPU that it terminates, truncates and meets s' == s:
+    om_pop_run_kernel<SLIP = false, LUT_LDS = false>"""
+    c = G0
+    o, ref = reference_g0("om")
+    assert (c["w"], c["h"], c["slip"]) == (12, 14, 0.0) and not PITCHES["12x14"]["lut_lds"] and RUN_KW == EDGE_KW["q"]
+    b, q = _device_run([c["T"]], c["w"], c["h"], c["slip"], "greedy", "greedy", c["n"], c["max_steps"])
+    assert_om_population_equal(q.read(), ref.state())
+    assert_state_equal(b, o)
+    assert b.tick == o.tick == c["T"] + 1
+    hist, misuse = b.stats()
+    np.testing.assert_array_equal(hist, o.hist)
+    assert misuse == 0 and ref.n_left_out == 0
+    assert q.steps == c["T"] and (q.alpha == ref.alpha).all()
+    assert ref.n_truncated_only > 0 and ref.n_terminated > 0 and ref.n_same > 0 and ref.n_first_seen > 0 and hist.sum() > 0
     b.close()
 
 

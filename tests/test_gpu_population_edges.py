@@ -15,8 +15,9 @@ from gym_soccer_littman94_amd import SoccerBatch, _lib
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from test_gpu_q_learning import assert_batches_equal, assert_state_equal  # noqa: E402
 from test_matrix_game_host import build_games_host  # noqa: E402
-from test_population_edges_np import (CASES, CONFIGS, GAMMA, KINDS, KW, LDS_TABLE_LIMIT, PER_MEMBER, SEED, TABLES, W_ENV, W_GRID,  # noqa: E402
-                                      assert_read_equal, case_of, counts, population_args, reference, reference_w_then_update)
+from test_population_edges_np import (CASES, CONFIGS, G0_KINDS, GAMMA, KINDS, KW, LDS_TABLE_LIMIT, PER_MEMBER, SEED, TABLES, W_ENV,  # noqa: E402
+                                      W_GRID, assert_read_equal, case_of, counts, population_args, reference, reference_g0,
+                                      reference_w_then_update)
 
 pytestmark = pytest.mark.gpu
 
@@ -247,5 +248,21 @@ def test_run_kernels_with_the_observation_table_in_global_memory(host, kind):
     # the move table alone is staged: the observation table is read from global memory (LUT_LDS = false)
     assert 0 < sh["dynamic_lds_bytes"] < 2 * o.tables()[0].size and sh["dynamic_lds_bytes"] + 2 * o.tables()[0].size > LDS_TABLE_LIMIT
     q.close()                                                  # before the handle: a failure shows up here, not in the next test
+    assert b.misuse() == 0
+    b.close()
+
+
+@pytest.mark.parametrize("kind", [k for k in KINDS if k in G0_KINDS])
+def test_run_kernels_with_the_observation_table_in_global_memory_without_slip(kind):
+    """G0: the <SLIP = false, LUT_LDS = false> run kernels of the populations whose members are threads (minimax-Q's takes no
+    LUT_LDS); the opponent-modelling and the league populations run the case in their own suites"""
+    c = CASES["G0"]
+    o, ref = reference_g0(kind)
+    assert 2 * o.tables()[0].size > LDS_TABLE_LIMIT and c["slip"] == 0.0
+    assert ref.n_terminated > 0 and ref.n_truncated_only > 0 and ref.n_same > 0
+    b, q = device_run(kind, c, [c["T"]])
+    assert b.nS == 56113
+    assert_equals_reference(kind, b, q, o, ref)
+    q.close()
     assert b.misuse() == 0
     b.close()

@@ -14,7 +14,9 @@ import pytest
 from oracle.oracle import Oracle
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from league_np import QLeagueNumpy  # noqa: E402
 from minimax_q_population_np import MinimaxQPopulationNumpy, assert_minimax_q_population_equal  # noqa: E402
+from om_population_np import OMPopulationNumpy  # noqa: E402
 from q_learning_np import thresholds  # noqa: E402
 from q_population_np import QPopulationNumpy, assert_population_equal  # noqa: E402
 from wolf_population_np import WolfPopulationNumpy, assert_wolf_population_equal  # noqa: E402
@@ -41,6 +43,10 @@ CASES = {
     # terminates and truncates in 30 steps (test_case_G_leaves_the_tables_in_global_memory): with 3 members, slip 0 and
     # max_steps 4 the Q kind terminated nothing.
     "G": dict(w=12, h=14, slip=0.2, n=17, max_steps=7, T=30),
+    # the same pitch without slip, for the <SLIP = false, LUT_LDS = false> run kernels of the four thread-per-member populations
+    # (G0_KINDS).  33 members: with 17 the Q and the opponent-modelling kinds terminated one episode in 30 steps, with 33 two
+    # (test_case_G0_takes_every_branch_of_the_carry_rule_without_slip).
+    "G0": dict(w=12, h=14, slip=0.0, n=33, max_steps=7, T=30),
 }
 CASES["O0"] = dict(CASES["O"], lane_offset=0)                  # the same handle at offset 0: what O must differ from
 # W: two full grids of the run kernel and a ragged third, every fifth member of the third frozen.  A grid is 2 workgroups of
@@ -132,6 +138,35 @@ def reference(kind, name, host, config="learn"):
         ref = started_restatement(kind, name, config, c["n"], o.nS, host)
         ref.run(o, obs, c["T"])
         _REFERENCE[key] = (o, ref, st, masks)
+    return _REFERENCE[key]
+
+
+# G0 is run by the four populations whose members are threads (pop_run_kernel, phc_pop_run_kernel, om_pop_run_kernel,
+# pop_league_run_kernel): the two kinds above that are, and the opponent-modelling and the league populations through their own
+# restatements with the Q kind's settings.  The GPU suites of those two take the case from here.
+G0_KINDS = ("q", "wolf", "om", "league")
+G0_LEAGUE_PLAYER = 1
+
+
+def g0_league(nS):
+    """three mixed league policies, every weight positive"""
+    return np.random.default_rng(SEED).dirichlet(np.ones(5), (3, nS)), np.array([0.5, 0.2, 0.3])
+
+
+def reference_g0(kind):
+    """(oracle, restatement) after case G0's run; computed once per kind and left unchanged"""
+    if kind in KINDS:
+        return reference(kind, "G0", None)[:2]
+    key = (kind, "G0", "learn")
+    if key not in _REFERENCE:
+        c = CASES["G0"]
+        o = new_oracle(c)
+        if kind == "om":
+            ref = OMPopulationNumpy(c["n"], o.nS, GAMMA, **KW["q"])
+        else:
+            ref = QLeagueNumpy(c["n"], o.nS, GAMMA, G0_LEAGUE_PLAYER, *g0_league(o.nS), other="greedy", **KW["q"])
+        ref.run(o, o.reset(), c["T"])
+        _REFERENCE[key] = (o, ref)
     return _REFERENCE[key]
 
 
@@ -272,6 +307,24 @@ def test_case_G_leaves_the_tables_in_global_memory(host, kind):
     assert ref.n_terminated > 0 and ref.n_truncated_only > 0 and ref.n_left_out == 0
     # one pitch row less and the tables fit again: this is the smallest pitch of its width that leaves LDS
     assert 2 * ((c["w"] + 2) * (c["h"] - 1)) ** 2 * 2 <= LDS_TABLE_LIMIT and 2 * ((c["w"] + 1) * c["h"]) ** 2 * 2 <= LDS_TABLE_LIMIT
+
+
+@pytest.mark.parametrize("kind", G0_KINDS)
+def test_case_G0_takes_every_branch_of_the_carry_rule_without_slip(kind):
+    """what the GPU cases on 12x14 at slip 0 rest on: the restatement alone shows an episode that terminates (a reload after
+    the reset), one that truncates (a reload, and a bootstrap from final_obs), an update with s' == s (the registers already
+    hold what was written); the league holds two picks at once"""
+    c = CASES["G0"]
+    o, ref = reference_g0(kind)
+    print("%s G0: %s" % (kind, counts(ref)))
+    assert (c["w"], c["h"], c["slip"]) == (CASES["G"]["w"], CASES["G"]["h"], 0.0) and o.nS == 56113 and c["n"] <= 33
+    assert 2 * o.tables()[0].size > LDS_TABLE_LIMIT
+    assert ref.n_terminated >= 1 and ref.n_truncated_only >= 1 and ref.n_same >= 1 and ref.n_left_out == 0
+    assert ref.steps == c["T"]
+    if kind == "wolf":
+        assert_branches(kind, ref, c)
+    if kind == "league":
+        assert ref.max_live >= 2 and len(ref.seen - {-1}) >= 2 and ref.n_redraws > 0
 
 
 @pytest.mark.parametrize("kind", KINDS)
