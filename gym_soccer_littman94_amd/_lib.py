@@ -197,6 +197,8 @@ PROTOTYPES = {
                                            C.c_void_p, C.c_void_p]),
     "soccer_cross_play": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "soccer_match_outcomes": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_int32,
+                                        C.c_int32] + [C.c_void_p] * 5),
     "soccer_solve_meta_games": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                           C.POINTER(MetaGameResult)]),
     "soccer_minimax_q_create": (C.c_int, [C.c_void_p, C.POINTER(MinimaxQConfig), C.POINTER(C.c_void_p)]),

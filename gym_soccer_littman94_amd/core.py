@@ -209,6 +209,12 @@ class _Population(_Learner):
         opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
         return _meta_of_cross_play(self.batch, *self.cross_play(theta, first, count, discount_factor), max_pivots)
 
+    def match_outcomes(self, theta=1e-10, first=0, count=None, continue_prob=None):
+        """How often each member's player A beats each member's player B, how often they draw and how long they play:
+        SoccerBatch.match_outcomes' dict on cross_play's policies of members first .. first + count - 1 (at most 1024).
+        continue_prob None: the range's common discount, ValueError if the members differ."""
+        return _population_match_outcomes(self, self._policies, "pi_a", "pi_b", theta, first, count, continue_prob)
+
 
 class MinimaxQLearner(_Learner):
     """A minimax-Q learner (Littman 1994) on a two-player auto-reset SoccerBatch: one shared Q[nS, 5, 5] on the device,
@@ -446,21 +452,35 @@ def q_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e
 def _population_cross_play(pop, read, key_a, key_b, theta, first, count, discount_factor):
     """Members first .. first + count - 1 of a population against one another (SoccerBatch.cross_play): player A's policies
     read(first, count)[key_a] meet the same members' player-B policies [key_b], read in chunks of at most 256 members."""
+    pa, pb, discount_factor = _population_sides(pop, read, key_a, key_b, first, count, discount_factor, "cross_play", "discount_factor")
+    return pop.batch.cross_play(pa, pb, theta, discount_factor)
+
+
+def _population_match_outcomes(pop, read, key_a, key_b, theta, first, count, continue_prob):
+    """_population_cross_play's members and policies through SoccerBatch.match_outcomes; continue_prob None: the range's
+    common discount"""
+    pa, pb, continue_prob = _population_sides(pop, read, key_a, key_b, first, count, continue_prob, "match_outcomes", "continue_prob")
+    return pop.batch.match_outcomes(pa, pb, theta, continue_prob)
+
+
+def _population_sides(pop, read, key_a, key_b, first, count, discount, what, name):
+    """(pi_a[count, nS, 5], pi_b[count, nS, 5], the discount) of members first .. first + count - 1; discount None: the one
+    they share, ValueError if they differ"""
     first, count = pop._range(first, count)
-    assert 1 <= count <= _lib.CROSS_MAX_POLICIES, "cross_play takes 1 .. %d members, not %d" % (_lib.CROSS_MAX_POLICIES, count)
+    assert 1 <= count <= _lib.CROSS_MAX_POLICIES, "%s takes 1 .. %d members, not %d" % (what, _lib.CROSS_MAX_POLICIES, count)
     gam = pop.discount_factor[first:first + count]
-    if discount_factor is None:
+    if discount is None:
         other = np.flatnonzero(gam != gam[0])
         if other.size:
-            raise ValueError("members %d and %d have different discounts (%r and %r): pass discount_factor" % (
-                first, first + other[0], float(gam[0]), float(gam[other[0]])))
-        discount_factor = float(gam[0])
+            raise ValueError("members %d and %d have different discounts (%r and %r): pass %s" % (
+                first, first + other[0], float(gam[0]), float(gam[other[0]]), name))
+        discount = float(gam[0])
     pa = np.zeros((count, pop.nS, 5)); pb = np.zeros((count, pop.nS, 5))
     for c0 in range(0, count, _lib.BR_MAX_POLICIES):
         c = min(_lib.BR_MAX_POLICIES, count - c0)
         r = read(first + c0, c)
         pa[c0:c0 + c] = r[key_a]; pb[c0:c0 + c] = r[key_b]
-    return pop.batch.cross_play(pa, pb, theta, float(discount_factor))
+    return pa, pb, float(discount)
 
 
 def meta_lds_bytes(n_a, n_b):
@@ -691,6 +711,13 @@ class OpponentModelPopulation(_Population):
         """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
         opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
         return _meta_of_cross_play(self.batch, *self.cross_play(which, theta, first, count, discount_factor), max_pivots)
+
+    def match_outcomes(self, which="greedy", theta=1e-10, first=0, count=None, continue_prob=None):
+        """How often each member's player A beats each member's player B, how often they draw and how long they play:
+        SoccerBatch.match_outcomes' dict on cross_play's policies (which) of members first .. first + count - 1 (at most 1024).
+        continue_prob None: the range's common discount, ValueError if the members differ."""
+        assert which in self._WHICH, "which must be 'greedy' or 'model'"
+        return _population_match_outcomes(self, self.read, *self._WHICH[which], theta, first, count, continue_prob)
 
     def load(self, Q_a=None, Q_b=None, C_a=None, C_b=None, alpha=None, steps=None, first=0):
         """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged): Q_a /
@@ -952,6 +979,14 @@ class WolfPopulation(_Population):
         """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
         opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
         return _meta_of_cross_play(self.batch, *self.cross_play(which, theta, first, count, discount_factor), max_pivots)
+
+    def match_outcomes(self, which="pi", theta=1e-10, first=0, count=None, continue_prob=None):
+        """How often each member's player A beats each member's player B, how often they draw and how long they play:
+        SoccerBatch.match_outcomes' dict on cross_play's policies (which) of members first .. first + count - 1 (at most 1024).
+        continue_prob None: the range's common discount, ValueError if the members differ."""
+        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
+        return _population_match_outcomes(self, lambda f, c: self._read(f, c, (which + "_a", which + "_b")), which + "_a", which + "_b",
+                                          theta, first, count, continue_prob)
 
     def load(self, Q_a=None, Q_b=None, pi_a=None, pi_b=None, avg_a=None, avg_b=None, updates=None, alpha=None, dscale=None, steps=None,
              first=0):
@@ -1420,6 +1455,37 @@ class SoccerBatch:
                                           int(max_sweeps), int(pairs_per_pass), payoff.ctypes.data,
                                           V.ctypes.data if values else None, it.ctypes.data)
         out = (payoff, it.astype(np.int64)) + ((V,) if values else ())
+        try:
+            self._check(code)
+        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
+            e.results = out
+            raise
+        return out
+
+    def match_outcomes(self, pi_a, pi_b, theta, continue_prob, max_sweeps=1000000, pairs_per_pass=0, values=False):
+        """Littman's columns for two sets of mixed policies, exactly (include/soccer_hip.h, "match outcomes"): after every step
+        the game goes on with probability continue_prob and is a draw otherwise.  pi_a, pi_b, pairs_per_pass and the limits are
+        cross_play's.  Returns a dict of [n_a, n_b] arrays at kick-off, pi_a[i] against pi_b[j]:
+          win_a, win_b    the probability that A's side, B's side scores the goal that ends the game
+          draw            1.0 - win_a - win_b
+          length          the expected number of steps of a game,  games_per_step  1 / length
+          iterations      the sweeps of each pair's solve (int64)
+          values          [n_a, n_b, 3, nS] with values=True: W_A, W_B and L at every state
+        RuntimeError if max_sweeps is reached (its .results holds the dict, iterations == max_sweeps marks the open pairs,
+        which hold the max_sweeps-step numbers)."""
+        a, _ = self._policies(pi_a, "pi_a")
+        b, _ = self._policies(pi_b, "pi_b")
+        na, nb = a.shape[0], b.shape[0]
+        win_a = np.zeros((na, nb)); win_b = np.zeros((na, nb)); length = np.zeros((na, nb)); it = np.zeros((na, nb), np.int32)
+        V = np.zeros((na, nb, 3, self.nS)) if values else None
+        code = self.lib.soccer_match_outcomes(self.h, na, a.ctypes.data, nb, b.ctypes.data, float(theta), float(continue_prob),
+                                              int(max_sweeps), int(pairs_per_pass), win_a.ctypes.data, win_b.ctypes.data,
+                                              length.ctypes.data, V.ctypes.data if values else None, it.ctypes.data)
+        with np.errstate(divide="ignore"):
+            out = {"win_a": win_a, "win_b": win_b, "draw": 1.0 - win_a - win_b, "length": length, "games_per_step": 1.0 / length,
+                   "iterations": it.astype(np.int64)}
+        if values:
+            out["values"] = V
         try:
             self._check(code)
         except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception

@@ -208,6 +208,17 @@ struct soccer_handle {
     double* cx_values = nullptr;            // [cx_stride][nS] V of the pass in the caller's order (cx_has_values: allocated)
     int cx_policies = 0, cx_stride = 0; bool cx_has_values = false;
     OwnedBufs cx_bufs{"the cross-play solver"};
+    // soccer_match_outcomes: cross-play's buffers with three channels in V, the kick-off means and the values, see match_buffers
+    double* mo_pol = nullptr;               // [mo_policies][nS][5] player A's policies, then player B's
+    double* mo_V[2] = {nullptr, nullptr};   // [nS][3][mo_stride] W_A, W_B and L double-buffered across sweeps
+    unsigned long long* mo_words = nullptr; // [kMinimaxBatch + 1][mo_stride] per-sweep, per-pair max over the channels (bits)
+    int32_t* mo_done = nullptr;             // [mo_stride] each pair's stopping sweep
+    int32_t* mo_iter = nullptr;             // [mo_stride] ... as it is returned (max_sweeps for an open pair)
+    double* mo_kickoff = nullptr;           // [3][mo_stride]
+    int32_t* mo_open = nullptr;             // the number of open pairs after a batch
+    double* mo_values = nullptr;            // [mo_stride][3][nS] in the caller's order (mo_has_values: allocated)
+    int mo_policies = 0, mo_stride = 0; bool mo_has_values = false;
+    OwnedBufs mo_bufs{"the match-outcome solver"};
     // soccer_solve_meta_games: one pass's buffers, allocated on first use and again when a pass needs more of any, see meta_buffers
     double* mg_A = nullptr;                 // [games][n_a][n_b] the caller's matrices
     double* mg_T = nullptr;                 // [games][n_a + 1][stride] the tableaux (the global path only)

@@ -92,6 +92,20 @@ struct CrossFinishIO {
     int32_t n_isd, nS, stride, pairs, max_sweeps;
 };
 
+// match outcomes of n_a x n_b mixed policies (soccer_match_outcomes): three value vectors per pair, the win probabilities of
+// A and of B and the game's length.  match_sweep_kernel takes a CrossIO whose V and V_out are [nS][3][stride] and whose gamma
+// is the continuation probability, cross_batch_kernel its CrossBatchIO; after the last batch (match_finish_kernel,
+// match_values_kernel):
+struct MatchFinishIO {
+    const double* V[2];              // [nS][3][stride] each
+    const int32_t* done_at;          // [stride]
+    double* kickoff;                 // [3][stride] the mean of each channel over the initial states
+    int32_t* iterations;             // [stride]
+    double* values;                  // [pairs][3][nS] (match_values_kernel only)
+    int32_t isd[4];                  // the initial states' observation indices in ISD order
+    int32_t n_isd, nS, stride, pairs, max_sweeps;
+};
+
 // a pass of n_a x n_b zero-sum matrix games (soccer_solve_meta_games): the record of a game, and what every kernel of
 // soccer_metagame_kernels.hpp is given
 constexpr int kMetaRec = 8;

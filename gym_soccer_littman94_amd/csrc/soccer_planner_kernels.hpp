@@ -1,4 +1,4 @@
-// soccer_planner_kernels.hpp — enumerate_kernel (the transition table), planner_kernel, the minimax kernels, response_sweep_kernel, the cross-play kernels, games_kernel.
+// soccer_planner_kernels.hpp — enumerate_kernel (the transition table), planner_kernel, the minimax kernels, response_sweep_kernel, the cross-play kernels, the match-outcome kernels, games_kernel.
 // Included by soccer_planners.hip only: every kernel is emitted by exactly one translation unit.
 #pragma once
 #include "soccer_kernels.hpp"
@@ -505,6 +505,122 @@ __global__ __launch_bounds__(kCrossBlock) void cross_values_kernel(const CrossFi
     __syncthreads();
     for (int r = row0; r < 64; r += kCrossWaves)
         if (p0 + r < IO.pairs && s0 + col < IO.nS) IO.values[(size_t)(p0 + r) * IO.nS + s0 + col] = tile[col][r];
+}
+
+// =================================================================================================
+// match outcomes of n_a x n_b mixed policies (soccer_match_outcomes)
+// =================================================================================================
+// cross_sweep_kernel's work layout, scheme and stopping, with three value vectors per pair instead of one: W_A (A scores the
+// goal that ends the game), W_B (B does) and L (the steps the game lasts).  A list entry is fetched once, by scalar loads, and
+// feeds all three accumulators; the two goal indicators are wave-uniform like the entry they come from.  The V buffers are
+// laid out [nS][3][stride]: a channel's V[next] of the 64 lanes is one contiguous 512-byte load as in cross-play, and the
+// three loads of an entry are 8 * stride bytes apart, rows of one block, where [3][nS][stride] would put them nS * stride * 8
+// bytes apart.  IO is a CrossIO whose V and V_out have that layout and whose gamma is the continuation probability; one word
+// per pair and sweep carries the maximum over the three channels, so cross_batch_kernel serves unchanged.
+constexpr int kMatchChannels = 3;
+
+__global__ __launch_bounds__(kCrossBlock) void match_sweep_kernel(const CrossIO IO) {
+    __shared__ unsigned long long sD[kCrossWaves][64];
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int p = (int)blockIdx.y * 64 + lane;
+    const bool live = p < IO.pairs && !(__longlong_as_double((long long)IO.prev[p]) < IO.theta);
+    if (__ballot(live) == 0ull) return;                                 // the same in every wave: they share the 64 pairs
+    const int s = (int)blockIdx.x * kCrossWaves + wave;                 // wave-uniform, and so is every list index below
+    const size_t stride = (size_t)IO.stride;
+    unsigned long long d = 0ull;
+    if (s < IO.nS) {
+        const int g = min(IO.first + p, IO.last);                       // (a lane past the end reads the last pair's rows)
+        const int i = g / IO.n_b, j = g - i * IO.n_b;
+        const double* xr = IO.x + ((size_t)i * IO.nS + s) * 5;
+        const double* yr = IO.y + ((size_t)j * IO.nS + s) * 5;
+        const double* Vp = IO.V + p;
+        double vA = 0.0, vB = 0.0, vL = 0.0;
+#pragma unroll 1
+        for (int a = 0; a < 5; ++a) {
+            const double xa = xr[a];
+            double iA = 0.0, iB = 0.0, iL = 0.0;
+#pragma unroll 1
+            for (int b = 0; b < 5; ++b) {
+                const double yb = yr[b];
+                const int key = s * 25 + a * 5 + b;
+                const int end = IO.offset[key + 1];
+                double qA = 0.0, qB = 0.0, qL = 0.0;                    // minimax_list_q's expression, three rewards
+                for (int e = IO.offset[key]; e < end; e += kPlanPad) {
+                    PlanEntry x[kPlanPad];
+                    double fA[kPlanPad], fB[kPlanPad], fL[kPlanPad];
+#pragma unroll
+                    for (int t = 0; t < kPlanPad; ++t) x[t] = IO.list[e + t];
+#pragma unroll
+                    for (int t = 0; t < kPlanPad; ++t) {
+                        const double* row = Vp + (size_t)(x[t].next_done & 0x7fffffff) * (kMatchChannels * stride);
+                        fA[t] = row[0]; fB[t] = row[stride]; fL[t] = row[2 * stride];
+                    }
+#pragma unroll
+                    for (int t = 0; t < kPlanPad; ++t) {
+                        const double go = x[t].next_done < 0 ? 0.0 : 1.0;
+                        qA = qA + x[t].prob * ((x[t].reward > 0.0f ? 1.0 : 0.0) + (IO.gamma * fA[t]) * go);
+                        qB = qB + x[t].prob * ((x[t].reward < 0.0f ? 1.0 : 0.0) + (IO.gamma * fB[t]) * go);
+                        qL = qL + x[t].prob * (1.0 + (IO.gamma * fL[t]) * go);
+                    }
+                }
+                iA = iA + yb * qA; iB = iB + yb * qB; iL = iL + yb * qL;
+            }
+            vA = vA + xa * iA; vB = vB + xa * iB; vL = vL + xa * iL;
+        }
+        if (live) {
+            const size_t at = (size_t)s * (kMatchChannels * stride) + p;
+            IO.V_out[at] = vA; IO.V_out[at + stride] = vB; IO.V_out[at + 2 * stride] = vL;
+            const double* old = IO.V + at;
+            // non-negative doubles order like their bit patterns
+            d = (unsigned long long)__double_as_longlong(fabs(vA - old[0]));
+            d = max(d, (unsigned long long)__double_as_longlong(fabs(vB - old[stride])));
+            d = max(d, (unsigned long long)__double_as_longlong(fabs(vL - old[2 * stride])));
+        }
+    }
+    sD[wave][lane] = d;
+    __syncthreads();
+    if (wave == 0 && live) {
+#pragma unroll
+        for (int w = 1; w < kCrossWaves; ++w) d = max(d, sD[w][lane]);
+        // a non-atomic look first: the word only grows
+        if (d > *reinterpret_cast<volatile unsigned long long*>(IO.delta + p)) atomicMax(IO.delta + p, d);
+    }
+}
+
+// a thread per pair: the sweep count (max_sweeps for an open pair) and the three kick-off means, from the buffer of the pair's
+// own parity
+__global__ __launch_bounds__(kCrossBlock) void match_finish_kernel(const MatchFinishIO IO) {
+    const int p = (int)blockIdx.x * kCrossBlock + (int)threadIdx.x;
+    if (p >= IO.pairs) return;
+    const int k = IO.done_at[p] ? IO.done_at[p] : IO.max_sweeps;
+    const size_t stride = (size_t)IO.stride;
+    for (int c = 0; c < kMatchChannels; ++c) {
+        const double* V = IO.V[k & 1] + (size_t)c * stride + p;
+        double sum = 0.0;
+        for (int i = 0; i < IO.n_isd; ++i) sum = sum + V[(size_t)IO.isd[i] * (kMatchChannels * stride)];
+        IO.kickoff[(size_t)c * stride + p] = sum / (double)IO.n_isd;
+    }
+    IO.iterations[p] = k;
+}
+
+// V[nS][3][stride] -> values[pair][3][nS]: cross_values_kernel's 64 x 64 tile in LDS, the channel in blockIdx.z
+__global__ __launch_bounds__(kCrossBlock) void match_values_kernel(const MatchFinishIO IO) {
+    __shared__ double tile[64][65];
+    const int col = (int)(threadIdx.x & 63u), row0 = (int)(threadIdx.x >> 6);
+    const int p0 = (int)blockIdx.x * 64, s0 = (int)blockIdx.y * 64, c = (int)blockIdx.z;
+    const size_t stride = (size_t)IO.stride;
+    {
+        const int p = p0 + col;
+        const int k = p < IO.pairs ? (IO.done_at[p] ? IO.done_at[p] : IO.max_sweeps) : 0;
+        const double* V = IO.V[k & 1] + (size_t)c * stride + p;
+        for (int r = row0; r < 64; r += kCrossWaves)
+            if (p < IO.pairs && s0 + r < IO.nS) tile[r][col] = V[(size_t)(s0 + r) * (kMatchChannels * stride)];
+    }
+    __syncthreads();
+    for (int r = row0; r < 64; r += kCrossWaves)
+        if (p0 + r < IO.pairs && s0 + col < IO.nS)
+            IO.values[((size_t)(p0 + r) * kMatchChannels + c) * IO.nS + s0 + col] = tile[col][r];
 }
 
 // the two-player lists assembled on the device from enumerate_kernel's output (build_minimax): a thread per (state, joint

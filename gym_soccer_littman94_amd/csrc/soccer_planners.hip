@@ -624,3 +624,112 @@ extern "C" int soccer_cross_play(soccer_handle* h, int32_t n_a, const double* pi
                                 (long long)open_total, total, max_sweeps);
     return SOCCER_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// match outcomes: for every pair (pi_a[i], pi_b[j]) the probability that A, and that B, scores the goal that ends the game,
+// and the expected number of steps it lasts, when every step is followed by another with probability continue_prob.
+// cross-play's host scheme (passes, batches of sweeps, the stopping sweeps found on the device) over three-channel buffers:
+// a sweep is one launch of match_sweep_kernel, which reads every list entry once for the three sums.
+static int match_buffers(soccer_handle* h, int policies, int stride, bool values) {
+    if (policies <= h->mo_policies && stride <= h->mo_stride && (!values || h->mo_has_values)) return SOCCER_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    policies = std::max(policies, h->mo_policies); stride = std::max(stride, h->mo_stride); values = values || h->mo_has_values;
+    h->mo_bufs.clear();
+    h->mo_policies = 0; h->mo_stride = 0; h->mo_has_values = false;
+    const size_t nS = (size_t)h->mm.nS, cells = kMatchChannels * nS * (size_t)stride;
+    int rc = h->mo_bufs.alloc(h, (size_t)policies * nS * 5, &h->mo_pol);
+    if (!rc) rc = h->mo_bufs.alloc(h, cells, &h->mo_V[0]);
+    if (!rc) rc = h->mo_bufs.alloc(h, cells, &h->mo_V[1]);
+    if (!rc) rc = h->mo_bufs.alloc(h, (size_t)stride * (kMinimaxBatch + 1), &h->mo_words);
+    if (!rc) rc = h->mo_bufs.alloc(h, (size_t)stride, &h->mo_done);
+    if (!rc) rc = h->mo_bufs.alloc(h, (size_t)stride, &h->mo_iter);
+    if (!rc) rc = h->mo_bufs.alloc(h, (size_t)kMatchChannels * stride, &h->mo_kickoff);
+    if (!rc) rc = h->mo_bufs.alloc(h, (size_t)1, &h->mo_open);
+    if (!rc && values) rc = h->mo_bufs.alloc(h, cells, &h->mo_values);
+    if (rc) { h->mo_bufs.clear(); return rc; }
+    h->mo_policies = policies; h->mo_stride = stride; h->mo_has_values = values;
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_match_outcomes(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t n_b, const double* pi_b, double theta,
+                                     double continue_prob, int32_t max_sweeps, int32_t pairs_per_pass, double* win_a, double* win_b,
+                                     double* length, double* values, int32_t* iterations) {
+    const char* what = "soccer_match_outcomes";
+    if (int rc = minimax_check(h, what, 0.0)) return rc;
+    if (!(continue_prob >= 0.0 && continue_prob <= 1.0)) return fail(h, SOCCER_E_INVALID, "continue_prob must be in [0, 1]");
+    if (n_a < 1 || n_a > SOCCER_CROSS_MAX_POLICIES || n_b < 1 || n_b > SOCCER_CROSS_MAX_POLICIES)
+        return fail(h, SOCCER_E_INVALID, "%s: the number of policies of each player must be 1 .. %d, not %d and %d", what,
+                    SOCCER_CROSS_MAX_POLICIES, n_a, n_b);
+    if (max_sweeps < 1) return fail(h, SOCCER_E_INVALID, "max_sweeps must be >= 1");
+    if (!(theta >= 0.0)) return fail(h, SOCCER_E_INVALID, "theta must be >= 0");
+    if (pairs_per_pass < 0 || pairs_per_pass % 64)
+        return fail(h, SOCCER_E_INVALID, "%s: pairs_per_pass must be 0 (the library chooses) or a positive multiple of 64, not %d", what, pairs_per_pass);
+    if (int rc = response_rows(h, what, "pi_a", n_a, pi_a)) return rc;
+    if (int rc = response_rows(h, what, "pi_b", n_b, pi_b)) return rc;
+    if (int rc = minimax_prepare(h)) return rc;
+    const int nS = h->mm.nS;
+    const int total = n_a * n_b, total64 = (total + 63) / 64 * 64;
+    // the library's choice: the two three-channel buffers of a pass, 2 * 3 * nS * pairs * 8 bytes, stay at or under 1 GiB
+    int per_pass = pairs_per_pass ? pairs_per_pass : std::max(64, (int)(((size_t)1 << 30) / ((size_t)16 * kMatchChannels * nS) / 64 * 64));
+    per_pass = std::min(per_pass, total64);
+    if (int rc = match_buffers(h, n_a + n_b, per_pass, values != nullptr)) return rc;
+    const int stride = h->mo_stride;                                    // (what an earlier, larger pass left: no result depends on it)
+    const size_t cells = (size_t)kMatchChannels * nS * stride;
+    double* d_x = h->mo_pol; double* d_y = h->mo_pol + (size_t)n_a * nS * 5;
+    if (int rc = response_upload(h, d_x, pi_a, n_a)) return rc;
+    if (int rc = response_upload(h, d_y, pi_b, n_b)) return rc;
+    constexpr int kWords = kMinimaxBatch + 1;
+    CrossIO io{};
+    io.offset = h->mm.offset; io.list = h->mm.list; io.x = d_x; io.y = d_y; io.gamma = continue_prob; io.theta = theta;
+    io.nS = nS; io.n_b = n_b; io.stride = stride; io.last = total - 1;
+    CrossBatchIO bio{};
+    bio.words = h->mo_words; bio.done_at = h->mo_done; bio.open = h->mo_open; bio.theta = theta; bio.stride = stride; bio.n_words = kWords;
+    MatchFinishIO fio{};
+    fio.V[0] = h->mo_V[0]; fio.V[1] = h->mo_V[1]; fio.done_at = h->mo_done; fio.kickoff = h->mo_kickoff; fio.iterations = h->mo_iter;
+    fio.values = h->mo_values; fio.n_isd = h->rules.n_isd; fio.nS = nS; fio.stride = stride; fio.max_sweeps = max_sweeps;
+    for (int i = 0; i < h->rules.n_isd; ++i) fio.isd[i] = (int32_t)h->rules.isd_obs[i];
+    double* const outs[kMatchChannels] = {win_a, win_b, length};
+    int64_t open_total = 0;
+    for (int first = 0; first < total; first += per_pass) {
+        const int pairs = std::min(per_pass, total - first);
+        const unsigned pair_blocks = (unsigned)((pairs + kCrossBlock - 1) / kCrossBlock);
+        io.first = first; io.pairs = pairs; bio.pairs = pairs; fio.pairs = pairs;
+        HIP_TRY(h, hipMemsetAsync(h->mo_V[0], 0, cells * 8, h->stream));                     // W_A = W_B = L = 0
+        HIP_TRY(h, hipMemsetAsync(h->mo_V[1], 0, cells * 8, h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->mo_open, 0, sizeof(int32_t), h->stream));
+        bio.k0 = 0; bio.nb = 0;
+        hipLaunchKernelGGL(cross_batch_kernel, dim3(pair_blocks), dim3(kCrossBlock), 0, h->stream, bio);
+        const dim3 grid((unsigned)((nS + kCrossWaves - 1) / kCrossWaves), (unsigned)((pairs + 63) / 64));
+        int32_t k0 = 1, open = pairs;                                                          // k0: first sweep of the batch
+        while (k0 <= max_sweeps && open) {
+            const int nb = (int)std::min<int64_t>(kMinimaxBatch, (int64_t)max_sweeps - k0 + 1);
+            for (int j = 1; j <= nb; ++j) {
+                const int32_t k = k0 + j - 1;
+                io.V = h->mo_V[(k - 1) & 1]; io.V_out = h->mo_V[k & 1];
+                io.delta = h->mo_words + (size_t)j * stride; io.prev = h->mo_words + (size_t)(j - 1) * stride;
+                hipLaunchKernelGGL(match_sweep_kernel, grid, dim3(kCrossBlock), 0, h->stream, io);
+            }
+            HIP_TRY(h, hipMemsetAsync(h->mo_open, 0, sizeof(int32_t), h->stream));
+            bio.k0 = k0; bio.nb = nb;
+            hipLaunchKernelGGL(cross_batch_kernel, dim3(pair_blocks), dim3(kCrossBlock), 0, h->stream, bio);
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipMemcpyAsync(&open, h->mo_open, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            k0 += nb;
+        }
+        open_total += open;
+        hipLaunchKernelGGL(match_finish_kernel, dim3(pair_blocks), dim3(kCrossBlock), 0, h->stream, fio);
+        if (values) hipLaunchKernelGGL(match_values_kernel, dim3((unsigned)((pairs + 63) / 64), (unsigned)((nS + 63) / 64), kMatchChannels),
+                                       dim3(kCrossBlock), 0, h->stream, fio);
+        HIP_TRY(h, hipGetLastError());
+        for (int c = 0; c < kMatchChannels; ++c)
+            if (outs[c]) HIP_TRY(h, hipMemcpyAsync(outs[c] + first, h->mo_kickoff + (size_t)c * stride, (size_t)pairs * 8, hipMemcpyDeviceToHost, h->stream));
+        if (iterations) HIP_TRY(h, hipMemcpyAsync(iterations + first, h->mo_iter, (size_t)pairs * 4, hipMemcpyDeviceToHost, h->stream));
+        if (values) HIP_TRY(h, hipMemcpyAsync(values + (size_t)first * kMatchChannels * nS, h->mo_values, (size_t)pairs * kMatchChannels * nS * 8,
+                                              hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    if (open_total) return fail(h, SOCCER_E_STATE, "%s: %lld of %d pairs had not converged after max_sweeps = %d sweeps", what,
+                                (long long)open_total, total, max_sweeps);
+    return SOCCER_OK;
+}

@@ -517,6 +517,12 @@ class VectorSoccerEnv:
         assert self.multiagent, "cross_play needs a two-player environment (no player with a fixed policy)"
         return self._batch.cross_play(pi_a, pi_b, theta, discount_factor, **params)
 
+    def match_outcomes(self, pi_a, pi_b, theta, continue_prob, **params):
+        """Win, loss and draw odds and the game length of two sets of mixed policies (SoccerBatch.match_outcomes): consumes no
+        tick, leaves the lanes alone."""
+        assert self.multiagent, "match_outcomes needs a two-player environment (no player with a fixed policy)"
+        return self._batch.match_outcomes(pi_a, pi_b, theta, continue_prob, **params)
+
     def solve_meta_game(self, payoff, **params):
         """The maximin mixtures of zero-sum matrix games, cross_play's for instance (SoccerBatch.solve_meta_game): nothing to do
         with the pitch, so any environment will do; consumes no tick, leaves the lanes alone."""

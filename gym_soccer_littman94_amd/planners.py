@@ -285,6 +285,14 @@ def cross_play(env, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000):
             "bounds": (float(row_min.max()), float(col_max.min()))}
 
 
+def match_outcomes(env, pi_a, pi_b, theta, continue_prob, max_sweeps=1000000):
+    """Littman's columns for two sets of mixed policies, exactly, on the device (include/soccer_hip.h, "match outcomes"): after
+    every step the game goes on with probability continue_prob and is a draw otherwise.  pi_a is [n_a, nS, 5], pi_b
+    [n_b, nS, 5].  Returns a dict of [n_a, n_b] arrays at kick-off: win_a, win_b, draw = 1 - win_a - win_b, length (steps per
+    game), games_per_step = 1 / length and iterations."""
+    return _two_player_batch(env, "match_outcomes").match_outcomes(pi_a, pi_b, theta, continue_prob, max_sweeps=max_sweeps)
+
+
 def meta_game(env, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000, max_pivots=None):
     """cross_play followed by the solve of its meta-game, both on the device (include/soccer_hip.h, "the meta-game"): which
     mixture of player A's policies can a rational mixture of player B's not beat?  Returns cross_play's dict plus

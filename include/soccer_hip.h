@@ -67,7 +67,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_* (soccer_q_population_create_league and soccer_q_population_league_* among them), soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies, soccer_cross_play, soccer_solve_meta_games and soccer_rollout_shape were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_* (soccer_q_population_create_league and soccer_q_population_league_* among them), soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies, soccer_cross_play, soccer_match_outcomes, soccer_solve_meta_games and soccer_rollout_shape were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -465,6 +465,37 @@ int soccer_evaluate_policies(soccer_handle* h, int32_t n_pairs, const double* pi
 int soccer_cross_play(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t n_b, const double* pi_b,
                       double theta, double discount_factor, int32_t max_sweeps, int32_t pairs_per_pass,
                       double* payoff, double* V, int32_t* iterations);
+/* ---- match outcomes: who wins, how often it is a draw, how long a game lasts (two-player handles) -----------------------
+ * Littman's columns for every pair (x = pi_a[i], y = pi_b[j]): after every step the game goes on with probability
+ * continue_prob = c in [0, 1] and is called a draw otherwise.  Three value vectors per pair, all 0 before sweep 1:
+ *   W_A[n_states]  the probability that A's side is credited with the goal that ends the game
+ *   W_B[n_states]  the same for B
+ *   L[n_states]    the expected number of steps the game lasts
+ * Sweep k, for every state s and joint action (a, b), over the list in list order, each sum acc = acc + .. from 0.0 in
+ * float64, not contracted (the expression of Q above with three rewards):
+ *   qA = sum prob * ((reward > 0 ? 1.0 : 0.0) + (c * W_A[next]) * (not done))
+ *   qB = sum prob * ((reward < 0 ? 1.0 : 0.0) + (c * W_B[next]) * (not done))
+ *   qL = sum prob * (1.0                      + (c * L  [next]) * (not done))
+ * then each channel is mixed as soccer_evaluate_policies mixes Q: F_k[s] = sum_a x[s][a] * (sum_b y[s][b] * q[a][b]).
+ * Padding entries are accumulated like any other.  Row 0 of a policy is not read and counts as zeros, so all three
+ * channels are 0 at state 0.  (The lists' rewards are -1, 0 or +1 and nonzero only on entries that end the game.)
+ * A pair stops at its first sweep k where the maximum over the three channels and all states of |F_k - F_{k-1}| is
+ * < theta and keeps that sweep's vectors.  win_a, win_b and length are the kick-off numbers of W_A, W_B and L: the
+ * sequential sum over the handle's initial states in ISD order, from 0.0, divided by n_isd, as soccer_cross_play's payoff.
+ * The share of draws is 1 - win_a - win_b, and with c the discount, W_A - W_B is soccer_cross_play's V up to the stopping
+ * error of three fixed points.  Every pair returns the bits and the sweep count it has when it is solved alone.
+ * win_a, win_b, length and iterations are HOST [n_a][n_b], values is HOST [n_a][n_b][3][n_states] (W_A, W_B, L); any of
+ * them may be NULL, and only what is asked for is formed and copied.  The checks, refusals, limits
+ * (SOCCER_CROSS_MAX_POLICIES) and pairs_per_pass are soccer_cross_play's, the default pass keeping the two three-channel
+ * buffers, 2 * 3 * n_states * pairs * 8 bytes, at or under 1 GiB.  continue_prob == 1 is allowed, as discount_factor == 1
+ * is: L then grows by one per sweep wherever the pair never scores, and such pairs need not converge.
+ * SOCCER_E_STATE when some pair has not converged after max_sweeps: iterations == max_sweeps marks those, whose outputs
+ * hold the last iterate (the max_sweeps-step probabilities and the length truncated there), and the other pairs are
+ * complete.  Like the calls above this one consumes no tick, leaves the lanes alone and returns SOCCER_E_STATE during a
+ * graph capture. */
+int soccer_match_outcomes(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t n_b, const double* pi_b,
+                          double theta, double continue_prob, int32_t max_sweeps, int32_t pairs_per_pass,
+                          double* win_a, double* win_b, double* length, double* values, int32_t* iterations);
 /* ---- the meta-game: maximin mixtures of n_a x n_b zero-sum matrix games (any handle) ------------------------------------
  * Which mixture of the rows of a payoff matrix (soccer_cross_play's, or any other) can a rational opponent not beat?
  * A is HOST [n_games][n_a][n_b], the row player's (the maximiser's) payoffs.  Per game, in float64, nothing contracted
