@@ -140,6 +140,7 @@ PHC_LEARN, PHC_UNIFORM, PHC_FIXED = 0, 1, 2
 MQ_MAX_LANES = 1 << 22
 BR_MAX_POLICIES = 256
 CROSS_MAX_POLICIES = 1024
+OCC_MAX_FEATURES = 16
 LEAGUE_MAX_POLICIES = 1024
 META_MAX_POLICIES = 1024
 MISUSE_FROZEN, MISUSE_ACTION, MISUSE_OBSERVATION = 1, 2, 4
@@ -199,6 +200,8 @@ PROTOTYPES = {
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "soccer_match_outcomes": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_int32,
                                         C.c_int32] + [C.c_void_p] * 5),
+    "soccer_occupancy": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_int32,
+                                   C.c_int32, C.c_int32] + [C.c_void_p] * 5),
     "soccer_solve_meta_games": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                           C.POINTER(MetaGameResult)]),
     "soccer_minimax_q_create": (C.c_int, [C.c_void_p, C.POINTER(MinimaxQConfig), C.POINTER(C.c_void_p)]),

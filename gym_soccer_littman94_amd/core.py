@@ -215,6 +215,12 @@ class _Population(_Learner):
         continue_prob None: the range's common discount, ValueError if the members differ."""
         return _population_match_outcomes(self, self._policies, "pi_a", "pi_b", theta, first, count, continue_prob)
 
+    def occupancy(self, theta=1e-10, first=0, count=None, continue_prob=None, features=None, values=False):
+        """Where each member's player A and each member's player B play their game: SoccerBatch.occupancy's dict on cross_play's
+        policies of members first .. first + count - 1 (at most 1024).  continue_prob None: the range's common discount,
+        ValueError if the members differ."""
+        return _population_occupancy(self, self._policies, "pi_a", "pi_b", theta, first, count, continue_prob, features, values)
+
 
 class MinimaxQLearner(_Learner):
     """A minimax-Q learner (Littman 1994) on a two-player auto-reset SoccerBatch: one shared Q[nS, 5, 5] on the device,
@@ -461,6 +467,13 @@ def _population_match_outcomes(pop, read, key_a, key_b, theta, first, count, con
     common discount"""
     pa, pb, continue_prob = _population_sides(pop, read, key_a, key_b, first, count, continue_prob, "match_outcomes", "continue_prob")
     return pop.batch.match_outcomes(pa, pb, theta, continue_prob)
+
+
+def _population_occupancy(pop, read, key_a, key_b, theta, first, count, continue_prob, features, values):
+    """_population_cross_play's members and policies through SoccerBatch.occupancy; continue_prob None: the range's common
+    discount"""
+    pa, pb, continue_prob = _population_sides(pop, read, key_a, key_b, first, count, continue_prob, "occupancy", "continue_prob")
+    return pop.batch.occupancy(pa, pb, theta, continue_prob, features=features, values=values)
 
 
 def _population_sides(pop, read, key_a, key_b, first, count, discount, what, name):
@@ -718,6 +731,13 @@ class OpponentModelPopulation(_Population):
         continue_prob None: the range's common discount, ValueError if the members differ."""
         assert which in self._WHICH, "which must be 'greedy' or 'model'"
         return _population_match_outcomes(self, self.read, *self._WHICH[which], theta, first, count, continue_prob)
+
+    def occupancy(self, which="greedy", theta=1e-10, first=0, count=None, continue_prob=None, features=None, values=False):
+        """Where each member's player A and each member's player B play their game: SoccerBatch.occupancy's dict on cross_play's
+        policies (which) of members first .. first + count - 1 (at most 1024).  continue_prob None: the range's common discount,
+        ValueError if the members differ."""
+        assert which in self._WHICH, "which must be 'greedy' or 'model'"
+        return _population_occupancy(self, self.read, *self._WHICH[which], theta, first, count, continue_prob, features, values)
 
     def load(self, Q_a=None, Q_b=None, C_a=None, C_b=None, alpha=None, steps=None, first=0):
         """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged): Q_a /
@@ -987,6 +1007,14 @@ class WolfPopulation(_Population):
         assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
         return _population_match_outcomes(self, lambda f, c: self._read(f, c, (which + "_a", which + "_b")), which + "_a", which + "_b",
                                           theta, first, count, continue_prob)
+
+    def occupancy(self, which="pi", theta=1e-10, first=0, count=None, continue_prob=None, features=None, values=False):
+        """Where each member's player A and each member's player B play their game: SoccerBatch.occupancy's dict on cross_play's
+        policies (which) of members first .. first + count - 1 (at most 1024).  continue_prob None: the range's common discount,
+        ValueError if the members differ."""
+        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
+        return _population_occupancy(self, lambda f, c: self._read(f, c, (which + "_a", which + "_b")), which + "_a", which + "_b",
+                                     theta, first, count, continue_prob, features, values)
 
     def load(self, Q_a=None, Q_b=None, pi_a=None, pi_b=None, avg_a=None, avg_b=None, updates=None, alpha=None, dscale=None, steps=None,
              first=0):
@@ -1486,6 +1514,42 @@ class SoccerBatch:
                    "iterations": it.astype(np.int64)}
         if values:
             out["values"] = V
+        try:
+            self._check(code)
+        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
+            e.results = out
+            raise
+        return out
+
+    def occupancy(self, pi_a, pi_b, theta, continue_prob, features=None, values=False, max_sweeps=1000000, pairs_per_pass=0):
+        """Where the game is played when two sets of mixed policies meet, exactly (include/soccer_hip.h, "state occupancy"): the
+        expected number of visits to every state from kick-off when after every step the game goes on with probability
+        continue_prob — the dual of the value.  pi_a, pi_b, pairs_per_pass and the limits are cross_play's; features is
+        [n_f, nS] (or one [nS] vector), at most 16 of them.  Returns a dict, pi_a[i] against pi_b[j]:
+          length          [n_a, n_b] the expected number of steps of a game, the sum of the occupancy over the states
+          expect          [n_a, n_b, n_f] the sum over the states of occupancy * features[q]: with an indicator, the steps
+                          spent in its states
+          iterations      [n_a, n_b] the sweeps of each pair's solve (int64)
+          occupancy       [n_a, n_b, nS] with values=True, and  visit_share = occupancy / length
+        RuntimeError if max_sweeps is reached (its .results holds the dict, iterations == max_sweeps marks the open pairs,
+        which hold the last iterate)."""
+        a, _ = self._policies(pi_a, "pi_a")
+        b, _ = self._policies(pi_b, "pi_b")
+        na, nb = a.shape[0], b.shape[0]
+        F = np.zeros((0, self.nS)) if features is None else np.ascontiguousarray(features, np.float64)
+        F = F[None] if F.ndim == 1 else F
+        assert F.ndim == 2 and F.shape[1] == self.nS, "features must be [n_f, n_states] or [n_states]"
+        nf = F.shape[0]
+        length = np.zeros((na, nb)); expect = np.zeros((na, nb, nf)); it = np.zeros((na, nb), np.int32)
+        D = np.zeros((na, nb, self.nS)) if values else None
+        code = self.lib.soccer_occupancy(self.h, na, a.ctypes.data, nb, b.ctypes.data, float(theta), float(continue_prob),
+                                         int(max_sweeps), int(pairs_per_pass), nf, F.ctypes.data if nf else None, length.ctypes.data,
+                                         expect.ctypes.data if nf else None, D.ctypes.data if values else None, it.ctypes.data)
+        out = {"length": length, "expect": expect, "iterations": it.astype(np.int64)}
+        if values:
+            out["occupancy"] = D
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out["visit_share"] = D / length[:, :, None]
         try:
             self._check(code)
         except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception

@@ -4,7 +4,7 @@
 //   soccer_hip.hip       create / destroy, seed / tick, reset, state, staging, one-environment calls, statistics, timers, graphs
 //   soccer_step.hip      batched_step*
 //   soccer_rollout.hip   batched_rollout*
-//   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, cross-play, the matrix-game solver
+//   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, cross-play, match outcomes, state occupancy, the matrix-game solver
 //   soccer_metagame.hip  soccer_solve_meta_games: the maximin mixtures of n_a x n_b matrix games
 //   soccer_learners.hip  the seven kinds of learners on one host skeleton: minimax-Q, independent Q, WoLF-PHC, a population of each, and a
 //                        population of opponent-modelling Q-learners
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/soccer_hip.h"
+#include "soccer_inlists.hpp"
 #include "soccer_kernels.hpp"
 #include "soccer_plan_io.hpp"
 #include "soccer_rules.hpp"
@@ -219,6 +220,24 @@ struct soccer_handle {
     double* mo_values = nullptr;            // [mo_stride][3][nS] in the caller's order (mo_has_values: allocated)
     int mo_policies = 0, mo_stride = 0; bool mo_has_values = false;
     OwnedBufs mo_bufs{"the match-outcome solver"};
+    // soccer_occupancy: the two-player lists the other way round (build_inlists, once per handle like the lists they derive
+    // from), and cross-play's buffers with the policies transposed, see occupancy_buffers
+    const int32_t* oc_in_offset = nullptr;  // [nS + 1]
+    const InEntry* oc_in_list = nullptr;    // padded to kPlanPad
+    OwnedBufs oc_lists{"the occupancy solver's in-lists"};
+    double* oc_pol = nullptr;               // [oc_policies][nS][5] as the caller gives them: player A's policies, then player B's
+    double* oc_polT = nullptr;              // [nS][5][n_a] player A's with the policy along the fastest axis, then [nS][5][n_b]
+    double* oc_D[2] = {nullptr, nullptr};   // [nS][oc_stride] D double-buffered across sweeps
+    unsigned long long* oc_words = nullptr; // [kMinimaxBatch + 1][oc_stride] per-sweep, per-pair max |D_k - D_{k-1}| (bits)
+    int32_t* oc_done = nullptr;             // [oc_stride] each pair's stopping sweep
+    int32_t* oc_iter = nullptr;             // [oc_stride] ... as it is returned (max_sweeps for an open pair)
+    double* oc_length = nullptr;            // [oc_stride]
+    double* oc_expect = nullptr;            // [pairs of the pass][n_f], room for [oc_stride][SOCCER_OCC_MAX_FEATURES]
+    double* oc_features = nullptr;          // [SOCCER_OCC_MAX_FEATURES][nS] the caller's
+    int32_t* oc_open = nullptr;             // the number of open pairs after a batch
+    double* oc_values = nullptr;            // [oc_stride][nS] D of the pass in the caller's order (oc_has_values: allocated)
+    int oc_policies = 0, oc_stride = 0; bool oc_has_values = false;
+    OwnedBufs oc_bufs{"the occupancy solver"};
     // soccer_solve_meta_games: one pass's buffers, allocated on first use and again when a pass needs more of any, see meta_buffers
     double* mg_A = nullptr;                 // [games][n_a][n_b] the caller's matrices
     double* mg_T = nullptr;                 // [games][n_a + 1][stride] the tableaux (the global path only)

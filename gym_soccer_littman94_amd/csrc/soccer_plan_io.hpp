@@ -106,6 +106,45 @@ struct MatchFinishIO {
     int32_t n_isd, nS, stride, pairs, max_sweeps;
 };
 
+// state occupancy of n_a x n_b mixed policies (soccer_occupancy): the expected discounted number of visits to every state.
+// The sweep runs the transition relation backwards, over in-lists (soccer_inlists.hpp builds them from MinimaxIO's lists):
+// one in-entry, 16 bytes = one dwordx4 load, is the probability of the out-entry it mirrors and that entry's key
+// s * 25 + a * 5 + b; in-lists are padded to kPlanPad with (prob 0.0, source key 0) entries.
+struct __attribute__((aligned(16))) InEntry { double prob; int32_t source_key; int32_t pad; };
+
+// occupancy_sweep_kernel; cross_batch_kernel takes its CrossBatchIO between the batches, cross_values_kernel a CrossFinishIO
+struct OccupancyIO {
+    const int32_t* in_offset; const InEntry* in_list;   // [nS + 1], the in-lists
+    const double* xT;                // [nS][5][n_a] player A's policies, the policy along the fastest axis, row 0 zeroed
+    const double* yT;                // [nS][5][n_b] player B's
+    const double* D;                 // [nS][stride] D_{k-1}
+    double* D_out;                   // [nS][stride] D_k
+    unsigned long long* delta;       // [stride] this sweep's word of every pair of the pass
+    const unsigned long long* prev;  // [stride] the previous sweep's
+    double c, theta, mu;             // the continuation probability; 1.0 / n_isd
+    int32_t isd[4];                  // the initial states' observation indices
+    int32_t n_isd, nS, n_a, n_b;
+    int32_t stride, pairs;
+    int32_t first, last;             // as CrossIO's
+};
+
+// the caller's policies [n][nS][5] -> [nS][5][n], row 0 as zeros (occupancy_transpose_kernel)
+struct OccupancyPolicyIO {
+    const double* pol; double* polT;
+    int32_t n, rows;                 // rows = nS * 5
+};
+
+// after the last batch (occupancy_finish_kernel): a thread per (pair, sum) from the D buffer of the pair's own parity
+struct OccupancyFinishIO {
+    const double* D[2];              // [nS][stride] each
+    const int32_t* done_at;          // [stride]
+    const double* features;          // [n_f][nS]
+    double* length;                  // [stride] (NULL: not asked for)
+    double* expect;                  // [pairs][n_f]
+    int32_t* iterations;             // [stride]
+    int32_t nS, stride, pairs, max_sweeps, n_f;
+};
+
 // a pass of n_a x n_b zero-sum matrix games (soccer_solve_meta_games): the record of a game, and what every kernel of
 // soccer_metagame_kernels.hpp is given
 constexpr int kMetaRec = 8;

@@ -1,4 +1,4 @@
-// soccer_planner_kernels.hpp — enumerate_kernel (the transition table), planner_kernel, the minimax kernels, response_sweep_kernel, the cross-play kernels, the match-outcome kernels, games_kernel.
+// soccer_planner_kernels.hpp — enumerate_kernel (the transition table), planner_kernel, the minimax kernels, response_sweep_kernel, the cross-play kernels, the match-outcome kernels, the occupancy kernels, games_kernel.
 // Included by soccer_planners.hip only: every kernel is emitted by exactly one translation unit.
 #pragma once
 #include "soccer_kernels.hpp"
@@ -621,6 +621,102 @@ __global__ __launch_bounds__(kCrossBlock) void match_values_kernel(const MatchFi
     for (int r = row0; r < 64; r += kCrossWaves)
         if (p0 + r < IO.pairs && s0 + col < IO.nS)
             IO.values[((size_t)(p0 + r) * kMatchChannels + c) * IO.nS + s0 + col] = tile[col][r];
+}
+
+// =================================================================================================
+// state occupancy of n_a x n_b mixed policies (soccer_occupancy)
+// =================================================================================================
+// The dual of cross-play's evaluation: D_k[s'] = mu[s'] + sum over the in-entries of s' of prob * ((x[s][a] * y[s][b]) *
+// (c * D_{k-1}[s])), the transition relation run backwards.  A gather over in-lists (soccer_inlists.hpp) rather than a
+// scatter along the out-lists, so every D_k[s'] is one sequential sum in one fixed order and needs no atomics.
+// cross_sweep_kernel's work layout, scheme and stopping: a lane owns a pair, a wave owns (s', 64 consecutive pairs of the
+// pass), D is [nS][stride], the in-entries sit at wave-uniform addresses (scalar loads, kPlanPad per wait) and an entry's
+// D[s] of the 64 lanes is one contiguous 512-byte load.  New here: the policy entries are read per in-entry, at that entry's
+// (s, a) and (s, b), not once per state.  They come from transposed copies [nS][5][n] (occupancy_transpose_kernel), so the
+// 64 lanes' y[s][b][j] are consecutive doubles (j = pair mod n_b) and their x[s][a][i] one or two addresses, where the
+// caller's [n][nS][5] would put each lane's y in a cache line of its own, nS * 40 bytes from its neighbour's.  Row 0 of D is
+// never written and stays 0.0; a padding in-entry (key 0) reads the zeroed row 0 of both policies and adds +0.0.
+__global__ __launch_bounds__(kCrossBlock) void occupancy_transpose_kernel(const OccupancyPolicyIO IO) {
+    const size_t at = (size_t)blockIdx.x * kCrossBlock + threadIdx.x;
+    if (at >= (size_t)IO.rows * (size_t)IO.n) return;
+    const size_t r = at / (size_t)IO.n, i = at - r * (size_t)IO.n;
+    IO.polT[at] = r < 5 ? 0.0 : IO.pol[i * (size_t)IO.rows + r];
+}
+
+__global__ __launch_bounds__(kCrossBlock) void occupancy_sweep_kernel(const OccupancyIO IO) {
+    __shared__ unsigned long long sD[kCrossWaves][64];
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int p = (int)blockIdx.y * 64 + lane;
+    const bool live = p < IO.pairs && !(__longlong_as_double((long long)IO.prev[p]) < IO.theta);
+    if (__ballot(live) == 0ull) return;                                 // the same in every wave: they share the 64 pairs
+    const int s1 = (int)blockIdx.x * kCrossWaves + wave;                // s': wave-uniform, and so is every in-list index below
+    const size_t stride = (size_t)IO.stride;
+    unsigned long long d = 0ull;
+    if (s1 >= 1 && s1 < IO.nS) {
+        const int g = min(IO.first + p, IO.last);                       // (a lane past the end reads the last pair's rows)
+        const int i = g / IO.n_b, j = g - i * IO.n_b;
+        const double* xp = IO.xT + i;
+        const double* yp = IO.yT + j;
+        const double* Dp = IO.D + p;
+        double mu = 0.0;
+        for (int t = 0; t < IO.n_isd; ++t) mu = IO.isd[t] == s1 ? IO.mu : mu;
+        const int end = IO.in_offset[s1 + 1];
+        double acc = 0.0;
+        for (int e = IO.in_offset[s1]; e < end; e += kPlanPad) {
+            InEntry x[kPlanPad];
+            double xa[kPlanPad], yb[kPlanPad], ds[kPlanPad];
+#pragma unroll
+            for (int t = 0; t < kPlanPad; ++t) x[t] = IO.in_list[e + t];
+#pragma unroll
+            for (int t = 0; t < kPlanPad; ++t) {
+                const int key = x[t].source_key, s = key / 25;         // key = s * 25 + a * 5 + b
+                xa[t] = xp[(size_t)(key / 5) * (size_t)IO.n_a];                            // x[s][a]
+                yb[t] = yp[(size_t)(s * 5 + (key - (key / 5) * 5)) * (size_t)IO.n_b];      // y[s][b]
+                ds[t] = Dp[(size_t)s * stride];
+            }
+#pragma unroll
+            for (int t = 0; t < kPlanPad; ++t) acc = acc + x[t].prob * ((xa[t] * yb[t]) * (IO.c * ds[t]));
+        }
+        if (live) {
+            const double v = mu + acc;
+            IO.D_out[(size_t)s1 * stride + p] = v;
+            d = (unsigned long long)__double_as_longlong(fabs(v - Dp[(size_t)s1 * stride]));   // non-negative doubles order like their bits
+        }
+    }
+    sD[wave][lane] = d;
+    __syncthreads();
+    if (wave == 0 && live) {
+#pragma unroll
+        for (int w = 1; w < kCrossWaves; ++w) d = max(d, sD[w][lane]);
+        // a non-atomic look first: the word only grows
+        if (d > *reinterpret_cast<volatile unsigned long long*>(IO.delta + p)) atomicMax(IO.delta + p, d);
+    }
+}
+
+// a thread per (pair, sum), the sum in blockIdx.y: 0 is the sweep count (max_sweeps for an open pair) and, if asked for, the
+// length sum_s D[s]; q >= 1 the expectation sum_s D[s] * features[q - 1][s].  Each sum is sequential over ascending s from
+// 0.0, from the buffer of the pair's own parity; the 64 lanes' D[s] are one contiguous load and the feature is wave-uniform.
+__global__ __launch_bounds__(kCrossBlock) void occupancy_finish_kernel(const OccupancyFinishIO IO) {
+    const int p = (int)blockIdx.x * kCrossBlock + (int)threadIdx.x;
+    const int q = (int)blockIdx.y;
+    if (p >= IO.pairs) return;
+    const int k = IO.done_at[p] ? IO.done_at[p] : IO.max_sweeps;
+    if (q == 0) {
+        IO.iterations[p] = k;
+        if (!IO.length) return;
+    }
+    const double* D = IO.D[k & 1] + p;
+    const size_t stride = (size_t)IO.stride;
+    double sum = 0.0;
+    if (q == 0) {
+        for (int s = 0; s < IO.nS; ++s) sum = sum + D[(size_t)s * stride];
+        IO.length[p] = sum;
+    } else {
+        const double* f = IO.features + (size_t)(q - 1) * IO.nS;
+        for (int s = 0; s < IO.nS; ++s) sum = sum + D[(size_t)s * stride] * f[s];
+        IO.expect[(size_t)p * IO.n_f + (q - 1)] = sum;
+    }
 }
 
 // the two-player lists assembled on the device from enumerate_kernel's output (build_minimax): a thread per (state, joint

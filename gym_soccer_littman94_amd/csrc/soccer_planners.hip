@@ -733,3 +733,153 @@ extern "C" int soccer_match_outcomes(soccer_handle* h, int32_t n_a, const double
                                 (long long)open_total, total, max_sweeps);
     return SOCCER_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// state occupancy: for every pair (pi_a[i], pi_b[j]) the expected discounted number of visits to every state from kick-off,
+// the dual of cross-play's value.  The sweep sums over in-lists, the two-player lists the other way round, which are built
+// on the host once per handle (soccer_inlists.hpp) from a copy of the device's lists; the rest is cross-play's host scheme
+// (passes, batches of sweeps, the stopping sweeps found on the device), with the policies transposed on the device once per
+// call so that the per-entry policy reads of occupancy_sweep_kernel are contiguous across the lanes.
+static int build_occupancy_lists(soccer_handle* h) {
+    if (h->oc_lists.ready) return SOCCER_OK;
+    const int nS = h->mm.nS;
+    const size_t nkeys = (size_t)nS * 25;
+    std::vector<int32_t> off(nkeys + 1);
+    HIP_TRY(h, hipMemcpyAsync(off.data(), h->mm.offset, off.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::vector<PlanEntry> list((size_t)off[nkeys]);
+    HIP_TRY(h, hipMemcpyAsync(list.data(), h->mm.list, list.size() * sizeof(PlanEntry), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    std::vector<int32_t> in_off; std::vector<InEntry> in_list;
+    if (!build_inlists(nS, off.data(), list.data(), in_off, in_list))
+        return fail(h, SOCCER_E_INVALID, "internal error: the two-player lists have an entry whose next state is not a state");
+    h->oc_lists.clear();
+    int rc = h->oc_lists.upload(h, in_off, &h->oc_in_offset);
+    if (!rc) rc = h->oc_lists.upload(h, in_list, &h->oc_in_list);
+    if (rc) { h->oc_lists.clear(); return rc; }
+    h->oc_lists.ready = true;
+    return SOCCER_OK;
+}
+
+static int occupancy_buffers(soccer_handle* h, int policies, int stride, bool values) {
+    if (policies <= h->oc_policies && stride <= h->oc_stride && (!values || h->oc_has_values)) return SOCCER_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    policies = std::max(policies, h->oc_policies); stride = std::max(stride, h->oc_stride); values = values || h->oc_has_values;
+    h->oc_bufs.clear();
+    h->oc_policies = 0; h->oc_stride = 0; h->oc_has_values = false;
+    const size_t nS = (size_t)h->mm.nS, cells = nS * (size_t)stride;
+    int rc = h->oc_bufs.alloc(h, (size_t)policies * nS * 5, &h->oc_pol);
+    if (!rc) rc = h->oc_bufs.alloc(h, (size_t)policies * nS * 5, &h->oc_polT);
+    if (!rc) rc = h->oc_bufs.alloc(h, cells, &h->oc_D[0]);
+    if (!rc) rc = h->oc_bufs.alloc(h, cells, &h->oc_D[1]);
+    if (!rc) rc = h->oc_bufs.alloc(h, (size_t)stride * (kMinimaxBatch + 1), &h->oc_words);
+    if (!rc) rc = h->oc_bufs.alloc(h, (size_t)stride, &h->oc_done);
+    if (!rc) rc = h->oc_bufs.alloc(h, (size_t)stride, &h->oc_iter);
+    if (!rc) rc = h->oc_bufs.alloc(h, (size_t)stride, &h->oc_length);
+    if (!rc) rc = h->oc_bufs.alloc(h, (size_t)stride * SOCCER_OCC_MAX_FEATURES, &h->oc_expect);
+    if (!rc) rc = h->oc_bufs.alloc(h, (size_t)SOCCER_OCC_MAX_FEATURES * nS, &h->oc_features);
+    if (!rc) rc = h->oc_bufs.alloc(h, (size_t)1, &h->oc_open);
+    if (!rc && values) rc = h->oc_bufs.alloc(h, cells, &h->oc_values);
+    if (rc) { h->oc_bufs.clear(); return rc; }
+    h->oc_policies = policies; h->oc_stride = stride; h->oc_has_values = values;
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_occupancy(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t n_b, const double* pi_b, double theta,
+                                double continue_prob, int32_t max_sweeps, int32_t pairs_per_pass, int32_t n_f, const double* features,
+                                double* length, double* expect, double* occupancy, int32_t* iterations) {
+    const char* what = "soccer_occupancy";
+    if (int rc = minimax_check(h, what, 0.0)) return rc;
+    if (!(continue_prob >= 0.0 && continue_prob <= 1.0)) return fail(h, SOCCER_E_INVALID, "continue_prob must be in [0, 1]");
+    if (n_a < 1 || n_a > SOCCER_CROSS_MAX_POLICIES || n_b < 1 || n_b > SOCCER_CROSS_MAX_POLICIES)
+        return fail(h, SOCCER_E_INVALID, "%s: the number of policies of each player must be 1 .. %d, not %d and %d", what,
+                    SOCCER_CROSS_MAX_POLICIES, n_a, n_b);
+    if (max_sweeps < 1) return fail(h, SOCCER_E_INVALID, "max_sweeps must be >= 1");
+    if (!(theta >= 0.0)) return fail(h, SOCCER_E_INVALID, "theta must be >= 0");
+    if (pairs_per_pass < 0 || pairs_per_pass % 64)
+        return fail(h, SOCCER_E_INVALID, "%s: pairs_per_pass must be 0 (the library chooses) or a positive multiple of 64, not %d", what, pairs_per_pass);
+    if (n_f < 0 || n_f > SOCCER_OCC_MAX_FEATURES)
+        return fail(h, SOCCER_E_INVALID, "%s: the number of features must be 0 .. %d, not %d", what, SOCCER_OCC_MAX_FEATURES, n_f);
+    if (n_f > 0 && !features) return fail(h, SOCCER_E_INVALID, "%s: features is NULL", what);
+    if (int rc = response_rows(h, what, "pi_a", n_a, pi_a)) return rc;
+    if (int rc = response_rows(h, what, "pi_b", n_b, pi_b)) return rc;
+    if (int rc = minimax_prepare(h)) return rc;
+    if (int rc = build_occupancy_lists(h)) return rc;
+    const int nS = h->mm.nS;
+    const int total = n_a * n_b, total64 = (total + 63) / 64 * 64;
+    const int sums = expect ? n_f : 0;                                  // the expectations that are formed
+    // the library's choice: the two D buffers of a pass, 2 * nS * pairs * 8 bytes, stay at or under 1 GiB
+    int per_pass = pairs_per_pass ? pairs_per_pass : std::max(64, (int)(((size_t)1 << 30) / ((size_t)16 * nS) / 64 * 64));
+    per_pass = std::min(per_pass, total64);
+    if (int rc = occupancy_buffers(h, n_a + n_b, per_pass, occupancy != nullptr)) return rc;
+    const int stride = h->oc_stride;                                    // (what an earlier, larger pass left: no result depends on it)
+    const size_t rows = (size_t)nS * 5;
+    double* d_x = h->oc_pol; double* d_y = h->oc_pol + (size_t)n_a * rows;
+    double* d_xT = h->oc_polT; double* d_yT = h->oc_polT + (size_t)n_a * rows;
+    if (int rc = response_upload(h, d_x, pi_a, n_a)) return rc;
+    if (int rc = response_upload(h, d_y, pi_b, n_b)) return rc;
+    for (int side = 0; side < 2; ++side) {
+        OccupancyPolicyIO pio{};
+        pio.pol = side ? d_y : d_x; pio.polT = side ? d_yT : d_xT; pio.n = side ? n_b : n_a; pio.rows = (int32_t)rows;
+        const size_t cells = rows * (size_t)pio.n;
+        hipLaunchKernelGGL(occupancy_transpose_kernel, dim3((unsigned)((cells + kCrossBlock - 1) / kCrossBlock)), dim3(kCrossBlock), 0, h->stream, pio);
+    }
+    HIP_TRY(h, hipGetLastError());
+    if (sums) HIP_TRY(h, hipMemcpyAsync(h->oc_features, features, (size_t)sums * nS * 8, hipMemcpyHostToDevice, h->stream));
+    constexpr int kWords = kMinimaxBatch + 1;
+    OccupancyIO io{};
+    io.in_offset = h->oc_in_offset; io.in_list = h->oc_in_list; io.xT = d_xT; io.yT = d_yT; io.c = continue_prob; io.theta = theta;
+    io.n_isd = h->rules.n_isd; io.mu = 1.0 / (double)h->rules.n_isd;
+    for (int i = 0; i < h->rules.n_isd; ++i) io.isd[i] = (int32_t)h->rules.isd_obs[i];
+    io.nS = nS; io.n_a = n_a; io.n_b = n_b; io.stride = stride; io.last = total - 1;
+    CrossBatchIO bio{};
+    bio.words = h->oc_words; bio.done_at = h->oc_done; bio.open = h->oc_open; bio.theta = theta; bio.stride = stride; bio.n_words = kWords;
+    OccupancyFinishIO fio{};
+    fio.D[0] = h->oc_D[0]; fio.D[1] = h->oc_D[1]; fio.done_at = h->oc_done; fio.features = h->oc_features;
+    fio.length = length ? h->oc_length : nullptr; fio.expect = h->oc_expect; fio.iterations = h->oc_iter;
+    fio.nS = nS; fio.stride = stride; fio.max_sweeps = max_sweeps; fio.n_f = sums;
+    CrossFinishIO vio{};                                                // cross_values_kernel's: D is laid out like cross-play's V
+    vio.V[0] = h->oc_D[0]; vio.V[1] = h->oc_D[1]; vio.done_at = h->oc_done; vio.values = h->oc_values;
+    vio.nS = nS; vio.stride = stride; vio.max_sweeps = max_sweeps;
+    int64_t open_total = 0;
+    for (int first = 0; first < total; first += per_pass) {
+        const int pairs = std::min(per_pass, total - first);
+        const unsigned pair_blocks = (unsigned)((pairs + kCrossBlock - 1) / kCrossBlock);
+        io.first = first; io.pairs = pairs; bio.pairs = pairs; fio.pairs = pairs; vio.pairs = pairs;
+        HIP_TRY(h, hipMemsetAsync(h->oc_D[0], 0, (size_t)nS * stride * 8, h->stream));      // D_0 = 0, and row 0 of both for good
+        HIP_TRY(h, hipMemsetAsync(h->oc_D[1], 0, (size_t)nS * stride * 8, h->stream));
+        HIP_TRY(h, hipMemsetAsync(h->oc_open, 0, sizeof(int32_t), h->stream));
+        bio.k0 = 0; bio.nb = 0;
+        hipLaunchKernelGGL(cross_batch_kernel, dim3(pair_blocks), dim3(kCrossBlock), 0, h->stream, bio);
+        const dim3 grid((unsigned)((nS + kCrossWaves - 1) / kCrossWaves), (unsigned)((pairs + 63) / 64));
+        int32_t k0 = 1, open = pairs;                                                          // k0: first sweep of the batch
+        while (k0 <= max_sweeps && open) {
+            const int nb = (int)std::min<int64_t>(kMinimaxBatch, (int64_t)max_sweeps - k0 + 1);
+            for (int j = 1; j <= nb; ++j) {
+                const int32_t k = k0 + j - 1;
+                io.D = h->oc_D[(k - 1) & 1]; io.D_out = h->oc_D[k & 1];
+                io.delta = h->oc_words + (size_t)j * stride; io.prev = h->oc_words + (size_t)(j - 1) * stride;
+                hipLaunchKernelGGL(occupancy_sweep_kernel, grid, dim3(kCrossBlock), 0, h->stream, io);
+            }
+            HIP_TRY(h, hipMemsetAsync(h->oc_open, 0, sizeof(int32_t), h->stream));
+            bio.k0 = k0; bio.nb = nb;
+            hipLaunchKernelGGL(cross_batch_kernel, dim3(pair_blocks), dim3(kCrossBlock), 0, h->stream, bio);
+            HIP_TRY(h, hipGetLastError());
+            HIP_TRY(h, hipMemcpyAsync(&open, h->oc_open, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            k0 += nb;
+        }
+        open_total += open;
+        hipLaunchKernelGGL(occupancy_finish_kernel, dim3(pair_blocks, (unsigned)(1 + sums)), dim3(kCrossBlock), 0, h->stream, fio);
+        if (occupancy) hipLaunchKernelGGL(cross_values_kernel, dim3((unsigned)((pairs + 63) / 64), (unsigned)((nS + 63) / 64)), dim3(kCrossBlock), 0, h->stream, vio);
+        HIP_TRY(h, hipGetLastError());
+        if (length) HIP_TRY(h, hipMemcpyAsync(length + first, h->oc_length, (size_t)pairs * 8, hipMemcpyDeviceToHost, h->stream));
+        if (sums) HIP_TRY(h, hipMemcpyAsync(expect + (size_t)first * sums, h->oc_expect, (size_t)pairs * sums * 8, hipMemcpyDeviceToHost, h->stream));
+        if (iterations) HIP_TRY(h, hipMemcpyAsync(iterations + first, h->oc_iter, (size_t)pairs * 4, hipMemcpyDeviceToHost, h->stream));
+        if (occupancy) HIP_TRY(h, hipMemcpyAsync(occupancy + (size_t)first * nS, h->oc_values, (size_t)pairs * nS * 8, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    if (open_total) return fail(h, SOCCER_E_STATE, "%s: %lld of %d pairs had not converged after max_sweeps = %d sweeps", what,
+                                (long long)open_total, total, max_sweeps);
+    return SOCCER_OK;
+}

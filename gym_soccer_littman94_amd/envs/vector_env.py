@@ -523,6 +523,12 @@ class VectorSoccerEnv:
         assert self.multiagent, "match_outcomes needs a two-player environment (no player with a fixed policy)"
         return self._batch.match_outcomes(pi_a, pi_b, theta, continue_prob, **params)
 
+    def occupancy(self, pi_a, pi_b, theta, continue_prob, **params):
+        """Where the game is played when two sets of mixed policies meet: the expected visits to every state, the game length
+        and the expectations of per-state features (SoccerBatch.occupancy): consumes no tick, leaves the lanes alone."""
+        assert self.multiagent, "occupancy needs a two-player environment (no player with a fixed policy)"
+        return self._batch.occupancy(pi_a, pi_b, theta, continue_prob, **params)
+
     def solve_meta_game(self, payoff, **params):
         """The maximin mixtures of zero-sum matrix games, cross_play's for instance (SoccerBatch.solve_meta_game): nothing to do
         with the pitch, so any environment will do; consumes no tick, leaves the lanes alone."""

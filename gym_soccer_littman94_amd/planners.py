@@ -293,6 +293,69 @@ def match_outcomes(env, pi_a, pi_b, theta, continue_prob, max_sweeps=1000000):
     return _two_player_batch(env, "match_outcomes").match_outcomes(pi_a, pi_b, theta, continue_prob, max_sweeps=max_sweeps)
 
 
+def occupancy(env, pi_a, pi_b, theta, continue_prob, features=None, values=False, max_sweeps=1000000):
+    """Where the game is played when two sets of mixed policies meet, exactly, on the device (include/soccer_hip.h, "state
+    occupancy"): the expected number of visits to every state from kick-off when after every step the game goes on with
+    probability continue_prob.  pi_a is [n_a, nS, 5], pi_b [n_b, nS, 5], features [n_f, nS] (pitch_features' vectors, for
+    instance).  Returns a dict: length [n_a, n_b], expect [n_a, n_b, n_f] = sum_s occupancy * features, iterations, and with
+    values=True occupancy [n_a, n_b, nS] and visit_share = occupancy / length."""
+    return _two_player_batch(env, "occupancy").occupancy(pi_a, pi_b, theta, continue_prob, features=features, values=values,
+                                                         max_sweeps=max_sweeps)
+
+
+def pitch_features(env):
+    """Per-state vectors [nS] decoded from the handle's tables, to weigh an occupancy with (occupancy's features, or a dot
+    product with its values): possession_a / possession_b (1.0 where that side has the ball), row_a, col_a, row_b, col_b (the
+    players' squares, in the coordinates of the handle's state) and ball_row / ball_col (the square of the side that has the
+    ball).  State 0, the end of the game, is 0.0 in all of them."""
+    b = getattr(env, "_batch", env)                                     # (any environment of the package, or a SoccerBatch)
+    lut = b.tables()[0].astype(np.int64)
+    W, H = b.internal_width, b.height
+    f = np.flatnonzero((lut != 0) & (lut != 0xFFFF))
+    s = lut[f]
+    p = f & 1; r = f >> 1
+    cb = r % W; r //= W; rb = r % H; r //= H; ca = r % W; ra = r // W
+    out = {}
+    for name, v in (("possession_a", p == 0), ("possession_b", p == 1), ("row_a", ra), ("col_a", ca), ("row_b", rb), ("col_b", cb),
+                    ("ball_row", np.where(p == 0, ra, rb)), ("ball_col", np.where(p == 0, ca, cb))):
+        out[name] = np.zeros(b.nS)
+        out[name][s] = v
+    return out
+
+
+def collapse_occupancies(policies, weights, D):
+    """The one Markov policy that plays like a kick-off mixture: sigma[s] = sum_k w_k D_k[s] policies[k][s] / sum_k w_k D_k[s]
+    for policies [K, nS, 5], weights [K] and the members' occupancies D [K, nS] against one opponent; uniform where the
+    denominator is 0 (the mixture never gets there).  Returns (sigma[nS, 5], the mixture's occupancy sum_k w_k D_k [nS]).
+    Sums run over ascending k in float64."""
+    policies = np.asarray(policies, np.float64); weights = np.asarray(weights, np.float64); D = np.asarray(D, np.float64)
+    K, nS = policies.shape[:2]
+    assert policies.shape == (K, nS, 5) and weights.shape == (K,) and D.shape == (K, nS)
+    den = np.zeros(nS); num = np.zeros((nS, 5))
+    for k in range(K):
+        wd = weights[k] * D[k]
+        den = den + wd
+        num = num + wd[:, None] * policies[k]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sigma = np.where(den[:, None] > 0, num / den[:, None], 0.2)
+    return sigma, den
+
+
+def collapse_mixture(env, policies, weights, player, opponent, theta, continue_prob, max_sweeps=1000000):
+    """A league as a single Markov policy, against a given opponent.  Drawing policies[k] with probability weights[k] at
+    kick-off and keeping it for the game is not the state-wise average sum_k w_k policies[k]: the members reach a state
+    with different probabilities.  Weighted by the members' occupancies D_k against `opponent` ([nS, 5]; occupancy on the
+    device) it is a Markov policy: collapse_occupancies' sigma visits every state as often as the mixture does and scores
+    what the mixture scores, against this opponent.  player 0: the policies are player A's and the opponent is B's, 1: the
+    other way round.  Returns (sigma[nS, 5], occupancy[nS])."""
+    assert player in (0, 1), "player must be 0 (the policies are player A's) or 1 (player B's)"
+    b = _two_player_batch(env, "collapse_mixture")
+    policies = np.asarray(policies, np.float64)
+    sides = (policies, opponent) if player == 0 else (opponent, policies)
+    D = b.occupancy(sides[0], sides[1], theta, continue_prob, values=True, max_sweeps=max_sweeps)["occupancy"]
+    return collapse_occupancies(policies, weights, D.reshape(policies.shape[0], -1))
+
+
 def meta_game(env, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000, max_pivots=None):
     """cross_play followed by the solve of its meta-game, both on the device (include/soccer_hip.h, "the meta-game"): which
     mixture of player A's policies can a rational mixture of player B's not beat?  Returns cross_play's dict plus

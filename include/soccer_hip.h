@@ -67,7 +67,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_* (soccer_q_population_create_league and soccer_q_population_league_* among them), soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies, soccer_cross_play, soccer_match_outcomes, soccer_solve_meta_games and soccer_rollout_shape were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_* (soccer_q_population_create_league and soccer_q_population_league_* among them), soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies, soccer_cross_play, soccer_match_outcomes, soccer_occupancy, soccer_solve_meta_games and soccer_rollout_shape were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -496,6 +496,42 @@ int soccer_cross_play(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t
 int soccer_match_outcomes(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t n_b, const double* pi_b,
                           double theta, double continue_prob, int32_t max_sweeps, int32_t pairs_per_pass,
                           double* win_a, double* win_b, double* length, double* values, int32_t* iterations);
+/* ---- state occupancy: where a game is played (two-player handles) -------------------------------------------------------
+ * The occupancy measure of every pair (x = pi_a[i], y = pi_b[j]): D[s] is the expected number of visits to state s from
+ * kick-off when after every step the game goes on with probability continue_prob = c in [0, 1], as in
+ * soccer_match_outcomes — the dual of the value, computed forwards from the start instead of backwards from the goals.
+ * The start distribution: mu[s] = 1.0 / (double)n_isd at each of the handle's initial observation indices (they are
+ * distinct), 0.0 elsewhere.  D_0 = 0.  Sweep k, for every state s':
+ *   acc = 0.0
+ *   for every in-entry e of s', in in-list order:
+ *       acc = acc + e.prob * ((x[s][a] * y[s][b]) * (c * D_{k-1}[s]))          with (s, a, b) e's source key
+ *   D_k[s'] = mu[s'] + acc
+ * in float64, nothing contracted: every product and sum is its own rounding, in exactly this association.
+ * The in-list of s' holds every entry of the two-player lists (the lists of Q above, by state and joint action a * 5 + b)
+ * whose next is s', whose done bit is clear and whose source state is not 0, ordered by ascending source key
+ * s * 25 + a * 5 + b, then by position inside that key's list; padding entries of those lists are dropped.  Each in-list
+ * is padded to a multiple of 4 entries with (prob 0.0, source key 0), which adds an exact +0.0.  Row 0 of a policy is not
+ * read and counts as zeros, and D[0] is 0.0 in every sweep.
+ * A pair stops at its first sweep k where max over s of |D_k[s] - D_{k-1}[s]| < theta and keeps that sweep's vector; every
+ * pair returns the bits and the sweep count it has when it is solved alone.  For c < 1 this always happens (sweep k moves
+ * no state by more than c^(k-1)); c == 1 is allowed and need not converge.
+ *   length[n_a][n_b]            sum over s of D[s], sequential over ascending s from 0.0: the expected number of steps
+ *   expect[n_a][n_b][n_f]       sum over s of D[s] * features[q][s], in the same order; features is HOST [n_f][n_states],
+ *                               n_f is 0 .. SOCCER_OCC_MAX_FEATURES (an indicator gives the steps spent in a set of states)
+ *   occupancy[n_a][n_b][n_states]
+ *   iterations[n_a][n_b]
+ * are HOST arrays; any of them may be NULL, and only what is asked for is formed and copied (features is not read when
+ * expect is NULL).  sum D equals soccer_match_outcomes' length, and sum D * (the pair's expected reward per state) equals
+ * soccer_cross_play's payoff with c the discount, each up to the stopping errors.  The checks, refusals, limits
+ * (SOCCER_CROSS_MAX_POLICIES) and pairs_per_pass are soccer_cross_play's, the default pass keeping the two D buffers,
+ * 2 * n_states * pairs * 8 bytes, at or under 1 GiB.  SOCCER_E_STATE when some pair has not converged after max_sweeps:
+ * iterations == max_sweeps marks those, whose outputs hold the last iterate, and the other pairs are complete.  Like the
+ * calls above this one consumes no tick, leaves the lanes alone and returns SOCCER_E_STATE during a graph capture. */
+#define SOCCER_OCC_MAX_FEATURES 16
+int soccer_occupancy(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t n_b, const double* pi_b,
+                     double theta, double continue_prob, int32_t max_sweeps, int32_t pairs_per_pass,
+                     int32_t n_f, const double* features,
+                     double* length, double* expect, double* occupancy, int32_t* iterations);
 /* ---- the meta-game: maximin mixtures of n_a x n_b zero-sum matrix games (any handle) ------------------------------------
  * Which mixture of the rows of a payoff matrix (soccer_cross_play's, or any other) can a rational opponent not beat?
  * A is HOST [n_games][n_a][n_b], the row player's (the maximiser's) payoffs.  Per game, in float64, nothing contracted
