@@ -123,6 +123,13 @@ class MetaGameResult(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("value", "x", "y", "lo", "hi", "pivots", "status")]
 
 
+class GradientPlayConfig(C.Structure):
+    """soccer_gradient_play_config"""
+    _fields_ = [("n_a", C.c_int32), ("n_b", C.c_int32), ("eta_a", C.c_double), ("eta_b", C.c_double), ("optimism", C.c_double),
+                ("discount_factor", C.c_double), ("theta", C.c_double), ("normalize", C.c_int32), ("max_sweeps", C.c_int32),
+                ("pairs_per_pass", C.c_int32), ("reserved_", C.c_int32), ("pi_a", C.c_void_p), ("pi_b", C.c_void_p)]
+
+
 class MinimaxQPopulationConfig(C.Structure):
     """soccer_minimax_q_population_config"""
     _fields_ = MinimaxQConfig._fields_ + [(n, C.c_void_p) for n in (
@@ -202,6 +209,14 @@ PROTOTYPES = {
                                         C.c_int32] + [C.c_void_p] * 5),
     "soccer_occupancy": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_int32,
                                    C.c_int32, C.c_int32] + [C.c_void_p] * 5),
+    "soccer_policy_gradient": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_int32,
+                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 10),
+    "soccer_gradient_play_create": (C.c_int, [C.c_void_p, C.POINTER(GradientPlayConfig), C.POINTER(C.c_void_p)]),
+    "soccer_gradient_play_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "soccer_gradient_play_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "soccer_gradient_play_read": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 7 + [C.POINTER(C.c_int64)]),
+    "soccer_gradient_play_load": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(C.c_int64)]),
+    "soccer_gradient_play_set_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "soccer_solve_meta_games": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                           C.POINTER(MetaGameResult)]),
     "soccer_minimax_q_create": (C.c_int, [C.c_void_p, C.POINTER(MinimaxQConfig), C.POINTER(C.c_void_p)]),

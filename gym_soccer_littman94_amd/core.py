@@ -1189,6 +1189,106 @@ class MinimaxQPopulation(_Population):
         return self
 
 
+class GradientPlay(_Learner):
+    """Gradient play on a two-player SoccerBatch (include/soccer_hip.h, "gradient play"): n_a policies of player A and n_b of
+    player B live on the device; a step solves policy_gradient's exact gradients of the resident policies against each other's
+    weighted mixture and moves every row of every policy along them, projected back onto the simplex.  Nothing is sampled: the
+    lanes are left alone and no tick is consumed.  optimism 1 is the optimistic (predictive) step g + (g - previous g)."""
+    _C = "soccer_gradient_play"
+
+    def __init__(self, batch, n_a, n_b, discount_factor, eta_a=1.0, eta_b=1.0, optimism=0.0, normalize=True, theta=1e-10,
+                 max_sweeps=1000000, pairs_per_pass=0, pi_a=None, pi_b=None):
+        nS = batch.nS
+        keep = []
+        for p, n, name in ((pi_a, n_a, "pi_a"), (pi_b, n_b, "pi_b")):
+            if p is not None:
+                p = np.ascontiguousarray(p, np.float64)
+                p = p[None] if p.ndim == 2 else p
+                assert p.shape == (n, nS, 5), "%s must be [%d, n_states, 5]" % (name, n)
+            keep.append(p)
+        cfg = _lib.GradientPlayConfig(int(n_a), int(n_b), float(eta_a), float(eta_b), float(optimism), float(discount_factor),
+                                      float(theta), int(bool(normalize)), int(max_sweeps), int(pairs_per_pass), 0,
+                                      None if keep[0] is None else keep[0].ctypes.data, None if keep[1] is None else keep[1].ctypes.data)
+        self._create(batch, cfg)
+        del keep
+        self.n_a, self.n_b, self.discount_factor, self.theta = int(n_a), int(n_b), float(discount_factor), float(theta)
+
+    def run(self, n_steps, trace=False):
+        """n_steps steps.  With trace=True returns [n_steps, n_a, n_b]: each step's payoff matrix before its update.  RuntimeError
+        if a step's solves are still open at max_sweeps: that step is not applied, steps counts the completed ones (its .results
+        holds the trace so far, the rest zeros)."""
+        b = self.batch
+        tr = np.zeros((int(n_steps), self.n_a, self.n_b)) if trace else None
+        code = b.lib.soccer_gradient_play_run(b.h, self.q, int(n_steps), tr.ctypes.data if trace else None)
+        try:
+            b._check(code)
+        except RuntimeError as e:
+            e.results = tr
+            raise
+        return tr if trace else self
+
+    def read(self):
+        """dict: pi_a[n_a, nS, 5], pi_b[n_b, nS, 5], prev_a, prev_b (the last step's gradients), w_a[n_a], w_b[n_b], payoff
+        [n_a, n_b] (the last step's, before its update) and steps."""
+        b, nS = self.batch, self.nS
+        out = {"pi_a": np.zeros((self.n_a, nS, 5)), "pi_b": np.zeros((self.n_b, nS, 5)), "prev_a": np.zeros((self.n_a, nS, 5)),
+               "prev_b": np.zeros((self.n_b, nS, 5)), "w_a": np.zeros(self.n_a), "w_b": np.zeros(self.n_b),
+               "payoff": np.zeros((self.n_a, self.n_b))}
+        st = C.c_int64()
+        b._check(b.lib.soccer_gradient_play_read(b.h, self.q, *[out[k].ctypes.data for k in
+                                                                ("pi_a", "pi_b", "prev_a", "prev_b", "w_a", "w_b", "payoff")], C.byref(st)))
+        out["steps"] = int(st.value)
+        return out
+
+    def load(self, pi_a=None, pi_b=None, prev_a=None, prev_b=None, payoff=None, steps=None, **ignored):
+        """Resume from read()'s dict (load(**learner.read())): a fresh learner continues bit for bit; the weights go through
+        weights().  None leaves a part as it is."""
+        b, nS = self.batch, self.nS
+        arrs = []
+        for p, n, name in ((pi_a, self.n_a, "pi_a"), (pi_b, self.n_b, "pi_b"), (prev_a, self.n_a, "prev_a"), (prev_b, self.n_b, "prev_b")):
+            if p is not None:
+                p = np.ascontiguousarray(p, np.float64)
+                assert p.shape == (n, nS, 5), "%s must be [%d, n_states, 5]" % (name, n)
+            arrs.append(p)
+        if payoff is not None:
+            payoff = np.ascontiguousarray(payoff, np.float64)
+            assert payoff.shape == (self.n_a, self.n_b), "payoff must be [n_a, n_b]"
+        arrs.append(payoff)
+        st = None if steps is None else C.byref(C.c_int64(int(steps)))
+        b._check(b.lib.soccer_gradient_play_load(b.h, self.q, *[None if p is None else p.ctypes.data for p in arrs], st))
+        return self
+
+    def weights(self, w_a=None, w_b=None):
+        """Sets the mixtures the policies are trained against from the next step on: w_b [n_b] weighs player A's opponents, w_a
+        [n_a] player B's; None is uniform."""
+        b = self.batch
+        wa, wb = b._weights(w_a, self.n_a, "w_a"), b._weights(w_b, self.n_b, "w_b")
+        b._check(b.lib.soccer_gradient_play_set_weights(b.h, self.q, None if wa is None else wa.ctypes.data,
+                                                        None if wb is None else wb.ctypes.data))
+        return self
+
+    def exploitability(self, theta=None):
+        """planners.exploitability of the current sets at the learner's discount: policy i of A with policy i of B (the sets
+        must be equally large, or one of them a single policy)."""
+        from . import planners
+        assert self.n_a == self.n_b or 1 in (self.n_a, self.n_b), "exploitability pairs policy i of A with policy i of B"
+        r = self.read()
+        return planners.exploitability(self.batch, r["pi_a"], r["pi_b"], self.theta if theta is None else theta, self.discount_factor)
+
+    def cross_play(self, theta=None):
+        """planners.cross_play's dict of the current sets at the learner's discount"""
+        from . import planners
+        r = self.read()
+        return planners.cross_play(self.batch, r["pi_a"], r["pi_b"], self.theta if theta is None else theta, self.discount_factor)
+
+    def meta_game(self, theta=None, max_pivots=None):
+        """planners.meta_game's dict of the current sets at the learner's discount"""
+        from . import planners
+        r = self.read()
+        return planners.meta_game(self.batch, r["pi_a"], r["pi_b"], self.theta if theta is None else theta, self.discount_factor,
+                                  max_pivots=max_pivots)
+
+
 class SoccerBatch:
     """N lanes of the Littman-94 soccer game resident on one GPU.
 
@@ -1556,6 +1656,56 @@ class SoccerBatch:
             e.results = out
             raise
         return out
+
+    def _weights(self, w, n, name):
+        if w is None:
+            return None
+        w = np.ascontiguousarray(w, np.float64)
+        assert w.shape == (n,), "%s must hold one weight per policy (%d)" % (name, n)
+        return w
+
+    def policy_gradient(self, pi_a, pi_b, theta, discount_factor, w_a=None, w_b=None, normalize=False, values=False,
+                        max_sweeps=1000000, pairs_per_pass=0):
+        """The exact policy gradients of two sets of mixed policies (include/soccer_hip.h, "exact policy gradients"): under the
+        direct parametrisation d payoff / d x[s][a] = D[s] * Q_a[s][a], D the discounted occupancy from kick-off and Q_a player
+        A's action values against the opponent's policy.  pi_a, pi_b, pairs_per_pass and the limits are cross_play's; w_b [n_b]
+        weighs the opponents of A's policies and w_a [n_a] those of B's (None: uniform).  Returns a dict:
+          payoff      [n_a, n_b] cross_play's,  iterations  [n_a, n_b, 2] the sweeps of each pair's V and D solves (int64)
+          grad_a      [n_a, nS, 5] the gradient of sum_j w_b[j] * payoff[i, j] in pi_a[i],  reach_a [n_a, nS] = sum_j w_b[j] D_ij
+          grad_b      [n_b, nS, 5] the gradient of sum_i w_a[i] * payoff[i, j] in pi_b[j] (player A's payoff: B descends it),
+                      reach_b [n_b, nS]
+          q_a, q_b    [n_a, n_b, nS, 5], V and occupancy [n_a, n_b, nS], with values=True
+        normalize=True divides every grad row by its reach (0 where the reach is 0).
+        RuntimeError if max_sweeps is reached (its .results holds the dict, iterations == max_sweeps marks the open solves)."""
+        a, _ = self._policies(pi_a, "pi_a")
+        b, _ = self._policies(pi_b, "pi_b")
+        na, nb, nS = a.shape[0], b.shape[0], self.nS
+        wa, wb = self._weights(w_a, na, "w_a"), self._weights(w_b, nb, "w_b")
+        out = {"payoff": np.zeros((na, nb)), "grad_a": np.zeros((na, nS, 5)), "grad_b": np.zeros((nb, nS, 5)),
+               "reach_a": np.zeros((na, nS)), "reach_b": np.zeros((nb, nS))}
+        if values:
+            out.update(q_a=np.zeros((na, nb, nS, 5)), q_b=np.zeros((na, nb, nS, 5)), V=np.zeros((na, nb, nS)),
+                       occupancy=np.zeros((na, nb, nS)))
+        it = np.zeros((na, nb, 2), np.int32)
+        ptr = [out[k].ctypes.data if k in out else None
+               for k in ("payoff", "grad_a", "grad_b", "reach_a", "reach_b", "q_a", "q_b", "V", "occupancy")]
+        code = self.lib.soccer_policy_gradient(self.h, na, a.ctypes.data, nb, b.ctypes.data, float(theta), float(discount_factor),
+                                               int(max_sweeps), int(pairs_per_pass), None if wa is None else wa.ctypes.data,
+                                               None if wb is None else wb.ctypes.data, int(bool(normalize)), *ptr, it.ctypes.data)
+        out["iterations"] = it.astype(np.int64)
+        try:
+            self._check(code)
+        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
+            e.results = out
+            raise
+        return out
+
+    def gradient_play(self, n_a=1, n_b=1, discount_factor=0.9, eta_a=1.0, eta_b=1.0, optimism=0.0, normalize=True, theta=1e-10,
+                      max_sweeps=1000000, pairs_per_pass=0, pi_a=None, pi_b=None):
+        """A GradientPlay on this batch (two players): n_a policies of player A and n_b of player B on the device that take
+        projected steps along policy_gradient's exact gradients of themselves."""
+        return GradientPlay(self, n_a, n_b, discount_factor, eta_a=eta_a, eta_b=eta_b, optimism=optimism, normalize=normalize,
+                            theta=theta, max_sweeps=max_sweeps, pairs_per_pass=pairs_per_pass, pi_a=pi_a, pi_b=pi_b)
 
     def solve_meta_game(self, payoff, max_pivots=None, path=0, pivots_per_sync=0):
         """The maximin mixtures of zero-sum matrix games of any shape up to 1024 a side (include/soccer_hip.h, "the meta-game"):

@@ -4,7 +4,7 @@
 //   soccer_hip.hip       create / destroy, seed / tick, reset, state, staging, one-environment calls, statistics, timers, graphs
 //   soccer_step.hip      batched_step*
 //   soccer_rollout.hip   batched_rollout*
-//   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, cross-play, match outcomes, state occupancy, the matrix-game solver
+//   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, cross-play, match outcomes, state occupancy, policy gradients and gradient play, the matrix-game solver
 //   soccer_metagame.hip  soccer_solve_meta_games: the maximin mixtures of n_a x n_b matrix games
 //   soccer_learners.hip  the seven kinds of learners on one host skeleton: minimax-Q, independent Q, WoLF-PHC, a population of each, and a
 //                        population of opponent-modelling Q-learners
@@ -238,6 +238,25 @@ struct soccer_handle {
     double* oc_values = nullptr;            // [oc_stride][nS] D of the pass in the caller's order (oc_has_values: allocated)
     int oc_policies = 0, oc_stride = 0; bool oc_has_values = false;
     OwnedBufs oc_bufs{"the occupancy solver"};
+    // soccer_policy_gradient (and soccer_gradient_play_run): a buffer family of its own, because a pass's V and D cover the
+    // same pairs at one stride, see gradient_buffers
+    double* pg_pol = nullptr;               // [pg_policies][nS][5] player A's policies, then player B's, row 0 of each zeroed
+    double* pg_polT = nullptr;              // [nS][5][n_a], then [nS][5][n_b]
+    double* pg_V[2] = {nullptr, nullptr};   // [nS][pg_stride] V double-buffered across sweeps
+    double* pg_D[2] = {nullptr, nullptr};   // [nS][pg_stride] D
+    double* pg_Q = nullptr;                 // [2][nS][5][pg_stride] Q_a, then Q_b: the ten action-value planes
+    unsigned long long* pg_words = nullptr; // [kMinimaxBatch + 1][pg_stride] the words of the solve that runs
+    int32_t* pg_done[2] = {nullptr, nullptr};   // [pg_stride] each pair's stopping sweep of the V solve, of the D solve
+    int32_t* pg_iter = nullptr;             // [pg_stride] cross_finish_kernel's sweep counts (the host forms its own from pg_done)
+    double* pg_payoff = nullptr;            // [pg_stride]
+    int32_t* pg_open = nullptr;             // the number of open pairs after a batch
+    double* pg_grad = nullptr;              // [pg_policies][nS][5] the running sums: grad_a, then grad_b
+    double* pg_reach = nullptr;             // [pg_policies][nS]
+    double* pg_w = nullptr;                 // [pg_policies] w_a, then w_b
+    double* pg_values = nullptr;            // [pg_stride][nS][5] a pass's V, D, q_a or q_b in the caller's order (pg_has_values)
+    int pg_policies = 0, pg_stride = 0; bool pg_has_values = false;
+    OwnedBufs pg_bufs{"the policy-gradient solver"};
+    std::vector<soccer_gradient_play*> gradient_players;       // soccer_gradient_play_create's, freed with the handle
     // soccer_solve_meta_games: one pass's buffers, allocated on first use and again when a pass needs more of any, see meta_buffers
     double* mg_A = nullptr;                 // [games][n_a][n_b] the caller's matrices
     double* mg_T = nullptr;                 // [games][n_a + 1][stride] the tableaux (the global path only)
@@ -301,5 +320,7 @@ static inline int flush_pending(soccer_handle* h) { return h->run.len ? flush_ru
 void comm_release(soccer_handle* h);
 // soccer_learners.hip: frees the learners the caller did not destroy (the handle's destructor; the stream has drained)
 void learners_release(soccer_handle* h);
+// soccer_planners.hip: frees the gradient-play learners the caller did not destroy (the handle's destructor; the stream has drained)
+void gradient_players_release(soccer_handle* h);
 
 #pragma GCC visibility pop

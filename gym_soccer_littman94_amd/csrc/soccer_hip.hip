@@ -50,6 +50,7 @@ soccer_handle::~soccer_handle() {
     (void)hipStreamSynchronize(stream);
     comm_release(this);
     learners_release(this);
+    gradient_players_release(this);
     bufs.clear(); plan_bufs.clear(); mm_bufs.clear(); br_bufs.clear();      // here, not as members after this body: the stream is still alive
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);

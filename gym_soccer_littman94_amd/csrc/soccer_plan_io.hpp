@@ -145,6 +145,53 @@ struct OccupancyFinishIO {
     int32_t nS, stride, pairs, max_sweeps, n_f;
 };
 
+// exact policy gradients of n_a x n_b mixed policies (soccer_policy_gradient): a pass's V is solved as cross-play's and its D
+// as the occupancy's, over the same pairs at one stride; then (action_values_kernel) one more backup from every pair's final V,
+// mixed with the other side's policy
+struct ActionValuesIO {
+    const int32_t* offset; const PlanEntry* list;   // MinimaxIO's lists
+    const double* x;                 // [n_a][nS][5] player A's policies, row 0 of each zeroed
+    const double* y;                 // [n_b][nS][5] player B's
+    const double* V[2];              // [nS][stride] each; a pair's final V is in the buffer of its own parity
+    const int32_t* done_at;          // [stride] the V solve's stopping sweeps
+    double* Qa;                      // [nS][5][stride] Q_a[s][a] = sum_b y[s][b] * q[a][b]
+    double* Qb;                      // [nS][5][stride] Q_b[s][b] = sum_a x[s][a] * q[a][b]
+    double gamma;
+    int32_t nS, n_b;
+    int32_t stride, pairs;
+    int32_t first, last;             // as CrossIO's
+    int32_t max_sweeps;
+};
+
+// gradient_reduce_kernel: a pass's pairs added to one side's running sums, in ascending order of the other side's index
+struct GradientReduceIO {
+    const double* D[2];              // [nS][stride] each; a pair's final D is in the buffer of its own parity
+    const int32_t* done_at;          // [stride] the D solve's stopping sweeps
+    const double* Q;                 // [nS][5][stride] this side's action values
+    const double* w;                 // the OTHER side's weights
+    double* grad;                    // [n_own][nS][5] the running sums, carried from pass to pass
+    double* reach;                   // [n_own][nS]
+    int32_t side;                    // 0: player A's (a row i of the matrix, summed over j), 1: player B's (a column j, over i)
+    int32_t n_a, n_b, nS;
+    int32_t stride, pairs, first, max_sweeps;
+};
+
+// gradient_normalize_kernel, after the last pass: grad[r][a] = reach[r] > 0.0 ? grad[r][a] / reach[r] : 0.0
+struct GradientNormalizeIO {
+    double* grad; const double* reach;
+    int64_t rows;                    // n_own * nS
+};
+
+// gradient_step_kernel (soccer_gradient_play_run): one projected step of every row of both players' policies
+struct GradientStepIO {
+    double* pol;                     // [n_a + n_b][nS][5] the resident policies, player A's first
+    double* prev;                    // [n_a + n_b][nS][5] the previous step's gradients
+    const double* grad;              // [n_a + n_b][nS][5] this step's
+    double eta_a, eta_b, optimism;
+    int64_t rows_a, rows;            // n_a * nS, (n_a + n_b) * nS
+    int32_t nS, first_step;
+};
+
 // a pass of n_a x n_b zero-sum matrix games (soccer_solve_meta_games): the record of a game, and what every kernel of
 // soccer_metagame_kernels.hpp is given
 constexpr int kMetaRec = 8;

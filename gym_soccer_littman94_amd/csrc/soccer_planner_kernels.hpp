@@ -1,8 +1,9 @@
-// soccer_planner_kernels.hpp — enumerate_kernel (the transition table), planner_kernel, the minimax kernels, response_sweep_kernel, the cross-play kernels, the match-outcome kernels, the occupancy kernels, games_kernel.
+// soccer_planner_kernels.hpp — enumerate_kernel (the transition table), planner_kernel, the minimax kernels, response_sweep_kernel, the cross-play kernels, the match-outcome kernels, the occupancy kernels, the policy-gradient kernels, games_kernel.
 // Included by soccer_planners.hip only: every kernel is emitted by exactly one translation unit.
 #pragma once
 #include "soccer_kernels.hpp"
 #include "soccer_plan_io.hpp"
+#include "soccer_simplex.hpp"
 
 namespace soccer {
 
@@ -717,6 +718,153 @@ __global__ __launch_bounds__(kCrossBlock) void occupancy_finish_kernel(const Occ
         for (int s = 0; s < IO.nS; ++s) sum = sum + D[(size_t)s * stride] * f[s];
         IO.expect[(size_t)p * IO.n_f + (q - 1)] = sum;
     }
+}
+
+// =================================================================================================
+// exact policy gradients of n_a x n_b mixed policies (soccer_policy_gradient), and gradient play on them
+// =================================================================================================
+// After a pass's V and D have stopped: one more backup from every pair's final V, q[a][b] = minimax_list_q's expression
+// (padding entries accumulated), mixed with the other side's policy — Q_a[s][a] = sum_b y[s][b] * q[a][b] over b = 0..4 from
+// 0.0 and Q_b[s][b] = sum_a x[s][a] * q[a][b] over a = 0..4 from 0.0.  cross_sweep_kernel's layout: a lane owns a pair, a wave
+// (state, 64 consecutive pairs), the list entries come by scalar loads, kPlanPad per wait, and an entry's V[next] of the 64
+// lanes is one contiguous 512-byte load — from the buffer of each lane's own parity, a per-lane select of the base pointer as
+// in cross_finish_kernel.  Q_a and Q_b are [nS][5][stride]: ten coalesced 512-byte stores per wave.  The loop over b is
+// unrolled so that the five Q_b accumulators are named registers; the loop over a is not.
+__device__ __forceinline__ double pair_list_q(const int32_t* offset, const PlanEntry* list, const double* Vp, size_t stride, double gamma, int key) {
+    const int end = offset[key + 1];
+    double q = 0.0;                                                     // minimax_list_q's expression
+    for (int e = offset[key]; e < end; e += kPlanPad) {
+        PlanEntry x[kPlanPad];
+        double vn[kPlanPad];
+#pragma unroll
+        for (int t = 0; t < kPlanPad; ++t) x[t] = list[e + t];
+#pragma unroll
+        for (int t = 0; t < kPlanPad; ++t) vn[t] = Vp[(size_t)(x[t].next_done & 0x7fffffff) * stride];
+#pragma unroll
+        for (int t = 0; t < kPlanPad; ++t) {
+            const double cont = (gamma * vn[t]) * (x[t].next_done < 0 ? 0.0 : 1.0);
+            q = q + x[t].prob * ((double)x[t].reward + cont);
+        }
+    }
+    return q;
+}
+
+__global__ __launch_bounds__(kCrossBlock) void action_values_kernel(const ActionValuesIO IO) {
+    const int lane = (int)(threadIdx.x & 63u);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int p = (int)blockIdx.y * 64 + lane;                          // (< stride: a multiple of 64 that is >= pairs)
+    const int s = (int)blockIdx.x * kCrossWaves + wave;                 // wave-uniform, and so is every list index below
+    if (s >= IO.nS) return;
+    const bool live = p < IO.pairs;
+    const size_t stride = (size_t)IO.stride;
+    int k = 0;
+    if (live) k = IO.done_at[p] ? IO.done_at[p] : IO.max_sweeps;
+    const double* Vp = ((k & 1) ? IO.V[1] : IO.V[0]) + p;               // (a lane past the end reads buffer 0: in bounds, not stored)
+    const int g = min(IO.first + p, IO.last);                           // (... and the last pair's rows)
+    const int i = g / IO.n_b, j = g - i * IO.n_b;
+    const double* xr = IO.x + ((size_t)i * IO.nS + s) * 5;
+    const double* yr = IO.y + ((size_t)j * IO.nS + s) * 5;
+    double yb[5], qa[5], qb[5];
+#pragma unroll
+    for (int b = 0; b < 5; ++b) { yb[b] = yr[b]; qa[b] = 0.0; qb[b] = 0.0; }
+    // Nothing is stored before the last list entry is read: a store inside the loop would let the compiler no longer prove
+    // the lists unchanged, and it would fetch the entries by vector loads at a uniform address instead of scalar loads.
+#pragma unroll 1
+    for (int a = 0; a < 5; ++a) {
+        const double xa = xr[a];
+        double inner = 0.0;
+#pragma unroll
+        for (int b = 0; b < 5; ++b) {
+            const double q = pair_list_q(IO.offset, IO.list, Vp, stride, IO.gamma, s * 25 + a * 5 + b);
+            inner = inner + yb[b] * q;
+            qb[b] = qb[b] + xa * q;
+        }
+#pragma unroll
+        for (int c = 0; c < 5; ++c) qa[c] = c == a ? inner : qa[c];     // (a is wave-uniform: five selects, no indexed array)
+    }
+    if (live) {
+#pragma unroll
+        for (int c = 0; c < 5; ++c) IO.Qa[((size_t)s * 5 + c) * stride + p] = qa[c];
+#pragma unroll
+        for (int b = 0; b < 5; ++b) IO.Qb[((size_t)s * 5 + b) * stride + p] = qb[b];
+    }
+}
+
+// a thread per (policy of this side, state): the pass's pairs of that policy's row (player A) or column (player B) of the
+// matrix, in ascending order of the other side's index, added to the running reach and grad — reach = reach + w * D[s] and
+// grad[a] = grad[a] + w * (D[s] * Q[s][a]).  The running values start as 0.0 (the host clears them once per call) and are
+// carried from pass to pass, so a row that spans passes is one sequential sum.
+__global__ __launch_bounds__(kCrossBlock) void gradient_reduce_kernel(const GradientReduceIO IO) {
+    const size_t t = (size_t)blockIdx.x * kCrossBlock + threadIdx.x;
+    const int n_own = IO.side ? IO.n_b : IO.n_a;
+    if (t >= (size_t)n_own * (size_t)IO.nS) return;
+    const int s = (int)(t / (size_t)n_own), own = (int)(t - (size_t)s * (size_t)n_own);
+    // the other side's indices lo .. hi - 1 whose pair with `own` lies in this pass: matrix index g0 + o * step
+    const long long first = IO.first, end = first + IO.pairs, nb = IO.n_b;
+    long long g0, step, lo, hi;
+    if (IO.side == 0) {
+        g0 = (long long)own * nb; step = 1;
+        lo = max(0ll, first - g0); hi = min(nb, end - g0);
+    } else {
+        g0 = own; step = nb;
+        lo = first > g0 ? (first - g0 + nb - 1) / nb : 0ll;
+        hi = end > g0 ? min((long long)IO.n_a, (end - 1 - g0) / nb + 1) : 0ll;
+    }
+    if (hi <= lo) return;
+    const size_t stride = (size_t)IO.stride;
+    double* gr = IO.grad + ((size_t)own * IO.nS + s) * 5;
+    double* re = IO.reach + (size_t)own * IO.nS + s;
+    double r = *re, g[5];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) g[a] = gr[a];
+    for (long long o = lo; o < hi; ++o) {
+        const size_t p = (size_t)(g0 + o * step - first);
+        const int k = IO.done_at[p] ? IO.done_at[p] : IO.max_sweeps;
+        const double d = IO.D[k & 1][(size_t)s * stride + p];
+        const double w = IO.w[o];
+        r = r + w * d;
+#pragma unroll
+        for (int a = 0; a < 5; ++a) g[a] = g[a] + w * (d * IO.Q[((size_t)s * 5 + a) * stride + p]);
+    }
+    *re = r;
+#pragma unroll
+    for (int a = 0; a < 5; ++a) gr[a] = g[a];
+}
+
+__global__ __launch_bounds__(kCrossBlock) void gradient_normalize_kernel(const GradientNormalizeIO IO) {
+    const size_t t = (size_t)blockIdx.x * kCrossBlock + threadIdx.x;
+    if (t >= (size_t)IO.rows) return;
+    const double r = IO.reach[t];
+    double* g = IO.grad + t * 5;
+#pragma unroll
+    for (int a = 0; a < 5; ++a) g[a] = r > 0.0 ? g[a] / r : 0.0;
+}
+
+// a thread per row (policy, state) of both players: prev = g at the first step; d = g + optimism * (g - prev); prev = g; for
+// every state but 0 the row becomes P(row + eta_a * d) (player A) or P(row - eta_b * d) (player B), P the projection of
+// soccer_simplex.hpp.  Row 0 of a policy is never touched, and neither is any row of a side whose eta is 0.0.
+__global__ __launch_bounds__(kCrossBlock) void gradient_step_kernel(const GradientStepIO IO) {
+    const size_t t = (size_t)blockIdx.x * kCrossBlock + threadIdx.x;
+    if (t >= (size_t)IO.rows) return;
+    const bool is_a = t < (size_t)IO.rows_a;
+    const size_t local = is_a ? t : t - (size_t)IO.rows_a;
+    const bool row0 = local % (size_t)IO.nS == 0;
+    const double* g = IO.grad + t * 5;
+    double* pv = IO.prev + t * 5;
+    double* pol = IO.pol + t * 5;
+    double v[5], out[5];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) {
+        const double ga = g[a];
+        const double before = IO.first_step ? ga : pv[a];
+        const double d = ga + IO.optimism * (ga - before);
+        pv[a] = ga;
+        v[a] = is_a ? pol[a] + IO.eta_a * d : pol[a] - IO.eta_b * d;
+    }
+    if (row0 || (is_a ? IO.eta_a : IO.eta_b) == 0.0) return;            // a side whose step is 0 is held fixed to the bit, not re-projected
+    project_simplex5(v, out);
+#pragma unroll
+    for (int a = 0; a < 5; ++a) pol[a] = out[a];
 }
 
 // the two-player lists assembled on the device from enumerate_kernel's output (build_minimax): a thread per (state, joint

@@ -529,6 +529,18 @@ class VectorSoccerEnv:
         assert self.multiagent, "occupancy needs a two-player environment (no player with a fixed policy)"
         return self._batch.occupancy(pi_a, pi_b, theta, continue_prob, **params)
 
+    def policy_gradient(self, pi_a, pi_b, theta, discount_factor, **params):
+        """The exact policy gradients of two sets of mixed policies against each other's weighted mixture
+        (SoccerBatch.policy_gradient): consumes no tick, leaves the lanes alone."""
+        assert self.multiagent, "policy_gradient needs a two-player environment (no player with a fixed policy)"
+        return self._batch.policy_gradient(pi_a, pi_b, theta, discount_factor, **params)
+
+    def gradient_play(self, **params):
+        """A GradientPlay (SoccerBatch.gradient_play): policies on the device that follow their exact gradients; it samples
+        nothing, consumes no tick and leaves the lanes alone."""
+        assert self.multiagent, "gradient_play needs a two-player environment (no player with a fixed policy)"
+        return self._batch.gradient_play(**params)
+
     def solve_meta_game(self, payoff, **params):
         """The maximin mixtures of zero-sum matrix games, cross_play's for instance (SoccerBatch.solve_meta_game): nothing to do
         with the pitch, so any environment will do; consumes no tick, leaves the lanes alone."""

@@ -303,6 +303,34 @@ def occupancy(env, pi_a, pi_b, theta, continue_prob, features=None, values=False
                                                          max_sweeps=max_sweeps)
 
 
+def policy_gradient(env, pi_a, pi_b, theta, discount_factor, w_a=None, w_b=None, normalize=False, values=False, max_sweeps=1000000):
+    """The exact policy gradients of two sets of mixed policies, on the device (include/soccer_hip.h, "exact policy
+    gradients"): grad_a[i] is the gradient of sum_j w_b[j] * payoff(pi_a[i], pi_b[j]) in pi_a[i] under the direct
+    parametrisation, occupancy times action value, and grad_b[j] that of sum_i w_a[i] * payoff(pi_a[i], pi_b[j]) in pi_b[j]
+    (player A's payoff: B descends it).  Returns SoccerBatch.policy_gradient's dict."""
+    return _two_player_batch(env, "policy_gradient").policy_gradient(pi_a, pi_b, theta, discount_factor, w_a=w_a, w_b=w_b,
+                                                                     normalize=normalize, values=values, max_sweeps=max_sweeps)
+
+
+def gradient_play(env, n_steps, discount_factor, n_a=1, n_b=1, eta_a=1.0, eta_b=1.0, optimism=0.0, normalize=True, theta=1e-10,
+                  max_sweeps=1000000, pi_a=None, pi_b=None, w_a=None, w_b=None):
+    """n_steps of gradient play on the device from pi_a / pi_b (None: uniform): every policy follows the exact gradient of its
+    payoff against the other side's weighted mixture, projected onto the simplex row by row.  Returns read()'s dict (pi_a, pi_b,
+    prev_a, prev_b, w_a, w_b, payoff, steps) plus trace [n_steps, n_a, n_b], each step's payoff matrix before its update."""
+    g = _two_player_batch(env, "gradient_play").gradient_play(n_a=n_a, n_b=n_b, discount_factor=discount_factor, eta_a=eta_a, eta_b=eta_b,
+                                                              optimism=optimism, normalize=normalize, theta=theta,
+                                                              max_sweeps=max_sweeps, pi_a=pi_a, pi_b=pi_b)
+    try:
+        if w_a is not None or w_b is not None:
+            g.weights(w_a, w_b)
+        trace = g.run(n_steps, trace=True)
+        out = g.read()
+    finally:
+        g.close()
+    out["trace"] = trace
+    return out
+
+
 def pitch_features(env):
     """Per-state vectors [nS] decoded from the handle's tables, to weigh an occupancy with (occupancy's features, or a dot
     product with its values): possession_a / possession_b (1.0 where that side has the ball), row_a, col_a, row_b, col_b (the

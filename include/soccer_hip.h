@@ -67,7 +67,7 @@ extern "C" {
 #define SOCCER_ABI_VERSION 3      /* 2: soccer_step_args grew reward_a_f32 / reward_b_f32 / finished
                                      3: the bits -> uniform convention above (half-step offset; eight ticks per block at slip_prob == 0)
                                      (still 3: soccer_trajectory_returns, soccer_comm_*, batched_rollout_ex, soccer_solve_matrix_games,
-                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_* (soccer_q_population_create_league and soccer_q_population_league_* among them), soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies, soccer_cross_play, soccer_match_outcomes, soccer_occupancy, soccer_solve_meta_games and soccer_rollout_shape were ADDED, captured sequences may hold an odd
+                                     soccer_minimax_backup, soccer_minimax_value_iteration, soccer_minimax_q_*, soccer_q_learner_*, soccer_wolf_phc_*, soccer_q_population_* (soccer_q_population_create_league and soccer_q_population_league_* among them), soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_best_response, soccer_evaluate_policies, soccer_cross_play, soccer_match_outcomes, soccer_occupancy, soccer_policy_gradient, soccer_gradient_play_*, soccer_solve_meta_games and soccer_rollout_shape were ADDED, captured sequences may hold an odd
                                      number of calls, and a caller's u >= 1 on a slip list follows the reference's comparison — nothing a
                                      round-3 caller relied on changed, and checkpoints record this number for the RNG convention alone) */
 
@@ -532,6 +532,83 @@ int soccer_occupancy(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t 
                      double theta, double continue_prob, int32_t max_sweeps, int32_t pairs_per_pass,
                      int32_t n_f, const double* features,
                      double* length, double* expect, double* occupancy, int32_t* iterations);
+/* ---- exact policy gradients of policy pairs, and gradient play on them (two-player handles) -----------------------------
+ * Under the direct parametrisation, with gamma = discount_factor and D the gamma-discounted occupancy from kick-off,
+ *   d payoff(x, y) / d x[s][a] = D[s] * Q_a[s][a],   Q_a[s][a] = sum_b y[s][b] * Q[s][a][b]
+ * and player B's has the same form with Q_b[s][b] = sum_a x[s][a] * Q[s][a][b].  All arithmetic is float64, nothing is
+ * contracted, and every product and sum is its own rounding in the association written.
+ * Per pair (i, j), with x = pi_a[i] and y = pi_b[j]:
+ *   V is exactly soccer_cross_play's vector for the pair: V_0 = 0, with its own stopping sweep k_V.
+ *   D is exactly soccer_occupancy's vector with continue_prob = discount_factor, with its own stopping sweep k_D.
+ *   One more backup from the pair's final V follows: q[a][b] is the list sum of "Q above", which is the expression of
+ *   soccer_minimax_value_iteration's Q with padding entries accumulated.
+ *   Q_a[s][a] = sum_b y[s][b] * q[a][b], for b = 0..4 from 0.0.
+ *   Q_b[s][b] = sum_a x[s][a] * q[a][b], for a = 0..4 from 0.0.
+ *   Row 0 of a policy counts as zeros, so both are 0 at state 0.
+ *   payoff is cross-play's kick-off mean of V.
+ * Per policy:
+ *   Weights: w_b is HOST [n_b], w_a is HOST [n_a].  NULL means every weight is 1.0 / (double)n.
+ *   reach_a[i][s] = sum_j w_b[j] * D_ij[s], sequential over ascending j from 0.0.
+ *   grad_a[i][s][a] = sum_j w_b[j] * (D_ij[s] * Q_a,ij[s][a]), in the same order.
+ *   reach_b[j][s] and grad_b[j][s][b] sum over ascending i with w_a[i].
+ *   With normalize != 0: grad_a[i][s][a] = reach_a[i][s] > 0.0 ? grad_a[i][s][a] / reach_a[i][s] : 0.0, and likewise for B.
+ *   grad_b is the gradient of player A's payoff, so B descends it.
+ * grad_a[i] is the exact gradient of sum_j w_b[j] * payoff(pi_a[i], pi_b[j]), player A's payoff against a kick-off mixture
+ * of opponents (up to the stopping errors of the solves), which no Markov policy of the opponent reproduces.
+ * Outputs, all HOST arrays; any may be NULL, and only what is asked for is formed and copied:
+ *   payoff[n_a][n_b]   grad_a[n_a][n_states][5]   grad_b[n_b][n_states][5]   reach_a[n_a][n_states]   reach_b[n_b][n_states]
+ *   q_a, q_b [n_a][n_b][n_states][5]   V, occupancy [n_a][n_b][n_states]   iterations[n_a][n_b][2] holding (k_V, k_D)
+ * The checks, limits (SOCCER_CROSS_MAX_POLICIES), pairs_per_pass and refusals are soccer_cross_play's.  Weights must be
+ * finite, >= 0 and not all zero.  The default pass keeps this call's buffers at or under 1 GiB: two V, two D and the ten
+ * action-value planes, 14 * n_states * pairs * 8 bytes.  SOCCER_E_STATE when some pair has an open V or D solve after
+ * max_sweeps: those pairs hold the last iterates, and what was formed from them (iterations == max_sweeps marks the open
+ * solve).  Every pair and every policy returns the bits it has when solved alone: no result depends on the passes, on
+ * earlier calls or on which outputs are asked for.  A row or column of the matrix that spans passes keeps the one sequential
+ * order: the running sums are carried from pass to pass.  Like the calls above this one consumes no tick, leaves the lanes
+ * alone and returns SOCCER_E_STATE during a graph capture. */
+int soccer_policy_gradient(soccer_handle* h, int32_t n_a, const double* pi_a, int32_t n_b, const double* pi_b,
+                           double theta, double discount_factor, int32_t max_sweeps, int32_t pairs_per_pass,
+                           const double* w_a, const double* w_b, int32_t normalize,
+                           double* payoff, double* grad_a, double* grad_b, double* reach_a, double* reach_b,
+                           double* q_a, double* q_b, double* V, double* occupancy, int32_t* iterations);
+/* Gradient play: n_a policies of player A and n_b of player B live on the device and take projected gradient steps against
+ * each other's weighted mixture.  Resident state: x[n_a][n_states][5], y[n_b][n_states][5], the previous step's gradients
+ * prev_a and prev_b, steps, the weights (uniform until soccer_gradient_play_set_weights; NULL there is uniform again) and the
+ * last completed step's payoff matrix.  One step of soccer_gradient_play_run:
+ *   g_a and g_b are exactly soccer_policy_gradient's grad_a and grad_b on the resident policies, with the resident weights
+ *   and the config's normalize, discount_factor, theta, max_sweeps and pairs_per_pass; no policy leaves the device.
+ *   At steps == 0, prev = g.  The direction is d = g + optimism * (g - prev).  Then prev = g.
+ *   For every s >= 1: x[s] = P(x[s][a] + eta_a * d_a[s][a]) and y[s] = P(y[s][b] - eta_b * d_b[s][b]).  Row 0 is never touched.
+ *   A side whose eta is 0.0 is held fixed: none of its rows is written (P of a row whose sum is not exactly 1.0 would move it
+ *   by ulps), only its prev follows g.
+ * P is the projection onto the simplex of five: u is v sorted in descending order; css is the running sum of u from 0.0;
+ * for k = 1..5, t = (css_k - 1.0) / (double)k, and tau = t at k = 1 and whenever u_k - t > 0.0; out[a] = v[a] - tau where that
+ * is > 0.0, else 0.0 (csrc/soccer_simplex.hpp, a plain header a host program can run).
+ * trace is HOST [n_steps][n_a][n_b] or NULL: each completed step's payoff matrix before its update.  A step whose solves are
+ * still open at max_sweeps is not applied: run returns SOCCER_E_STATE, and steps counts the completed steps.
+ * The config: n_a, n_b as soccer_policy_gradient's; eta_a, eta_b finite and >= 0; optimism in [0, 1]; pi_a / pi_b HOST
+ * [n][n_states][5] checked like soccer_cross_play's, NULL means uniform.  run(T) leaves the bits that T rounds of
+ * soccer_policy_gradient on what _read returns, followed by the update above, leave.  A learner is owned by the handle and
+ * freed with it; its calls consume no tick and return SOCCER_E_STATE during a graph capture.  _read: any output may be NULL;
+ * _load: NULL leaves that part as it is, and the policies are checked like the config's; with everything _read returns but
+ * the weights, a fresh learner continues bit for bit. */
+typedef struct soccer_gradient_play soccer_gradient_play;
+typedef struct soccer_gradient_play_config {
+    int32_t n_a, n_b;
+    double eta_a, eta_b, optimism;
+    double discount_factor, theta;
+    int32_t normalize, max_sweeps, pairs_per_pass, reserved_;
+    const double* pi_a;
+    const double* pi_b;
+} soccer_gradient_play_config;
+int soccer_gradient_play_create(soccer_handle* h, const soccer_gradient_play_config* cfg, soccer_gradient_play** out);
+int soccer_gradient_play_destroy(soccer_handle* h, soccer_gradient_play* g);
+int soccer_gradient_play_run(soccer_handle* h, soccer_gradient_play* g, int32_t n_steps, double* trace);
+int soccer_gradient_play_read(soccer_handle* h, soccer_gradient_play* g, double* pi_a, double* pi_b, double* prev_a, double* prev_b,
+                              double* w_a, double* w_b, double* payoff, int64_t* steps);
+int soccer_gradient_play_load(soccer_handle* h, soccer_gradient_play* g, const double* pi_a, const double* pi_b,
+                              const double* prev_a, const double* prev_b, const double* payoff, const int64_t* steps);
+int soccer_gradient_play_set_weights(soccer_handle* h, soccer_gradient_play* g, const double* w_a, const double* w_b);
 /* ---- the meta-game: maximin mixtures of n_a x n_b zero-sum matrix games (any handle) ------------------------------------
  * Which mixture of the rows of a payoff matrix (soccer_cross_play's, or any other) can a rational opponent not beat?
  * A is HOST [n_games][n_a][n_b], the row player's (the maximiser's) payoffs.  Per game, in float64, nothing contracted
