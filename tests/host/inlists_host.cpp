@@ -16,7 +16,7 @@ int main(int argc, char** argv) {
     std::FILE* f = std::fopen(argv[1], "r");
     if (!f) return 1;
     long long nS = 0, n = 0;
-    if (std::fscanf(f, "%lld %lld", &nS, &n) != 2 || nS < 1 || nS > 4096 || n < 0 || n > (1 << 22)) { std::fclose(f); return 1; }
+    if (std::fscanf(f, "%lld %lld", &nS, &n) != 2 || nS < 1 || nS > 65535 || n < 0 || n > (1 << 22)) { std::fclose(f); return 1; }
     std::vector<int32_t> offset((size_t)nS * 25 + 1);
     for (int32_t& o : offset) {
         long long v;

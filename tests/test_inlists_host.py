@@ -1,6 +1,7 @@
 """CPU: the in-list builder of soccer_occupancy (csrc/soccer_inlists.hpp) run by a stand-alone host program
 (tests/host/inlists_host.cpp, built with AddressSanitizer and UndefinedBehaviorSanitizer) on a small hand-made out-list and on
-the oracle's 5x4 lists, against tests/occupancy_np.py's in_lists integer for integer: entries that end the game, padding and
+the oracle's lists of 5x4, and of 6x5, 7x5 at slip 1 and 8x7 without slip — the three shapes the in-lists take, 344, 152 and 40
+entries at the longest — against tests/occupancy_np.py's in_lists integer for integer: entries that end the game, padding and
 source state 0 are dropped, the rest stand by ascending source key and then by position, every in-list padded to four."""
 import os
 import subprocess
@@ -98,8 +99,9 @@ def test_a_next_state_past_the_end_is_refused(host, tmp_path):
     assert run(host, tmp_path, nS, offset, prob, nd)[0] == 2
 
 
-def test_the_oracle_s_lists(host, tmp_path):
-    Pp, Pn, Pr, Pd = shapley_lists(Oracle(5, 4, 0.2, n=1, seed=0))
+def oracle_lists_through_the_program(host, tmp_path, w, h, slip):
+    """the program's in-lists of the oracle's lists against numpy's, integer for integer: (in_offset, in_key, the out-lists)"""
+    Pp, Pn, Pr, Pd = shapley_lists(Oracle(w, h, slip, n=1, seed=0))
     nS, _, K = Pp.shape
     # CSR with the padded arrays' rows as they are: padding is (prob 0, next 0, done)
     offset = np.arange(nS * 25 + 1) * K
@@ -109,7 +111,23 @@ def test_the_oracle_s_lists(host, tmp_path):
     assert status == 0 and off.tolist() == w_off.tolist()
     assert np.array_equal(pb, w_prob.view(np.uint64)) and np.array_equal(key, w_key) and (pad == 0).all()
     size = np.diff(off)
-    print("5x4 at slip 0.2: %d in-entries with padding, in-lists of %d .. %d" % (off[-1], size.min(), size.max()))
+    print("%dx%d at slip %.1f: K %d, %d in-entries with padding, in-lists of %d .. %d" % (w, h, slip, K, off[-1], size.min(), size.max()))
     assert (size % 4 == 0).all() and size[0] == 0 and (key[pb == 0] >= 0).all() and off[-1] == w_prob.size
     live = key[key != 0]
     assert (live >= 25).all() and live.size == int(((Pd != 0) & (np.arange(nS)[:, None, None] != 0)).sum())
+    return off, key, (Pp, Pn, Pr, Pd)
+
+
+def test_the_oracle_s_lists(host, tmp_path):
+    oracle_lists_through_the_program(host, tmp_path, 5, 4, 0.2)
+
+
+@pytest.mark.parametrize("w,h,slip,longest,K", [(6, 5, 0.2, 344, 15), (7, 5, 1.0, 152, 7), (8, 7, 0.0, 40, 4)], ids=["6x5", "7x5_slip1", "8x7_slip0"])
+def test_the_oracle_s_lists_of_the_other_in_list_shapes(host, tmp_path, w, h, slip, longest, K):
+    """an ordinary slip on an even width, slip 1 (every move may go astray: fewer distinct outcomes a key, K = 7) and no slip on a
+    large pitch (K = 4: in-lists of 40 at the longest)"""
+    off, key, lists = oracle_lists_through_the_program(host, tmp_path, w, h, slip)
+    assert int(np.diff(off).max()) == longest and lists[0].shape[2] == K
+    # every state but 0 is reached from somewhere, and the longest in-list is no outlier of one state
+    size = np.diff(off)
+    assert (size[1:] > 0).all() and (size == longest).sum() > 1
