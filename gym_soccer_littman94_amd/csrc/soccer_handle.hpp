@@ -157,8 +157,6 @@ struct soccer_handle {
     bool graph_fuse = true;                 // SOCCER_GRAPH_FUSE=0 (A/B runs): every captured step is a launch of its own
     int capture_kernels = 0;                // kernel nodes the batched_* calls of this capture recorded (note_kernel)
     int64_t capture_steps_fused = 0; int capture_fused_launches = 0;
-    unsigned long long* d_hist_unread = nullptr;   // as large as d_hist and never read: where a fused run of a handle without
-                                            // SOCCER_F_STEP_STATS lets rollout_swar_kernel count its episodes
     int n_cu = 256;
     size_t lds_limit = 64 * 1024;           // hipDeviceProp_t::sharedMemPerBlockOptin: what a workgroup may be given (160 KB on gfx950)
     uint4* d_sub = nullptr;                 // integer slip thresholds (KernelParams::sub)

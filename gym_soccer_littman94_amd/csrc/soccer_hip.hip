@@ -133,9 +133,6 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
     while (h->hist_slots < (n + 255) / 256) h->hist_slots <<= 1;
     if (int rc = h->bufs.alloc(nullptr, h->hist_slots * kHistStride, &h->d_hist)) return rc;
     HIP_TRY(nullptr, hipMemset(h->d_hist, 0, sizeof(unsigned long long) * h->hist_slots * kHistStride));
-    // its twin for the fused runs of a capture when the handle counts no step statistics (flush_run): written, never read
-    if (int rc = h->bufs.alloc(nullptr, h->hist_slots * kHistStride, &h->d_hist_unread)) return rc;
-    HIP_TRY(nullptr, hipMemset(h->d_hist_unread, 0, sizeof(unsigned long long) * h->hist_slots * kHistStride));
     if (int rc = h->bufs.alloc_pinned(nullptr, kMappedBytes / sizeof(unsigned int), OwnedBufs::kPinnedMapped, &h->misuse_host)) return rc;
     std::memset(h->misuse_host, 0, kMappedBytes);
     HIP_TRY(nullptr, hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_misuse), h->misuse_host, 0));

@@ -94,11 +94,15 @@ extern "C" int batched_rollout_ex(soccer_handle* h, const soccer_rollout_args* a
     return rollout_enqueue(h, a, x, h->P.hist);
 }
 
+// hist == nullptr: nobody reads this rollout's episode statistics (flush_run on a handle without step statistics) — the
+// byte-parallel kernel then takes its shape that does not count; only a run that step_can_fuse admits may ask for it
 int rollout_enqueue(soccer_handle* h, const soccer_rollout_args* a, const soccer_rollout_extra* x, unsigned long long* hist) {
     uint16_t* x_fin = x ? x->final_obs : nullptr; uint8_t* x_code = x ? x->prob_code : nullptr;
     int E = h->E;
     while (E > 1 && !rollout_vec_ok(a, x, E)) E = E == 4 ? 1 : E / 2;
     const bool swar_roll = rollout_takes_swar(h, a, x);
+    if (!hist && (!swar_roll || (h->P.n & 3ull) || a->sample_actions || h->P.policy_a || h->P.policy_b || x_fin || x_code))
+        return fail(h, SOCCER_E_STATE, "rollout without statistics: not the shape of a fused run of captured steps");
     // one launch covers at most kChunk steps (per-thread episode counters are 16 bit wide); the tick
     // sequence of consecutive launches is contiguous, so chunking does not change any result
     constexpr int kChunk = 4096;
@@ -163,8 +167,11 @@ int rollout_enqueue(soccer_handle* h, const soccer_rollout_args* a, const soccer
             uint64_t blocks = (groups + kBlock - 1) / kBlock;
             if (blocks > (uint64_t)h->grid_cap) blocks = h->grid_cap;
             const dim3 g((unsigned)blocks), bl(kBlock);
-#define LAUNCH_F(DV, SV, GV, FV) do { if (smem > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_swar_kernel<DV, SV, GV, FV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-                                      hipLaunchKernelGGL((rollout_swar_kernel<DV, SV, GV, FV>), g, bl, smem, h->stream, RS, io); } while (0)
+#define LAUNCH_T(DV, SV, GV, FV, TV) do { if (smem > 48 * 1024) HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_swar_kernel<DV, SV, GV, FV, TV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
+                                          hipLaunchKernelGGL((rollout_swar_kernel<DV, SV, GV, FV, TV>), g, bl, smem, h->stream, RS, io); } while (0)
+            // (the shape without statistics exists for streamed actions and the plain result streams only: checked on entry)
+#define LAUNCH_F(DV, SV, GV, FV) do { if constexpr (kUnreadShape<DV, FV>) { if (!hist) LAUNCH_T(DV, SV, GV, FV, false); else LAUNCH_T(DV, SV, GV, FV, true); } \
+                                      else LAUNCH_T(DV, SV, GV, FV, true); } while (0)
 #define LAUNCH_G(DV, SV, GV) do { if (io.final_obs || io.prob_code) LAUNCH_F(DV, SV, GV, true); else LAUNCH_F(DV, SV, GV, false); } while (0)
 #define LAUNCH_S(DV, SV) do { if (h->swar_c.small) LAUNCH_G(DV, SV, 1); else LAUNCH_G(DV, SV, 0); } while (0)
             // the action source as a compile-time shape (rollout_swar_group): streams / sampled uniformly / both sides from
@@ -182,6 +189,7 @@ int rollout_enqueue(soccer_handle* h, const soccer_rollout_args* a, const soccer
 #undef LAUNCH_S
 #undef LAUNCH_G
 #undef LAUNCH_F
+#undef LAUNCH_T
             }
             if (n4 < n_all) {
                 KernelParams Q = h->P;

@@ -165,6 +165,15 @@ __device__ __forceinline__ uint32_t count8_le15(uint32_t hs, uint32_t tx, uint32
 __device__ __forceinline__ uint32_t draw_a15(uint32_t wm) { return swar::perm(0u, wm, 0x01000100u); }
 __device__ __forceinline__ uint32_t draw_b15(uint32_t wm) { return swar::perm(0u, wm, 0x03020302u); }
 
+// the shapes a fused run of captured steps can take (step_can_fuse): streamed actions, the four plain result streams
+template <int DYNM, bool FULL> constexpr bool kUnreadShape = DYNM == 0 && !FULL;
+// which instantiations hold one half of each small-pitch byte table in a vector register across the step loop: the steady
+// state of the table geometry, except the three kernels whom the five registers cost a wave of occupancy (uniformly sampled
+// actions at slip 0: 7 -> 6; a fixed policy against a streamed side with the one-by-one slip selection and FULL: 5 -> 4)
+template <int DYNM, int SLIPM, bool GENERAL, int GEO, bool FULL, bool STATS>
+constexpr bool kHoistTables = GEO == 1 && !GENERAL && !(DYNM == 1 && SLIPM == 0 && !FULL) &&
+                              !((DYNM == 4 || DYNM == 5) && SLIPM == 1 && FULL);
+
 // the T steps of one thread's four lanes.  GENERAL = false: no lane is frozen or in a goal tuple on entry and the handle
 // auto-resets, so none ever will be (the steady state): the step's code for those cases is compiled out.
 // DYNM — where the actions come from: 0 both from the action streams; 1 both sampled uniformly in the kernel; 2 both
@@ -176,7 +185,9 @@ __device__ __forceinline__ uint32_t draw_b15(uint32_t wm) { return swar::perm(0u
 // Randomness (include/soccer_hip.h): with SLIP one step/reset block per tick; without, one block per EIGHT ticks — the
 // thread keeps it transposed (swar::transpose4) in p0..p3, p0 serving the current pair of ticks — which takes the Philox
 // rounds from ~45 to ~6 vector instructions per step; sampled actions take the lane's word of the tick's purpose-1 block.
-template <int DYNM, int SLIPM, bool GENERAL, int GEO, bool FULL = false>
+// STATS = false (a fused captured run of a handle without step statistics): nothing reads the episode counts, so the step
+// does not make them.
+template <int DYNM, int SLIPM, bool GENERAL, int GEO, bool FULL = false, bool STATS = true>
 __device__ __forceinline__ void rollout_swar_group(const RolloutSwar& R, const RolloutIO& IO, const SlipSrc& slip,
                                                    const uint2* mix_a_in, const uint2* mix_b_in, const int8_t* pol_a_in, const int8_t* pol_b_in,
                                                    uint32_t* act_lds,
@@ -242,7 +253,17 @@ __device__ __forceinline__ void rollout_swar_group(const RolloutSwar& R, const R
         const uint32_t cc0 = swar::bfi(swar::mask_of(S.ps << 7), S.cb, S.ca);
         swar::obs4<true>(R.C, S.ra, S.ca, S.rb, S.cb, S.ps & swar::K01, swar::is_zero(cc0) | swar::is_zero(cc0 ^ R.C.Wm1x4), s_lo, s_hi);
     }
-    const swar::Consts& C = R.C;
+    // The byte tables of the small-pitch geometry take two dwords each and v_perm_b32 one scalar operand: the other half would
+    // be moved into a vector register in front of its lookup, every step.  The steady state holds that half in a vector
+    // register across the loop instead (opaque, else the optimiser sinks the move back to its use).
+    swar::Consts Cv = R.C;
+    if (kHoistTables<DYNM, SLIPM, GENERAL, GEO, FULL, STATS>) {
+        asm volatile("" : "+v"(Cv.row_lo), "+v"(Cv.col_lo), "+v"(Cv.grow_lo), "+v"(Cv.rew_lo), "+v"(Cv.term_lo));
+    }
+    const swar::Consts& C = Cv;
+    // the steady state carries its state in step form (swar::Carry4) from step to step
+    swar::Carry4 K{};
+    if (!GENERAL) K = swar::carry_of(C, S);
     const unsigned long long q = (R.lane_offset + i0) >> 2;
     uint32_t fin_loc = 0u, nz_loc = 0u, neg_loc = 0u;                   // this group's finished episodes / steps with a reward / see below
     uint32_t p0 = 0u, p1 = 0u, p2 = 0u, p3 = 0u;                        // !SLIP: the current eight-tick block, transposed
@@ -304,7 +325,8 @@ __device__ __forceinline__ void rollout_swar_group(const RolloutSwar& R, const R
         if (SLIP) {
             const Philox4 blk = philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)tick, (uint32_t)(tick >> 32), R.key0, R.key1);
             uint32_t k4 = 0u;
-            const uint32_t ca4 = TRUSTED ? a4 : swar::canon4(a4), cb4 = TRUSTED ? b4 : swar::canon4(b4);
+            // (the low three bits: the slip tables map 5..7 to NOOP like every other action table)
+            const uint32_t ca4 = TRUSTED ? a4 : a4 & 0x07070707u, cb4 = TRUSTED ? b4 : b4 & 0x07070707u;
             if (SLIPM == 2) swar::slip_select4_lut(slip.lut, slip.T, R.L.c_off, ca4, cb4, blk.w[0], blk.w[1], blk.w[2], blk.w[3], sa, sb, k4, cls4);
             else swar::slip_select4(R.L, slip.sub, ca4, cb4, blk.w[0], blk.w[1], blk.w[2], blk.w[3], sa, sb, k4, cls4);
             rnd = swar::Rand4{k4 << 6, swar::pack_byte0(blk.w[0], blk.w[1], blk.w[2], blk.w[3]) >> C.isd_shift};
@@ -322,7 +344,8 @@ __device__ __forceinline__ void rollout_swar_group(const RolloutSwar& R, const R
             // was three v_cndmask_b32 every step, each several times the cost of a move (tools/labs/valu_rate_lab.hip).
             if (t & 1u) { asm volatile(""); p0 = p1; p1 = p2; p2 = p3; }
         }
-        swar::step4<GENERAL, FULL, SLIP, GEO, TRUSTED>(C, S, a4, b4, sa, sb, cls4, rnd, o);
+        if constexpr (GENERAL) swar::step4<true, FULL, SLIP, GEO, TRUSTED>(C, S, a4, b4, sa, sb, cls4, rnd, o);
+        else swar::step4_carry<FULL, SLIP, GEO, TRUSTED>(C, K, a4, b4, sa, sb, cls4, rnd, o);
         s_lo = o.obs_lo; s_hi = o.obs_hi;
         // the step's row of every stream as a uniform base (scalar registers) + this thread's 32-bit byte offset: stores of the
         // form v_off, data, s[base] (the offset passes through an empty asm per step, else the optimiser keeps one 64-bit
@@ -340,9 +363,9 @@ __device__ __forceinline__ void rollout_swar_group(const RolloutSwar& R, const R
             if (IO.prob_code) __builtin_nontemporal_store(o.code, reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(IO.prob_code + row) + j0));
         }
         // finished episodes by return: a reward byte is 0x01 / 0xff only on the step that ends an episode
-        fin_loc += (uint32_t)__builtin_popcount(o.finished & swar::K80);
-        if (GENERAL) { nz_loc += (uint32_t)__builtin_popcount(o.rew & swar::K01); neg_loc += (uint32_t)__builtin_popcount(o.rew & swar::K80); }
-        else {
+        if (STATS) fin_loc += (uint32_t)__builtin_popcount(o.finished & swar::K80);
+        if (STATS && GENERAL) { nz_loc += (uint32_t)__builtin_popcount(o.rew & swar::K01); neg_loc += (uint32_t)__builtin_popcount(o.rew & swar::K80); }
+        else if (STATS) {
             // without frozen / goal-tuple lanes a step terminates exactly when it carries a reward, so the clean 0 / 1 bytes of
             // `terminated` count the rewards and the bits of the reward bytes (0x01 / 0xff) count (+1) + 8 x (-1): two
             // population counts without a mask
@@ -359,17 +382,21 @@ __device__ __forceinline__ void rollout_swar_group(const RolloutSwar& R, const R
         if (!TRUSTED) bad_any |= o.bad_action;
         if (!STAGED) { aa = naa; ab = nab; }
     }
+    if (!GENERAL) S = swar::group_of(C, K);
     fin_tot += fin_loc; nz_tot += nz_loc;
     neg_tot += GENERAL ? neg_loc : (neg_loc - nz_loc) / 7u;             // (pos + 8 neg) - (pos + neg) = 7 neg
 }
 
 // FULL: also the per-step final_obs / prob_code trajectories (batched_rollout_ex; +3 B per env-step and the second observation index)
-template <int DYNM, int SLIPM, int GEO = 0, bool FULL = false>
+// STATS = false: the shape of a fused captured run whose handle keeps no step statistics (flush_run) — no per-step counts, no
+// histogram slot is read or written (R.hist is null).  Instantiated only for the shapes such a run can take (kUnreadShape).
+template <int DYNM, int SLIPM, int GEO = 0, bool FULL = false, bool STATS = true>
 __global__ __launch_bounds__(kBlock) void rollout_swar_kernel(const RolloutSwar R, const RolloutIO IO) {
     constexpr bool SLIP = SLIPM != 0;
     constexpr bool DYN = DYNM >= 2;          // the forms that look something up by the observation
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    HistAcc<false> hist; hist.init_at(R.hist, R.hist_mask);
+    static_assert(STATS || kUnreadShape<DYNM, FULL>, "only a fused run of captured steps goes without statistics");
+    HistAcc<false> hist; if (STATS) hist.init_at(R.hist, R.hist_mask);
     // LDS: the slip thresholds — SLIPM == 1: dynamic [0, 36) the nine rows; SLIPM == 2: a STATIC array (its address is an
     // immediate of the ds_read, not an add per lane) holding the bucket table and the ascending list — then, dynamic from
     // R.tab_off (DYN, when they fit), the mixed-policy rows — DYNM == 2: one 16-byte row { a's
@@ -426,8 +453,8 @@ __global__ __launch_bounds__(kBlock) void rollout_swar_kernel(const RolloutSwar 
         // any lane frozen, any player in a goal column (= a goal tuple), or no auto-reset: the general step
         const uint32_t edge = swar::is_zero(S.ca) | swar::is_zero(S.cb) | swar::is_zero(S.ca ^ R.C.Wm1x4) | swar::is_zero(S.cb ^ R.C.Wm1x4);
         const bool special = R.C.autoreset == 0u || (((S.ps << 6) | edge) & swar::K80) != 0u;
-        if (special) rollout_swar_group<DYNM, SLIPM, true, GEO, FULL>(R, IO, slip, mix_a, mix_b, pol_a, pol_b, act_lds, i0, tick0, S, fin_tot, nz_tot, neg_tot, acc, frozen_any, bad_any);
-        else rollout_swar_group<DYNM, SLIPM, false, GEO, FULL>(R, IO, slip, mix_a, mix_b, pol_a, pol_b, act_lds, i0, tick0, S, fin_tot, nz_tot, neg_tot, acc, frozen_any, bad_any);
+        if (special) rollout_swar_group<DYNM, SLIPM, true, GEO, FULL, STATS>(R, IO, slip, mix_a, mix_b, pol_a, pol_b, act_lds, i0, tick0, S, fin_tot, nz_tot, neg_tot, acc, frozen_any, bad_any);
+        else rollout_swar_group<DYNM, SLIPM, false, GEO, FULL, STATS>(R, IO, slip, mix_a, mix_b, pol_a, pol_b, act_lds, i0, tick0, S, fin_tot, nz_tot, neg_tot, acc, frozen_any, bad_any);
         uint8_t* sw = R.state + i0;
         if (R.layout == kStatePacked) {
             uint32_t pa, pb, pt;
@@ -438,7 +465,7 @@ __global__ __launch_bounds__(kBlock) void rollout_swar_kernel(const RolloutSwar 
         *reinterpret_cast<uint32_t*>(sw + 2 * R.state_stride) = S.rb; *reinterpret_cast<uint32_t*>(sw + 3 * R.state_stride) = S.cb;
         *reinterpret_cast<uint32_t*>(sw + 4 * R.state_stride) = S.ps; *reinterpret_cast<uint32_t*>(sw + 5 * R.state_stride) = S.tt;
         }
-        hist.add_totals(fin_tot, (int32_t)nz_tot - 2 * (int32_t)neg_tot, nz_tot);
+        if (STATS) hist.add_totals(fin_tot, (int32_t)nz_tot - 2 * (int32_t)neg_tot, nz_tot);
         if (IO.return_sum != nullptr || IO.episode_count != nullptr) {
             int32_t ret[4] = {(int32_t)(int16_t)(acc[0] & 0xffffu), (int32_t)(int16_t)(acc[0] >> 16), (int32_t)(int16_t)(acc[1] & 0xffffu), (int32_t)(int16_t)(acc[1] >> 16)};
             int32_t eps[4] = {(int32_t)(acc[2] & 0xffffu), (int32_t)(acc[2] >> 16), (int32_t)(acc[3] & 0xffffu), (int32_t)(acc[3] >> 16)};
@@ -448,7 +475,7 @@ __global__ __launch_bounds__(kBlock) void rollout_swar_kernel(const RolloutSwar 
     }
     if (frozen_any) R.misuse[0] = 1u;
     if (bad_any) R.misuse[1] = 1u;
-    hist.flush_at(R.hist, R.hist_mask);
+    if (STATS) hist.flush_at(R.hist, R.hist_mask);
 }
 
 }  // namespace soccer

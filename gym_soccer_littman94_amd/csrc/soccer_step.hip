@@ -211,10 +211,10 @@ int flush_run(soccer_handle* h) {
     HIP_TRY(h, hipSetDevice(h->cfg.device));     // (the caller may be soccer_graph_end or a call that has not set it yet)
     if (R.len == 1) return launch_one_step(h, &R.first);
     const soccer_rollout_args r = run_as_rollout(R.first, R.len, R.act_stride, R.out_stride);
-    // rollout_swar_kernel always counts finished episodes, a step only with SOCCER_F_STEP_STATS: without it the run counts
-    // into the block nobody reads; soccer_rollout_shape keeps describing the caller's own last rollout
+    // a step counts finished episodes only with SOCCER_F_STEP_STATS: without it the run takes the kernel's shape that does not
+    // count (no histogram at all); soccer_rollout_shape keeps describing the caller's own last rollout
     const soccer_rollout_shape_info keep = h->last_rollout;
-    const int rc = rollout_enqueue(h, &r, nullptr, h->P.step_stats ? h->d_hist : h->d_hist_unread);
+    const int rc = rollout_enqueue(h, &r, nullptr, h->P.step_stats ? h->d_hist : nullptr);
     h->last_rollout = keep;
     if (rc == SOCCER_OK) { h->capture_steps_fused += R.len; h->capture_fused_launches += 1; }
     return rc;

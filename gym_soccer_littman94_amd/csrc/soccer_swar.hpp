@@ -129,7 +129,8 @@ struct Consts {
     uint32_t gr_hi_add;    // (0x7f - goal_hi) in every byte: bit 7 of row + this  <=>  row >  goal_hi
     uint32_t trunc_add;    // (0x80 - max_steps) in every byte: bit 7 of t + this   <=>  t >= max_steps   (:404)
     uint32_t obs_mul;      // 2 * (NI - 1) in both halves, NI = H * (W - 2) interior cells
-    uint32_t isd_ra, isd_rb, isd_p;   // byte k = row of A / row of B / possession of ISD entry k (:146-165)
+    uint32_t isd_ra, isd_rb, isd_p;   // byte k = row of A / row of B / possession of ISD entry k (:146-165); possession as a
+                                      // byte MASK (0xff: B has the ball), the form the step selects it in
     uint32_t isd_ca4, isd_cb4;        // the entries' columns (2 and W - 3) in every byte
     uint32_t isd_shift, isd_mask;     // entry index = (two random bits >> shift), 4 or 2 entries
     uint32_t autoreset;
@@ -140,7 +141,7 @@ struct Consts {
     uint32_t small;                   // != 0: the tables below are valid, take the GEO = 1 instantiations
     uint32_t row_lo, row_hi;          // [u] = clamp(u - 1, 0, H - 1) for u = row + 1 + drow in 0 .. H + 1
     uint32_t col_lo, col_hi;          // [c] = clamp(c, 1, W - 2): a step into a goal column undone
-    uint32_t grow_lo, grow_hi;        // flag byte 0x80 for the goal rows (:60)
+    uint32_t grow_lo, grow_hi;        // 0xff for the goal rows (:60): a flag word that is a byte mask already
     uint32_t rew_lo, rew_hi;          // player A's reward by the carrier's column: 0xff at column 0, 0x01 at W - 1 (:237-240)
     uint32_t term_lo, term_hi;        // 0x01 at the two goal columns
 };
@@ -169,7 +170,7 @@ inline Consts make_consts(int H, int W, int goal_lo, int goal_hi, int max_steps,
         const int e = k < n_isd ? k : 0;
         C.isd_ra |= (uint32_t)(uint8_t)isd[e][0] << (8 * k);
         C.isd_rb |= (uint32_t)(uint8_t)isd[e][2] << (8 * k);
-        C.isd_p |= (uint32_t)(uint8_t)isd[e][4] << (8 * k);
+        C.isd_p |= (isd[e][4] ? 0xffu : 0u) << (8 * k);
     }
     C.isd_ca4 = splat((uint32_t)(uint8_t)isd[0][1]);
     C.isd_cb4 = splat((uint32_t)(uint8_t)isd[0][3]);
@@ -194,7 +195,7 @@ inline Consts make_consts(int H, int W, int goal_lo, int goal_hi, int max_steps,
             for (int u = 0; u < 8 && u < n; ++u) t |= (uint64_t)(uint8_t)f(u) << (8 * u);
             tlo = (uint32_t)t; thi = (uint32_t)(t >> 32);
         };
-        flags(H, [&](int r) { return r >= goal_lo && r <= goal_hi ? 0x80 : 0; }, C.grow_lo, C.grow_hi);
+        flags(H, [&](int r) { return r >= goal_lo && r <= goal_hi ? 0xff : 0; }, C.grow_lo, C.grow_hi);
         flags(W, [&](int c) { return c == 0 ? 0xff : (c == W - 1 ? 0x01 : 0); }, C.rew_lo, C.rew_hi);
         flags(W, [&](int c) { return c == 0 || c == W - 1 ? 0x01 : 0; }, C.term_lo, C.term_hi);
     }
@@ -281,18 +282,27 @@ SOCCER_HD uint32_t lut8(uint32_t hi, uint32_t lo, uint32_t a) { return perm(hi, 
 constexpr uint32_t T_DR1_LO = 0x01020001u, T_DR1_HI = 0x01010101u;   // row delta + 1
 constexpr uint32_t T_E_LO = 0x01000000u, T_E_HI = 0u;                  // 1 for EAST
 constexpr uint32_t T_W_LO = 0u, T_W_HI = 0x00000001u;                  // 1 for WEST
-constexpr uint32_t T_NZ_LO = 0x80808000u, T_NZ_HI = 0x00000080u;       // flag: the action is not NOOP
+constexpr uint32_t T_DC1_LO = 0x02010101u, T_DC1_HI = 0x01010100u;     // column delta + 1
+// flag: the action is not NOOP.  A flag word's low seven bits are don't-care, so bit 0 of the same table says "the entry
+// is 5..7": with the bits above the low three that is the whole misuse report (bad_actions4)
+constexpr uint32_t T_NZ_LO = 0x80808000u, T_NZ_HI = 0x01010180u;
 // an action byte as the kernels execute it: table[byte & 7] with 5..7 -> NOOP, so no byte value can index outside a
 // rule table; canon4(x) != x exactly when some byte of x is outside 0..4 (the reference raises IndexError, :393)
 constexpr uint32_t T_CANON_LO = 0x03020100u, T_CANON_HI = 0x00000004u;
 SOCCER_HD uint32_t canon4(uint32_t x) { return perm(T_CANON_HI, T_CANON_LO, x & 0x07070707u); }
+// The step itself needs only the low three bits — every action table maps 5..7 to NOOP — and reports misuse from the two
+// not-NOOP lookups (T_NZ) it makes anyway: non-zero exactly when some byte of a_raw / b_raw is outside 0..4.
+SOCCER_HD uint32_t bad_actions4(uint32_t a_raw, uint32_t b_raw, uint32_t nz_a, uint32_t nz_b) {
+    return ((nz_a | nz_b) & K01) | ((a_raw | b_raw) & 0xf8f8f8f8u);
+}
 // slipped move of an action (:205-206): NOOP->NOOP,NOOP NORTH->EAST,WEST SOUTH->WEST,EAST EAST->SOUTH,NORTH WEST->NORTH,SOUTH
 constexpr uint32_t T_SLIP1_LO = 0x02040300u, T_SLIP1_HI = 0x00000001u;
 constexpr uint32_t T_SLIP2_LO = 0x01030400u, T_SLIP2_HI = 0x00000002u;
 
 // one player's tentative cell (_next_cell :364-373) for four lanes: rows clamped to the pitch, a step into a goal
 // column reverted unless the player holds the ball and stands in a goal row.  `mv` = the (possibly slipped) move,
-// `score` = flag word "holds the ball and is in a goal row" (an EAST / WEST move never changes the row).
+// `score` = flag word "holds the ball and is in a goal row" (an EAST / WEST move never changes the row); with GEO = 1 a
+// byte mask (Consts::grow_* holds masks, and so does the possession it is combined with).
 // DELTAS: the caller has looked the move up already (move_delta): `mv` is the row delta + 1 per byte and `dc` the column
 // delta, east - west, as ONE 32-bit word whose borrows cancel when it is added to the columns.
 SOCCER_HD void move_delta(uint32_t mv, uint32_t& dr1, uint32_t& dc) {
@@ -309,10 +319,11 @@ SOCCER_HD void move4(const Consts& C, uint32_t r, uint32_t c, uint32_t mv, uint3
         const uint32_t at_bot = one_of(is_zero(u ^ C.Hp1x4));              // stepped south off row H - 1
         nr = u + at_top + 0xFEFEFEFFu - at_bot;                            // (u + at_top) >= 1 in every byte
     }
-    const uint32_t ct = DELTAS ? c + dc : c + lut8(T_E_HI, T_E_LO, mv) - lut8(T_W_HI, T_W_LO, mv);   // :366
+    // :366.  One table of dcol + 1 and one three-operand add of -K01: every byte of c + (dcol + 1) is >= 1, nothing borrows
+    const uint32_t ct = DELTAS ? c + dc : c + lut8(T_DC1_HI, T_DC1_LO, mv) + 0xFEFEFEFFu;
     if (GEO == 1) {
         // a step into a goal column that is not a score is undone (:369-372): from column 1 / W - 2 that is a clamp
-        nc = bfi(mask_of(score), ct, perm(C.col_hi, C.col_lo, ct));
+        nc = bfi(score, ct, perm(C.col_hi, C.col_lo, ct));
     } else {
         const uint32_t edge = is_zero(ct) | is_zero(ct ^ C.Wm1x4);        // the target is a goal column (:369)
         const uint32_t revert = bfi(score, 0u, edge);                      // ... and this is not a score (:370-372)
@@ -405,17 +416,20 @@ SOCCER_HD void slip_select4_lut(const uint8_t* lut, const uint32_t* T, uint32_t 
 // Observation index of four tuples (ra, ca, rb, cb, p): 1 + 2 * (iA * (NI - 1) + iB - (iB > iA)) + p over interior-cell
 // indices i = row * (W - 2) + col - 1 (Rules::build checks the table against this closed form of the reference's
 // enumeration order, :63-109), evaluated as iA * 2(NI - 1) + (2 * (iB - gt) + 1 + p) on two 16-bit halves at a time.
-// j = i + 1 comes straight out of one packed multiply-add per player; every byte stays within 0..255 and never borrows:
-// 2 * jB + p <= 2 * NI + 3 <= 255 (swar::fits), and jB >= 2 whenever iB > iA.  ZERO: lanes flagged in `zero7` (goal
-// tuples, :493-494) get index 0 (their bytes above are meaningless but still borrow-free: a carrier in a goal column
-// stands in a goal row >= 1, so j >= W - 2).
+// j = i + 1 comes straight out of one packed multiply-add per player.  With nge2 = 2 * [jA >= jB] = 2 - 2 * (iB > iA) the
+// low term is q = (2 * jB + p + nge2) - 3, one shift-add and one three-operand add; its bytes are exact because every
+// byte of the result lies in 0..255 (the sum is one 32-bit addition, so only the final value matters): the players stand on
+// different cells, so jB = 1 implies jA >= jB and 2 * jB + p + nge2 >= 4 >= 3 always, and jB = NI implies jA < jB, so
+// q <= 2 * NI + 1 <= 255 (swar::fits).  ZERO: lanes flagged in `zero7` (goal tuples, :493-494) get index 0 (their bytes
+// above are meaningless but still in range: a carrier in a goal column stands in a goal row >= 1, so W - 2 <= j <= NI + 1,
+// and j = NI + 1 is B alone on its goal line: q = 2 * NI there).
 template <bool ZERO>
 SOCCER_HD void obs4(const Consts& C, uint32_t r_a, uint32_t c_a, uint32_t r_b, uint32_t c_b, uint32_t p01, uint32_t zero7,
                     uint32_t& lo, uint32_t& hi) {
     const uint32_t jA = pk_mad(r_a, C.Wm2x2, c_a), jB = pk_mad(r_b, C.Wm2x2, c_b);
-    const uint32_t gt2 = (((jB | K80) - jA) >> 6) & 0x02020202u;           // 2 * (iB > iA)
+    const uint32_t nge2 = (((jA | K80) - jB) >> 6) & 0x02020202u;          // 2 * (iA >= iB)
     const uint32_t iA = jA - K01;
-    const uint32_t q = (jB << 1) + p01 - gt2 - K01;                         // 2 * (iB - gt) + 1 + p
+    const uint32_t q = ((jB << 1) + p01) + nge2 + 0xFCFCFCFDu;              // 2 * (iB - (iB > iA)) + 1 + p
     lo = pk_mad(perm(0u, iA, 0x0c010c00u), C.obs_mul, perm(0u, q, 0x0c010c00u));
     hi = pk_mad(perm(0u, iA, 0x0c030c02u), C.obs_mul, perm(0u, q, 0x0c030c02u));
     if (ZERO) {
@@ -430,7 +444,7 @@ SOCCER_HD void obs4(const Consts& C, uint32_t r_a, uint32_t c_a, uint32_t r_b, u
 template <bool MASKED>
 SOCCER_HD void reset4(const Consts& C, Group& S, uint32_t mask4, const Rand4& R, uint32_t& obs_lo, uint32_t& obs_hi) {
     const uint32_t idx = R.rs & C.isd_mask;
-    const uint32_t ira = perm(0u, C.isd_ra, idx), irb = perm(0u, C.isd_rb, idx), ip = perm(0u, C.isd_p, idx);
+    const uint32_t ira = perm(0u, C.isd_ra, idx), irb = perm(0u, C.isd_rb, idx), ip = perm(0u, C.isd_p, idx) & K01;
     uint32_t zero7 = 0u;
     if (MASKED) {
         const uint32_t m = mask_of(((mask4 & K7F) + K7F) | mask4);         // byte != 0
@@ -458,7 +472,7 @@ struct Moves4 {
     uint32_t aa, ab;               // the actions as executed (canon4)
     uint32_t sa, sb;               // the moves: the actions, or with SLIP the selected combination's (low three bits)
     uint32_t dra, dca, drb, dcb;   // move_delta of sa / sb
-    uint32_t ira, irb, ip;         // the ISD entry (row of A, row of B, possession) of each lane's reset draw (:414)
+    uint32_t ira, irb, ip;         // the ISD entry (row of A, row of B, possession as a mask) of each lane's reset draw (:414)
     uint32_t bad_action;           // non-zero: some action byte was outside 0..4
 };
 template <bool SLIP>
@@ -485,18 +499,22 @@ SOCCER_HD Moves4 step4_moves(const Consts& C, uint32_t aa_raw, uint32_t ab_raw, 
 // TRUSTED: the action bytes were produced by the kernel itself (sampled in 0..4): no canonical form, no misuse report.
 // GEO: 0 the pitch geometry by arithmetic (any pitch that fits), 1 by byte tables (Consts::small).
 // PRE (step4_state): the actions, the moves and, unless GENERAL, their tables come from M (step4_moves).
-template <bool GENERAL, bool FULL, bool SLIP, int GEO, bool TRUSTED, bool PRE>
+// CARRY (step4_carry, never GENERAL): S is in step form — S.ps holds the possession as a byte mask and S.tt the timestep
+//   biased by Consts::trunc_add (Carry4) — and leaves in it: what the step computes anyway is what the next step reads.
+template <bool GENERAL, bool FULL, bool SLIP, int GEO, bool TRUSTED, bool PRE, bool CARRY = false>
 SOCCER_HD void step4_body(const Consts& C, Group& S, uint32_t aa_raw, uint32_t ab_raw, uint32_t sa, uint32_t sb,
                           uint32_t cls4, const Rand4& R, const Moves4& M, Out& o) {
+    static_assert(!(CARRY && GENERAL), "the step form has no room for the needs_reset bit");
     constexpr bool TABLES = PRE && !GENERAL;                               // M's deltas and ISD entry are the lanes'
     const uint32_t ra = S.ra, ca = S.ca, rb = S.rb, cb = S.cb, ps = S.ps, t = S.tt;
     // ---- actions: the low three bits select the move, 5..7 are NOOP; any byte outside 0..4 is reported ---------------
     uint32_t aa = aa_raw, ab = ab_raw;
-    if (PRE) { aa = M.aa; ab = M.ab; sa = M.sa; sb = M.sb; o.bad_action = M.bad_action; }
-    else if (TRUSTED) o.bad_action = 0u;
-    else { aa = canon4(aa_raw); ab = canon4(ab_raw); o.bad_action = (aa ^ aa_raw) | (ab ^ ab_raw); }
-    const uint32_t p7 = ps << 7;                                           // flag: B has the ball
-    const uint32_t pm = mask_of(p7);
+    if (PRE) { aa = M.aa; ab = M.ab; sa = M.sa; sb = M.sb; }
+    else if (!TRUSTED) { aa = aa_raw & 0x07070707u; ab = ab_raw & 0x07070707u; }
+    uint32_t nzA = lut8(T_NZ_HI, T_NZ_LO, aa), nzB = lut8(T_NZ_HI, T_NZ_LO, ab);   // the ORIGINAL actions (:330-339)
+    o.bad_action = PRE ? M.bad_action : TRUSTED ? 0u : bad_actions4(aa_raw, ab_raw, nzA, nzB);
+    // B has the ball: as a byte mask, which is a flag word as well
+    const uint32_t pm = CARRY ? ps : mask_of(ps << 7);
     uint32_t frz7 = 0u, hold_m = 0u, frz_m = 0u;
     if (GENERAL) {
         // lanes that are left as they are: frozen (needs_reset, :376) or in a goal tuple (absorbing, :300-301)
@@ -505,22 +523,22 @@ SOCCER_HD void step4_body(const Consts& C, Group& S, uint32_t aa_raw, uint32_t a
         const uint32_t hold7 = frz7 | is_zero(cc0) | is_zero(cc0 ^ C.Wm1x4);
         hold_m = mask_of(hold7); frz_m = mask_of(frz7);
         aa = bfi(hold_m, 0u, aa); ab = bfi(hold_m, 0u, ab);                // NOOP / NOOP leaves the tuple unchanged
+        nzA = bfi(hold_m, 0u, nzA); nzB = bfi(hold_m, 0u, nzB);
         if (SLIP) { sa = bfi(hold_m, 0u, sa); sb = bfi(hold_m, 0u, sb); }
     }
     if (!SLIP) { sa = aa; sb = ab; } else { sa &= 0x07070707u; sb &= 0x07070707u; }
     // ---- tentative cells (:307-312) ---------------------------------------------------------------------------------
-    uint32_t gra, grb;                                                     // flag: row in the goal rows
+    uint32_t gra, grb;                                                     // flag: row in the goal rows (GEO = 1: a mask)
     if (GEO == 1) { gra = perm(C.grow_hi, C.grow_lo, ra); grb = perm(C.grow_hi, C.grow_lo, rb); }
     else { gra = bfi(ra + C.gr_hi_add, 0u, ra + C.gr_lo_add); grb = bfi(rb + C.gr_hi_add, 0u, rb + C.gr_lo_add); }
     uint32_t nra, nca, nrb, ncb;
-    move4<GEO, TABLES>(C, ra, ca, TABLES ? M.dra : sa, M.dca, bfi(p7, 0u, gra), nra, nca);   // A holds the ball when p == 0
-    move4<GEO, TABLES>(C, rb, cb, TABLES ? M.drb : sb, M.dcb, grb & p7, nrb, ncb);
+    move4<GEO, TABLES>(C, ra, ca, TABLES ? M.dra : sa, M.dca, bfi(pm, 0u, gra), nra, nca);   // A holds the ball when p == 0
+    move4<GEO, TABLES>(C, rb, cb, TABLES ? M.drb : sb, M.dcb, grb & pm, nrb, ncb);
     // ---- ordered collision resolution (:315-360) on cell ids ---------------------------------------------------------
     const uint32_t A = pk_mad(ra, C.Wx2, ca), B = pk_mad(rb, C.Wx2, cb);
     const uint32_t nA = pk_mad(nra, C.Wx2, nca), nB = pk_mad(nrb, C.Wx2, ncb);
     const uint32_t e1 = is_zero(nA ^ B), e2 = is_zero(nB ^ A);
     const uint32_t sA = is_zero(nA ^ A), sB = is_zero(nB ^ B), same = is_zero(nA ^ nB);
-    const uint32_t nzA = lut8(T_NZ_HI, T_NZ_LO, aa), nzB = lut8(T_NZ_HI, T_NZ_LO, ab);   // the ORIGINAL actions (:330-339)
     const uint32_t swap = e1 & e2;                                         // :315-322
     const uint32_t stander = bfi(nzB, 0u, e1) | bfi(nzA, 0u, e2);          // :330-331
     const uint32_t bounce = ((sA & nzA) & e2) | ((sB & nzB) & e1);         // :338-339
@@ -537,7 +555,7 @@ SOCCER_HD void step4_body(const Consts& C, Group& S, uint32_t aa_raw, uint32_t a
     const uint32_t bmv = bfi(kb1, mv, four | mv);                          // B takes its cell: k < 2
     const uint32_t am = mask_of(amv), bm = mask_of(bmv);
     uint32_t fra = bfi(am, nra, ra), fca = bfi(am, nca, ca), frb = bfi(bm, nrb, rb), fcb = bfi(bm, ncb, cb);
-    const uint32_t p7n = bfi(coin | four, bfi(coin, kb0c, kb0f), p7 ^ flip);
+    const uint32_t p7n = bfi(coin | four, bfi(coin, kb0c, kb0f), pm ^ flip);
     // ---- done / reward (:235-240), bookkeeping (:399-406) -------------------------------------------------------------
     const uint32_t pmn = mask_of(p7n);
     const uint32_t cc = bfi(pmn, fcb, fca);                                // the carrier's column after the step
@@ -550,7 +568,7 @@ SOCCER_HD void step4_body(const Consts& C, Group& S, uint32_t aa_raw, uint32_t a
     }
     if (GENERAL) rew = bfi(hold_m, 0u, rew);                               // from a goal tuple: reward 0 (:235-236)
     uint32_t tt = t + (GENERAL ? bfi(frz_m, 0u, K01) : K01);               // :399 (a frozen lane keeps its timestep)
-    const uint32_t trunc7 = tt + C.trunc_add;                              // :404
+    const uint32_t trunc7 = CARRY ? tt : tt + C.trunc_add;                 // :404 (CARRY: the bias is in t already)
     const uint32_t need7 = goal7 | trunc7;                                 // :406
     const uint32_t fin7 = GENERAL ? bfi(frz7, 0u, need7) : need7;          // episodes that ended at this step
     o.rew = rew; o.term = term01; o.trunc = one_of(trunc7);
@@ -562,8 +580,8 @@ SOCCER_HD void step4_body(const Consts& C, Group& S, uint32_t aa_raw, uint32_t a
         if (GENERAL && SLIP) code = bfi(frz_m, 0u, code);
         o.code = code;
     }
-    uint32_t p01 = one_of(p7n);
-    if (FULL) obs4<true>(C, fra, fca, frb, fcb, p01, goal7, o.fin_lo, o.fin_hi);      // before any reset (goal tuples -> 0)
+    uint32_t pmo = pmn;                                                    // possession after any reset, as a mask
+    if (FULL) obs4<true>(C, fra, fca, frb, fcb, pmn & K01, goal7, o.fin_lo, o.fin_hi);   // before any reset (goal tuples -> 0)
     // ---- in-step reset (:410-424): lanes whose episode ended draw an ISD entry with their two low random bits --------
     uint32_t need_out7 = GENERAL ? (need7 | frz7) : need7;
     uint32_t obs_zero7 = goal7;
@@ -572,20 +590,41 @@ SOCCER_HD void step4_body(const Consts& C, Group& S, uint32_t aa_raw, uint32_t a
         const uint32_t idx = R.rs & C.isd_mask;                            // lane j's reset draw
         fra = bfi(rm, TABLES ? M.ira : perm(0u, C.isd_ra, idx), fra); fca = bfi(rm, C.isd_ca4, fca);
         frb = bfi(rm, TABLES ? M.irb : perm(0u, C.isd_rb, idx), frb); fcb = bfi(rm, C.isd_cb4, fcb);
-        p01 = bfi(rm, TABLES ? M.ip : perm(0u, C.isd_p, idx), p01);
-        tt = bfi(rm, 0u, tt);
+        pmo = bfi(rm, TABLES ? M.ip : perm(0u, C.isd_p, idx), pmn);
+        tt = bfi(rm, CARRY ? C.trunc_add : 0u, tt);
         need_out7 = frz7;
         obs_zero7 = bfi(fin7, 0u, goal7);                                  // only a frozen lane can still sit in a goal tuple
     }
     // the observation of the tuple the lane now holds; without frozen lanes no tuple is a goal tuple after the reset
+    const uint32_t p01 = pmo & K01;
     obs4<GENERAL>(C, fra, fca, frb, fcb, p01, obs_zero7, o.obs_lo, o.obs_hi);
     S.ra = fra; S.ca = fca; S.rb = frb; S.cb = fcb; S.tt = tt;
-    S.ps = p01 | ((need_out7 >> 6) & 0x02020202u);
+    S.ps = CARRY ? pmo : p01 | ((need_out7 >> 6) & 0x02020202u);
 }
 template <bool GENERAL, bool FULL, bool SLIP, int GEO = 0, bool TRUSTED = false>
 SOCCER_HD void step4(const Consts& C, Group& S, uint32_t aa_raw, uint32_t ab_raw, uint32_t sa, uint32_t sb,
                      uint32_t cls4, const Rand4& R, Out& o) {
     step4_body<GENERAL, FULL, SLIP, GEO, TRUSTED, false>(C, S, aa_raw, ab_raw, sa, sb, cls4, R, Moves4{}, o);
+}
+
+// The steady state (GENERAL = false) in step form: what a loop over steps carries from one to the next.  Rows and columns as in
+// Group; possession as the byte mask the step computes for its selects (a valid flag word, and `& K01` away from the 0 / 1 the
+// observation takes); the timestep biased by Consts::trunc_add, so that the increment itself is the truncation flag (:404)
+// and a reset writes the bias instead of 0.  No lane of the steady state needs a reset, so bit 1 of Group::ps has no
+// counterpart.  Convert once on entry and once on exit; the step is the same step4_body.
+struct Carry4 { uint32_t ra, ca, rb, cb, pm, tb; };
+SOCCER_HD Carry4 carry_of(const Consts& C, const Group& S) {
+    return Carry4{S.ra, S.ca, S.rb, S.cb, mask_of(S.ps << 7), S.tt + C.trunc_add};
+}
+SOCCER_HD Group group_of(const Consts& C, const Carry4& K) {
+    return Group{K.ra, K.ca, K.rb, K.cb, K.pm & K01, K.tb - C.trunc_add};
+}
+template <bool FULL, bool SLIP, int GEO = 0, bool TRUSTED = false>
+SOCCER_HD void step4_carry(const Consts& C, Carry4& K, uint32_t aa_raw, uint32_t ab_raw, uint32_t sa, uint32_t sb,
+                           uint32_t cls4, const Rand4& R, Out& o) {
+    Group S{K.ra, K.ca, K.rb, K.cb, K.pm, K.tb};
+    step4_body<false, FULL, SLIP, GEO, TRUSTED, false, true>(C, S, aa_raw, ab_raw, sa, sb, cls4, R, Moves4{}, o);
+    K = Carry4{S.ra, S.ca, S.rb, S.cb, S.ps, S.tt};
 }
 template <bool GENERAL, bool FULL, bool SLIP, int GEO = 0>
 SOCCER_HD void step4_state(const Consts& C, Group& S, const Moves4& M, uint32_t cls4, const Rand4& R, Out& o) {
