@@ -4,7 +4,8 @@
 //   soccer_hip.hip       create / destroy, seed / tick, reset, state, staging, one-environment calls, statistics, timers, graphs
 //   soccer_step.hip      batched_step*
 //   soccer_rollout.hip   batched_rollout*
-//   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, cross-play, match outcomes, state occupancy, policy gradients and gradient play, the matrix-game solver
+//   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, the matrix-game solver
+//   soccer_pairs.hip     the pair evaluators on one host skeleton: cross-play, match outcomes, state occupancy, policy gradients, and gradient play
 //   soccer_metagame.hip  soccer_solve_meta_games: the maximin mixtures of n_a x n_b matrix games
 //   soccer_learners.hip  the seven kinds of learners on one host skeleton: minimax-Q, independent Q, WoLF-PHC, a population of each, and a
 //                        population of opponent-modelling Q-learners
@@ -119,6 +120,43 @@ struct PendingRun {
 
 struct Learner;                             // soccer_learners.hip: what the seven kinds of learners have in common
 
+// What solve_pass (soccer_pairs.hip) works on: the buffers of one solve over the pairs of a pass, the pairs along the fastest axis.
+struct PassBufs {
+    double* buf[2] = {nullptr, nullptr};    // [rows][stride] the iterate, double-buffered across sweeps
+    unsigned long long* words = nullptr;    // [kMinimaxBatch + 1][stride] per-sweep, per-pair max |change| (bits)
+    int32_t* done = nullptr;                // [stride] each pair's stopping sweep
+    int32_t* open = nullptr;                // the number of open pairs after a batch
+    int stride = 0;
+};
+
+// The buffer family of one pair evaluator: a call's policies and one pass's buffers.  `policies`, `pass.stride` and
+// `has_values` say what is held; pair_buffers (soccer_pairs.hip) is the only one to allocate here.
+struct PairBufs {
+    OwnedBufs bufs;
+    PassBufs pass;                          // rows: nS (soccer_match_outcomes: kMatchChannels * nS, the channels of a state side by side)
+    double* pol = nullptr;                  // [policies][nS][5] as the caller gives them: player A's policies, then player B's
+    double* polT = nullptr;                 // [nS][5][n_a] player A's with the policy along the fastest axis, then [nS][5][n_b] (where the sweep reads in-lists)
+    int32_t* iter = nullptr;                // [stride] the sweep counts as they are returned (max_sweeps for an open pair)
+    double* values = nullptr;               // [stride][width] a pass's iterate in the caller's order (has_values: allocated)
+    int policies = 0; bool has_values = false;
+    explicit PairBufs(const char* owner) : bufs(owner) {}
+};
+struct CrossOwn { double* payoff = nullptr; };                          // [stride]
+struct MatchOwn { double* kickoff = nullptr; };                         // [kMatchChannels][stride]
+struct OccupancyOwn {
+    double* length = nullptr;               // [stride]
+    double* expect = nullptr;               // [pairs of the pass][n_f], room for [stride][SOCCER_OCC_MAX_FEATURES]
+    double* features = nullptr;             // [SOCCER_OCC_MAX_FEATURES][nS] the caller's
+};
+struct GradientOwn {                        // the family's own pass is V's; its values buffer takes V, D, q_a or q_b in turn
+    PassBufs D;                             // the occupancy's solve over the same pairs: buffers and stopping sweeps of its own, V's words and count
+    double* Q = nullptr;                    // [2][nS][5][stride] Q_a, then Q_b: the ten action-value planes
+    double* payoff = nullptr;               // [stride]
+    double* grad = nullptr;                 // [policies][nS][5] the running sums: grad_a, then grad_b
+    double* reach = nullptr;                // [policies][nS]
+    double* w = nullptr;                    // [policies] w_a, then w_b
+};
+
 struct soccer_handle {
     soccer_config cfg{};
     Rules rules;
@@ -195,65 +233,17 @@ struct soccer_handle {
     unsigned long long* br_words = nullptr; // [br_cap][kMinimaxBatch + 1] per-policy, per-sweep max |V_k - V_{k-1}| (bits)
     int br_cap = 0; bool br_pairs = false;
     OwnedBufs br_bufs{"the best-response solver"};
-    // soccer_cross_play: the policies of a call and one pass's buffers ([..][cx_stride], the pass's pairs along the fastest
-    // axis), allocated on first use and again when a call needs more of either, see cross_buffers
-    double* cx_pol = nullptr;               // [cx_policies][nS][5] player A's policies, then player B's
-    double* cx_V[2] = {nullptr, nullptr};   // [nS][cx_stride] V double-buffered across sweeps
-    unsigned long long* cx_words = nullptr; // [kMinimaxBatch + 1][cx_stride] per-sweep, per-pair max |V_k - V_{k-1}| (bits)
-    int32_t* cx_done = nullptr;             // [cx_stride] each pair's stopping sweep
-    int32_t* cx_iter = nullptr;             // [cx_stride] ... as it is returned (max_sweeps for an open pair)
-    double* cx_payoff = nullptr;            // [cx_stride]
-    int32_t* cx_open = nullptr;             // the number of open pairs after a batch
-    double* cx_values = nullptr;            // [cx_stride][nS] V of the pass in the caller's order (cx_has_values: allocated)
-    int cx_policies = 0, cx_stride = 0; bool cx_has_values = false;
-    OwnedBufs cx_bufs{"the cross-play solver"};
-    // soccer_match_outcomes: cross-play's buffers with three channels in V, the kick-off means and the values, see match_buffers
-    double* mo_pol = nullptr;               // [mo_policies][nS][5] player A's policies, then player B's
-    double* mo_V[2] = {nullptr, nullptr};   // [nS][3][mo_stride] W_A, W_B and L double-buffered across sweeps
-    unsigned long long* mo_words = nullptr; // [kMinimaxBatch + 1][mo_stride] per-sweep, per-pair max over the channels (bits)
-    int32_t* mo_done = nullptr;             // [mo_stride] each pair's stopping sweep
-    int32_t* mo_iter = nullptr;             // [mo_stride] ... as it is returned (max_sweeps for an open pair)
-    double* mo_kickoff = nullptr;           // [3][mo_stride]
-    int32_t* mo_open = nullptr;             // the number of open pairs after a batch
-    double* mo_values = nullptr;            // [mo_stride][3][nS] in the caller's order (mo_has_values: allocated)
-    int mo_policies = 0, mo_stride = 0; bool mo_has_values = false;
-    OwnedBufs mo_bufs{"the match-outcome solver"};
-    // soccer_occupancy: the two-player lists the other way round (build_inlists, once per handle like the lists they derive
-    // from), and cross-play's buffers with the policies transposed, see occupancy_buffers
-    const int32_t* oc_in_offset = nullptr;  // [nS + 1]
-    const InEntry* oc_in_list = nullptr;    // padded to kPlanPad
-    OwnedBufs oc_lists{"the occupancy solver's in-lists"};
-    double* oc_pol = nullptr;               // [oc_policies][nS][5] as the caller gives them: player A's policies, then player B's
-    double* oc_polT = nullptr;              // [nS][5][n_a] player A's with the policy along the fastest axis, then [nS][5][n_b]
-    double* oc_D[2] = {nullptr, nullptr};   // [nS][oc_stride] D double-buffered across sweeps
-    unsigned long long* oc_words = nullptr; // [kMinimaxBatch + 1][oc_stride] per-sweep, per-pair max |D_k - D_{k-1}| (bits)
-    int32_t* oc_done = nullptr;             // [oc_stride] each pair's stopping sweep
-    int32_t* oc_iter = nullptr;             // [oc_stride] ... as it is returned (max_sweeps for an open pair)
-    double* oc_length = nullptr;            // [oc_stride]
-    double* oc_expect = nullptr;            // [pairs of the pass][n_f], room for [oc_stride][SOCCER_OCC_MAX_FEATURES]
-    double* oc_features = nullptr;          // [SOCCER_OCC_MAX_FEATURES][nS] the caller's
-    int32_t* oc_open = nullptr;             // the number of open pairs after a batch
-    double* oc_values = nullptr;            // [oc_stride][nS] D of the pass in the caller's order (oc_has_values: allocated)
-    int oc_policies = 0, oc_stride = 0; bool oc_has_values = false;
-    OwnedBufs oc_bufs{"the occupancy solver"};
-    // soccer_policy_gradient (and soccer_gradient_play_run): a buffer family of its own, because a pass's V and D cover the
-    // same pairs at one stride, see gradient_buffers
-    double* pg_pol = nullptr;               // [pg_policies][nS][5] player A's policies, then player B's, row 0 of each zeroed
-    double* pg_polT = nullptr;              // [nS][5][n_a], then [nS][5][n_b]
-    double* pg_V[2] = {nullptr, nullptr};   // [nS][pg_stride] V double-buffered across sweeps
-    double* pg_D[2] = {nullptr, nullptr};   // [nS][pg_stride] D
-    double* pg_Q = nullptr;                 // [2][nS][5][pg_stride] Q_a, then Q_b: the ten action-value planes
-    unsigned long long* pg_words = nullptr; // [kMinimaxBatch + 1][pg_stride] the words of the solve that runs
-    int32_t* pg_done[2] = {nullptr, nullptr};   // [pg_stride] each pair's stopping sweep of the V solve, of the D solve
-    int32_t* pg_iter = nullptr;             // [pg_stride] cross_finish_kernel's sweep counts (the host forms its own from pg_done)
-    double* pg_payoff = nullptr;            // [pg_stride]
-    int32_t* pg_open = nullptr;             // the number of open pairs after a batch
-    double* pg_grad = nullptr;              // [pg_policies][nS][5] the running sums: grad_a, then grad_b
-    double* pg_reach = nullptr;             // [pg_policies][nS]
-    double* pg_w = nullptr;                 // [pg_policies] w_a, then w_b
-    double* pg_values = nullptr;            // [pg_stride][nS][5] a pass's V, D, q_a or q_b in the caller's order (pg_has_values)
-    int pg_policies = 0, pg_stride = 0; bool pg_has_values = false;
-    OwnedBufs pg_bufs{"the policy-gradient solver"};
+    // the pair evaluators (soccer_pairs.hip): a buffer family each, allocated on first use and again when a call needs more
+    // policies, a longer pass or the values for the first time (pair_buffers); what only one of them has sits beside it
+    PairBufs cross{"the cross-play solver"};          CrossOwn cross_own;
+    PairBufs match{"the match-outcome solver"};       MatchOwn match_own;      // kMatchChannels rows per state in the iterate and the values
+    PairBufs occupancy{"the occupancy solver"};       OccupancyOwn occupancy_own;
+    PairBufs gradient{"the policy-gradient solver"};  GradientOwn gradient_own;    // (soccer_gradient_play_run steps along gradient_own.grad)
+    // soccer_occupancy and soccer_policy_gradient: the two-player lists the other way round (build_inlists, once per handle
+    // like the lists they derive from)
+    const int32_t* in_offset = nullptr;     // [nS + 1]
+    const InEntry* in_list = nullptr;       // padded to kPlanPad
+    OwnedBufs in_lists{"the occupancy solver's in-lists"};
     std::vector<soccer_gradient_play*> gradient_players;       // soccer_gradient_play_create's, freed with the handle
     // soccer_solve_meta_games: one pass's buffers, allocated on first use and again when a pass needs more of any, see meta_buffers
     double* mg_A = nullptr;                 // [games][n_a][n_b] the caller's matrices
@@ -318,7 +308,17 @@ static inline int flush_pending(soccer_handle* h) { return h->run.len ? flush_ru
 void comm_release(soccer_handle* h);
 // soccer_learners.hip: frees the learners the caller did not destroy (the handle's destructor; the stream has drained)
 void learners_release(soccer_handle* h);
-// soccer_planners.hip: frees the gradient-play learners the caller did not destroy (the handle's destructor; the stream has drained)
+// soccer_pairs.hip: frees the gradient-play learners the caller did not destroy (the handle's destructor; the stream has drained)
 void gradient_players_release(soccer_handle* h);
+// soccer_planners.hip and soccer_pairs.hip: sweeps a two-player solver enqueues between two synchronisations
+constexpr int kMinimaxBatch = 16;
+// soccer_planners.hip: the checks every two-player solver begins with: the handle, no capture, no fixed policy, gamma in [0, 1]
+int minimax_check(soccer_handle* h, const char* what, double gamma);
+// soccer_planners.hip: after every argument is checked: the device and the cached two-player lists (h->mm)
+int minimax_prepare(soccer_handle* h);
+// soccer_planners.hip: soccer_minimax_q_create's check of opponent_policy, on every live row of n policies (row 0 is not read)
+int response_rows(soccer_handle* h, const char* what, const char* name, int n, const double* pol);
+// soccer_planners.hip: n policies into a device block, row 0 of each as zeros
+int response_upload(soccer_handle* h, double* dst, const double* pol, int n, hipMemcpyKind kind = hipMemcpyHostToDevice);
 
 #pragma GCC visibility pop

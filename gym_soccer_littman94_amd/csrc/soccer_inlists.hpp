@@ -1,5 +1,5 @@
 // soccer_inlists.hpp — the two-player lists the other way round (include/soccer_hip.h, "state occupancy"): for every state s'
-// the entries that lead to it, which soccer_occupancy's sweep sums over.  Plain C++ with no HIP in it: soccer_planners.hip
+// the entries that lead to it, which soccer_occupancy's sweep sums over.  Plain C++ with no HIP in it: soccer_pairs.hip
 // builds the in-lists with it once per handle, and tests/host/inlists_host.cpp compiles it for the CPU tests.
 #pragma once
 #include <cstddef>

@@ -2,7 +2,8 @@
 // one lane (lane_step), the packed lane vectors and the episode histogram.  The kernels themselves are in one header per
 // family, each included by exactly one translation unit (the library is built without relocatable device code, so a
 // kernel must be emitted once): soccer_step_kernels.hpp, soccer_rollout_kernels.hpp, soccer_env_kernels.hpp (reset, the
-// one-environment call, trajectory returns), soccer_planner_kernels.hpp (transition table, planners, minimax) and
+// one-environment call, trajectory returns), soccer_planner_kernels.hpp (transition table, planners, minimax),
+// soccer_pair_kernels.hpp (the pair evaluators: cross-play, match outcomes, occupancy, policy gradients) and
 // soccer_metagame_kernels.hpp (the n_a x n_b matrix games of soccer_solve_meta_games).
 //
 // What is evaluated per lane, and where the reference states it

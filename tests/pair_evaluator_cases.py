@@ -105,7 +105,7 @@ PLAY = dict(eta_a=1.0, eta_b=1.0, optimism=0.5, normalize=True)         # gradie
 LIMIT_SHAPES = [(1024, 1), (1, 1024), (1024, 2)]
 LIMIT_C = 0.5
 SPAN_SHAPE, SPAN_PASSES = (67, 7), (64, 128)                            # the policy gradient's columns spanning passes
-# the library's own pass split (soccer_planners.hip: per_pass of soccer_occupancy, soccer_match_outcomes and gradient_solve)
+# the library's own pass split (soccer_pairs.hip: what soccer_occupancy, soccer_match_outcomes and gradient_solve hand to pass_pairs)
 PASS_BYTES = {"occupancy": 16, "match": 48, "gradient": 112}            # bytes a pair and state of one pass: 2 D; 2 x 3 F; 2 V, 2 D, 10 Q
 PASS_PAIRS = {k: 2 ** 30 // (v * NS) // 64 * 64 for k, v in PASS_BYTES.items()}
 PASS_NB = {"occupancy": 87, "match": 29, "gradient": 13}                # x 1024 of pass_policies(): just above one pass

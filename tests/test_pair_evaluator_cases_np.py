@@ -17,6 +17,7 @@ import best_response_np as brn  # noqa: E402
 import match_outcomes_np as mon  # noqa: E402
 import occupancy_np as ocn  # noqa: E402
 import pair_evaluator_cases as pc  # noqa: E402
+import two_player_cases as tpc  # noqa: E402
 from two_player_cases import (INF, NS, SLIPS, THETA, THETA0_CAPS, UNDISCOUNTED_CAP, boundary_sample, edge_policies, odd_rows,  # noqa: E402
                               pitch, row_accepted)
 
@@ -169,16 +170,24 @@ def test_the_pass_sizes_are_the_library_s():
     assert (89088, 29696, 13312) == tuple(1024 * pc.PASS_NB[c] for c in ("occupancy", "match", "gradient"))
     # the boundary of the policy gradient's split lies inside row 964: its pairs 0 .. 11 in the first pass, pair 12 in the second
     assert divmod(pc.PASS_PAIRS["gradient"], 13) == (964, 12)
-    # the divisors are the source's: per_pass of soccer_occupancy, soccer_match_outcomes (16 * kMatchChannels) and gradient_solve
-    with open(os.path.join(ROOT, "gym_soccer_littman94_amd", "csrc", "soccer_planners.hip")) as f:
+    # the divisors are the source's: the bytes a pair and state that soccer_cross_play, soccer_occupancy, soccer_match_outcomes
+    # (16 * kMatchChannels) and gradient_solve hand to pass_pairs, which holds the rule itself, once
+    with open(os.path.join(ROOT, "gym_soccer_littman94_amd", "csrc", "soccer_pairs.hip")) as f:
         src = f.read()
-    with open(os.path.join(ROOT, "gym_soccer_littman94_amd", "csrc", "soccer_planner_kernels.hpp")) as f:
+    with open(os.path.join(ROOT, "gym_soccer_littman94_amd", "csrc", "soccer_pair_kernels.hpp")) as f:
         assert re.search(r"constexpr int kMatchChannels = 3;", f.read())
+    rule = re.findall(r"static int pass_pairs\(int32_t pairs_per_pass, size_t bytes, int nS, int total\) \{\n"
+                      r"    const int per_pass = pairs_per_pass \? pairs_per_pass : std::max\(64, \(int\)\(\(\(size_t\)1 << 30\) / "
+                      r"\(bytes \* nS\) / 64 \* 64\)\);\n", src)
+    assert len(rule) == 1 and src.count("1 << 30") == 1
 
     def per_pass_of(function):
         body = src[src.index(function):]
-        return re.search(r"int per_pass = pairs_per_pass \? pairs_per_pass : std::max\(64, \(int\)\(\(\(size_t\)1 << 30\) / "
-                         r"\(\(size_t\)([0-9a-zA-Z* ]+) \* nS\) / 64 \* 64\)\);", body).group(1)
+        body = body[:body.index("\n}\n")]                                # the function's own lines
+        calls = re.findall(r"const int per_pass = pass_pairs\(pairs_per_pass, ([0-9a-zA-Z* ]+), nS, total\);", body)
+        assert len(calls) == 1
+        return calls[0]
+    assert per_pass_of('extern "C" int soccer_cross_play(') == "16" and tpc.PASS_PAIRS == 2 ** 30 // (16 * NS) // 64 * 64
     assert per_pass_of('extern "C" int soccer_occupancy(') == "16" and pc.PASS_BYTES["occupancy"] == 16
     assert per_pass_of('extern "C" int soccer_match_outcomes(') == "16 * kMatchChannels" and pc.PASS_BYTES["match"] == 16 * 3
     assert per_pass_of("static int gradient_solve(") == "112" and pc.PASS_BYTES["gradient"] == 112
