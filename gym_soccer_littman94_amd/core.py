@@ -9,491 +9,12 @@ import weakref
 import numpy as np
 
 from . import _lib
+from ._device import DeviceArray, _ptr
 from ._lib import Config, RolloutArgs, StepArgs
-
-
-class DeviceArray:
-    """A caller-owned device buffer allocated through the handle (no torch needed)."""
-
-    def __init__(self, batch, shape, dtype):
-        self.batch = batch
-        self.shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
-        self.dtype = np.dtype(dtype)
-        self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
-        p = C.c_void_p()
-        batch._check(batch.lib.soccer_malloc(batch.h, self.nbytes, C.byref(p)))
-        self.ptr = p.value
-
-    def upload(self, host):
-        a = np.ascontiguousarray(host, dtype=self.dtype)
-        assert a.nbytes == self.nbytes, "size mismatch: %d vs %d bytes" % (a.nbytes, self.nbytes)
-        b = self.batch
-        b._check(b.lib.soccer_memcpy_h2d(b.h, self.ptr, a.ctypes.data, self.nbytes))
-        return self
-
-    def upload_rows(self, first_row, host):
-        """Copy `host` (rows of the same width) into rows first_row.. of a 2-D+ buffer."""
-        a = np.ascontiguousarray(host, dtype=self.dtype)
-        row_bytes = int(np.prod(self.shape[1:])) * self.dtype.itemsize
-        assert a.nbytes % row_bytes == 0 and int(first_row) * row_bytes + a.nbytes <= self.nbytes
-        b = self.batch
-        b._check(b.lib.soccer_memcpy_h2d(b.h, self.ptr + int(first_row) * row_bytes, a.ctypes.data, a.nbytes))
-        return self
-
-    def download_rows(self, first_row, n_rows):
-        row_bytes = int(np.prod(self.shape[1:])) * self.dtype.itemsize
-        out = np.empty((int(n_rows),) + self.shape[1:], self.dtype)
-        b = self.batch
-        b._check(b.lib.soccer_memcpy_d2h(b.h, out.ctypes.data, self.ptr + int(first_row) * row_bytes, out.nbytes))
-        return out
-
-    def download(self, out=None):
-        if out is None:
-            out = np.empty(self.shape, self.dtype)
-        b = self.batch
-        b._check(b.lib.soccer_memcpy_d2h(b.h, out.ctypes.data, self.ptr, self.nbytes))
-        return out
-
-    def fill(self, value):
-        b = self.batch
-        b._check(b.lib.soccer_memset(b.h, self.ptr, int(value), self.nbytes))
-        return self
-
-    def row(self, k):
-        """Device pointer of row k of a 2-D buffer."""
-        return self.ptr + int(k) * self.shape[-1] * self.dtype.itemsize
-
-    def free(self):
-        if self.ptr and self.batch.h:
-            self.batch.lib.soccer_free(self.batch.h, self.ptr)
-        self.ptr = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-def _ptr(x):
-    """Device pointer of a DeviceArray / torch tensor / int / None."""
-    if x is None:
-        return None
-    if isinstance(x, DeviceArray):
-        return x.ptr
-    if isinstance(x, int):
-        return x
-    if hasattr(x, "data_ptr"):          # torch tensor on the handle's device
-        return x.data_ptr()
-    raise TypeError("expected a DeviceArray, a device tensor or an integer address, got %r" % type(x))
-
-
-def minimax_q_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, opponent="uniform"):
-    """Checks the parameters of a minimax-Q learner (AssertionError, before any library call) and returns
-    (soccer_minimax_q_config, the array it points into or None)."""
-    g, a, d, e, q0 = float(discount_factor), float(alpha), float(decay), float(explor), float(q_init)
-    assert 0.0 <= g < 1.0, "discount_factor must be in [0, 1)"
-    assert 0.0 <= a <= 1.0, "alpha must be in [0, 1]"
-    assert 0.0 < d <= 1.0, "decay must be in (0, 1]"
-    assert 0.0 <= e <= 1.0, "explor must be in [0, 1]"
-    assert -1.0 <= q0 <= 1.0, "q_init must be in [-1, 1]"
-    pol = None
-    if isinstance(opponent, str):
-        assert opponent in ("uniform", "self"), "opponent must be 'uniform', 'self' or an [nS, 5] mixed policy"
-        kind = _lib.MQ_UNIFORM if opponent == "uniform" else _lib.MQ_SELF
-    else:
-        pol = np.ascontiguousarray(opponent, np.float64)
-        assert pol.shape == (int(nS), 5) and (pol >= 0).all() and np.allclose(pol.sum(1), 1.0), \
-            "a fixed opponent must be [n_states, 5] rows summing to 1"
-        kind = _lib.MQ_FIXED
-    return _lib.MinimaxQConfig(g, a, d, e, q0, kind, 0, None if pol is None else pol.ctypes.data), pol
-
-
-def _learner_update(b, call, q, obs, act_a, act_b, reward, terminated, next_obs):
-    """a learner's update(): numpy arrays are copied to the device first and freed after the call"""
-    args = (obs, act_a, act_b, reward, terminated, next_obs)
-    dts = (np.uint16, np.int8, np.int8, np.int8, np.uint8, np.uint16)
-    tmp = []
-    if all(isinstance(x, (np.ndarray, list, tuple)) for x in args):
-        host = [np.ascontiguousarray(x, dt).reshape(-1) for x, dt in zip(args, dts)]
-        n = host[0].size
-        assert all(x.size == n for x in host), "the six transition arrays must have one length"
-        assert n <= _lib.MQ_MAX_LANES, "at most 2**22 transitions per update"
-        if n:
-            tmp = [DeviceArray(b, n, dt).upload(x) for x, dt in zip(host, dts)]
-        ptrs = [a.ptr for a in tmp] if n else [None] * 6
-    else:
-        def length(x):
-            return int(np.prod(x.shape)) if hasattr(x, "shape") else None
-        n = length(obs)
-        assert n is not None and all(length(x) == n for x in args), "the six transition arrays must have one length"
-        ptrs = [_ptr(x) for x in args]
-    try:
-        b._check(call(b.h, q, n, *ptrs))
-    finally:
-        if tmp:
-            b.sync()
-            for a in tmp:
-                a.free()
-
-
-class _Learner:
-    """What the six wrappers of a C learner share: they keep the batch and the learner, run() and close().  _C is the prefix
-    of the kind's C entry points: _C + "_create", "_run", "_destroy"."""
-    _C = None
-
-    def _create(self, batch, cfg, *league):
-        """the C learner of a config, whose arrays the caller keeps alive until this returns (create copies what it needs);
-        league: what soccer_q_population_create_league takes between the config and the result"""
-        self.batch, self.q = batch, None
-        q = C.c_void_p()
-        create = getattr(batch.lib, self._C + ("_create_league" if league else "_create"))
-        batch._check(create(batch.h, C.byref(cfg), *league, C.byref(q)))
-        self.q, self.nS = q, batch.nS
-        batch._learners.add(self)
-
-    def run(self, n_steps):
-        """n_steps learner steps (every lane acts, the environment steps, the kind's tables and policies are updated; a
-        population: every member's, from its lane), enqueued."""
-        b = self.batch
-        b._check(getattr(b.lib, self._C + "_run")(b.h, self.q, int(n_steps)))
-        return self
-
-    def close(self):
-        if self.q and self.batch.h:
-            getattr(self.batch.lib, self._C + "_destroy")(self.batch.h, self.q)
-        self.q = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class _Population(_Learner):
-    """What the three populations share: a member per lane with its own discount, ranges of members, update()."""
-
-    def _create(self, batch, cfg, per_member, *league):
-        """per_member: the config function's arrays of per-member hyperparameters (None: the scalar for every member)"""
-        super()._create(batch, cfg, *league)
-        self.n = batch.n
-        gam = per_member["discount_factor"]
-        self.discount_factor = np.full(batch.n, cfg.discount_factor) if gam is None else gam.copy()
-
-    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
-        """One step's update on n transitions, transition i for member i (reward is player A's): DeviceArrays (or device
-        tensors) of n elements, or numpy arrays, which are copied to the device first."""
-        n = self.n
-
-        def call(h, q, count, *ptrs):
-            assert count == n, "a population's update takes one transition per member (%d)" % n
-            return getattr(self.batch.lib, self._C + "_update")(h, q, *ptrs)
-        _learner_update(self.batch, call, self.q, obs, act_a, act_b, reward, terminated, next_obs)
-        return self
-
-    def _range(self, first, count):
-        first = int(first)
-        count = self.n - first if count is None else int(count)
-        assert 0 <= first <= self.n and 0 <= count <= self.n - first, "members %d .. %d + %d are outside the population of %d" % (first, first, count, self.n)
-        return first, count
-
-    def cross_play(self, theta=1e-10, first=0, count=None, discount_factor=None):
-        """What each member's player A scores against each member's player B: (payoff[count, count], iterations) of
-        SoccerBatch.cross_play on pi_a and pi_b (Q-learners: the one-hot greedy policies) of members first ..
-        first + count - 1 (at most 1024).  discount_factor None: the range's common discount, ValueError if the members differ."""
-        return _population_cross_play(self, self._policies, "pi_a", "pi_b", theta, first, count, discount_factor)
-
-    def meta_game(self, theta=1e-10, first=0, count=None, discount_factor=None, max_pivots=None):
-        """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
-        opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
-        return _meta_of_cross_play(self.batch, *self.cross_play(theta, first, count, discount_factor), max_pivots)
-
-    def match_outcomes(self, theta=1e-10, first=0, count=None, continue_prob=None):
-        """How often each member's player A beats each member's player B, how often they draw and how long they play:
-        SoccerBatch.match_outcomes' dict on cross_play's policies of members first .. first + count - 1 (at most 1024).
-        continue_prob None: the range's common discount, ValueError if the members differ."""
-        return _population_match_outcomes(self, self._policies, "pi_a", "pi_b", theta, first, count, continue_prob)
-
-    def occupancy(self, theta=1e-10, first=0, count=None, continue_prob=None, features=None, values=False):
-        """Where each member's player A and each member's player B play their game: SoccerBatch.occupancy's dict on cross_play's
-        policies of members first .. first + count - 1 (at most 1024).  continue_prob None: the range's common discount,
-        ValueError if the members differ."""
-        return _population_occupancy(self, self._policies, "pi_a", "pi_b", theta, first, count, continue_prob, features, values)
-
-
-class MinimaxQLearner(_Learner):
-    """A minimax-Q learner (Littman 1994) on a two-player auto-reset SoccerBatch: one shared Q[nS, 5, 5] on the device,
-    the batch's lanes as actors (include/soccer_hip.h, "learners").  run() enqueues and returns; the properties
-    synchronise and copy."""
-    _C = "soccer_minimax_q"
-
-    def __init__(self, batch, discount_factor, **params):
-        cfg, keep = minimax_q_config(batch.nS, discount_factor, **params)
-        self._create(batch, cfg)
-        del keep                                   # (create has copied the opponent's thresholds)
-        self.discount_factor = float(discount_factor)
-
-    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
-        """One learner step's reduce / update / re-solve on a batch of transitions: DeviceArrays (or device tensors) of one
-        length, or numpy arrays, which are copied to the device first."""
-        _learner_update(self.batch, self.batch.lib.soccer_minimax_q_update, self.q, obs, act_a, act_b, reward, terminated, next_obs)
-        return self
-
-    def read(self):
-        """dict: Q[nS, 5, 5], V[nS], pi_a / pi_b [nS, 5], visits[nS, 25], alpha, steps (synchronises)."""
-        nS, b = self.nS, self.batch
-        out = {"Q": np.zeros((nS, 5, 5)), "V": np.zeros(nS), "pi_a": np.zeros((nS, 5)), "pi_b": np.zeros((nS, 5)),
-               "visits": np.zeros((nS, 25), np.uint64)}
-        al, st = C.c_double(), C.c_uint64()
-        b._check(b.lib.soccer_minimax_q_read(b.h, self.q, *[out[k].ctypes.data for k in ("Q", "V", "pi_a", "pi_b", "visits")],
-                                             C.byref(al), C.byref(st)))
-        out["alpha"], out["steps"] = float(al.value), int(st.value)
-        return out
-
-    def _one(self, key, shape, dtype=np.float64):
-        b = self.batch
-        a = np.zeros(shape, dtype)
-        ptrs = [a.ctypes.data if k == key else None for k in ("Q", "V", "pi_a", "pi_b", "visits")]
-        b._check(b.lib.soccer_minimax_q_read(b.h, self.q, *ptrs, None, None))
-        return a
-
-    Q = property(lambda self: self._one("Q", (self.nS, 5, 5)))
-    V = property(lambda self: self._one("V", self.nS))
-    pi_a = property(lambda self: self._one("pi_a", (self.nS, 5)))
-    pi_b = property(lambda self: self._one("pi_b", (self.nS, 5)))
-    visits = property(lambda self: self._one("visits", (self.nS, 25), np.uint64))
-
-    @property
-    def alpha(self):
-        b, al = self.batch, C.c_double()
-        b._check(b.lib.soccer_minimax_q_read(b.h, self.q, None, None, None, None, None, C.byref(al), None))
-        return float(al.value)
-
-    @property
-    def steps(self):
-        b, st = self.batch, C.c_uint64()
-        b._check(b.lib.soccer_minimax_q_read(b.h, self.q, None, None, None, None, None, None, C.byref(st)))
-        return int(st.value)
-
-    def exploitability(self, theta=1e-10):
-        """How badly the best possible opponent beats the strategies the learner holds now, at its discount:
-        planners.exploitability of (pi_a, pi_b).  Synchronises and copies; run() does not."""
-        from . import planners
-        r = self.read()
-        return planners.exploitability(self.batch, r["pi_a"], r["pi_b"], theta, self.discount_factor)
-
-    def load(self, Q, visits=None, alpha=None, steps=None):
-        """Resume from a checkpoint: Q[nS, 5, 5] in, V and the strategies re-solved on the device.  With `visits` (and the
-        `alpha` / `steps` of read()) a fresh learner continues bit for bit; without, every state is solved."""
-        b = self.batch
-        Q = np.ascontiguousarray(Q, np.float64)
-        assert Q.shape == (self.nS, 5, 5), "Q must be [n_states, 5, 5]"
-        assert (np.abs(Q[1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
-        v = None
-        if visits is not None:
-            v = np.ascontiguousarray(visits, np.uint64)
-            assert v.shape == (self.nS, 25), "visits must be [n_states, 25]"
-        assert alpha is None or 0.0 <= float(alpha) <= 1.0, "alpha must be in [0, 1]"
-        al = None if alpha is None else C.byref(C.c_double(float(alpha)))
-        st = None if steps is None else C.byref(C.c_uint64(int(steps)))
-        b._check(b.lib.soccer_minimax_q_load(b.h, self.q, Q.ctypes.data, None if v is None else v.ctypes.data, al, st))
-        return self
-
-
-def q_learning_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
-    """Checks the parameters of the independent Q-learners (AssertionError, before any library call) and returns
-    (soccer_q_learner_config, the arrays it points into)."""
-    g, a, d, e, q0 = float(discount_factor), float(alpha), float(decay), float(explor), float(q_init)
-    assert 0.0 <= g < 1.0, "discount_factor must be in [0, 1)"
-    assert 0.0 <= a <= 1.0, "alpha must be in [0, 1]"
-    assert 0.0 < d <= 1.0, "decay must be in (0, 1]"
-    assert 0.0 <= e <= 1.0, "explor must be in [0, 1]"
-    assert -1.0 <= q0 <= 1.0, "q_init must be in [-1, 1]"
-    kinds, pols = [], []
-    for name, act in (("act_a", act_a), ("act_b", act_b)):
-        pol = None
-        if isinstance(act, str):
-            assert act in ("greedy", "uniform"), "%s must be 'greedy', 'uniform' or an [nS, 5] mixed policy" % name
-            kinds.append(_lib.QL_GREEDY if act == "greedy" else _lib.QL_UNIFORM)
-        else:
-            pol = np.ascontiguousarray(act, np.float64)
-            assert pol.shape == (int(nS), 5) and (pol >= 0).all() and np.allclose(pol.sum(1), 1.0), \
-                "a fixed %s must be [n_states, 5] rows summing to 1" % name
-            kinds.append(_lib.QL_FIXED)
-        pols.append(pol)
-    return _lib.QLearnerConfig(g, a, d, e, q0, kinds[0], kinds[1], *[None if x is None else x.ctypes.data for x in pols]), pols
-
-
-class QLearner(_Learner):
-    """Independent Q-learners for both players (Littman 1994's baseline and challenger) on a two-player auto-reset
-    SoccerBatch: Q_a[nS, 5] and Q_b[nS, 5] (player B's in its own reward) on the device, the batch's lanes as actors
-    (include/soccer_hip.h, "learners, independent Q").  run() enqueues and returns; read() and the properties synchronise
-    and copy."""
-    _C = "soccer_q_learner"
-
-    def __init__(self, batch, discount_factor, **params):
-        cfg, keep = q_learning_config(batch.nS, discount_factor, **params)
-        self._create(batch, cfg)
-        del keep                                   # (create has copied the fixed policies' thresholds)
-        self.discount_factor = float(discount_factor)
-
-    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
-        """One learner step's reduce / update on a batch of transitions (reward is player A's): DeviceArrays (or device
-        tensors) of one length, or numpy arrays, which are copied to the device first."""
-        _learner_update(self.batch, self.batch.lib.soccer_q_learner_update, self.q, obs, act_a, act_b, reward, terminated, next_obs)
-        return self
-
-    def read(self):
-        """dict: Q_a / Q_b [nS, 5], V_a / V_b [nS] (the row maxima), pi_a / pi_b [nS, 5] (one-hot of the first greedy action:
-        they plug into rollout(mixed_policies=...) and planners.exploitability as they are; row 0, the terminal observation,
-        is whatever argmax of zeros gives and is never read), visits[nS, 25], alpha, steps.  Synchronises."""
-        nS, b = self.nS, self.batch
-        out = {"Q_a": np.zeros((nS, 5)), "Q_b": np.zeros((nS, 5)), "visits": np.zeros((nS, 25), np.uint64)}
-        al, st = C.c_double(), C.c_uint64()
-        b._check(b.lib.soccer_q_learner_read(b.h, self.q, *[out[k].ctypes.data for k in ("Q_a", "Q_b", "visits")],
-                                             C.byref(al), C.byref(st)))
-        for p in "ab":
-            out["V_" + p] = out["Q_" + p].max(1)
-            out["pi_" + p] = np.eye(5)[out["Q_" + p].argmax(1)]
-        out["alpha"], out["steps"] = float(al.value), int(st.value)
-        return out
-
-    @property
-    def alpha(self):
-        b, al = self.batch, C.c_double()
-        b._check(b.lib.soccer_q_learner_read(b.h, self.q, None, None, None, C.byref(al), None))
-        return float(al.value)
-
-    @property
-    def steps(self):
-        b, st = self.batch, C.c_uint64()
-        b._check(b.lib.soccer_q_learner_read(b.h, self.q, None, None, None, None, C.byref(st)))
-        return int(st.value)
-
-    def exploitability(self, theta=1e-10):
-        """How badly the best possible opponent beats the greedy pair the learners hold now, at their discount:
-        planners.exploitability of (pi_a, pi_b).  Synchronises and copies; run() does not."""
-        from . import planners
-        r = self.read()
-        return planners.exploitability(self.batch, r["pi_a"], r["pi_b"], theta, self.discount_factor)
-
-    def load(self, Q_a, Q_b, visits=None, alpha=None, steps=None):
-        """Resume from a checkpoint: Q_a / Q_b [nS, 5] in; everything derived from them is recomputed on the device.  With
-        the `visits`, `alpha` and `steps` of read() a fresh learner continues bit for bit; without `visits` the counts are
-        zeroed."""
-        b = self.batch
-        Q = [np.ascontiguousarray(x, np.float64) for x in (Q_a, Q_b)]
-        for x in Q:
-            assert x.shape == (self.nS, 5), "Q_a / Q_b must be [n_states, 5]"
-            assert (np.abs(x[1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
-        v = None
-        if visits is not None:
-            v = np.ascontiguousarray(visits, np.uint64)
-            assert v.shape == (self.nS, 25), "visits must be [n_states, 25]"
-        assert alpha is None or 0.0 <= float(alpha) <= 1.0, "alpha must be in [0, 1]"
-        al = None if alpha is None else C.byref(C.c_double(float(alpha)))
-        st = None if steps is None else C.byref(C.c_uint64(int(steps)))
-        b._check(b.lib.soccer_q_learner_load(b.h, self.q, Q[0].ctypes.data, Q[1].ctypes.data, None if v is None else v.ctypes.data, al, st))
-        return self
-
-
-def league_config(nS, act_a, act_b, league_policies, league_weights):
-    """Checks a league (AssertionError, before any library call): exactly one of act_a / act_b is "league", and then
-    league_policies is [K, nS, 5] rows summing to 1 and league_weights [K] values >= 0 summing to 1, K in 1 .. 1024.
-    Returns None without a league, else (player, K, policies, weights) with the arrays contiguous float64."""
-    sides = [isinstance(a, str) and a == "league" for a in (act_a, act_b)]
-    if not any(sides):
-        assert league_policies is None and league_weights is None, "league_policies / league_weights go with act_a or act_b = 'league'"
-        return None
-    assert not all(sides), "exactly one player may be a league, not both"
-    assert league_policies is not None and league_weights is not None, "a league needs league_policies [K, n_states, 5] and league_weights [K]"
-    pol = np.ascontiguousarray(league_policies, np.float64)
-    w = np.ascontiguousarray(league_weights, np.float64)
-    assert pol.ndim == 3 and pol.shape[1:] == (int(nS), 5), "league_policies must be [K, n_states, 5]"
-    K = pol.shape[0]
-    assert 1 <= K <= _lib.LEAGUE_MAX_POLICIES, "a league holds 1 .. %d policies, not %d" % (_lib.LEAGUE_MAX_POLICIES, K)
-    assert w.shape == (K,), "league_weights must hold one weight per league policy (%d)" % K
-    bad = np.flatnonzero(~(np.isfinite(w) & (w >= 0)))
-    assert bad.size == 0, "league_weights[%d] is negative or not a finite number" % (bad[0] if bad.size else -1)
-    assert np.allclose(w.sum(), 1.0), "league_weights does not sum to 1"
-    rows = (pol >= 0).all(2) & np.isclose(pol.sum(2), 1.0)
-    bad = np.argwhere(~rows)
-    assert bad.size == 0, "league_policies[%d][%d] is not a row >= 0 summing to 1" % (tuple(bad[0]) if bad.size else (-1, -1))
-    return sides.index(True), K, pol, w
-
-
-def q_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy",
-                        league=None):
-    """Checks the parameters of a population of Q-learners (AssertionError, before any library call) and returns
-    (soccer_q_population_config, the arrays it points into).  discount_factor, alpha, decay and explor are scalars for every
-    member or arrays of n, one value per member.  league: league_config's tuple, or None; its player is SOCCER_QL_FIXED
-    with a NULL policy in the config."""
-    if league is not None:                      # (the other checks see a placeholder for the league's player)
-        act_a, act_b = ("uniform", act_b) if league[0] == 0 else (act_a, "uniform")
-    ranges = (("discount_factor", discount_factor, lambda x: (0.0 <= x) & (x < 1.0), "[0, 1)"),
-              ("alpha", alpha, lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
-              ("decay", decay, lambda x: (0.0 < x) & (x <= 1.0), "(0, 1]"),
-              ("explor", explor, lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"))
-    scalars, arrays = {}, {}
-    for name, value, ok, rng in ranges:
-        if np.ndim(value) == 0:
-            scalars[name], arrays[name] = float(value), None
-            assert ok(scalars[name]), "%s must be in %s" % (name, rng)
-        else:
-            a = np.ascontiguousarray(value, np.float64)
-            assert a.shape == (int(n),), "a per-member %s must have one value per lane (%d)" % (name, n)
-            assert ok(a).all(), "every per-member %s must be in %s" % (name, rng)
-            scalars[name], arrays[name] = float(a[0]), a
-    # (the scalar checks of q_learning_config hold for the kinds, the fixed policies and q_init)
-    base, pols = q_learning_config(nS, scalars["discount_factor"], scalars["alpha"], scalars["decay"], scalars["explor"], q_init, act_a, act_b)
-    cfg = _lib.QPopulationConfig(base.discount_factor, base.alpha, base.decay, base.explor, base.q_init, base.act_a, base.act_b,
-                                 base.policy_a, base.policy_b,
-                                 *[None if arrays[k] is None else arrays[k].ctypes.data for k in ("alpha", "decay", "explor", "discount_factor")])
-    if league is not None:
-        setattr(cfg, "act_b" if league[0] else "act_a", _lib.QL_FIXED)
-    return cfg, (pols, arrays)
-
-
-def _population_cross_play(pop, read, key_a, key_b, theta, first, count, discount_factor):
-    """Members first .. first + count - 1 of a population against one another (SoccerBatch.cross_play): player A's policies
-    read(first, count)[key_a] meet the same members' player-B policies [key_b], read in chunks of at most 256 members."""
-    pa, pb, discount_factor = _population_sides(pop, read, key_a, key_b, first, count, discount_factor, "cross_play", "discount_factor")
-    return pop.batch.cross_play(pa, pb, theta, discount_factor)
-
-
-def _population_match_outcomes(pop, read, key_a, key_b, theta, first, count, continue_prob):
-    """_population_cross_play's members and policies through SoccerBatch.match_outcomes; continue_prob None: the range's
-    common discount"""
-    pa, pb, continue_prob = _population_sides(pop, read, key_a, key_b, first, count, continue_prob, "match_outcomes", "continue_prob")
-    return pop.batch.match_outcomes(pa, pb, theta, continue_prob)
-
-
-def _population_occupancy(pop, read, key_a, key_b, theta, first, count, continue_prob, features, values):
-    """_population_cross_play's members and policies through SoccerBatch.occupancy; continue_prob None: the range's common
-    discount"""
-    pa, pb, continue_prob = _population_sides(pop, read, key_a, key_b, first, count, continue_prob, "occupancy", "continue_prob")
-    return pop.batch.occupancy(pa, pb, theta, continue_prob, features=features, values=values)
-
-
-def _population_sides(pop, read, key_a, key_b, first, count, discount, what, name):
-    """(pi_a[count, nS, 5], pi_b[count, nS, 5], the discount) of members first .. first + count - 1; discount None: the one
-    they share, ValueError if they differ"""
-    first, count = pop._range(first, count)
-    assert 1 <= count <= _lib.CROSS_MAX_POLICIES, "%s takes 1 .. %d members, not %d" % (what, _lib.CROSS_MAX_POLICIES, count)
-    gam = pop.discount_factor[first:first + count]
-    if discount is None:
-        other = np.flatnonzero(gam != gam[0])
-        if other.size:
-            raise ValueError("members %d and %d have different discounts (%r and %r): pass %s" % (
-                first, first + other[0], float(gam[0]), float(gam[other[0]]), name))
-        discount = float(gam[0])
-    pa = np.zeros((count, pop.nS, 5)); pb = np.zeros((count, pop.nS, 5))
-    for c0 in range(0, count, _lib.BR_MAX_POLICIES):
-        c = min(_lib.BR_MAX_POLICIES, count - c0)
-        r = read(first + c0, c)
-        pa[c0:c0 + c] = r[key_a]; pb[c0:c0 + c] = r[key_b]
-    return pa, pb, float(discount)
+from .learners import (GradientPlay, MinimaxQLearner, MinimaxQPopulation, OpponentModelPopulation, QLearner, QPopulation,  # noqa: F401
+                       WolfPHCLearner, WolfPopulation, _meta_of_cross_play, league_config, minimax_q_config,
+                       minimax_q_population_config, om_derive, om_model, om_population_config, q_learning_config,
+                       q_population_config, wolf_phc_config, wolf_population_config)
 
 
 def meta_lds_bytes(n_a, n_b):
@@ -501,792 +22,6 @@ def meta_lds_bytes(n_a, n_b):
     path=1 of solve_meta_game needs this to be at most the device's limit, 163 840 bytes on gfx950."""
     stride = (n_a + n_b + 2) | 1
     return 128 + 8 * ((n_a + 2) * stride + n_a + 1) + 4 * n_a
-
-
-def _meta_of_cross_play(batch, payoff, iterations, max_pivots):
-    """cross-play's dict (planners.cross_play) plus the solved meta-game and what mixing buys player A"""
-    row_min, col_max = payoff.min(1), payoff.max(0)
-    out = {"payoff": payoff, "iterations": iterations, "row_min": row_min, "col_max": col_max,
-           "bounds": (float(row_min.max()), float(col_max.min()))}
-    m = batch.solve_meta_game(payoff, max_pivots=max_pivots)
-    out.update({k: m[k] for k in ("x", "y", "value", "lo", "hi", "status")})
-    out["gain"] = out["lo"] - out["bounds"][0]
-    return out
-
-
-class QPopulation(_Population):
-    """A population of independent Q-learners on a two-player auto-reset SoccerBatch, a learner per lane: member i has its own
-    Q_a[nS, 5], Q_b[nS, 5] and alpha and learns from lane i alone (include/soccer_hip.h, "learners, a population of
-    independent Q-learners").  run() enqueues and returns; read() and the properties synchronise and copy.  Whole populations
-    run to gigabytes, so read(), load() and exploitability() take a range of members."""
-    _C = "soccer_q_population"
-
-    def __init__(self, batch, discount_factor, league_policies=None, league_weights=None, **params):
-        lg = league_config(batch.nS, params.get("act_a", "greedy"), params.get("act_b", "greedy"), league_policies, league_weights)
-        cfg, keep = q_population_config(batch.n, batch.nS, discount_factor, league=lg, **params)
-        self.league, self.n_policies = (None, 0) if lg is None else lg[:2]      # the league's player (0 = A, 1 = B) and its K
-        self._create(batch, cfg, keep[1], *(() if lg is None else (lg[0], lg[1], lg[2].ctypes.data, lg[3].ctypes.data)))
-        del keep                                   # (create has copied the parameters and the fixed policies' thresholds)
-
-    def _policies(self, first, count):
-        return self.read(first, count)
-
-    def read(self, first=0, count=None):
-        """dict for members first .. first + count - 1 (count None: to the end): Q_a / Q_b [count, nS, 5], V_a / V_b
-        [count, nS] (the row maxima), pi_a / pi_b [count, nS, 5] (one-hot of the first greedy action), alpha[count], steps.
-        Synchronises."""
-        first, count = self._range(first, count)
-        nS, b = self.nS, self.batch
-        out = {"Q_a": np.zeros((count, nS, 5)), "Q_b": np.zeros((count, nS, 5)), "alpha": np.zeros(count)}
-        st = C.c_uint64()
-        b._check(b.lib.soccer_q_population_read(b.h, self.q, first, count, *[out[k].ctypes.data for k in ("Q_a", "Q_b", "alpha")], C.byref(st)))
-        for p in "ab":
-            out["V_" + p] = out["Q_" + p].max(2)
-            out["pi_" + p] = np.eye(5)[out["Q_" + p].argmax(2)]
-        out["steps"] = int(st.value)
-        return out
-
-    @property
-    def alpha(self):
-        """every member's learning rate, [n]"""
-        b, al = self.batch, np.zeros(self.n)
-        b._check(b.lib.soccer_q_population_read(b.h, self.q, 0, self.n, None, None, al.ctypes.data, None))
-        return al
-
-    @property
-    def steps(self):
-        b, st = self.batch, C.c_uint64()
-        b._check(b.lib.soccer_q_population_read(b.h, self.q, 0, 0, None, None, None, C.byref(st)))
-        return int(st.value)
-
-    def exploitability(self, theta=1e-10, first=0, count=None):
-        """How badly the best possible opponent beats the greedy pair of each member of a range, at that member's discount:
-        the one-hot greedy policies go through SoccerBatch.best_response in batches of at most 256 members with one
-        discount.  Returns {"v_a", "v_b", "gap"}, arrays of [count, nS] (planners.exploitability's per member)."""
-        first, count = self._range(first, count)
-        b = self.batch
-        out = {k: np.zeros((count, self.nS)) for k in ("v_a", "v_b", "gap")}
-        for c0 in range(0, count, _lib.BR_MAX_POLICIES):
-            c = min(_lib.BR_MAX_POLICIES, count - c0)
-            r = self.read(first + c0, c)
-            gam = self.discount_factor[first + c0:first + c0 + c]
-            for g in np.unique(gam):                # (one solve per discount in the chunk: a batch shares its discount)
-                idx = np.flatnonzero(gam == g)
-                out["v_a"][c0 + idx] = b.best_response(r["pi_a"][idx], 0, theta, float(g))[1]
-                out["v_b"][c0 + idx] = b.best_response(r["pi_b"][idx], 1, theta, float(g))[1]
-        out["gap"] = out["v_b"] - out["v_a"]
-        return out
-
-    def picks(self, first=0, count=None):
-        """A league population's picks, int32[count]: the league policy each member's lane follows until its episode ends,
-        -1 where the next step draws one.  Synchronises.  AssertionError on a population without a league."""
-        first, count = self._range(first, count)
-        b, out = self.batch, np.zeros(count, np.int32)
-        b._check(b.lib.soccer_q_population_league_read(b.h, self.q, first, count, out.ctypes.data))
-        return out
-
-    def load_picks(self, picks, first=0):
-        """Resume the picks of members first .. first + len(picks) - 1: values in -1 .. K - 1, -1 forces a draw at the next
-        step.  With read() + picks() a fresh population continues bit for bit via load() + load_picks(), mid-episode
-        included.  A refused load changes nothing."""
-        p = np.ascontiguousarray(picks, np.int32)
-        assert p.ndim == 1, "picks must be a vector, one value per member"
-        first, count = self._range(first, p.shape[0])
-        b = self.batch
-        b._check(b.lib.soccer_q_population_league_load(b.h, self.q, first, count, p.ctypes.data))
-        return self
-
-    def load(self, Q_a=None, Q_b=None, alpha=None, steps=None, first=0):
-        """Resume members first .. first + count - 1 from a checkpoint: Q_a / Q_b [count, nS, 5] in [-1, 1] and alpha[count]
-        (count is what the arrays hold; None = unchanged), steps for the population.  With what read() gave, a fresh
-        population continues bit for bit.  A refused load changes nothing."""
-        b = self.batch
-        arrs = [None if x is None else np.ascontiguousarray(x, np.float64) for x in (Q_a, Q_b, alpha)]
-        counts = {x.shape[0] for x in arrs if x is not None and x.ndim >= 1}
-        assert len(counts) <= 1, "Q_a, Q_b and alpha must hold the same number of members"
-        first, count = self._range(first, counts.pop() if counts else 0)
-        for x in arrs[:2]:
-            if x is not None:
-                assert x.shape == (count, self.nS, 5), "Q_a / Q_b must be [count, n_states, 5]"
-                assert (np.abs(x[:, 1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
-        if arrs[2] is not None:
-            assert arrs[2].shape == (count,) and ((arrs[2] >= 0.0) & (arrs[2] <= 1.0)).all(), "alpha must be [count] values in [0, 1]"
-        st = None if steps is None else C.byref(C.c_uint64(int(steps)))
-        b._check(b.lib.soccer_q_population_load(b.h, self.q, first, count, *[None if x is None else x.ctypes.data for x in arrs], st))
-        return self
-
-
-def om_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
-    """Checks the parameters of a population of opponent-modelling Q-learners (AssertionError, before any library call) and
-    returns (soccer_om_population_config, the arrays it points into): q_population_config's checks and layout, no league."""
-    cfg, keep = q_population_config(n, nS, discount_factor, alpha, decay, explor, q_init, act_a, act_b)
-    return _lib.OMPopulationConfig.from_buffer_copy(cfg), keep
-
-
-def om_derive(Q, counts):
-    """The derived values of an opponent-modelling Q-learner by the definition's expression (include/soccer_hip.h, "learners, a
-    population of opponent-modelling Q-learners"), operation for operation, so they equal the device's: Q [..., 5, 5] (own
-    action, other's action) and counts [..., 5] (uint64) -> (V [...], g [...])."""
-    Q = np.asarray(Q, np.float64); counts = np.asarray(counts, np.uint64)
-    n = counts.sum(-1, dtype=np.uint64)
-    w = np.where((n > 0)[..., None], counts.astype(np.float64), 1.0)
-    N = np.where(n > 0, n.astype(np.float64), 5.0)
-    W = w[..., None, 0] * Q[..., 0]
-    for k in range(1, 5):
-        W = W + w[..., None, k] * Q[..., k]
-    g = W.argmax(-1)                                # the first index that attains the maximum
-    V = np.minimum(1.0, np.maximum(-1.0, np.take_along_axis(W, g[..., None], -1)[..., 0] / N))
-    return V, g
-
-
-def om_model(counts):
-    """Counts [..., 5] of a player's actions as a mixed policy: the frequencies, 0.2 where nothing was seen; renormalised in
-    float64 so that a row whose quotients sum an ulp off 1 is a policy row to the library."""
-    c = np.asarray(counts, np.uint64).astype(np.float64)
-    n = c.sum(-1, keepdims=True)
-    m = np.where(n > 0, c / np.where(n > 0, n, 1.0), 0.2)
-    return m / m.sum(-1, keepdims=True)
-
-
-class OpponentModelPopulation(_Population):
-    """A population of opponent-modelling Q-learners (joint-action learners; fictitious play in self-play) on a two-player
-    auto-reset SoccerBatch, a learner per lane: member i has, per player, a joint-action table Q[nS, 5, 5] over (own action,
-    the other's action) in that player's own reward and the counts C[nS, 5] of the other player's actions, and its alpha, and
-    learns from lane i alone (include/soccer_hip.h, "learners, a population of opponent-modelling Q-learners").  A player
-    answers the other's empirical frequencies greedily.  run() enqueues and returns; read() and the properties synchronise and
-    copy.  read(), load() and exploitability() take a range of members (a member is 390 KB on 5x4)."""
-    _C = "soccer_om_population"
-    _WHICH = {"greedy": ("pi_a", "pi_b"), "model": ("model_a", "model_b")}
-
-    def __init__(self, batch, discount_factor, **params):
-        cfg, keep = om_population_config(batch.n, batch.nS, discount_factor, **params)
-        self._create(batch, cfg, keep[1])
-        del keep                                   # (create has copied the parameters and the fixed policies' thresholds)
-
-    def _read(self, first, count, keys):
-        """the library's arrays alone: any of Q_a, Q_b, C_a, C_b, alpha, steps"""
-        nS, b = self.nS, self.batch
-        shapes = {"Q_a": ((count, nS, 5, 5), np.float64), "Q_b": ((count, nS, 5, 5), np.float64), "C_a": ((count, nS, 5), np.uint64),
-                  "C_b": ((count, nS, 5), np.uint64), "alpha": ((count,), np.float64)}
-        out = {k: np.zeros(*shapes[k]) for k in keys if k != "steps"}
-        st = C.c_uint64()
-        b._check(b.lib.soccer_om_population_read(b.h, self.q, first, count, *[out[k].ctypes.data if k in out else None for k in shapes],
-                                                 C.byref(st) if "steps" in keys else None))
-        if "steps" in keys:
-            out["steps"] = int(st.value)
-        return out
-
-    def read(self, first=0, count=None):
-        """dict for members first .. first + count - 1 (count None: to the end): Q_a / Q_b [count, nS, 5, 5], C_a / C_b
-        [count, nS, 5] (uint64), alpha[count], steps; and, computed here by the definition's expression, V_a / V_b [count, nS]
-        and pi_a / pi_b [count, nS, 5] (one-hot of g); and model_a = C_b as frequencies (what B has seen A play; 0.2 where
-        nothing was seen), model_b = C_a likewise.  Synchronises."""
-        first, count = self._range(first, count)
-        out = self._read(first, count, ("Q_a", "Q_b", "C_a", "C_b", "alpha", "steps"))
-        for p, other in (("a", "b"), ("b", "a")):
-            out["V_" + p], g = om_derive(out["Q_" + p], out["C_" + p])
-            out["pi_" + p] = np.eye(5)[g]
-            out["model_" + p] = om_model(out["C_" + other])
-        return out
-
-    alpha = property(lambda self: self._read(0, self.n, ("alpha",))["alpha"], doc="every member's learning rate, [n]")
-    steps = property(lambda self: self._read(0, 0, ("steps",))["steps"])
-
-    def exploitability(self, which="greedy", theta=1e-10, first=0, count=None):
-        """How badly the best possible opponent beats the pair of greedy policies (which='greedy') or the pair of models
-        (which='model': model_a, what B has seen A play, with model_b) of each member of a range, at that member's discount:
-        through SoccerBatch.best_response in batches of at most 256 members with one discount.  Returns {"v_a", "v_b", "gap"},
-        arrays of [count, nS] (planners.exploitability's per member)."""
-        assert which in self._WHICH, "which must be 'greedy' or 'model'"
-        ka, kb = self._WHICH[which]
-        first, count = self._range(first, count)
-        b = self.batch
-        out = {k: np.zeros((count, self.nS)) for k in ("v_a", "v_b", "gap")}
-        for c0 in range(0, count, _lib.BR_MAX_POLICIES):
-            c = min(_lib.BR_MAX_POLICIES, count - c0)
-            r = self.read(first + c0, c)
-            gam = self.discount_factor[first + c0:first + c0 + c]
-            for g in np.unique(gam):                # (one solve per discount in the chunk: a batch shares its discount)
-                idx = np.flatnonzero(gam == g)
-                out["v_a"][c0 + idx] = b.best_response(r[ka][idx], 0, theta, float(g))[1]
-                out["v_b"][c0 + idx] = b.best_response(r[kb][idx], 1, theta, float(g))[1]
-        out["gap"] = out["v_b"] - out["v_a"]
-        return out
-
-    def cross_play(self, which="greedy", theta=1e-10, first=0, count=None, discount_factor=None):
-        """What each member's player A scores against each member's player B: (payoff[count, count], iterations) of
-        SoccerBatch.cross_play on the greedy policies (which='greedy') or the models (which='model') of members first ..
-        first + count - 1 (at most 1024).  discount_factor None: the range's common discount, ValueError if the members differ."""
-        assert which in self._WHICH, "which must be 'greedy' or 'model'"
-        return _population_cross_play(self, self.read, *self._WHICH[which], theta, first, count, discount_factor)
-
-    def meta_game(self, which="greedy", theta=1e-10, first=0, count=None, discount_factor=None, max_pivots=None):
-        """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
-        opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
-        return _meta_of_cross_play(self.batch, *self.cross_play(which, theta, first, count, discount_factor), max_pivots)
-
-    def match_outcomes(self, which="greedy", theta=1e-10, first=0, count=None, continue_prob=None):
-        """How often each member's player A beats each member's player B, how often they draw and how long they play:
-        SoccerBatch.match_outcomes' dict on cross_play's policies (which) of members first .. first + count - 1 (at most 1024).
-        continue_prob None: the range's common discount, ValueError if the members differ."""
-        assert which in self._WHICH, "which must be 'greedy' or 'model'"
-        return _population_match_outcomes(self, self.read, *self._WHICH[which], theta, first, count, continue_prob)
-
-    def occupancy(self, which="greedy", theta=1e-10, first=0, count=None, continue_prob=None, features=None, values=False):
-        """Where each member's player A and each member's player B play their game: SoccerBatch.occupancy's dict on cross_play's
-        policies (which) of members first .. first + count - 1 (at most 1024).  continue_prob None: the range's common discount,
-        ValueError if the members differ."""
-        assert which in self._WHICH, "which must be 'greedy' or 'model'"
-        return _population_occupancy(self, self.read, *self._WHICH[which], theta, first, count, continue_prob, features, values)
-
-    def load(self, Q_a=None, Q_b=None, C_a=None, C_b=None, alpha=None, steps=None, first=0):
-        """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged): Q_a /
-        Q_b [count, nS, 5, 5] in [-1, 1], C_a / C_b [count, nS, 5] counts, alpha[count], steps for the population.  V and the
-        greedy actions follow on the device.  With what read() gave, a fresh population continues bit for bit.  A refused
-        load changes nothing."""
-        b = self.batch
-        arrs = [None if x is None else np.ascontiguousarray(x, dt) for x, dt in
-                zip((Q_a, Q_b, C_a, C_b, alpha), (np.float64, np.float64, np.uint64, np.uint64, np.float64))]
-        counts = {x.shape[0] for x in arrs if x is not None and x.ndim >= 1}
-        assert len(counts) <= 1, "Q_a, Q_b, C_a, C_b and alpha must hold the same number of members"
-        first, count = self._range(first, counts.pop() if counts else 0)
-        for x in arrs[:2]:
-            if x is not None:
-                assert x.shape == (count, self.nS, 5, 5), "Q_a / Q_b must be [count, n_states, 5, 5]"
-                assert (np.abs(x[:, 1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
-        for x in arrs[2:4]:
-            assert x is None or x.shape == (count, self.nS, 5), "C_a / C_b must be [count, n_states, 5]"
-        if arrs[4] is not None:
-            assert arrs[4].shape == (count,) and ((arrs[4] >= 0.0) & (arrs[4] <= 1.0)).all(), "alpha must be [count] values in [0, 1]"
-        st = None if steps is None else C.byref(C.c_uint64(int(steps)))
-        b._check(b.lib.soccer_om_population_load(b.h, self.q, first, count, *[None if x is None else x.ctypes.data for x in arrs], st))
-        return self
-
-
-def wolf_phc_config(nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
-                    delta_decay=1.0, act_a="learn", act_b="learn"):
-    """Checks the parameters of the policy hill-climbers (AssertionError, before any library call) and returns
-    (soccer_wolf_phc_config, the arrays it points into)."""
-    g, a, d, e, q0 = float(discount_factor), float(alpha), float(decay), float(explor), float(q_init)
-    dw, dl, dd = float(delta_win), float(delta_lose), float(delta_decay)
-    assert 0.0 <= g < 1.0, "discount_factor must be in [0, 1)"
-    assert 0.0 <= a <= 1.0, "alpha must be in [0, 1]"
-    assert 0.0 < d <= 1.0, "decay must be in (0, 1]"
-    assert 0.0 <= e <= 1.0, "explor must be in [0, 1]"
-    assert -1.0 <= q0 <= 1.0, "q_init must be in [-1, 1]"
-    assert 0.0 <= dw <= 1.0, "delta_win must be in [0, 1]"
-    assert 0.0 <= dl <= 1.0, "delta_lose must be in [0, 1]"
-    assert 0.0 < dd <= 1.0, "delta_decay must be in (0, 1]"
-    kinds, pols = [], []
-    for name, act in (("act_a", act_a), ("act_b", act_b)):
-        pol = None
-        if isinstance(act, str):
-            assert act in ("learn", "uniform"), "%s must be 'learn', 'uniform' or an [nS, 5] mixed policy" % name
-            kinds.append(_lib.PHC_LEARN if act == "learn" else _lib.PHC_UNIFORM)
-        else:
-            pol = np.ascontiguousarray(act, np.float64)
-            assert pol.shape == (int(nS), 5) and (pol >= 0).all() and np.allclose(pol.sum(1), 1.0), \
-                "a fixed %s must be [n_states, 5] rows summing to 1" % name
-            kinds.append(_lib.PHC_FIXED)
-        pols.append(pol)
-    return _lib.WolfPHCConfig(g, a, d, e, q0, dw, dl, dd, kinds[0], kinds[1], *[None if x is None else x.ctypes.data for x in pols]), pols
-
-
-class WolfPHCLearner(_Learner):
-    """Policy hill-climbers for both players (PHC and WoLF-PHC, Bowling & Veloso 2002) on a two-player auto-reset
-    SoccerBatch: the Q-learners' two tables plus a mixed policy pi_p[nS, 5] and its running average avg_p per player on
-    the device, the batch's lanes as actors (include/soccer_hip.h, "learners, policy hill-climbing").  run() enqueues
-    and returns; read() and the properties synchronise and copy."""
-    _C = "soccer_wolf_phc"
-    _ROWS = ("Q_a", "Q_b", "pi_a", "pi_b", "avg_a", "avg_b")
-
-    def __init__(self, batch, discount_factor, **params):
-        cfg, keep = wolf_phc_config(batch.nS, discount_factor, **params)
-        self._create(batch, cfg)
-        del keep                                   # (create has copied the fixed policies)
-        self.discount_factor = float(discount_factor)
-
-    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
-        """One learner step's reduce / update / policy step on a batch of transitions (reward is player A's): DeviceArrays
-        (or device tensors) of one length, or numpy arrays, which are copied to the device first."""
-        _learner_update(self.batch, self.batch.lib.soccer_wolf_phc_update, self.q, obs, act_a, act_b, reward, terminated, next_obs)
-        return self
-
-    def read(self):
-        """dict: Q_a / Q_b, pi_a / pi_b, avg_a / avg_b [nS, 5], V_a / V_b [nS] (the row maxima, computed here), visits[nS, 25],
-        updates[nS], alpha, dscale, steps.  The policies plug into rollout(mixed_policies=...) and planners.exploitability
-        as they are.  Synchronises."""
-        nS, b = self.nS, self.batch
-        out = {k: np.zeros((nS, 5)) for k in self._ROWS}
-        out["visits"] = np.zeros((nS, 25), np.uint64); out["updates"] = np.zeros(nS, np.uint64)
-        al, ds, st = C.c_double(), C.c_double(), C.c_uint64()
-        state = _lib.WolfPHCState(*[out[k].ctypes.data for k in self._ROWS + ("visits", "updates")],
-                                  C.pointer(al), C.pointer(ds), C.pointer(st))
-        b._check(b.lib.soccer_wolf_phc_read(b.h, self.q, C.byref(state)))
-        for p in "ab":
-            out["V_" + p] = out["Q_" + p].max(1)
-        out["alpha"], out["dscale"], out["steps"] = float(al.value), float(ds.value), int(st.value)
-        return out
-
-    def _scalar(self, name, ctype):
-        b, v = self.batch, ctype()
-        state = _lib.WolfPHCState(**{name: C.pointer(v)})
-        b._check(b.lib.soccer_wolf_phc_read(b.h, self.q, C.byref(state)))
-        return v.value
-
-    alpha = property(lambda self: float(self._scalar("alpha", C.c_double)))
-    dscale = property(lambda self: float(self._scalar("dscale", C.c_double)))
-    steps = property(lambda self: int(self._scalar("steps", C.c_uint64)))
-
-    def exploitability(self, which="pi", theta=1e-10):
-        """How badly the best possible opponent beats the pair of policies (which='pi') or of average policies
-        (which='avg') the learners hold now, at their discount: planners.exploitability.  Synchronises and copies."""
-        from . import planners
-        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
-        r = self.read()
-        return planners.exploitability(self.batch, r[which + "_a"], r[which + "_b"], theta, self.discount_factor)
-
-    def load(self, Q_a, Q_b, pi_a=None, pi_b=None, avg_a=None, avg_b=None, visits=None, updates=None, alpha=None, dscale=None,
-             steps=None):
-        """Resume from a checkpoint: everything derived is recomputed on the device.  With all of read()'s arrays and
-        scalars a fresh learner continues bit for bit.  A policy array that is None is left as it is (those of a player
-        that does not learn are ignored); without `visits` / `updates` the counts are zeroed."""
-        b = self.batch
-        rows = {"Q_a": Q_a, "Q_b": Q_b, "pi_a": pi_a, "pi_b": pi_b, "avg_a": avg_a, "avg_b": avg_b}
-        keep = {}
-        for k, x in rows.items():
-            if x is None:
-                assert not k.startswith("Q"), "Q_a / Q_b are required"
-                continue
-            x = keep[k] = np.ascontiguousarray(x, np.float64)
-            assert x.shape == (self.nS, 5), "%s must be [n_states, 5]" % k
-            if k.startswith("Q"):
-                assert (np.abs(x[1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
-        for k, x, shape in (("visits", visits, (self.nS, 25)), ("updates", updates, (self.nS,))):
-            if x is not None:
-                keep[k] = np.ascontiguousarray(x, np.uint64)
-                assert keep[k].shape == shape, "%s must be %r" % (k, list(shape))
-        assert alpha is None or 0.0 <= float(alpha) <= 1.0, "alpha must be in [0, 1]"
-        assert dscale is None or 0.0 <= float(dscale) <= 1.0, "dscale must be in [0, 1]"
-        state = _lib.WolfPHCState(**{k: x.ctypes.data for k, x in keep.items()})
-        if alpha is not None:
-            state.alpha = C.pointer(C.c_double(float(alpha)))
-        if dscale is not None:
-            state.dscale = C.pointer(C.c_double(float(dscale)))
-        if steps is not None:
-            state.steps = C.pointer(C.c_uint64(int(steps)))
-        b._check(b.lib.soccer_wolf_phc_load(b.h, self.q, C.byref(state)))
-        return self
-
-
-_WOLF_HYPER = (("discount_factor", lambda x: (0.0 <= x) & (x < 1.0), "[0, 1)"), ("alpha", lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
-               ("decay", lambda x: (0.0 < x) & (x <= 1.0), "(0, 1]"), ("explor", lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
-               ("delta_win", lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"), ("delta_lose", lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
-               ("delta_decay", lambda x: (0.0 < x) & (x <= 1.0), "(0, 1]"))
-
-
-def wolf_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, delta_win=0.01,
-                           delta_lose=0.04, delta_decay=1.0, act_a="learn", act_b="learn"):
-    """Checks the parameters of a population of policy hill-climbers (AssertionError, before any library call) and returns
-    (soccer_wolf_population_config, the arrays it points into).  The seven hyperparameters are scalars for every member or
-    arrays of n, one value per member; act_a / act_b: 'learn', 'uniform', one fixed [nS, 5] mixed policy for every member, or
-    [n, nS, 5], a fixed policy per member."""
-    given = dict(discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, delta_win=delta_win, delta_lose=delta_lose,
-                 delta_decay=delta_decay)
-    scalars, arrays = {}, {}
-    for name, ok, rng in _WOLF_HYPER:
-        value = given[name]
-        if np.ndim(value) == 0:
-            scalars[name], arrays[name] = float(value), None
-            assert ok(scalars[name]), "%s must be in %s" % (name, rng)
-        else:
-            a = np.ascontiguousarray(value, np.float64)
-            assert a.shape == (int(n),), "a per-member %s must have one value per lane (%d)" % (name, n)
-            assert ok(a).all(), "every per-member %s must be in %s" % (name, rng)
-            scalars[name], arrays[name] = float(a[0]), a
-    q0 = float(q_init)
-    assert -1.0 <= q0 <= 1.0, "q_init must be in [-1, 1]"
-    kinds, shared, each = [], [None, None], [None, None]
-    for p, (name, act) in enumerate((("act_a", act_a), ("act_b", act_b))):
-        if isinstance(act, str):
-            assert act in ("learn", "uniform"), "%s must be 'learn', 'uniform', an [nS, 5] or an [n, nS, 5] mixed policy" % name
-            kinds.append(_lib.PHC_LEARN if act == "learn" else _lib.PHC_UNIFORM)
-            continue
-        pol = np.ascontiguousarray(act, np.float64)
-        assert pol.shape in ((int(nS), 5), (int(n), int(nS), 5)) and (pol >= 0).all() and np.allclose(pol.sum(-1), 1.0), \
-            "a fixed %s must be [n_states, 5] or [n_lanes, n_states, 5] rows summing to 1" % name
-        (shared if pol.ndim == 2 else each)[p] = pol
-        kinds.append(_lib.PHC_FIXED)
-    ptr = lambda x: None if x is None else x.ctypes.data  # noqa: E731
-    cfg = _lib.WolfPopulationConfig(scalars["discount_factor"], scalars["alpha"], scalars["decay"], scalars["explor"], q0,
-                                    scalars["delta_win"], scalars["delta_lose"], scalars["delta_decay"], kinds[0], kinds[1],
-                                    ptr(shared[0]), ptr(shared[1]), ptr(each[0]), ptr(each[1]),
-                                    *[ptr(arrays[k]) for k in ("alpha", "decay", "explor", "discount_factor", "delta_win", "delta_lose", "delta_decay")])
-    return cfg, ((shared, each), arrays)
-
-
-class WolfPopulation(_Population):
-    """A population of policy hill-climbers (PHC / WoLF-PHC) on a two-player auto-reset SoccerBatch, a learner per lane:
-    member i has its own Q_a, Q_b, pi_a, pi_b, avg_a, avg_b [nS, 5], updates[nS], alpha and dscale and learns from lane i alone
-    (include/soccer_hip.h, "learners, a population of policy hill-climbers").  A fixed player's policy is per member.  run()
-    enqueues and returns; read() and the properties synchronise and copy.  read(), load() and exploitability() take a range
-    of members."""
-    _C = "soccer_wolf_population"
-    _ROWS = ("Q_a", "Q_b", "pi_a", "pi_b", "avg_a", "avg_b")
-
-    def __init__(self, batch, discount_factor, **params):
-        cfg, keep = wolf_population_config(batch.n, batch.nS, discount_factor, **params)
-        self._create(batch, cfg, keep[1])
-        del keep                                   # (create has copied the parameters and the fixed policies)
-        self.modes = (cfg.act_a, cfg.act_b)
-
-    def _read(self, first, count, keys):
-        nS, b = self.nS, self.batch
-        shapes = {"updates": ((count, nS), np.uint64), "alpha": ((count,), np.float64), "dscale": ((count,), np.float64)}
-        out = {k: np.zeros(*shapes.get(k, ((count, nS, 5), np.float64))) for k in keys if k != "steps"}
-        st = C.c_uint64()
-        state = _lib.WolfPopulationState(**{k: x.ctypes.data for k, x in out.items()})
-        if "steps" in keys:
-            state.steps = C.pointer(st)
-        b._check(b.lib.soccer_wolf_population_read(b.h, self.q, first, count, C.byref(state)))
-        if "steps" in keys:
-            out["steps"] = int(st.value)
-        return out
-
-    def read(self, first=0, count=None):
-        """dict for members first .. first + count - 1 (count None: to the end): Q_a / Q_b, pi_a / pi_b, avg_a / avg_b
-        [count, nS, 5], V_a / V_b [count, nS] (the row maxima, computed here), updates[count, nS], alpha[count],
-        dscale[count], steps.  Synchronises."""
-        first, count = self._range(first, count)
-        out = self._read(first, count, self._ROWS + ("updates", "alpha", "dscale", "steps"))
-        for p in "ab":
-            out["V_" + p] = out["Q_" + p].max(2)
-        return out
-
-    alpha = property(lambda self: self._read(0, self.n, ("alpha",))["alpha"], doc="every member's learning rate, [n]")
-    dscale = property(lambda self: self._read(0, self.n, ("dscale",))["dscale"], doc="every member's factor on both deltas, [n]")
-    steps = property(lambda self: self._read(0, 0, ("steps",))["steps"])
-
-    def exploitability(self, which="pi", theta=1e-10, first=0, count=None):
-        """How badly the best possible opponent beats the pair of policies (which='pi') or of average policies (which='avg')
-        of each member of a range, at that member's discount: through SoccerBatch.best_response in batches of at most 256
-        members with one discount.  Returns {"v_a", "v_b", "gap"}, arrays of [count, nS] (planners.exploitability's per
-        member)."""
-        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
-        first, count = self._range(first, count)
-        b = self.batch
-        out = {k: np.zeros((count, self.nS)) for k in ("v_a", "v_b", "gap")}
-        for c0 in range(0, count, _lib.BR_MAX_POLICIES):
-            c = min(_lib.BR_MAX_POLICIES, count - c0)
-            r = self._read(first + c0, c, (which + "_a", which + "_b"))
-            gam = self.discount_factor[first + c0:first + c0 + c]
-            for g in np.unique(gam):                # (one solve per discount in the chunk: a batch shares its discount)
-                idx = np.flatnonzero(gam == g)
-                out["v_a"][c0 + idx] = b.best_response(r[which + "_a"][idx], 0, theta, float(g))[1]
-                out["v_b"][c0 + idx] = b.best_response(r[which + "_b"][idx], 1, theta, float(g))[1]
-        out["gap"] = out["v_b"] - out["v_a"]
-        return out
-
-    def cross_play(self, which="pi", theta=1e-10, first=0, count=None, discount_factor=None):
-        """What each member's player A scores against each member's player B: (payoff[count, count], iterations) of
-        SoccerBatch.cross_play on the policies (which='pi') or the average policies (which='avg') of members first ..
-        first + count - 1 (at most 1024).  discount_factor None: the range's common discount, ValueError if the members differ."""
-        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
-        return _population_cross_play(self, lambda f, c: self._read(f, c, (which + "_a", which + "_b")), which + "_a", which + "_b",
-                                      theta, first, count, discount_factor)
-
-    def meta_game(self, which="pi", theta=1e-10, first=0, count=None, discount_factor=None, max_pivots=None):
-        """cross_play with the same arguments, then its meta-game solved (planners.meta_game): the members' mixture a rational
-        opponent cannot beat, x, y, value, lo, hi, status, and gain = lo - the best single member's row_min."""
-        return _meta_of_cross_play(self.batch, *self.cross_play(which, theta, first, count, discount_factor), max_pivots)
-
-    def match_outcomes(self, which="pi", theta=1e-10, first=0, count=None, continue_prob=None):
-        """How often each member's player A beats each member's player B, how often they draw and how long they play:
-        SoccerBatch.match_outcomes' dict on cross_play's policies (which) of members first .. first + count - 1 (at most 1024).
-        continue_prob None: the range's common discount, ValueError if the members differ."""
-        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
-        return _population_match_outcomes(self, lambda f, c: self._read(f, c, (which + "_a", which + "_b")), which + "_a", which + "_b",
-                                          theta, first, count, continue_prob)
-
-    def occupancy(self, which="pi", theta=1e-10, first=0, count=None, continue_prob=None, features=None, values=False):
-        """Where each member's player A and each member's player B play their game: SoccerBatch.occupancy's dict on cross_play's
-        policies (which) of members first .. first + count - 1 (at most 1024).  continue_prob None: the range's common discount,
-        ValueError if the members differ."""
-        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
-        return _population_occupancy(self, lambda f, c: self._read(f, c, (which + "_a", which + "_b")), which + "_a", which + "_b",
-                                     theta, first, count, continue_prob, features, values)
-
-    def load(self, Q_a=None, Q_b=None, pi_a=None, pi_b=None, avg_a=None, avg_b=None, updates=None, alpha=None, dscale=None, steps=None,
-             first=0):
-        """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged): the
-        six tables [count, nS, 5], updates[count, nS], alpha[count] and dscale[count], steps for the population.  With what
-        read() gave, a fresh population continues bit for bit.  A refused load changes nothing."""
-        b = self.batch
-        keep = {k: np.ascontiguousarray(x, np.float64) for k, x in zip(self._ROWS + ("alpha", "dscale"), (Q_a, Q_b, pi_a, pi_b, avg_a, avg_b, alpha, dscale))
-                if x is not None}
-        if updates is not None:
-            keep["updates"] = np.ascontiguousarray(updates, np.uint64)
-        counts = {x.shape[0] for x in keep.values() if x.ndim >= 1}
-        assert len(counts) <= 1 and all(x.ndim >= 1 for x in keep.values()), "the arrays must hold the same number of members"
-        first, count = self._range(first, counts.pop() if counts else 0)
-        for k, x in keep.items():
-            if k in self._ROWS:
-                assert x.shape == (count, self.nS, 5), "%s must be [count, n_states, 5]" % k
-                if k.startswith("Q"):
-                    assert (np.abs(x[:, 1:]) <= 1.0).all(), "Q must lie in [-1, 1]"
-            elif k == "updates":
-                assert x.shape == (count, self.nS), "updates must be [count, n_states]"
-            else:
-                assert x.shape == (count,) and ((x >= 0.0) & (x <= 1.0)).all(), "%s must be [count] values in [0, 1]" % k
-        state = _lib.WolfPopulationState(**{k: x.ctypes.data for k, x in keep.items()})
-        if steps is not None:
-            state.steps = C.pointer(C.c_uint64(int(steps)))
-        b._check(b.lib.soccer_wolf_population_load(b.h, self.q, first, count, C.byref(state)))
-        return self
-
-    def adopt(self, player, src, src_player, which="pi"):
-        """Freeze: every member's fixed policy of `player` (0 = A, 1 = B) becomes the pi (which='pi') or avg (which='avg') of
-        `src_player` of the same member of the population `src` on this batch, on the device, enqueued."""
-        assert which in ("pi", "avg"), "which must be 'pi' or 'avg'"
-        assert isinstance(src, WolfPopulation), "src must be a WolfPopulation"
-        b = self.batch
-        b._check(b.lib.soccer_wolf_population_adopt(b.h, self.q, int(player), src.q, int(src_player), 0 if which == "pi" else 1))
-        return self
-
-    def challengers(self, against, which="pi", **hyper):
-        """A second population on the same batch for the challenger protocol: its player `against` (0 = A, 1 = B) is fixed,
-        member by member, to this population's pi (or avg) of that player as it is now; its other player learns from scratch
-        with the hyperparameters given (WolfPopulation's; default discount: this population's)."""
-        assert against in (0, 1), "against must be 0 (player A is frozen) or 1 (player B)"
-        assert "act_a" not in hyper and "act_b" not in hyper, "challengers() sets act_a / act_b"
-        hyper.setdefault("discount_factor", self.discount_factor)
-        acts = ["learn", "learn"]
-        acts[against] = np.full((self.nS, 5), 0.2)          # a placeholder row table: adopt() overwrites every member's
-        c = WolfPopulation(self.batch, hyper.pop("discount_factor"), act_a=acts[0], act_b=acts[1], **hyper)
-        return c.adopt(against, self, against, which)
-
-
-def minimax_q_population_config(n, nS, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, opponent="uniform"):
-    """Checks the parameters of a population of minimax-Q learners (AssertionError, before any library call) and returns
-    (soccer_minimax_q_population_config, the arrays it points into).  discount_factor, alpha, decay and explor are scalars
-    for every member or arrays of n, one value per member; opponent: 'uniform', 'self', one fixed [nS, 5] mixed policy for
-    every member, or [n, nS, 5], a fixed policy per member."""
-    ranges = (("discount_factor", discount_factor, lambda x: (0.0 <= x) & (x < 1.0), "[0, 1)"),
-              ("alpha", alpha, lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"),
-              ("decay", decay, lambda x: (0.0 < x) & (x <= 1.0), "(0, 1]"),
-              ("explor", explor, lambda x: (0.0 <= x) & (x <= 1.0), "[0, 1]"))
-    scalars, arrays = {}, {}
-    for name, value, ok, rng in ranges:
-        if np.ndim(value) == 0:
-            scalars[name], arrays[name] = float(value), None
-            assert ok(scalars[name]), "%s must be in %s" % (name, rng)
-        else:
-            a = np.ascontiguousarray(value, np.float64)
-            assert a.shape == (int(n),), "a per-member %s must have one value per lane (%d)" % (name, n)
-            assert ok(a).all(), "every per-member %s must be in %s" % (name, rng)
-            scalars[name], arrays[name] = float(a[0]), a
-    q0 = float(q_init)
-    assert -1.0 <= q0 <= 1.0, "q_init must be in [-1, 1]"
-    shared = each = None
-    if isinstance(opponent, str):
-        assert opponent in ("uniform", "self"), "opponent must be 'uniform', 'self', an [nS, 5] or an [n, nS, 5] mixed policy"
-        kind = _lib.MQ_UNIFORM if opponent == "uniform" else _lib.MQ_SELF
-    else:
-        pol = np.ascontiguousarray(opponent, np.float64)
-        assert pol.shape in ((int(nS), 5), (int(n), int(nS), 5)), "a fixed opponent must be [n_states, 5] or [n_lanes, n_states, 5] rows summing to 1"
-        bad = np.argwhere(~((pol >= 0).all(-1) & np.isclose(pol.sum(-1), 1.0)))
-        if bad.size:
-            where = "state %d" % bad[0][0] if pol.ndim == 2 else "member %d, state %d" % tuple(bad[0])
-            raise AssertionError("a fixed opponent must be [n_states, 5] or [n_lanes, n_states, 5] rows >= 0 summing to 1: %s is not" % where)
-        if pol.ndim == 2:
-            shared = pol
-        else:
-            each = pol
-        kind = _lib.MQ_FIXED
-    ptr = lambda x: None if x is None else x.ctypes.data  # noqa: E731
-    cfg = _lib.MinimaxQPopulationConfig(scalars["discount_factor"], scalars["alpha"], scalars["decay"], scalars["explor"], q0, kind, 0,
-                                        ptr(shared), ptr(each), *[ptr(arrays[k]) for k in ("alpha", "decay", "explor", "discount_factor")])
-    return cfg, ((shared, each), arrays)
-
-
-class MinimaxQPopulation(_Population):
-    """A population of minimax-Q learners (Littman 1994) on a two-player auto-reset SoccerBatch, a learner per lane: member i
-    has its own Q[nS, 5, 5], V[nS], pi_a / pi_b [nS, 5] and alpha and learns from lane i alone (include/soccer_hip.h, "learners,
-    a population of minimax-Q learners").  run() enqueues and returns; read() and the properties synchronise and copy.  Whole
-    populations run to gigabytes, so read(), load() and exploitability() take a range of members."""
-    _C = "soccer_minimax_q_population"
-    _ROWS = ("Q", "V", "pi_a", "pi_b")
-
-    def __init__(self, batch, discount_factor, **params):
-        cfg, keep = minimax_q_population_config(batch.n, batch.nS, discount_factor, **params)
-        self._create(batch, cfg, keep[1])
-        del keep                                   # (create has copied the parameters and the fixed policies' thresholds)
-        self.opponent = cfg.opponent
-
-    def _policies(self, first, count):
-        return self._read(first, count, ("pi_a", "pi_b"))
-
-    def _read(self, first, count, keys):
-        nS, b = self.nS, self.batch
-        shapes = {"Q": (count, nS, 5, 5), "V": (count, nS), "pi_a": (count, nS, 5), "pi_b": (count, nS, 5), "alpha": (count,)}
-        out = {k: np.zeros(shapes[k]) for k in keys if k != "steps"}
-        st = C.c_uint64()
-        b._check(b.lib.soccer_minimax_q_population_read(b.h, self.q, first, count,
-                                                        *[out[k].ctypes.data if k in out else None for k in self._ROWS + ("alpha",)],
-                                                        C.byref(st) if "steps" in keys else None))
-        if "steps" in keys:
-            out["steps"] = int(st.value)
-        return out
-
-    def read(self, first=0, count=None):
-        """dict for members first .. first + count - 1 (count None: to the end): Q[count, nS, 5, 5], V[count, nS], pi_a / pi_b
-        [count, nS, 5], alpha[count], steps.  Synchronises."""
-        first, count = self._range(first, count)
-        return self._read(first, count, self._ROWS + ("alpha", "steps"))
-
-    alpha = property(lambda self: self._read(0, self.n, ("alpha",))["alpha"], doc="every member's learning rate, [n]")
-    steps = property(lambda self: self._read(0, 0, ("steps",))["steps"])
-
-    def exploitability(self, theta=1e-10, first=0, count=None):
-        """How badly the best possible opponent beats the strategies pi_a and pi_b of each member of a range, at that member's
-        discount: through SoccerBatch.best_response in batches of at most 256 members with one discount.  Returns
-        {"v_a", "v_b", "gap"}, arrays of [count, nS] (planners.exploitability's per member)."""
-        first, count = self._range(first, count)
-        b = self.batch
-        out = {k: np.zeros((count, self.nS)) for k in ("v_a", "v_b", "gap")}
-        for c0 in range(0, count, _lib.BR_MAX_POLICIES):
-            c = min(_lib.BR_MAX_POLICIES, count - c0)
-            r = self._read(first + c0, c, ("pi_a", "pi_b"))
-            gam = self.discount_factor[first + c0:first + c0 + c]
-            for g in np.unique(gam):                # (one solve per discount in the chunk: a batch shares its discount)
-                idx = np.flatnonzero(gam == g)
-                out["v_a"][c0 + idx] = b.best_response(r["pi_a"][idx], 0, theta, float(g))[1]
-                out["v_b"][c0 + idx] = b.best_response(r["pi_b"][idx], 1, theta, float(g))[1]
-        out["gap"] = out["v_b"] - out["v_a"]
-        return out
-
-    def load(self, Q=None, V=None, pi_a=None, pi_b=None, alpha=None, steps=None, first=0):
-        """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged):
-        Q[count, nS, 5, 5] and V[count, nS] in [-1, 1], pi_a / pi_b [count, nS, 5], alpha[count], steps for the population.  Q
-        alone: V and the strategies of every live state of the range are re-solved on the device.  With V, pi_a and pi_b
-        they are stored as given, so with what read() gave a fresh population continues bit for bit.  A refused load changes
-        nothing."""
-        b = self.batch
-        keep = {k: np.ascontiguousarray(x, np.float64) for k, x in zip(self._ROWS + ("alpha",), (Q, V, pi_a, pi_b, alpha)) if x is not None}
-        counts = {x.shape[0] for x in keep.values() if x.ndim >= 1}
-        assert len(counts) <= 1 and all(x.ndim >= 1 for x in keep.values()), "the arrays must hold the same number of members"
-        first, count = self._range(first, counts.pop() if counts else 0)
-        shapes = {"Q": (count, self.nS, 5, 5), "V": (count, self.nS), "pi_a": (count, self.nS, 5), "pi_b": (count, self.nS, 5), "alpha": (count,)}
-        for k, x in keep.items():
-            assert x.shape == shapes[k], "%s must be %s" % (k, list(shapes[k]))
-            if k in ("Q", "V"):
-                assert (np.abs(x[:, 1:]) <= 1.0).all(), "%s must lie in [-1, 1]" % k
-            elif k == "alpha":
-                assert ((x >= 0.0) & (x <= 1.0)).all(), "alpha must be [count] values in [0, 1]"
-        st = None if steps is None else C.byref(C.c_uint64(int(steps)))
-        b._check(b.lib.soccer_minimax_q_population_load(b.h, self.q, first, count,
-                                                        *[keep[k].ctypes.data if k in keep else None for k in self._ROWS + ("alpha",)], st))
-        return self
-
-
-class GradientPlay(_Learner):
-    """Gradient play on a two-player SoccerBatch (include/soccer_hip.h, "gradient play"): n_a policies of player A and n_b of
-    player B live on the device; a step solves policy_gradient's exact gradients of the resident policies against each other's
-    weighted mixture and moves every row of every policy along them, projected back onto the simplex.  Nothing is sampled: the
-    lanes are left alone and no tick is consumed.  optimism 1 is the optimistic (predictive) step g + (g - previous g)."""
-    _C = "soccer_gradient_play"
-
-    def __init__(self, batch, n_a, n_b, discount_factor, eta_a=1.0, eta_b=1.0, optimism=0.0, normalize=True, theta=1e-10,
-                 max_sweeps=1000000, pairs_per_pass=0, pi_a=None, pi_b=None):
-        nS = batch.nS
-        keep = []
-        for p, n, name in ((pi_a, n_a, "pi_a"), (pi_b, n_b, "pi_b")):
-            if p is not None:
-                p = np.ascontiguousarray(p, np.float64)
-                p = p[None] if p.ndim == 2 else p
-                assert p.shape == (n, nS, 5), "%s must be [%d, n_states, 5]" % (name, n)
-            keep.append(p)
-        cfg = _lib.GradientPlayConfig(int(n_a), int(n_b), float(eta_a), float(eta_b), float(optimism), float(discount_factor),
-                                      float(theta), int(bool(normalize)), int(max_sweeps), int(pairs_per_pass), 0,
-                                      None if keep[0] is None else keep[0].ctypes.data, None if keep[1] is None else keep[1].ctypes.data)
-        self._create(batch, cfg)
-        del keep
-        self.n_a, self.n_b, self.discount_factor, self.theta = int(n_a), int(n_b), float(discount_factor), float(theta)
-
-    def run(self, n_steps, trace=False):
-        """n_steps steps.  With trace=True returns [n_steps, n_a, n_b]: each step's payoff matrix before its update.  RuntimeError
-        if a step's solves are still open at max_sweeps: that step is not applied, steps counts the completed ones (its .results
-        holds the trace so far, the rest zeros)."""
-        b = self.batch
-        tr = np.zeros((int(n_steps), self.n_a, self.n_b)) if trace else None
-        code = b.lib.soccer_gradient_play_run(b.h, self.q, int(n_steps), tr.ctypes.data if trace else None)
-        try:
-            b._check(code)
-        except RuntimeError as e:
-            e.results = tr
-            raise
-        return tr if trace else self
-
-    def read(self):
-        """dict: pi_a[n_a, nS, 5], pi_b[n_b, nS, 5], prev_a, prev_b (the last step's gradients), w_a[n_a], w_b[n_b], payoff
-        [n_a, n_b] (the last step's, before its update) and steps."""
-        b, nS = self.batch, self.nS
-        out = {"pi_a": np.zeros((self.n_a, nS, 5)), "pi_b": np.zeros((self.n_b, nS, 5)), "prev_a": np.zeros((self.n_a, nS, 5)),
-               "prev_b": np.zeros((self.n_b, nS, 5)), "w_a": np.zeros(self.n_a), "w_b": np.zeros(self.n_b),
-               "payoff": np.zeros((self.n_a, self.n_b))}
-        st = C.c_int64()
-        b._check(b.lib.soccer_gradient_play_read(b.h, self.q, *[out[k].ctypes.data for k in
-                                                                ("pi_a", "pi_b", "prev_a", "prev_b", "w_a", "w_b", "payoff")], C.byref(st)))
-        out["steps"] = int(st.value)
-        return out
-
-    def load(self, pi_a=None, pi_b=None, prev_a=None, prev_b=None, payoff=None, steps=None, **ignored):
-        """Resume from read()'s dict (load(**learner.read())): a fresh learner continues bit for bit; the weights go through
-        weights().  None leaves a part as it is."""
-        b, nS = self.batch, self.nS
-        arrs = []
-        for p, n, name in ((pi_a, self.n_a, "pi_a"), (pi_b, self.n_b, "pi_b"), (prev_a, self.n_a, "prev_a"), (prev_b, self.n_b, "prev_b")):
-            if p is not None:
-                p = np.ascontiguousarray(p, np.float64)
-                assert p.shape == (n, nS, 5), "%s must be [%d, n_states, 5]" % (name, n)
-            arrs.append(p)
-        if payoff is not None:
-            payoff = np.ascontiguousarray(payoff, np.float64)
-            assert payoff.shape == (self.n_a, self.n_b), "payoff must be [n_a, n_b]"
-        arrs.append(payoff)
-        st = None if steps is None else C.byref(C.c_int64(int(steps)))
-        b._check(b.lib.soccer_gradient_play_load(b.h, self.q, *[None if p is None else p.ctypes.data for p in arrs], st))
-        return self
-
-    def weights(self, w_a=None, w_b=None):
-        """Sets the mixtures the policies are trained against from the next step on: w_b [n_b] weighs player A's opponents, w_a
-        [n_a] player B's; None is uniform."""
-        b = self.batch
-        wa, wb = b._weights(w_a, self.n_a, "w_a"), b._weights(w_b, self.n_b, "w_b")
-        b._check(b.lib.soccer_gradient_play_set_weights(b.h, self.q, None if wa is None else wa.ctypes.data,
-                                                        None if wb is None else wb.ctypes.data))
-        return self
-
-    def exploitability(self, theta=None):
-        """planners.exploitability of the current sets at the learner's discount: policy i of A with policy i of B (the sets
-        must be equally large, or one of them a single policy)."""
-        from . import planners
-        assert self.n_a == self.n_b or 1 in (self.n_a, self.n_b), "exploitability pairs policy i of A with policy i of B"
-        r = self.read()
-        return planners.exploitability(self.batch, r["pi_a"], r["pi_b"], self.theta if theta is None else theta, self.discount_factor)
-
-    def cross_play(self, theta=None):
-        """planners.cross_play's dict of the current sets at the learner's discount"""
-        from . import planners
-        r = self.read()
-        return planners.cross_play(self.batch, r["pi_a"], r["pi_b"], self.theta if theta is None else theta, self.discount_factor)
-
-    def meta_game(self, theta=None, max_pivots=None):
-        """planners.meta_game's dict of the current sets at the learner's discount"""
-        from . import planners
-        r = self.read()
-        return planners.meta_game(self.batch, r["pi_a"], r["pi_b"], self.theta if theta is None else theta, self.discount_factor,
-                                  max_pivots=max_pivots)
 
 
 class SoccerBatch:
@@ -1335,6 +70,16 @@ class SoccerBatch:
     # -- plumbing -------------------------------------------------------------------------------
     def _check(self, code):
         _lib.check(self.lib, self.h, code)
+
+    def _checked(self, code, out):
+        """`out` if the call succeeded; a RuntimeError (not converged, stopped at a cap, or a capture) takes what was reached
+        with it as its .results"""
+        try:
+            self._check(code)
+        except RuntimeError as e:
+            e.results = out
+            raise
+        return out
 
     def close(self):
         if self.h:
@@ -1515,12 +260,7 @@ class SoccerBatch:
         it = C.c_int32()
         code = self.lib.soccer_minimax_value_iteration(self.h, float(theta), float(discount_factor), int(max_sweeps),
                                                        V.ctypes.data, Q.ctypes.data, pa.ctypes.data, pb.ctypes.data, C.byref(it))
-        try:
-            self._check(code)
-        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
-            e.results = (pa, pb, V, Q, int(it.value))
-            raise
-        return pa, pb, V, Q, int(it.value)
+        return self._checked(code, (pa, pb, V, Q, int(it.value)))
 
     # -- best responses to mixed policies (two-player handles) ----------------------------------------
     def _policies(self, policy, name):
@@ -1529,14 +269,14 @@ class SoccerBatch:
         assert p.ndim in (2, 3) and p.shape[-2:] == (self.nS, 5), "%s must be [n_states, 5] or [P, n_states, 5]" % name
         return (p if p.ndim == 3 else p[None]), p.ndim == 3
 
+    def _policy_sets(self, pi_a, pi_b):
+        """the two sets of a pair evaluator: (pi_a [n_a, nS, 5], pi_b [n_b, nS, 5], n_a, n_b)"""
+        a, b = self._policies(pi_a, "pi_a")[0], self._policies(pi_b, "pi_b")[0]
+        return a, b, a.shape[0], b.shape[0]
+
     def _response_result(self, code, out, batched):
-        out = tuple(x if batched else x[0] for x in out[:-1]) + (out[-1].astype(np.int64) if batched else int(out[-1][0]),)
-        try:
-            self._check(code)
-        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
-            e.results = out
-            raise
-        return out
+        return self._checked(code, tuple(x if batched else x[0] for x in out[:-1]) +
+                             (out[-1].astype(np.int64) if batched else int(out[-1][0]),))
 
     def best_response(self, policy, player, theta, discount_factor, max_sweeps=1000000):
         """The best response to a mixed policy of `player` (0: the policy is player A's and B answers, minimising; 1: it is
@@ -1557,15 +297,14 @@ class SoccerBatch:
     def evaluate_policies(self, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000):
         """Player A's value of the pair (pi_a, pi_b) of mixed policies, iterated like best_response: (V, iterations).
         [nS, 5] each, or [P, nS, 5] (one of them may be a single policy: it meets every policy of the other)."""
-        a, ba = self._policies(pi_a, "pi_a")
-        b, bb = self._policies(pi_b, "pi_b")
-        n = max(a.shape[0], b.shape[0])
-        assert a.shape[0] in (1, n) and b.shape[0] in (1, n), "pi_a and pi_b must hold one policy or the same number of policies"
+        a, b, na, nb = self._policy_sets(pi_a, pi_b)
+        n = max(na, nb)
+        assert na in (1, n) and nb in (1, n), "pi_a and pi_b must hold one policy or the same number of policies"
         a = np.ascontiguousarray(np.broadcast_to(a, (n, self.nS, 5))); b = np.ascontiguousarray(np.broadcast_to(b, (n, self.nS, 5)))
         V = np.zeros((n, self.nS)); it = np.zeros(n, np.int32)
         code = self.lib.soccer_evaluate_policies(self.h, n, a.ctypes.data, b.ctypes.data, float(theta), float(discount_factor),
                                                  int(max_sweeps), V.ctypes.data, it.ctypes.data)
-        return self._response_result(code, (V, it), ba or bb)
+        return self._response_result(code, (V, it), np.ndim(pi_a) == 3 or np.ndim(pi_b) == 3)
 
     def cross_play(self, pi_a, pi_b, theta, discount_factor, max_sweeps=1000000, pairs_per_pass=0, values=False):
         """The payoff matrix of two sets of mixed policies: payoff[i, j] is player A's value at kick-off (the mean of V over the
@@ -1574,21 +313,13 @@ class SoccerBatch:
         Returns (payoff[n_a, n_b], iterations[n_a, n_b]), and with values=True also V[n_a, n_b, nS].  pairs_per_pass: how many
         pairs are solved together on the device (0: the library chooses; else a multiple of 64) — no result depends on it.
         RuntimeError if max_sweeps is reached (its .results holds the tuple, iterations == max_sweeps marks the open pairs)."""
-        a, _ = self._policies(pi_a, "pi_a")
-        b, _ = self._policies(pi_b, "pi_b")
-        na, nb = a.shape[0], b.shape[0]
+        a, b, na, nb = self._policy_sets(pi_a, pi_b)
         payoff = np.zeros((na, nb)); it = np.zeros((na, nb), np.int32)
         V = np.zeros((na, nb, self.nS)) if values else None
         code = self.lib.soccer_cross_play(self.h, na, a.ctypes.data, nb, b.ctypes.data, float(theta), float(discount_factor),
                                           int(max_sweeps), int(pairs_per_pass), payoff.ctypes.data,
                                           V.ctypes.data if values else None, it.ctypes.data)
-        out = (payoff, it.astype(np.int64)) + ((V,) if values else ())
-        try:
-            self._check(code)
-        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
-            e.results = out
-            raise
-        return out
+        return self._checked(code, (payoff, it.astype(np.int64)) + ((V,) if values else ()))
 
     def match_outcomes(self, pi_a, pi_b, theta, continue_prob, max_sweeps=1000000, pairs_per_pass=0, values=False):
         """Littman's columns for two sets of mixed policies, exactly (include/soccer_hip.h, "match outcomes"): after every step
@@ -1601,9 +332,7 @@ class SoccerBatch:
           values          [n_a, n_b, 3, nS] with values=True: W_A, W_B and L at every state
         RuntimeError if max_sweeps is reached (its .results holds the dict, iterations == max_sweeps marks the open pairs,
         which hold the max_sweeps-step numbers)."""
-        a, _ = self._policies(pi_a, "pi_a")
-        b, _ = self._policies(pi_b, "pi_b")
-        na, nb = a.shape[0], b.shape[0]
+        a, b, na, nb = self._policy_sets(pi_a, pi_b)
         win_a = np.zeros((na, nb)); win_b = np.zeros((na, nb)); length = np.zeros((na, nb)); it = np.zeros((na, nb), np.int32)
         V = np.zeros((na, nb, 3, self.nS)) if values else None
         code = self.lib.soccer_match_outcomes(self.h, na, a.ctypes.data, nb, b.ctypes.data, float(theta), float(continue_prob),
@@ -1614,12 +343,7 @@ class SoccerBatch:
                    "iterations": it.astype(np.int64)}
         if values:
             out["values"] = V
-        try:
-            self._check(code)
-        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
-            e.results = out
-            raise
-        return out
+        return self._checked(code, out)
 
     def occupancy(self, pi_a, pi_b, theta, continue_prob, features=None, values=False, max_sweeps=1000000, pairs_per_pass=0):
         """Where the game is played when two sets of mixed policies meet, exactly (include/soccer_hip.h, "state occupancy"): the
@@ -1633,9 +357,7 @@ class SoccerBatch:
           occupancy       [n_a, n_b, nS] with values=True, and  visit_share = occupancy / length
         RuntimeError if max_sweeps is reached (its .results holds the dict, iterations == max_sweeps marks the open pairs,
         which hold the last iterate)."""
-        a, _ = self._policies(pi_a, "pi_a")
-        b, _ = self._policies(pi_b, "pi_b")
-        na, nb = a.shape[0], b.shape[0]
+        a, b, na, nb = self._policy_sets(pi_a, pi_b)
         F = np.zeros((0, self.nS)) if features is None else np.ascontiguousarray(features, np.float64)
         F = F[None] if F.ndim == 1 else F
         assert F.ndim == 2 and F.shape[1] == self.nS, "features must be [n_f, n_states] or [n_states]"
@@ -1650,12 +372,7 @@ class SoccerBatch:
             out["occupancy"] = D
             with np.errstate(divide="ignore", invalid="ignore"):
                 out["visit_share"] = D / length[:, :, None]
-        try:
-            self._check(code)
-        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
-            e.results = out
-            raise
-        return out
+        return self._checked(code, out)
 
     def _weights(self, w, n, name):
         if w is None:
@@ -1677,9 +394,8 @@ class SoccerBatch:
           q_a, q_b    [n_a, n_b, nS, 5], V and occupancy [n_a, n_b, nS], with values=True
         normalize=True divides every grad row by its reach (0 where the reach is 0).
         RuntimeError if max_sweeps is reached (its .results holds the dict, iterations == max_sweeps marks the open solves)."""
-        a, _ = self._policies(pi_a, "pi_a")
-        b, _ = self._policies(pi_b, "pi_b")
-        na, nb, nS = a.shape[0], b.shape[0], self.nS
+        a, b, na, nb = self._policy_sets(pi_a, pi_b)
+        nS = self.nS
         wa, wb = self._weights(w_a, na, "w_a"), self._weights(w_b, nb, "w_b")
         out = {"payoff": np.zeros((na, nb)), "grad_a": np.zeros((na, nS, 5)), "grad_b": np.zeros((nb, nS, 5)),
                "reach_a": np.zeros((na, nS)), "reach_b": np.zeros((nb, nS))}
@@ -1693,12 +409,7 @@ class SoccerBatch:
                                                int(max_sweeps), int(pairs_per_pass), None if wa is None else wa.ctypes.data,
                                                None if wb is None else wb.ctypes.data, int(bool(normalize)), *ptr, it.ctypes.data)
         out["iterations"] = it.astype(np.int64)
-        try:
-            self._check(code)
-        except RuntimeError as e:               # not converged (or a capture): what was reached goes with the exception
-            e.results = out
-            raise
-        return out
+        return self._checked(code, out)
 
     def gradient_play(self, n_a=1, n_b=1, discount_factor=0.9, eta_a=1.0, eta_b=1.0, optimism=0.0, normalize=True, theta=1e-10,
                       max_sweeps=1000000, pairs_per_pass=0, pi_a=None, pi_b=None):
@@ -1734,12 +445,7 @@ class SoccerBatch:
         out["certified"] = out["status"] <= 1
         if single:
             out = {k: v[0] for k, v in out.items()}
-        try:
-            self._check(code)
-        except RuntimeError as e:               # a game stopped at the cap (or a capture): what was reached goes with the exception
-            e.results = out
-            raise
-        return out
+        return self._checked(code, out)
 
     # -- learners -------------------------------------------------------------------------------
     def minimax_q(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, opponent="uniform"):

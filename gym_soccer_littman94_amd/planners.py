@@ -65,25 +65,33 @@ def _two_player_batch(env, what):
     return b
 
 
+def _train(env, what, factory, n_steps, keys, members=(), **hyper):
+    """What the training drivers share: the SoccerBatch factory's learner with `hyper` (decay None: alpha falls to 1 % over
+    the run) runs n_steps from the lanes' current states, lanes that were never reset being reset first, and is closed;
+    returns read(*members)'s entries `keys`."""
+    b = _two_player_batch(env, what)
+    n_steps = int(n_steps)
+    assert n_steps >= 0, "n_steps must be >= 0"
+    if hyper["decay"] is None:
+        hyper["decay"] = 0.01 ** (1.0 / max(n_steps, 1))
+    learner = getattr(b, factory)(**hyper)
+    try:
+        if b.get_state()["needs_reset"].any():
+            (env if hasattr(env, "_batch") else b).reset()
+        learner.run(n_steps)
+        r = learner.read(*members)
+    finally:
+        learner.close()
+    return tuple(r[k] for k in keys)
+
+
 def minimax_q_learning(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, opponent="uniform"):
     """Minimax-Q (Littman 1994) on the device: n_steps learner steps with every lane of `env` acting, from the lanes'
     current states (lanes that were never reset are reset first).  decay None: alpha falls to 1 % over the run.
     Returns (pi_a[nS, 5], pi_b[nS, 5], V, Q[nS, 5, 5], visits[nS, 25]) — minimax_value_iteration's order with the visit
     counts in place of the iteration count, ready for VectorSoccerEnv.rollout(sample_actions=True, mixed_policies={...})."""
-    b = _two_player_batch(env, "minimax_q_learning")
-    n_steps = int(n_steps)
-    assert n_steps >= 0, "n_steps must be >= 0"
-    if decay is None:
-        decay = 0.01 ** (1.0 / max(n_steps, 1))
-    learner = b.minimax_q(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, opponent=opponent)
-    try:
-        if b.get_state()["needs_reset"].any():
-            (env if hasattr(env, "_batch") else b).reset()
-        learner.run(n_steps)
-        r = learner.read()
-    finally:
-        learner.close()
-    return r["pi_a"], r["pi_b"], r["V"], r["Q"], r["visits"]
+    return _train(env, "minimax_q_learning", "minimax_q", n_steps, ("pi_a", "pi_b", "V", "Q", "visits"),
+                  discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, opponent=opponent)
 
 
 def q_learning(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy"):
@@ -93,20 +101,8 @@ def q_learning(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2,
     Returns (pi_a[nS, 5], pi_b[nS, 5], V_a, V_b, Q_a[nS, 5], Q_b[nS, 5], visits[nS, 25]); the one-hot greedy policies are
     ready for VectorSoccerEnv.rollout(sample_actions=True, mixed_policies={...}) and for exploitability; Q_b and V_b are in
     player B's own reward."""
-    b = _two_player_batch(env, "q_learning")
-    n_steps = int(n_steps)
-    assert n_steps >= 0, "n_steps must be >= 0"
-    if decay is None:
-        decay = 0.01 ** (1.0 / max(n_steps, 1))
-    learner = b.q_learning(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
-    try:
-        if b.get_state()["needs_reset"].any():
-            (env if hasattr(env, "_batch") else b).reset()
-        learner.run(n_steps)
-        r = learner.read()
-    finally:
-        learner.close()
-    return r["pi_a"], r["pi_b"], r["V_a"], r["V_b"], r["Q_a"], r["Q_b"], r["visits"]
+    return _train(env, "q_learning", "q_learning", n_steps, ("pi_a", "pi_b", "V_a", "V_b", "Q_a", "Q_b", "visits"),
+                  discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
 
 
 def q_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy",
@@ -118,21 +114,9 @@ def q_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.
     (SoccerBatch.q_population).  Returns, for members first .. first + count - 1 (count None: to the end),
     (pi_a[count, nS, 5], pi_b, V_a[count, nS], V_b, Q_a[count, nS, 5], Q_b, alpha[count]); Q_b and V_b are in player B's
     own reward."""
-    b = _two_player_batch(env, "q_population")
-    n_steps = int(n_steps)
-    assert n_steps >= 0, "n_steps must be >= 0"
-    if decay is None:
-        decay = 0.01 ** (1.0 / max(n_steps, 1))
-    pop = b.q_population(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b,
-                         league_policies=league_policies, league_weights=league_weights)
-    try:
-        if b.get_state()["needs_reset"].any():
-            (env if hasattr(env, "_batch") else b).reset()
-        pop.run(n_steps)
-        r = pop.read(first, count)
-    finally:
-        pop.close()
-    return r["pi_a"], r["pi_b"], r["V_a"], r["V_b"], r["Q_a"], r["Q_b"], r["alpha"]
+    return _train(env, "q_population", "q_population", n_steps, ("pi_a", "pi_b", "V_a", "V_b", "Q_a", "Q_b", "alpha"), (first, count),
+                  discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b,
+                  league_policies=league_policies, league_weights=league_weights)
 
 
 def om_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, act_a="greedy", act_b="greedy",
@@ -144,20 +128,8 @@ def om_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0
     members first .. first + count - 1 (count None: to the end), (pi_a[count, nS, 5], pi_b, V_a[count, nS], V_b,
     Q_a[count, nS, 5, 5], Q_b, alpha[count]): the greedy answers to the modelled opponent and their values; Q_b and V_b are
     in player B's own reward."""
-    b = _two_player_batch(env, "om_population")
-    n_steps = int(n_steps)
-    assert n_steps >= 0, "n_steps must be >= 0"
-    if decay is None:
-        decay = 0.01 ** (1.0 / max(n_steps, 1))
-    pop = b.om_population(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
-    try:
-        if b.get_state()["needs_reset"].any():
-            (env if hasattr(env, "_batch") else b).reset()
-        pop.run(n_steps)
-        r = pop.read(first, count)
-    finally:
-        pop.close()
-    return r["pi_a"], r["pi_b"], r["V_a"], r["V_b"], r["Q_a"], r["Q_b"], r["alpha"]
+    return _train(env, "om_population", "om_population", n_steps, ("pi_a", "pi_b", "V_a", "V_b", "Q_a", "Q_b", "alpha"), (first, count),
+                  discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, act_a=act_a, act_b=act_b)
 
 
 def wolf_phc(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
@@ -168,21 +140,9 @@ def wolf_phc(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q
     plain PHC.  Returns (pi_a[nS, 5], pi_b[nS, 5], avg_a, avg_b, Q_a[nS, 5], Q_b[nS, 5], visits[nS, 25]); the policies and
     their averages are ready for VectorSoccerEnv.rollout(sample_actions=True, mixed_policies={...}) and for
     exploitability; Q_b is in player B's own reward."""
-    b = _two_player_batch(env, "wolf_phc")
-    n_steps = int(n_steps)
-    assert n_steps >= 0, "n_steps must be >= 0"
-    if decay is None:
-        decay = 0.01 ** (1.0 / max(n_steps, 1))
-    learner = b.wolf_phc(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, delta_win=delta_win,
-                         delta_lose=delta_lose, delta_decay=delta_decay, act_a=act_a, act_b=act_b)
-    try:
-        if b.get_state()["needs_reset"].any():
-            (env if hasattr(env, "_batch") else b).reset()
-        learner.run(n_steps)
-        r = learner.read()
-    finally:
-        learner.close()
-    return r["pi_a"], r["pi_b"], r["avg_a"], r["avg_b"], r["Q_a"], r["Q_b"], r["visits"]
+    return _train(env, "wolf_phc", "wolf_phc", n_steps, ("pi_a", "pi_b", "avg_a", "avg_b", "Q_a", "Q_b", "visits"),
+                  discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init,
+                  delta_win=delta_win, delta_lose=delta_lose, delta_decay=delta_decay, act_a=act_a, act_b=act_b)
 
 
 def wolf_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, delta_win=0.01, delta_lose=0.04,
@@ -193,21 +153,9 @@ def wolf_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor
     1 % over the run; act_a / act_b: 'learn', 'uniform', a fixed [nS, 5] policy or [n, nS, 5], one per member.  Returns, for
     members first .. first + count - 1 (count None: to the end), (pi_a[count, nS, 5], pi_b, avg_a, avg_b, Q_a, Q_b,
     alpha[count]); Q_b is in player B's own reward."""
-    b = _two_player_batch(env, "wolf_population")
-    n_steps = int(n_steps)
-    assert n_steps >= 0, "n_steps must be >= 0"
-    if decay is None:
-        decay = 0.01 ** (1.0 / max(n_steps, 1))
-    pop = b.wolf_population(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, delta_win=delta_win,
-                            delta_lose=delta_lose, delta_decay=delta_decay, act_a=act_a, act_b=act_b)
-    try:
-        if b.get_state()["needs_reset"].any():
-            (env if hasattr(env, "_batch") else b).reset()
-        pop.run(n_steps)
-        r = pop.read(first, count)
-    finally:
-        pop.close()
-    return r["pi_a"], r["pi_b"], r["avg_a"], r["avg_b"], r["Q_a"], r["Q_b"], r["alpha"]
+    return _train(env, "wolf_population", "wolf_population", n_steps, ("pi_a", "pi_b", "avg_a", "avg_b", "Q_a", "Q_b", "alpha"), (first, count),
+                  discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init,
+                  delta_win=delta_win, delta_lose=delta_lose, delta_decay=delta_decay, act_a=act_a, act_b=act_b)
 
 
 def minimax_q_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, opponent="uniform", first=0,
@@ -218,20 +166,8 @@ def minimax_q_population(env, n_steps, discount_factor, alpha=1.0, decay=None, e
     alpha falls to 1 % over the run; opponent: 'uniform', 'self', a fixed [nS, 5] policy or [n, nS, 5], one per member.
     Returns, for members first .. first + count - 1 (count None: to the end), (pi_a[count, nS, 5], pi_b, V[count, nS],
     Q[count, nS, 5, 5], alpha[count])."""
-    b = _two_player_batch(env, "minimax_q_population")
-    n_steps = int(n_steps)
-    assert n_steps >= 0, "n_steps must be >= 0"
-    if decay is None:
-        decay = 0.01 ** (1.0 / max(n_steps, 1))
-    pop = b.minimax_q_population(discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, opponent=opponent)
-    try:
-        if b.get_state()["needs_reset"].any():
-            (env if hasattr(env, "_batch") else b).reset()
-        pop.run(n_steps)
-        r = pop.read(first, count)
-    finally:
-        pop.close()
-    return r["pi_a"], r["pi_b"], r["V"], r["Q"], r["alpha"]
+    return _train(env, "minimax_q_population", "minimax_q_population", n_steps, ("pi_a", "pi_b", "V", "Q", "alpha"), (first, count),
+                  discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, opponent=opponent)
 
 
 def minimax_value_iteration(env, theta, discount_factor, max_sweeps=1000000):
@@ -239,15 +175,7 @@ def minimax_value_iteration(env, theta, discount_factor, max_sweeps=1000000):
     Returns (pi_a[nS, 5], pi_b[nS, 5], V, Q[nS, 5, 5], iterations): player A's maximin and player B's minimax stage-game
     strategies, ready for VectorSoccerEnv.rollout(sample_actions=True, mixed_policies={...}).  RuntimeError if max_sweeps is
     reached: the handle's exception passes through, its .results holding the tuple of sweep max_sweeps."""
-    from .core import SoccerBatch
-    if isinstance(env, SoccerBatch):
-        b = env
-    else:
-        b = getattr(env, "_batch", None)
-        if b is None:
-            raise TypeError("planners expect a gym_soccer_littman94_amd environment")
-        assert env.multiagent, "minimax_value_iteration needs a two-player environment (no player with a fixed policy)"
-    return b.minimax_value_iteration(theta, discount_factor, max_sweeps=max_sweeps)
+    return _two_player_batch(env, "minimax_value_iteration").minimax_value_iteration(theta, discount_factor, max_sweeps=max_sweeps)
 
 
 def best_response(env, policy, player, theta, discount_factor, max_sweeps=1000000):
