@@ -141,6 +141,20 @@ class OMPopulationConfig(C.Structure):
     _fields_ = QPopulationConfig._fields_
 
 
+class RegretPopulationConfig(C.Structure):
+    """soccer_regret_population_config"""
+    _fields_ = [("discount_factor", C.c_double), ("alpha", C.c_double), ("decay", C.c_double), ("explor", C.c_double),
+                ("q_init", C.c_double), ("act_a", C.c_int32), ("act_b", C.c_int32), ("plus", C.c_int32), ("linear", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("policy_a", "policy_b", "policy_a_per_member", "policy_b_per_member", "alpha_per_member",
+                                          "decay_per_member", "explor_per_member", "discount_factor_per_member")]
+
+
+class RegretPopulationState(C.Structure):
+    """soccer_regret_population_state"""
+    _fields_ = [(n, C.c_void_p) for n in ("Q_a", "Q_b", "R_a", "R_b", "Z_a", "Z_b", "updates", "alpha")] + \
+               [("steps", C.POINTER(C.c_uint64))]
+
+
 MQ_UNIFORM, MQ_SELF, MQ_FIXED = 0, 1, 2
 QL_GREEDY, QL_UNIFORM, QL_FIXED = 0, 1, 2
 PHC_LEARN, PHC_UNIFORM, PHC_FIXED = 0, 1, 2
@@ -266,6 +280,12 @@ PROTOTYPES = {
     "soccer_om_population_update": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
     "soccer_om_population_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64)]),
     "soccer_om_population_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64)]),
+    "soccer_regret_population_create": (C.c_int, [C.c_void_p, C.POINTER(RegretPopulationConfig), C.POINTER(C.c_void_p)]),
+    "soccer_regret_population_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "soccer_regret_population_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "soccer_regret_population_update": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
+    "soccer_regret_population_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(RegretPopulationState)]),
+    "soccer_regret_population_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(RegretPopulationState)]),
     "soccer_prob_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 12)]),
     "soccer_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint64)]),
     "soccer_reset_stats": (C.c_int, [C.c_void_p]),

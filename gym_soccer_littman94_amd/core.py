@@ -12,9 +12,10 @@ from . import _lib
 from ._device import DeviceArray, _ptr
 from ._lib import Config, RolloutArgs, StepArgs
 from .learners import (GradientPlay, MinimaxQLearner, MinimaxQPopulation, OpponentModelPopulation, QLearner, QPopulation,  # noqa: F401
-                       WolfPHCLearner, WolfPopulation, _meta_of_cross_play, league_config, minimax_q_config,
+                       RegretPopulation, WolfPHCLearner, WolfPopulation, _meta_of_cross_play, league_config, minimax_q_config,
                        minimax_q_population_config, om_derive, om_model, om_population_config, q_learning_config,
-                       q_population_config, wolf_phc_config, wolf_population_config)
+                       q_population_config, regret_average, regret_policy, regret_population_config, wolf_phc_config,
+                       wolf_population_config)
 
 
 def meta_lds_bytes(n_a, n_b):
@@ -495,6 +496,16 @@ class SoccerBatch:
         Q, V and strategies.  discount_factor, alpha, decay and explor are scalars or arrays of one value per lane; opponent:
         'uniform', 'self', a fixed [nS, 5] mixed policy for every member or [n, nS, 5], one per member."""
         return MinimaxQPopulation(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, opponent=opponent)
+
+    def regret_population(self, discount_factor, alpha=1.0, decay=0.01 ** (1 / 1e6), explor=0.2, q_init=1.0, plus=True, linear=False,
+                          act_a="learn", act_b="learn"):
+        """A RegretPopulation on this batch (two players, autoreset=True): a regret-matching learner per lane, each with its
+        own tables, cumulative regrets and policy sums.  discount_factor, alpha, decay and explor are scalars or arrays of one
+        value per lane; plus floors the regrets at 0 (regret matching+), linear weighs a step's policy by the state's visit
+        count; act_a / act_b: 'learn', 'uniform', a fixed [nS, 5] mixed policy for every member or [n, nS, 5], one per
+        member."""
+        return RegretPopulation(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, plus=plus, linear=linear,
+                                act_a=act_a, act_b=act_b)
 
     # -- hot path -------------------------------------------------------------------------------
     def reset(self, mask=None, u_reset=None, obs=None):

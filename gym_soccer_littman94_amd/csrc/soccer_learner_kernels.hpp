@@ -7,7 +7,8 @@
 // one-actor policy hill-climbers: phc_pop_run_kernel, phc_pop_update_kernel, phc_pop_init_kernel, phc_pop_adopt_kernel; and the
 // population of one-actor minimax-Q learners, a wave per member: mq_pop_run_kernel, mq_pop_update_kernel, mq_pop_solve_kernel,
 // mq_pop_init_kernel; and the population of one-actor opponent-modelling Q-learners: om_pop_run_kernel, om_pop_update_kernel,
-// om_pop_init_kernel, om_pop_derive_kernel (at the end).
+// om_pop_init_kernel, om_pop_derive_kernel; and the population of one-actor regret matchers: rm_pop_run_kernel,
+// rm_pop_update_kernel, rm_pop_init_kernel (at the end).
 // Included by soccer_learners.hip only: every kernel is emitted by exactly one translation unit.
 //
 // One learner step (include/soccer_hip.h, "learners") is two launches in stream order, no grid barrier between them:
@@ -1503,6 +1504,238 @@ __global__ __launch_bounds__(kBlock) void om_pop_derive_kernel(const PopIO L, un
         om_derive(row, V, g);
         om_store_derived(at, V, g);
     }
+}
+
+// =================================================================================================
+// a population of regret matchers, a learner per lane (include/soccer_hip.h, "learners, a population of regret matchers")
+// =================================================================================================
+// phc_pop_run_kernel's shape: a thread owns lane i and member i, the lane and the rows of the current state in registers over
+// the launch's steps, no atomics, no second launch.  lane_words / draw_from_word / lane_step / learner_thresholds are the same
+// functions the other learners call.
+// Table layout: the hill-climbers' [nS][32] float64 row with two columns reread, one 256-byte aligned row per state:
+//     0..4 Q_a   5..9 Q_b   10..14 R_a   15..19 Z_a   20..24 R_b   25..29 Z_b   30 updates (uint64)   31 pad
+// so phc_pop_load_q / _pi / _avg load Q, R and Z, and everything a step needs at s is two cache lines.  The policy is NOT
+// stored: rm_policy recomputes it from R (five divides per player and state instead of a third cache line; which is cheaper is
+// unmeasured).  A FIXED player's rows live in a buffer of their own, [n or 1][nS][5], read only on the wave-uniform
+// FIXED branch: at s for the draw and at s' for the bootstrap.
+// What a step carries: Q_a, Q_b, R_a, R_b at s (the next draw and, as the previous step's s' rows, the bootstrap).  Z and updates
+// at s are used only after the environment step: their loads are issued at the top of the step and nothing of them lives
+// across steps.  Everything is unrolled over the five actions with the action index COMPARED, never used as a subscript: the
+// rows stay in registers (0 bytes of scratch).
+constexpr int kRmR = kPhcPi, kRmZ = kPhcAvg, kRmPlayer = kPhcPlayer, kRmUpdates = kPhcUpdates;   // R_p at kRmR + p * kRmPlayer, Z_p at kRmZ + ...
+
+struct RmPopIO {
+    double* tab;                        // [n][nS][32]
+    double* alpha;                      // [n] every member's learning rate
+    const double* decay;                // [n]
+    const double* explor;               // [n]
+    const double* gamma;                // [n]
+    const double* fixed[2];             // a FIXED player's rows [nS][5] (fixed_member = 0) or [n][nS][5]; else nullptr
+    unsigned long long fixed_member[2]; // float64 elements between two members' rows
+    unsigned long long* steps;
+    unsigned int* misuse;               // the handle's sticky words
+    int32_t nS;
+    int32_t n_steps;                    // rm_pop_run_kernel: steps of this launch
+    int32_t mode[2];                    // SOCCER_PHC_* of player A, player B
+    int32_t plus, linear;               // regrets floored at 0; a step's policy weighed by the visit count
+};
+
+// policy(p, s) of the header for a LEARN player: the normalised positive part of its regrets R (rows of ten: both players')
+__device__ __forceinline__ void rm_policy(const double (&R)[10], int p, double (&pi)[10]) {
+    double pos[5], tot = 0.0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { pos[k] = R[5 * p + k] > 0.0 ? R[5 * p + k] : 0.0; tot = tot + pos[k]; }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) pi[5 * p + k] = tot > 0.0 ? pos[k] / tot : 0.2;
+}
+
+// policy(p, s) for both players: R = the regrets at s, s = the state (a FIXED player's row is loaded from its own buffer)
+__device__ __forceinline__ void rm_policies(const RmPopIO& L, const double* const (&fixed)[2], const double (&R)[10], uint32_t s,
+                                            double (&pi)[10]) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (L.mode[p] == kPhcLearn) {                              // wave-uniform
+            rm_policy(R, p, pi);
+        } else if (L.mode[p] == kPhcUniform) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) pi[5 * p + k] = 0.2;
+        } else {
+            const double* const row = fixed[p] + (size_t)s * 5;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) pi[5 * p + k] = row[k];
+        }
+    }
+}
+
+// a player's action from its 15-bit draw h: the null row table, or the thresholds of its policy row at s — with the member's
+// explor for a LEARN player, with 0.0 for a FIXED one (phc_pop_draw's rule)
+__device__ __forceinline__ uint32_t rm_pop_draw(const RmPopIO& L, int p, const double (&pi)[10], double explor, uint32_t h) {
+    if (L.mode[p] == kPhcUniform) return (h * 5u) >> 15;                      // wave-uniform
+    double row[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) row[k] = pi[5 * p + k];
+    __attribute__((aligned(8))) uint16_t t[4];
+    learner_thresholds(row, L.mode[p] == kPhcLearn ? explor : 0.0, t);
+    return thresholds_not_above(*reinterpret_cast<const uint2*>(t), h);
+}
+
+// steps 2-4 of one member on its one transition.  `at` = its row at s; q / R = Q_a | Q_b and R_a | R_b at s, Z and upd what
+// the row holds, pi = both policies at s; nq and npi = Q_a | Q_b and both policies at s' as they were BEFORE this update.
+// Leaves the new q and R in the caller's registers and stores everything that moved.
+__device__ __forceinline__ void rm_pop_learn(const RmPopIO& L, double* at, double (&q)[10], double (&R)[10], double (&Z)[10],
+                                             unsigned long long upd, const double (&pi)[10], const double (&nq)[10],
+                                             const double (&npi)[10], uint32_t a, uint32_t b, int32_t r, uint32_t term, double alpha,
+                                             double gamma) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {                                   // step 2: the bootstrap is the value of the player's own policy
+        double v = 0.0;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) v = v + npi[5 * p + k] * nq[5 * p + k];
+        v = term ? 0.0 : v;
+        const double m = (double)(p ? -r : r) + gamma * v;         // player B's own reward
+        const uint32_t act = p ? b : a;
+        double moved_q = 0.0;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const double old = q[5 * p + k];
+            const double moved = old + alpha * (m - old);
+            q[5 * p + k] = (uint32_t)k == act ? moved : old;
+            moved_q = (uint32_t)k == act ? moved : moved_q;
+        }
+        at[(p ? 5u : 0u) + act] = moved_q;
+    }
+    upd += 1ull;                                                    // step 3
+    *reinterpret_cast<unsigned long long*>(at + kRmUpdates) = upd;
+    const double w = L.linear ? (double)upd : 1.0;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {                                   // step 4
+        if (L.mode[p] != kPhcLearn) continue;                       // wave-uniform
+        double u = 0.0, r5[5], z5[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) u = u + pi[5 * p + k] * q[5 * p + k];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            double x = R[5 * p + k] + (q[5 * p + k] - u);
+            if (L.plus) x = x > 0.0 ? x : 0.0;
+            r5[k] = x; R[5 * p + k] = x;
+            z5[k] = Z[5 * p + k] + w * pi[5 * p + k];
+        }
+        double2* const to = reinterpret_cast<double2*>(at + kRmR + p * kRmPlayer);          // R_p | Z_p: ten values
+        to[0] = make_double2(r5[0], r5[1]); to[1] = make_double2(r5[2], r5[3]); to[2] = make_double2(r5[4], z5[0]);
+        to[3] = make_double2(z5[1], z5[2]); to[4] = make_double2(z5[3], z5[4]);
+    }
+}
+
+template <bool SLIP, bool LUT_LDS>
+__global__ __launch_bounds__(kBlock) void rm_pop_run_kernel(const KernelParams P, const RmPopIO L) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    HistAcc<false> hist; hist.init(P);
+    const Tables T = stage_tables<LUT_LDS>(P, smem);
+    const unsigned long long tick0 = *P.tick_in;
+    publish_tick(P, tick0, (unsigned long long)L.n_steps);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps += (unsigned long long)L.n_steps;
+    bool any_frozen = false;
+    for (unsigned long long g = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; g < P.n;
+         g += (unsigned long long)gridDim.x * kBlock) {
+        const unsigned long long i0 = P.first + g;                  // the lane, and the member
+        LaneVec<1> S; S.load(P, i0);
+        double* const tab = L.tab + (size_t)i0 * (size_t)L.nS * kPhcRow;
+        // (a null pointer plus zero for a player that is not FIXED: never read)
+        const double* const fixed[2] = {L.fixed[0] + (size_t)i0 * (size_t)L.fixed_member[0], L.fixed[1] + (size_t)i0 * (size_t)L.fixed_member[1]};
+        double alpha = L.alpha[i0];
+        const double decay = L.decay[i0], explor = L.explor[i0], gamma = L.gamma[i0];
+        uint32_t s = obs_of(T, P, S.L[0].A, S.L[0].B, S.L[0].p);
+        double q[10], R[10];
+        phc_pop_load_q(tab + (size_t)s * kPhcRow, q);
+        phc_pop_load_pi(tab + (size_t)s * kPhcRow, R);
+        int32_t ret = 0; uint32_t eps = 0u, nonzero = 0u;
+        for (int t = 0; t < L.n_steps; ++t) {
+            const unsigned long long tick = tick0 + (unsigned long long)t;
+            double* const at = tab + (size_t)s * kPhcRow;
+            // used after the environment step only: issued here, dead at the end of the step
+            double Z[10];
+            phc_pop_load_avg(at, Z);
+            const unsigned long long upd = *reinterpret_cast<const unsigned long long*>(at + kRmUpdates);
+            double pi[10];
+            rm_policies(L, fixed, R, s, pi);
+            uint32_t words[1], awords[1];
+            lane_words<1>(P, P.lane_offset + i0, block_tick<SLIP>(tick), 0u, words);
+            lane_words<1>(P, P.lane_offset + i0, tick, 1u, awords);
+            const Draw d = draw_from_word<SLIP>(words[0], tick);
+            // two actions from one 32-bit word, 15 bits each (rollout_group)
+            const uint32_t a = rm_pop_draw(L, 0, pi, explor, awords[0] & 0x7fffu);
+            const uint32_t b = rm_pop_draw(L, 1, pi, explor, (awords[0] >> 16) & 0x7fffu);
+            StepResult Rs;
+            const bool frozen = lane_step<SLIP, true>(T, P, S.L[0], a, b, d, Rs);
+            ret += Rs.reward; eps += Rs.finished; nonzero += (uint32_t)Rs.reward & 1u;
+            any_frozen |= frozen;
+            // (a lane parked in a goal tuple by soccer_set_state has s = 0: never a current state)
+            const bool learn = !frozen && s != 0u;
+            const uint32_t s2 = Rs.final_obs, sn = Rs.obs;
+            double nq[10], nR[10];
+            if (learn) {
+                phc_pop_load_q(tab + (size_t)s2 * kPhcRow, nq);     // before the stores below: s' may be s
+                phc_pop_load_pi(tab + (size_t)s2 * kPhcRow, nR);
+                double npi[10];
+                rm_policies(L, fixed, nR, s2, npi);
+                rm_pop_learn(L, at, q, R, Z, upd, pi, nq, npi, a, b, Rs.reward, Rs.term, alpha, gamma);
+            }
+            if (learn && sn == s2) {                                // the episode goes on: the rows at s' are the next rows at s
+                if (s2 != s) {
+#pragma unroll
+                    for (int k = 0; k < 10; ++k) { q[k] = nq[k]; R[k] = nR[k]; }
+                }                                                   // (s' == s: q and R already hold what the update wrote)
+            } else if (sn != s) {
+                phc_pop_load_q(tab + (size_t)sn * kPhcRow, q);      // after a reset
+                phc_pop_load_pi(tab + (size_t)sn * kPhcRow, R);
+            }
+            s = sn;
+            alpha = alpha * decay;
+        }
+        S.store(P, i0);
+        L.alpha[i0] = alpha;
+        hist.add_totals(eps, ret, nonzero);
+    }
+    if (any_frozen) P.misuse[0] = 1u;
+    hist.flush(P);
+}
+
+// soccer_regret_population_update: steps 1-5 on the caller's transitions, transition i for member i
+__global__ __launch_bounds__(kBlock) void rm_pop_update_kernel(const RmPopIO L, long long n, const uint16_t* obs, const int8_t* act_a,
+                                                               const int8_t* act_b, const int8_t* reward, const uint8_t* terminated,
+                                                               const uint16_t* next_obs) {
+    bool bad_act = false, bad_obs = false;
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
+        const uint32_t s = obs[i], s2 = next_obs[i], a = (uint8_t)act_a[i], b = (uint8_t)act_b[i];
+        const bool ba = a > 4u || b > 4u, bo = s == 0u || s >= (uint32_t)L.nS || s2 >= (uint32_t)L.nS;
+        bad_act |= ba; bad_obs |= bo;
+        const double alpha = L.alpha[i];
+        if (!ba && !bo) {
+            double* const tab = L.tab + (size_t)i * (size_t)L.nS * kPhcRow;
+            double* const at = tab + (size_t)s * kPhcRow;
+            const double* const fixed[2] = {L.fixed[0] + (size_t)i * (size_t)L.fixed_member[0], L.fixed[1] + (size_t)i * (size_t)L.fixed_member[1]};
+            double q[10], R[10], Z[10], pi[10], nq[10], nR[10], npi[10];
+            phc_pop_load_q(at, q); phc_pop_load_pi(at, R); phc_pop_load_avg(at, Z);
+            const unsigned long long upd = *reinterpret_cast<const unsigned long long*>(at + kRmUpdates);
+            phc_pop_load_q(tab + (size_t)s2 * kPhcRow, nq);
+            phc_pop_load_pi(tab + (size_t)s2 * kPhcRow, nR);
+            rm_policies(L, fixed, R, s, pi);
+            rm_policies(L, fixed, nR, s2, npi);
+            rm_pop_learn(L, at, q, R, Z, upd, pi, nq, npi, a, b, (int32_t)reward[i], terminated[i] != 0u ? 1u : 0u, alpha, L.gamma[i]);
+        }
+        L.alpha[i] = alpha * L.decay[i];
+    }
+    if (bad_act) L.misuse[1] = 1u;
+    if (bad_obs) L.misuse[2] = 1u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps += 1ull;
+}
+
+// creation: every member's Q_p = q_init on the live states and zero in row 0, R = Z = 0, updates = 0
+__global__ __launch_bounds__(kBlock) void rm_pop_init_kernel(const RmPopIO L, unsigned long long n, double q_init) {
+    const unsigned long long per = (unsigned long long)L.nS * kPhcRow, cells = n * per;
+    for (unsigned long long c = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; c < cells; c += (unsigned long long)gridDim.x * kBlock)
+        L.tab[c] = (unsigned)(c % kPhcRow) < 10u && (c % per) >= (unsigned long long)kPhcRow ? q_init : 0.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *L.steps = 0ull;
 }
 
 }  // namespace soccer

@@ -1,7 +1,7 @@
-// soccer_learners.hip — the seven kinds of learners (see soccer_handle.hpp): the minimax-Q learner soccer_minimax_q_*, the
+// soccer_learners.hip — the eight kinds of learners (see soccer_handle.hpp): the minimax-Q learner soccer_minimax_q_*, the
 // independent Q-learners soccer_q_learner_*, the policy hill-climbers soccer_wolf_phc_*, and the populations of one-actor
 // learners, a member per lane: soccer_q_population_*, soccer_wolf_population_*, soccer_minimax_q_population_*,
-// soccer_om_population_*.
+// soccer_om_population_*, soccer_regret_population_*.
 //
 // What the kinds share comes first and is written once: the registry of live learners with its checks and destroy, the
 // kernel-shape dispatch, the prologue and the hyperparameter checks of a creation, the messages of a refused table
@@ -108,6 +108,14 @@ struct soccer_om_population : Population {
     PopIO io{};
     int grid_blocks = 0;                // as soccer_q_population's
     explicit soccer_om_population(soccer_handle* handle) : Population(handle, kKind, "the population of opponent-modelling Q-learners") {}
+};
+
+// a member is a thread of rm_pop_run_kernel; a FIXED player's rows are a buffer of their own
+struct soccer_regret_population : Population {
+    static constexpr int kKind = 7;
+    RmPopIO io{};
+    int grid_blocks = 0;                // as soccer_q_population's
+    explicit soccer_regret_population(soccer_handle* handle) : Population(handle, kKind, "the population of regret matchers") {}
 };
 #pragma GCC visibility pop
 
@@ -1359,5 +1367,149 @@ extern "C" int soccer_om_population_load(soccer_handle* h, soccer_om_population*
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
+    return SOCCER_OK;
+}
+
+// ---- populations of regret matchers: soccer_regret_population_* ------------------------------------
+// (the modes are the hill-climbers': kPhcLearn / kPhcUniform / kPhcFixed, asserted above)
+// the parts of a member's rows as the caller sees them; has[p]: player p LEARNs, so its R and Z move
+template <class V, class U>
+static void rm_parts(V* Q_a, V* Q_b, V* R_a, V* R_b, V* Z_a, V* Z_b, U* updates, const bool (&has)[2], RowPart<V> (&parts)[7]) {
+    parts[0] = {Q_a, 0, 5, kRow0Zero}; parts[1] = {Q_b, 5, 5, kRow0Zero};
+    parts[2] = {has[0] ? R_a : nullptr, kRmR, 5, kRow0Zero}; parts[3] = {has[1] ? R_b : nullptr, kRmR + kRmPlayer, 5, kRow0Zero};
+    parts[4] = {has[0] ? Z_a : nullptr, kRmZ, 5, kRow0Zero}; parts[5] = {has[1] ? Z_b : nullptr, kRmZ + kRmPlayer, 5, kRow0Zero};
+    parts[6] = {updates, kRmUpdates, 1, kRow0Copy};
+}
+
+// rows 1.. of `members` tables [nS][5] of a checkpoint: every value finite, and >= 0 where `nonneg`
+static int finite_check(soccer_handle* h, const char* what, const char* name, const double* v, size_t members, size_t nS, bool nonneg) {
+    for (size_t m = 0; m < members; ++m)
+        for (size_t s = 1; s < nS; ++s)
+            for (size_t k = 0; k < 5; ++k) {
+                const double x = v[(m * nS + s) * 5 + k];
+                if (!std::isfinite(x) || (nonneg && x < 0.0))
+                    return fail(h, SOCCER_E_INVALID, "%s: %s[%zu][%zu][%zu] is %s", what, name, m, s, k,
+                                nonneg ? "negative or not a finite number" : "not a finite number");
+            }
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_regret_population_create(soccer_handle* h, const soccer_regret_population_config* cfg, soccer_regret_population** out) {
+    static const char* const what = "soccer_regret_population_create";
+    if (int rc = create_check(h, cfg, out, what)) return rc;
+    const size_t n = (size_t)h->cfg.n_lanes;
+    std::vector<double> par[4];         // alpha, decay, explor, discount_factor
+    if (int rc = pop_params(h, cfg, n, par)) return rc;
+    if (!phc_kind(cfg->act_a) || !phc_kind(cfg->act_b))
+        return fail(h, SOCCER_E_INVALID, "act_a / act_b must be SOCCER_PHC_LEARN, SOCCER_PHC_UNIFORM or SOCCER_PHC_FIXED");
+    if ((cfg->plus != 0 && cfg->plus != 1) || (cfg->linear != 0 && cfg->linear != 1))
+        return fail(h, SOCCER_E_INVALID, "plus / linear must be 0 or 1");
+    const int nS = h->rules.nS;
+    const int32_t kinds[2] = {cfg->act_a, cfg->act_b};
+    const double* shared[2] = {cfg->policy_a, cfg->policy_b};
+    const double* each[2] = {cfg->policy_a_per_member, cfg->policy_b_per_member};
+    static const char* const names[2][2] = {{"policy_a", "policy_a_per_member"}, {"policy_b", "policy_b_per_member"}};
+    for (int p = 0; p < 2; ++p) {
+        if ((kinds[p] == SOCCER_PHC_FIXED) != ((shared[p] != nullptr) != (each[p] != nullptr)) || (shared[p] && each[p]))
+            return fail(h, SOCCER_E_INVALID, "exactly one of %s and %s goes with act_%c == SOCCER_PHC_FIXED, and neither with another mode",
+                        names[p][0], names[p][1], p ? 'b' : 'a');
+        // (row 0 included, as a fixed policy's thresholds check it; a shared policy is member 0 of one)
+        if (shared[p]) if (int rc = rows_check(h, what, names[p][0], shared[p], 1, nS, 0)) return rc;
+        if (each[p]) if (int rc = rows_check(h, what, names[p][1], each[p], n, nS, 0)) return rc;
+    }
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, with_shape(h, [&](auto slip, auto lds) { return raise_lds_limit(h, rm_pop_run_kernel<slip, lds>); }));
+    std::unique_ptr<soccer_regret_population> owner(new soccer_regret_population(h));
+    soccer_regret_population* q = owner.get();
+    q->grid_blocks = (int)env_in("SOCCER_POP_GRID_BLOCKS", 1, h->grid_cap, 0);
+    RmPopIO& io = q->io;
+    double* dpar[4] = {nullptr, nullptr, nullptr, nullptr};
+    double* dfixed[2] = {nullptr, nullptr};
+    const size_t per = (size_t)nS * kPhcRow, rows = (size_t)nS * 5;
+    int rc = q->bufs.alloc(h, n * per, &io.tab);               // (a failure frees what was taken: `owner` goes, the handle is as it was)
+    for (int k = 0; k < 4; ++k) if (!rc) rc = q->bufs.alloc(h, n, &dpar[k]);
+    for (int p = 0; p < 2; ++p)
+        if (!rc && kinds[p] == SOCCER_PHC_FIXED) rc = q->bufs.alloc(h, (each[p] ? n : 1) * rows, &dfixed[p]);
+    if (!rc) rc = q->bufs.alloc(h, 1, &io.steps);
+    if (rc) return rc;
+    io.alpha = dpar[0]; io.decay = dpar[1]; io.explor = dpar[2]; io.gamma = dpar[3];
+    io.misuse = h->d_misuse;
+    io.nS = nS; io.n_steps = 0;
+    io.plus = cfg->plus; io.linear = cfg->linear;
+    for (int p = 0; p < 2; ++p) {
+        io.mode[p] = kinds[p];
+        io.fixed[p] = dfixed[p];
+        io.fixed_member[p] = each[p] ? (unsigned long long)rows : 0ull;
+        if (dfixed[p])          // (created() waits: the caller's array is pageable host memory)
+            HIP_TRY(h, hipMemcpyAsync(dfixed[p], each[p] ? each[p] : shared[p], (each[p] ? n : 1) * rows * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    for (int k = 0; k < 4; ++k) HIP_TRY(h, hipMemcpyAsync(dpar[k], par[k].data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(rm_pop_init_kernel, dim3(grid_for(h, (uint64_t)n * (uint64_t)per)), dim3(kBlock), 0, h->stream, io, (unsigned long long)n, cfg->q_init);
+    return created(owner, out);
+}
+
+extern "C" int soccer_regret_population_destroy(soccer_handle* h, soccer_regret_population* q) {
+    return destroy(h, q, "soccer_regret_population_destroy");
+}
+
+extern "C" int soccer_regret_population_run(soccer_handle* h, soccer_regret_population* q, int32_t n_steps) {
+    if (int rc = run_check(h, q, n_steps, "soccer_regret_population_run")) return rc;
+    return pop_run(h, q, n_steps, [&](const KernelParams& P, const RmPopIO& io) {
+        return with_shape(h, [&](auto slip, auto lds) {
+            hipLaunchKernelGGL((rm_pop_run_kernel<slip, lds>), dim3(pop_grid(h, q->grid_blocks, P.n)), dim3(kBlock), h->smem_bytes, h->stream, P, io);
+            return hipSuccess;
+        });
+    });
+}
+
+extern "C" int soccer_regret_population_update(soccer_handle* h, soccer_regret_population* q, const uint16_t* obs, const int8_t* act_a,
+                                               const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs) {
+    if (int rc = pop_update_check(h, q, "soccer_regret_population_update", obs, act_a, act_b, reward, terminated, next_obs)) return rc;
+    hipLaunchKernelGGL(rm_pop_update_kernel, dim3(pop_grid(h, q->grid_blocks, (uint64_t)q->n)), dim3(kBlock), 0, h->stream, q->io, (long long)q->n,
+                       obs, act_a, act_b, reward, terminated, next_obs);
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_regret_population_read(soccer_handle* h, soccer_regret_population* q, int64_t first, int64_t count,
+                                             const soccer_regret_population_state* out) {
+    if (int rc = check(h, q, "soccer_regret_population_read")) return rc;
+    if (int rc = range_check(h, q, "soccer_regret_population_read", first, count)) return rc;
+    if (!out) return fail(h, SOCCER_E_INVALID, "soccer_regret_population_read: out is NULL");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const RmPopIO& io = q->io;
+    if (out->alpha && count) HIP_TRY(h, hipMemcpyAsync(out->alpha, io.alpha + first, (size_t)count * 8, hipMemcpyDeviceToHost, h->stream));
+    if (out->steps) HIP_TRY(h, hipMemcpyAsync(out->steps, io.steps, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const bool all[2] = {true, true};   // (R and Z of a player that does not learn are the zeros creation gave)
+    RowPart<void> parts[7];
+    rm_parts<void, void>(out->Q_a, out->Q_b, out->R_a, out->R_b, out->Z_a, out->Z_b, out->updates, all, parts);
+    return pop_rows_read(h, PopTable{io.tab, (size_t)io.nS, kPhcRow}, first, count, parts);
+}
+
+extern "C" int soccer_regret_population_load(soccer_handle* h, soccer_regret_population* q, int64_t first, int64_t count,
+                                             const soccer_regret_population_state* in) {
+    static const char* const what = "soccer_regret_population_load";
+    if (int rc = check(h, q, what)) return rc;
+    if (int rc = range_check(h, q, what, first, count)) return rc;
+    if (!in) return fail(h, SOCCER_E_INVALID, "soccer_regret_population_load: in is NULL");
+    const RmPopIO& io = q->io;
+    const size_t nS = (size_t)io.nS;
+    const bool has[2] = {io.mode[0] == kPhcLearn, io.mode[1] == kPhcLearn};
+    RowPart<const void> parts[7];
+    rm_parts<const void, const void>(in->Q_a, in->Q_b, in->R_a, in->R_b, in->Z_a, in->Z_b, in->updates, has, parts);
+    static const char* const names[6] = {"Q_a", "Q_b", "R_a", "R_b", "Z_a", "Z_b"};
+    // everything is checked before anything is written
+    for (int i = 0; i < 2; ++i)
+        if (parts[i].host && count) if (int rc = bounds_check(h, what, names[i], (const double*)parts[i].host, (size_t)count, nS, 5)) return rc;
+    for (int i = 2; i < 6; ++i)
+        if (parts[i].host)
+            if (int rc = finite_check(h, what, names[i], (const double*)parts[i].host, (size_t)count, nS, i >= 4 || io.plus != 0)) return rc;
+    if (in->alpha) if (int rc = unit_check(h, what, "alpha", in->alpha, (size_t)count)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = pop_rows_load(h, PopTable{io.tab, nS, kPhcRow}, first, count, parts)) return rc;
+    if (in->alpha && count) HIP_TRY(h, hipMemcpy(io.alpha + first, in->alpha, (size_t)count * 8, hipMemcpyHostToDevice));
+    if (in->steps) HIP_TRY(h, hipMemcpy(io.steps, in->steps, 8, hipMemcpyHostToDevice));
     return SOCCER_OK;
 }

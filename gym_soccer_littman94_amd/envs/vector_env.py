@@ -506,6 +506,12 @@ class VectorSoccerEnv:
         assert self.multiagent, "wolf_population needs a two-player environment (no player with a fixed policy)"
         return self._batch.wolf_population(discount_factor, **params)
 
+    def regret_population(self, discount_factor, **params):
+        """A RegretPopulation (SoccerBatch.regret_population): a regret-matching learner per lane of this env, each with its
+        own tables, cumulative regrets and policy sums."""
+        assert self.multiagent, "regret_population needs a two-player environment (no player with a fixed policy)"
+        return self._batch.regret_population(discount_factor, **params)
+
     def minimax_q_population(self, discount_factor, **params):
         """A MinimaxQPopulation (SoccerBatch.minimax_q_population): a minimax-Q learner per lane of this env, each with its
         own Q, V and strategies."""

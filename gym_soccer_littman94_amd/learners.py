@@ -175,6 +175,23 @@ def wolf_population_config(n, nS, discount_factor, alpha=1.0, decay=DECAY, explo
     return cfg, ((list(shared), list(each)), arrays)
 
 
+def regret_population_config(n, nS, discount_factor, alpha=1.0, decay=DECAY, explor=0.2, q_init=1.0, plus=True, linear=False,
+                             act_a="learn", act_b="learn"):
+    """Checks the parameters of a population of regret matchers (AssertionError, before any library call) and returns
+    (soccer_regret_population_config, the arrays it points into).  discount_factor, alpha, decay and explor are scalars for
+    every member or arrays of n, one value per member; plus and linear are flags of the whole population; act_a / act_b:
+    'learn', 'uniform', one fixed [nS, 5] mixed policy for every member, or [n, nS, 5], a fixed policy per member."""
+    s, arrays = _members(n, discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor)
+    q0 = _scalar("q_init", q_init)
+    for name, flag in (("plus", plus), ("linear", linear)):
+        assert isinstance(flag, (bool, np.bool_)) or flag in (0, 1), "%s must be True or False" % name
+    kinds, shared, each = zip(_kind("act_a", act_a, _PHC_KINDS, nS, n, where=True), _kind("act_b", act_b, _PHC_KINDS, nS, n, where=True))
+    cfg = _lib.RegretPopulationConfig(s["discount_factor"], s["alpha"], s["decay"], s["explor"], q0, *kinds, int(bool(plus)),
+                                      int(bool(linear)), *[_data(x) for x in shared + each],
+                                      *[_data(arrays[k]) for k in ("alpha", "decay", "explor", "discount_factor")])
+    return cfg, ((list(shared), list(each)), arrays)
+
+
 def minimax_q_population_config(n, nS, discount_factor, alpha=1.0, decay=DECAY, explor=0.2, q_init=1.0, opponent="uniform"):
     """Checks the parameters of a population of minimax-Q learners (AssertionError, before any library call) and returns
     (soccer_minimax_q_population_config, the arrays it points into).  discount_factor, alpha, decay and explor are scalars
@@ -832,6 +849,90 @@ class MinimaxQPopulation(_Population):
         they are stored as given, so with what read() gave a fresh population continues bit for bit.  A refused load changes
         nothing."""
         return self._load(dict(Q=Q, V=V, pi_a=pi_a, pi_b=pi_b, alpha=alpha, steps=steps), first)
+
+
+def _ordered_sum(x):
+    """(((((0.0 + x[..., 0]) + x[..., 1]) + ...) + x[..., 4]): the device's order"""
+    tot = np.zeros(x.shape[:-1])
+    for k in range(5):
+        tot = tot + x[..., k]
+    return tot
+
+
+def regret_policy(R):
+    """policy(p, s) of a LEARN player by the definition's expression (include/soccer_hip.h, "learners, a population of regret
+    matchers"), operation for operation, so it equals the device's: regrets [..., 5] -> the normalised positive part, 0.2
+    where no regret is positive."""
+    R = np.asarray(R, np.float64)
+    pos = np.where(R > 0.0, R, 0.0)
+    tot = _ordered_sum(pos)[..., None]
+    return np.where(tot > 0.0, pos / np.where(tot > 0.0, tot, 1.0), 0.2)
+
+
+def regret_average(Z):
+    """The average policy of a LEARN player: policy sums [..., 5] -> Z / (the sum of the row, in the device's order), 0.2 where
+    that sum is 0."""
+    Z = np.asarray(Z, np.float64)
+    tot = _ordered_sum(Z)[..., None]
+    return np.where(tot == 0.0, 0.2, Z / np.where(tot == 0.0, 1.0, tot))
+
+
+class RegretPopulation(_population_with_a_choice("avg")):
+    """A population of regret matchers (Hart & Mas-Colell 2000; per state, with Q-values for counterfactual values) on a
+    two-player auto-reset SoccerBatch, a learner per lane: member i has its own Q_a, Q_b, cumulative regrets R_a, R_b and
+    policy sums Z_a, Z_b [nS, 5], updates[nS] and alpha and learns from lane i alone (include/soccer_hip.h, "learners, a
+    population of regret matchers").  plus floors the regrets at 0 (regret matching+), linear weighs a step's policy by the
+    state's visit count.  A fixed player's policy is shared or per member.  run() enqueues and returns; read() and the
+    properties synchronise and copy.  read(), load() and the evaluations take a range of members.  The evaluations take
+    which='avg', the pair of average policies (the one that carries the no-regret guarantee), or which='pi', the pair of
+    current policies."""
+    _C = "soccer_regret_population"
+    _STATE = _lib.RegretPopulationState
+    _FIELDS = tuple((k, _ROWS, np.float64) for k in ("Q_a", "Q_b", "R_a", "R_b", "Z_a", "Z_b")) + (
+        ("updates", (_S,), np.uint64), ("alpha", (), np.float64), ("steps", None, C.c_uint64))
+    _WHICH = {"avg": ("avg_a", "avg_b"), "pi": ("pi_a", "pi_b")}
+
+    def __init__(self, batch, discount_factor, **params):
+        cfg, keep = regret_population_config(batch.n, batch.nS, discount_factor, **params)
+        self._create(batch, cfg, keep[1])
+        self.modes = (cfg.act_a, cfg.act_b)
+        self.plus, self.linear = bool(cfg.plus), bool(cfg.linear)
+        # a fixed player's rows, [nS, 5] or [n, nS, 5]: read() hands them back (create has copied them to the device)
+        self._fixed = [None if x is None and y is None else (x if y is None else y).copy() for x, y in zip(*keep[0])]
+        del keep
+
+    def _policies(self, first, count, keys):
+        return self.read(first, count)
+
+    def read(self, first=0, count=None):
+        """dict for members first .. first + count - 1 (count None: to the end): Q_a / Q_b, R_a / R_b, Z_a / Z_b [count, nS, 5],
+        updates[count, nS], alpha[count], steps; and, computed here by the definition's expressions, pi_a / pi_b (the current
+        policies) and avg_a / avg_b (the average policies) [count, nS, 5]; a fixed or uniform player reads back its own rows
+        for both.  Synchronises."""
+        first, count = self._range(first, count)
+        out = self._read(None, first, count)
+        for p, name in enumerate("ab"):
+            if self.modes[p] == _lib.PHC_LEARN:
+                out["pi_" + name], out["avg_" + name] = regret_policy(out["R_" + name]), regret_average(out["Z_" + name])
+                continue
+            fixed = self._fixed[p]
+            rows = np.full((count, self.nS, 5), 0.2) if fixed is None else (
+                np.broadcast_to(fixed, (count, self.nS, 5)).copy() if fixed.ndim == 2 else fixed[first:first + count].copy())
+            out["pi_" + name], out["avg_" + name] = rows, rows.copy()
+        return out
+
+    alpha, steps = _field("alpha", "every member's learning rate, [n]"), _field("steps")
+
+    def load(self, Q_a=None, Q_b=None, R_a=None, R_b=None, Z_a=None, Z_b=None, updates=None, alpha=None, steps=None, first=0):
+        """Resume members first .. first + count - 1 from a checkpoint (count is what the arrays hold; None = unchanged): the
+        six tables [count, nS, 5] — Q in [-1, 1], R finite (and >= 0 under plus), Z finite and >= 0; those of a player that
+        does not learn are ignored —, updates[count, nS], alpha[count], steps for the population.  With what read() gave, a
+        fresh population continues bit for bit.  A refused load changes nothing."""
+        for k, x, nonneg in (("R_a", R_a, self.plus), ("R_b", R_b, self.plus), ("Z_a", Z_a, True), ("Z_b", Z_b, True)):
+            if x is not None:
+                x = np.asarray(x, np.float64)
+                assert np.isfinite(x).all() and (not nonneg or (x >= 0.0).all()), "%s must be finite%s" % (k, " and >= 0" if nonneg else "")
+        return self._load(dict(Q_a=Q_a, Q_b=Q_b, R_a=R_a, R_b=R_b, Z_a=Z_a, Z_b=Z_b, updates=updates, alpha=alpha, steps=steps), first)
 
 
 class GradientPlay(_Learner):

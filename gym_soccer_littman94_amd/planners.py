@@ -158,6 +158,20 @@ def wolf_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor
                   delta_win=delta_win, delta_lose=delta_lose, delta_decay=delta_decay, act_a=act_a, act_b=act_b)
 
 
+def regret_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, plus=True, linear=False,
+                      act_a="learn", act_b="learn", first=0, count=None):
+    """A population of regret matchers on the device, a learner per lane of `env`, each with its own tables, regrets, policy
+    sums and stream of experience: n_steps steps of every member from the lanes' current states (lanes that were never reset
+    are reset first).  discount_factor, alpha, decay and explor are scalars or arrays of one value per lane; decay None: alpha
+    falls to 1 % over the run; plus: regret matching+; linear: linear averaging; act_a / act_b: 'learn', 'uniform', a fixed
+    [nS, 5] policy or [n, nS, 5], one per member.  Returns, for members first .. first + count - 1 (count None: to the end),
+    (avg_a[count, nS, 5], avg_b, pi_a, pi_b, Q_a, Q_b, alpha[count]): the average policies first, they carry the guarantee; Q_b
+    is in player B's own reward."""
+    return _train(env, "regret_population", "regret_population", n_steps, ("avg_a", "avg_b", "pi_a", "pi_b", "Q_a", "Q_b", "alpha"), (first, count),
+                  discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, plus=plus, linear=linear,
+                  act_a=act_a, act_b=act_b)
+
+
 def minimax_q_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, opponent="uniform", first=0,
                          count=None):
     """A population of minimax-Q learners on the device, a learner per lane of `env`, each with its own table, strategies

@@ -1228,6 +1228,105 @@ int soccer_om_population_read(soccer_handle* h, soccer_om_population* q, int64_t
 int soccer_om_population_load(soccer_handle* h, soccer_om_population* q, int64_t first, int64_t count, const double* Q_a,
                               const double* Q_b, const uint64_t* C_a, const uint64_t* C_b, const double* alpha, const uint64_t* steps);
 
+/* ---- learners, a population of regret matchers (two-player handles; a regret-matching learner per lane)
+ * Regret matching (Hart & Mas-Colell 2000) per state, the "local no-regret" learner of Kash, Sullins & Hofmann (2020), the
+ * dynamic behind CFR and CFR+: Q-values stand in for counterfactual values, the policy is the normalised positive part of the
+ * cumulative regrets, and the AVERAGE policy is the one that carries the guarantee.  On a two-player SOCCER_F_AUTORESET handle
+ * of n lanes the population has n members, member i fed by lane i alone.  State of member i, float64 unless noted, per player
+ * p in {A, B}: Q_p[n_states][5] (B's in its own reward, -r), the cumulative regrets R_p[n_states][5], the policy sums
+ * Z_p[n_states][5]; updates[n_states] (uint64); alpha_i.  The population has one step counter.  Creation gives Q = q_init on the
+ * live states and 0 in row 0, R = Z = 0, updates = 0.  Two flags hold for the whole population: `plus` (regret matching+: the
+ * regrets are floored at 0) and `linear` (a step's policy is weighed by the state's visit count, CFR+'s averaging).
+ * A player is SOCCER_PHC_LEARN, SOCCER_PHC_UNIFORM or SOCCER_PHC_FIXED (the hill-climbers' constants, with their meanings); a
+ * FIXED player's policy is one [n_states][5] array shared by all members (policy_p) or a HOST array [n_lanes][n_states][5]
+ * (policy_p_per_member), exactly one of the two, checked as a fixed policy is; it is constant for the population's life.  BOTH
+ * Q tables always learn, however the players act.
+ * All arithmetic is float64, one operation at a time, never contracted.
+ *   policy(p, s), the row a player acts from before exploration:
+ *     LEARN:    pos[k] = R_p[s][k] > 0.0 ? R_p[s][k] : 0.0
+ *               tot    = (((((0.0 + pos[0]) + pos[1]) + pos[2]) + pos[3]) + pos[4])
+ *               pi[k]  = tot > 0.0 ? pos[k] / tot : 0.2
+ *     UNIFORM:  0.2 everywhere
+ *     FIXED:    the caller's row at s
+ * One step of member i on its lane's transition (s, a, b, r, terminated, s' = final_obs):
+ *   0. draw and step as the other populations do, the same Philox words and 15-bit halves: a LEARN player from the threshold
+ *      row of (1.0 - explor_i) * pi[k] + explor_i / 5.0 with pi = policy(p, s); a FIXED player the same with explor 0.0; a
+ *      UNIFORM player from the NULL row table, (h * 5) >> 15; batched_rollout(n_steps = 1, sample_actions = 1) with those rows
+ *   1. pi_p = policy(p, s) and pi'_p = policy(p, s') for both players; every read of row s' happens before any store of this
+ *      step (s' may be s)
+ *   2. for both players:  v = terminated ? 0.0 : sum_k pi'_p[k] * Q_p[s'][k], accumulated from 0.0 in k order;
+ *      m = (double)r_p + discount_factor_i * v with r_A = r, r_B = -r;  Q_p[s][act_p] = old + alpha_i * (m - old).  The
+ *      bootstrap is the value of the player's own current policy: not the maximum, and not quantised.  A truncated
+ *      transition that did not terminate bootstraps like any other
+ *   3. updates[s] += 1, n = (double)updates[s]
+ *   4. for each LEARN player, with the row of Q just written:  u = sum_k pi_p[k] * Q_p[s][k], accumulated from 0.0 in k
+ *      order;  for every k:  R_p[s][k] = R_p[s][k] + (Q_p[s][k] - u);  under `plus`  R = R > 0.0 ? R : 0.0;
+ *      Z_p[s][k] = Z_p[s][k] + w * pi_p[k] with w = linear ? n : 1.0.  A player that does not learn leaves R and Z untouched
+ *   5. alpha_i = alpha_i * decay_i; the step counter grows by one per step of the population
+ * A lane that still needs its first reset (SOCCER_MISUSE_FROZEN) and a lane whose current observation is 0 contribute
+ * nothing; their member's alpha still advances.  Derived by the reader, never state: pi_p = policy(p, .), and the average
+ * policy avg_p[s][k] = Z_p[s][k] / (the sum of Z_p[s], in the order of tot), 0.2 where that sum is 0.  The state is a fixed
+ * function of (seed, parameters, number of steps): it does not depend on how run() splits its launches, on the grid or on the
+ * state layout.
+ * Hyperparameters: scalars for everyone, or — where the pointer is not NULL — HOST arrays of n values, one per member, for
+ * alpha, decay, explor and discount_factor (the ranges of soccer_q_population_config); q_init, plus and linear are scalars.
+ * Refusals, SOCCER_E_STATE during a capture, the misuse flags and the ownership of the memory are those of the
+ * soccer_wolf_population_* calls (memory: n * n_states * 256 bytes of rows, 32 bytes of parameters per member and
+ * n_states * 40 bytes per fixed policy; SOCCER_E_NOMEM leaves the handle usable).  Populations of all kinds and the shared
+ * learners may share a handle.  Not offered: a league opponent, adopt / challengers, a shared-table form, a choice of
+ * bootstrap, per-member flags. */
+typedef struct soccer_regret_population soccer_regret_population;
+typedef struct soccer_regret_population_config {
+    double  discount_factor;        /* [0, 1) */
+    double  alpha;                  /* initial learning rate, [0, 1] */
+    double  decay;                  /* alpha's factor per step, (0, 1] */
+    double  explor;                 /* [0, 1] probability mass a LEARN player spreads uniformly over the five actions */
+    double  q_init;                 /* [-1, 1] */
+    int32_t act_a;                  /* SOCCER_PHC_* */
+    int32_t act_b;
+    int32_t plus;                   /* 0 or 1: regret matching+ */
+    int32_t linear;                 /* 0 or 1: linear averaging */
+    const double* policy_a;         /* act_a == SOCCER_PHC_FIXED: HOST [n_states][5], shared by every member; else NULL */
+    const double* policy_b;
+    const double* policy_a_per_member;         /* or HOST [n_lanes][n_states][5]: a FIXED player has exactly one of the two */
+    const double* policy_b_per_member;
+    const double* alpha_per_member;            /* HOST [n_lanes] or NULL: `alpha` for everyone */
+    const double* decay_per_member;
+    const double* explor_per_member;
+    const double* discount_factor_per_member;
+} soccer_regret_population_config;
+/* what soccer_regret_population_read fills and soccer_regret_population_load takes for `count` members: HOST pointers, any
+ * may be NULL */
+typedef struct soccer_regret_population_state {
+    double* Q_a; double* Q_b;       /* [count][n_states][5] */
+    double* R_a; double* R_b;       /* [count][n_states][5] */
+    double* Z_a; double* Z_b;       /* [count][n_states][5] */
+    uint64_t* updates;              /* [count][n_states] */
+    double* alpha;                  /* [count] */
+    uint64_t* steps;                /* one value */
+} soccer_regret_population_state;
+int soccer_regret_population_create(soccer_handle* h, const soccer_regret_population_config* cfg, soccer_regret_population** out);
+int soccer_regret_population_destroy(soccer_handle* h, soccer_regret_population* q);
+/* n_steps steps of every member in ceil(n_steps / K) launches (K = 4096; SOCCER_POP_LAUNCH_STEPS, read at creation, overrides
+ * it as for soccer_q_population_run), enqueued on the handle's stream: no synchronisation, no copy.  Consumes n_steps ticks.
+ * SOCCER_POP_GRID_BLOCKS caps the grid of run and update launches as for soccer_q_population_run. */
+int soccer_regret_population_run(soccer_handle* h, soccer_regret_population* q, int32_t n_steps);
+/* steps 1-5 on the caller's transitions: DEVICE arrays of n_lanes elements, transition i belongs to member i (reward is
+ * player A's).  A bad transition leaves its member's rows alone (its alpha still advances) and sets the misuse flag.
+ * Consumes no tick. */
+int soccer_regret_population_update(soccer_handle* h, soccer_regret_population* q, const uint16_t* obs, const int8_t* act_a,
+                                    const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs);
+/* Members first .. first + count - 1 (inside the population, else SOCCER_E_INVALID) into every array `out` points to (R and Z
+ * of a player that does not learn are zeros).  Synchronises. */
+int soccer_regret_population_read(soccer_handle* h, soccer_regret_population* q, int64_t first, int64_t count,
+                                  const soccer_regret_population_state* out);
+/* The same range from HOST arrays, any may be NULL (= unchanged): Q_p in [-1, 1]; R_p finite, and >= 0 under `plus`; Z_p finite
+ * and >= 0 (the message names array, member, state and action; R_p and Z_p of a player that does not learn are ignored); row 0
+ * of all six is taken as zeros; updates; alpha in [0, 1]; steps.  Everything is checked before anything is written: a refused
+ * load changes nothing.  read -> load of a range on a fresh population continues bit for bit. */
+int soccer_regret_population_load(soccer_handle* h, soccer_regret_population* q, int64_t first, int64_t count,
+                                  const soccer_regret_population_state* in);
+
 /* HOST output: prob[c*3+k] = slip-combination weight c (0: no slip, 1: B slips, 2: A slips,
  * 3: both; :211-222, evaluated left to right in float64) times outcome probability 1, 0.5, 0.25
  * (k = 0,1,2; :326-360).  prob_code values index this table (:241). */
