@@ -296,8 +296,6 @@ static inline int grid_for(const soccer_handle* h, uint64_t work_items) {
 // ---- what one unit needs from another ------------------------------------------------------------
 // soccer_rollout.hip: lets rollout_kernel<E, slip, lut_lds, *> of this handle's shape take `bytes` of dynamic LDS (soccer_create)
 hipError_t rollout_raise_smem_limit(const soccer_handle* h, size_t bytes);
-// soccer_rollout.hip: would a rollout with these arguments take rollout_swar_kernel (the byte-parallel arm)?
-bool rollout_takes_swar(const soccer_handle* h, const soccer_rollout_args* a, const soccer_rollout_extra* x);
 // soccer_rollout.hip: batched_rollout_ex behind its argument checks, counting episodes into `hist` (a captured run: flush_run)
 int rollout_enqueue(soccer_handle* h, const soccer_rollout_args* a, const soccer_rollout_extra* x, unsigned long long* hist);
 // soccer_step.hip: records the pending run of captured steps: one step as batched_step_ex would have, more as one rollout

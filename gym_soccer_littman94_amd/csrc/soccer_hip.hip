@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "soccer_dispatch.hpp"
 #include "soccer_handle.hpp"
 #include "soccer_env_kernels.hpp"
 #include "soccer_slip.hpp"
@@ -209,9 +210,10 @@ extern "C" int soccer_create(const soccer_config* cfg, soccer_handle** out) {
         const size_t b = h->smem_bytes;
         hipError_t se = rollout_raise_smem_limit(h, b);
         if (se == hipSuccess)
-            se = hipFuncSetAttribute(h->slip ? reinterpret_cast<const void*>(h->lut_lds ? &reset_kernel<true, true> : &reset_kernel<false, true>)
-                                             : reinterpret_cast<const void*>(h->lut_lds ? &reset_kernel<true, false> : &reset_kernel<false, false>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+            se = with_shape(h, [&](auto slip, auto lds) {
+                return hipFuncSetAttribute(reinterpret_cast<const void*>(&reset_kernel<decltype(lds)::value, decltype(slip)::value>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+            });
         HIP_TRY(nullptr, se);
     }
     hipDeviceProp_t prop;
@@ -279,26 +281,24 @@ extern "C" int batched_reset(soccer_handle* h, const uint8_t* mask, const double
     ResetIO io{mask, u_reset, obs};
     // the byte-parallel kernel over the 4-aligned part (Philox draws, dword-aligned streams); whatever is left — a ragged
     // tail, or everything — through the per-lane kernel on the same tick
-    unsigned long long n4 = 0;
-    if (h->swar_ok && !u_reset && h->E != 1 && (P.lane_offset & 3ull) == 0ull && aligned(mask, 4) && aligned(obs, 8)) n4 = P.n & ~3ull;
+    const ResetPlan R = plan_reset(handle_facts(h), ResetCall{mask != nullptr, u_reset != nullptr, aligned(mask, 4) && aligned(obs, 8)});
+    const unsigned long long n4 = R.n4;
     if (n4) {
         ResetSwar RS{h->swar_c, P.state, P.state_stride, P.state_layout, n4, P.lane_offset, P.tick_in, P.tick_out, P.key0, P.key1, mask, obs};
         const dim3 g(static_cast<unsigned>(((n4 >> 2) + kBlock - 1) / kBlock)), b(kBlock);
-        if (h->slip) { if (mask) hipLaunchKernelGGL((reset_kernel_swar<true, true>), g, b, 0, h->stream, RS);
-                       else hipLaunchKernelGGL((reset_kernel_swar<false, true>), g, b, 0, h->stream, RS); }
-        else { if (mask) hipLaunchKernelGGL((reset_kernel_swar<true, false>), g, b, 0, h->stream, RS);
-               else hipLaunchKernelGGL((reset_kernel_swar<false, false>), g, b, 0, h->stream, RS); }
+        with_flag(R.masked, [&](auto masked) { with_flag(R.slip, [&](auto slip) {
+            hipLaunchKernelGGL((reset_kernel_swar<decltype(masked)::value, decltype(slip)::value>), g, b, 0, h->stream, RS);
+        }); });
         note_kernel(h);
     }
     if (n4 < P.n) {
         KernelParams Q = P;
         Q.first = n4; Q.n = P.n - n4;
         if (n4) Q.tick_out = nullptr;           // the main launch publishes the tick
-        const int grid = grid_for(h, Q.n);
-        if (h->slip) { if (h->lut_lds) hipLaunchKernelGGL((reset_kernel<true, true>), dim3(grid), dim3(kBlock), h->smem_bytes, h->stream, Q, io);
-                       else hipLaunchKernelGGL((reset_kernel<false, true>), dim3(grid), dim3(kBlock), h->smem_bytes, h->stream, Q, io); }
-        else { if (h->lut_lds) hipLaunchKernelGGL((reset_kernel<true, false>), dim3(grid), dim3(kBlock), h->smem_bytes, h->stream, Q, io);
-               else hipLaunchKernelGGL((reset_kernel<false, false>), dim3(grid), dim3(kBlock), h->smem_bytes, h->stream, Q, io); }
+        const dim3 g(grid_for(h, Q.n)), b(kBlock);
+        with_flag(R.lut_lds, [&](auto lds) { with_flag(R.slip, [&](auto slip) {
+            hipLaunchKernelGGL((reset_kernel<decltype(lds)::value, decltype(slip)::value>), g, b, h->smem_bytes, h->stream, Q, io);
+        }); });
         note_kernel(h);
     }
     HIP_TRY(h, hipGetLastError());
@@ -557,8 +557,7 @@ static int scalar_call(soccer_handle* h, const char* what, uint32_t op, soccer_s
     k.record = h->rec_dev;
     KernelParams P = h->P;
     bind_tick(h, P, 1);
-    if (h->slip) hipLaunchKernelGGL(scalar_kernel<true>, dim3(1), dim3(64), 0, h->stream, P, k);
-    else hipLaunchKernelGGL(scalar_kernel<false>, dim3(1), dim3(64), 0, h->stream, P, k);
+    with_flag(h->slip, [&](auto slip) { hipLaunchKernelGGL(scalar_kernel<decltype(slip)::value>, dim3(1), dim3(64), 0, h->stream, P, k); });
     HIP_TRY(h, hipGetLastError());
     volatile uint32_t* flag = reinterpret_cast<volatile uint32_t*>(h->rec_host);
     const auto t_start = std::chrono::steady_clock::now();

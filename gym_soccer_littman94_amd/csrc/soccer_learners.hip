@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "soccer_dispatch.hpp"
 #include "soccer_handle.hpp"
 #include "soccer_learner_kernels.hpp"
 #include "soccer_policy_rows.hpp"
@@ -174,24 +175,6 @@ static int transitions_check(soccer_handle* h, const char* what, bool required, 
         return fail(h, SOCCER_E_INVALID, "%s: all six transition arrays are required", what);
     if (!aligned(obs, 2) || !aligned(next_obs, 2)) return fail(h, SOCCER_E_INVALID, "%s: obs / next_obs must be 2-byte aligned", what);
     return SOCCER_OK;
-}
-
-// =================================================================================================
-// the kernel shape of a handle
-// =================================================================================================
-// f(slip, lut_lds) with the handle's two shape bits as compile-time constants: f names the kernel template
-template <class F>
-static hipError_t with_shape(const soccer_handle* h, F f) {
-    using Y = std::true_type;
-    using N = std::false_type;
-    return h->slip ? (h->lut_lds ? f(Y{}, Y{}) : f(Y{}, N{})) : (h->lut_lds ? f(N{}, Y{}) : f(N{}, N{}));
-}
-
-// a creation: the rule tables of a large pitch need more than the default LDS
-template <class K>
-static hipError_t raise_lds_limit(const soccer_handle* h, K* kernel) {
-    return h->smem_bytes > 48 * 1024 ? hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                           (int)h->smem_bytes) : hipSuccess;
 }
 
 // =================================================================================================

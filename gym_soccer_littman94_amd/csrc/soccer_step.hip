@@ -3,6 +3,7 @@
 
 #include <algorithm>
 
+#include "soccer_dispatch.hpp"
 #include "soccer_handle.hpp"
 #include "soccer_step_kernels.hpp"
 
@@ -22,44 +23,16 @@ static bool ensure_worklist(soccer_handle* h) {
     return true;
 }
 
-template <bool EXPLICIT_U, bool VEC, bool SHARED>
-static void launch_step3(soccer_handle* h, const KernelParams& P, const StepIO& io) {
-    const int grid = grid_for(h, (P.n + 3) / 4);
-    const dim3 g(grid), b(kBlock);
-    if (h->slip) hipLaunchKernelGGL((step_kernel<true, EXPLICIT_U, VEC, SHARED>), g, b, 0, h->stream, P, io);
-    else hipLaunchKernelGGL((step_kernel<false, EXPLICIT_U, VEC, SHARED>), g, b, 0, h->stream, P, io);
-    note_kernel(h);
-}
-static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& io, bool explicit_u, bool vec) {
-    const bool shared = ((P.lane_offset + P.first) & 3ull) == 0ull;
-    const bool policy_only = explicit_u && !io.u_step && !io.u_reset;       // fixed-policy handle, Philox draws
-    const bool swar_fit = vec && shared && h->swar_ok && (!h->slip || h->slip_swar_ok) && aligned(io.last_return, 4);
-    // caller-supplied uniforms at slip_prob == 0: floor(4u) is the reference's decision for any double (step_kernel_swar, EXPL)
-    const bool expl = explicit_u && !policy_only && !h->slip && aligned(io.u_step, 16) && aligned(io.u_reset, 16);
-    // ... and at slip_prob > 0 the float64 decision against the nominal thresholds (SLIPM = 3); the groups it cannot decide safely go
-    // to the per-lane kernel's exact walk through a work list (one extra small launch per call)
-    const bool expl_slip = explicit_u && !policy_only && h->slip && io.u_step && aligned(io.u_step, 16) && aligned(io.u_reset, 16) &&
-                           vec && shared && h->swar_ok && aligned(io.last_return, 4) && (P.n >> 2) < 0xffffffffull &&
-                           (h->d_worklist || (!h->capturing && ensure_worklist(h)));      // (no allocation inside a capture: the per-lane kernel then)
-    if (((policy_only || !explicit_u || expl) && swar_fit) || expl_slip) {
+// one launch_step as planned (soccer_launch_plan.hpp: plan_step_part)
+static int launch_step(soccer_handle* h, const KernelParams& P, const StepIO& io, const StepLaunch& L) {
+    const dim3 b(kBlock);
+    const unsigned long long* tick_in = h->capturing ? P.tick_in : nullptr;
+    const unsigned long long tick = (unsigned long long)(h->tick - 1);
+    if (L.family == kStepSwar) {
         // the byte-parallel kernel (four lanes stay packed in their dwords, no rule-table reads)
-        // which outputs the launch needs decides the instantiation: 0 the four result streams, 1 + the gym floats /
-        // finished / last_return, 2 + final_obs / prob_code / episode histogram
-        const int out = (io.prob_code || io.final_obs || P.step_stats) ? 2
-                      : (io.reward_a_f32 || io.reward_b_f32 || io.finished || io.last_return) ? 1 : 0;
-        const dim3 b(kBlock);
         // every launch part covers a multiple of 4 lanes (h->swar_launch_lanes is one), so bit 0 of the lane count is free: it carries
         // the action-load policy into the kernel in a preloaded register (step_kernel_swar)
-        const unsigned long long act_stream = (h->cfg.flags & SOCCER_F_STREAM_ACTIONS) ? 1ull : 0ull;
-#define SWAR_ARGS P.state + c0, P.state_stride, off(io.act_a, c0), off(io.act_b, c0), (h->capturing ? P.tick_in : nullptr), cn | act_stream, (unsigned long long)(h->tick - 1), Q
-        // six-stream handles that fit the byte arithmetic are host-mapped facade handles, tall pitches and SOCCER_STATE_LAYOUT=wide:
-        // nobody times them, so they take the arithmetic geometry (GEO = 0, right for every pitch) instead of mirroring every shape
-#define SWAR_GO(OV, SV, PV, XV) do { if (P.state_layout == kStateWide) hipLaunchKernelGGL((step_kernel_swar<OV, SV, PV, 0, XV, kStateWide>), gh, b, 0, h->stream, SWAR_ARGS); \
-                                     else if (h->swar_c.small) hipLaunchKernelGGL((step_kernel_swar<OV, SV, PV, 1, XV, kStatePacked>), gh, b, 0, h->stream, SWAR_ARGS); \
-                                     else hipLaunchKernelGGL((step_kernel_swar<OV, SV, PV, 0, XV, kStatePacked>), gh, b, 0, h->stream, SWAR_ARGS); } while (0)
-#define SWAR_SLIP(OV, PV) do { if (expl_slip) SWAR_GO(OV, 3, PV, true); else if (expl) SWAR_GO(OV, 0, PV, true); else if (!h->slip) SWAR_GO(OV, 0, PV, false); \
-                               else if (h->d_slip_step_lut) SWAR_GO(OV, 2, PV, false); else SWAR_GO(OV, 1, PV, false); } while (0)
-#define SWAR_OUT(PV) do { if (out == 2) SWAR_SLIP(2, PV); else if (out == 1) SWAR_SLIP(1, PV); else SWAR_SLIP(0, PV); } while (0)
+        const unsigned long long act_stream = L.act_stream ? 1ull : 0ull;
         // The kernel's byte offsets are 32-bit (soccer_kernels.hpp): a handle beyond kSwarLaunchLanes lanes is stepped by
         // several launches on the same tick, each handed its part of every stream; only the last one publishes the tick.
         for (unsigned long long c0 = P.first; c0 < P.first + P.n; c0 += h->swar_launch_lanes) {
@@ -74,62 +47,97 @@ static void launch_step(soccer_handle* h, const KernelParams& P, const StepIO& i
                          h->slip_c, reinterpret_cast<const swar::Quad*>(P.sub), h->d_slip_step_lut,
                          P.policy_a, P.policy_b, off(io.u_step, c0), off(io.u_reset, c0),
                          h->d_slip_f64, h->d_worklist, worklist_count(h)};
-            if (P.policy_a || P.policy_b) SWAR_OUT(true); else SWAR_OUT(false);
+            const bool launched =
+            with_value<0, 1, 2>(L.out, [&](auto ov) { return
+            with_value<0, 1, 2, 3>(L.slipm, [&](auto sv) { return
+            with_flag(L.policy, [&](auto pv) { return
+            with_value<0, 1>(L.geo, [&](auto gv) { return
+            with_flag(L.expl, [&](auto xv) { return
+            with_flag(L.wide, [&](auto wv) {
+                constexpr int OUT = decltype(ov)::value, SLIPM = decltype(sv)::value, GEO = decltype(gv)::value;
+                constexpr bool POLICY = decltype(pv)::value, EXPL = decltype(xv)::value, WIDE = decltype(wv)::value;
+                // caller-supplied uniforms come with SLIPM 0 or 3 only, and SLIPM 3 with nothing else; the wide layout with GEO 0 only
+                constexpr bool compiled = (SLIPM == 3 ? EXPL : (!EXPL || SLIPM == 0)) && !(WIDE && GEO == 1);
+                if constexpr (compiled)
+                    hipLaunchKernelGGL((step_kernel_swar<OUT, SLIPM, POLICY, GEO, EXPL, WIDE ? kStateWide : kStatePacked>), gh, b, 0, h->stream,
+                                       P.state + c0, P.state_stride, off(io.act_a, c0), off(io.act_b, c0), tick_in, cn | act_stream, tick, Q);
+                return compiled;
+            }); }); }); }); }); });
+            if (!launched) return NOT_COMPILED(h, "step_kernel_swar");
             note_kernel(h);
-            if (expl_slip) {
+            if (L.exact_tail) {
                 // the groups of THIS part that were listed: the per-lane kernel, one workgroup, same tick (it publishes nothing)
                 KernelParams R = P; R.first = c0; R.n = cn; R.tick_out = nullptr;
                 StepIO jo = io; jo.worklist = h->d_worklist; jo.work_count = worklist_count(h);
-                hipLaunchKernelGGL((step_kernel<true, true, true, true>), dim3(1), dim3(kBlock), 0, h->stream, R, jo);
+                hipLaunchKernelGGL((step_kernel<true, true, true, true>), dim3(1), b, 0, h->stream, R, jo);
                 note_kernel(h);
             }
         }
-#undef SWAR_OUT
-#undef SWAR_SLIP
-#undef SWAR_GO
-#undef SWAR_ARGS
-    } else if (explicit_u) {    // caller-supplied uniforms (facade, tests) and fixed-policy handles beyond the byte arithmetic: generic kernel
-        if (vec && shared) launch_step3<true, true, true>(h, P, io); else launch_step3<true, false, false>(h, P, io);
-    } else if (vec && shared) {
-        // the per-lane kernels (slip handles, pitches beyond the byte arithmetic): step_kernel_hot has no code for
-        // prob_code / final_obs / last_return / the gym outputs / step stats, step_kernel writes them
-        const bool lean = !io.prob_code && !io.final_obs && !io.last_return && !io.reward_a_f32 && !io.reward_b_f32 && !io.finished && !P.step_stats;
-        const int grid = grid_for(h, (P.n + 3) / 4);
-        const dim3 g(grid), b(kBlock);
-        if (lean) {                 // one 4-lane group per thread, as many workgroups as it takes
-            const unsigned long long blocks = ((P.n >> 2) + kBlock - 1) / kBlock;
-            const dim3 gh(static_cast<unsigned>(blocks));
-#define HOT_ARGS P.state, P.state_stride, io.act_a, io.act_b, (h->capturing ? P.tick_in : nullptr), P.n, (unsigned long long)(h->tick - 1), P, io
-            if (h->slip && P.slip_int == 1u) hipLaunchKernelGGL((step_kernel_hot<true, true>), gh, b, 0, h->stream, HOT_ARGS);
-            else if (h->slip) hipLaunchKernelGGL(step_kernel_hot<true>, gh, b, 0, h->stream, HOT_ARGS);
-            else hipLaunchKernelGGL(step_kernel_hot<false>, gh, b, 0, h->stream, HOT_ARGS);
-            note_kernel(h);
-#undef HOT_ARGS
-        } else launch_step3<false, true, true>(h, P, io);
+    } else if (L.family == kStepHot) {      // one 4-lane group per thread, as many workgroups as it takes
+        const dim3 gh(static_cast<unsigned>(((P.n >> 2) + kBlock - 1) / kBlock));
+        const bool launched =
+        with_flag(L.slip, [&](auto slip) { return
+        with_flag(L.int_only, [&](auto int_only) {
+            constexpr bool compiled = decltype(slip)::value || !decltype(int_only)::value;      // (the integer-only decision is a slip decision)
+            if constexpr (compiled)
+                hipLaunchKernelGGL((step_kernel_hot<decltype(slip)::value, decltype(int_only)::value>), gh, b, 0, h->stream,
+                                   P.state, P.state_stride, io.act_a, io.act_b, tick_in, P.n, tick, P, io);
+            return compiled;
+        }); });
+        if (!launched) return NOT_COMPILED(h, "step_kernel_hot");
+        note_kernel(h);
+    } else {
+        const dim3 g(grid_for(h, (P.n + 3) / 4));
+        const bool launched =
+        with_flag(L.slip, [&](auto slip) { return
+        with_flag(L.explicit_u, [&](auto explicit_u) { return
+        with_flag(L.vec, [&](auto vec) { return
+        with_flag(L.shared, [&](auto shared) {
+            constexpr bool EXPLICIT_U = decltype(explicit_u)::value, VEC = decltype(vec)::value, SHARED = decltype(shared)::value;
+            // dword I/O on a shared phase or byte I/O; the draws of the kernel itself also with dword I/O off the phase
+            constexpr bool compiled = VEC ? (SHARED || !EXPLICIT_U) : !SHARED;
+            if constexpr (compiled)
+                hipLaunchKernelGGL((step_kernel<decltype(slip)::value, EXPLICIT_U, VEC, SHARED>), g, b, 0, h->stream, P, io);
+            return compiled;
+        }); }); }); });
+        if (!launched) return NOT_COMPILED(h, "step_kernel");
+        note_kernel(h);
     }
-    else if (vec) launch_step3<false, true, false>(h, P, io);
-    else launch_step3<false, false, false>(h, P, io);
+    return SOCCER_OK;
+}
+
+// which pointers of a step are given and to what they are aligned
+static StepCall step_call(const soccer_step_args* a) {
+    StepCall c;
+    // dword I/O needs every byte stream 4-aligned and the uint16 streams 8-aligned; else byte I/O
+    c.dword_io = aligned(a->act_a, 4) && aligned(a->act_b, 4) && aligned(a->reward, 4) &&
+                 aligned(a->terminated, 4) && aligned(a->truncated, 4) && aligned(a->prob_code, 4) &&
+                 aligned(a->obs, 8) && aligned(a->final_obs, 8) && aligned(a->reward_a_f32, 16) && aligned(a->reward_b_f32, 16) &&
+                 aligned(a->finished, 4);
+    c.u_step = a->u_step; c.u_reset = a->u_reset; c.u_aligned16 = aligned(a->u_step, 16) && aligned(a->u_reset, 16);
+    c.last_return = a->last_return; c.last_return_aligned4 = aligned(a->last_return, 4);
+    c.full = a->prob_code || a->final_obs; c.gym = a->reward_a_f32 || a->reward_b_f32 || a->finished;
+    return c;
 }
 
 // one step, one launch (two with a ragged tail); the arguments have been checked
 static int launch_one_step(soccer_handle* h, const soccer_step_args* a) {
-    // dword I/O needs every byte stream 4-aligned and the uint16 streams 8-aligned; else byte I/O
-    const bool vec = h->E != 1 && aligned(a->act_a, 4) && aligned(a->act_b, 4) && aligned(a->reward, 4) &&
-                     aligned(a->terminated, 4) && aligned(a->truncated, 4) && aligned(a->prob_code, 4) &&
-                     aligned(a->obs, 8) && aligned(a->final_obs, 8) && aligned(a->reward_a_f32, 16) && aligned(a->reward_b_f32, 16) &&
-                     aligned(a->finished, 4);
-    const bool explicit_u = a->u_step || a->u_reset || h->P.policy_a || h->P.policy_b;   // generic kernel
+    HandleFacts f = handle_facts(h);
+    const StepCall c = step_call(a);
+    StepPlan S = plan_step(f, c);
+    // the work list is allocated by the first call that will use it; where that fails the step takes the per-lane kernel
+    if (S.main.exact_tail && !h->d_worklist && !ensure_worklist(h)) S = plan_step(f, c, true);
     KernelParams P = h->P;
     bind_tick(h, P, 1);
     StepIO io{a->act_a, a->act_b, a->u_step, a->u_reset, a->obs, a->reward, a->terminated, a->truncated,
               a->prob_code, a->final_obs, a->last_return, a->reward_a_f32, a->reward_b_f32, a->finished, nullptr, nullptr};
-    const unsigned long long n = h->P.n, n4 = vec ? (n & ~3ull) : 0ull;
-    if (n4) { P.first = 0; P.n = n4; launch_step(h, P, io, explicit_u, true); }
+    const unsigned long long n = h->P.n, n4 = S.n4;
+    if (n4) { P.first = 0; P.n = n4; if (int rc = launch_step(h, P, io, S.main)) return rc; }
     if (n4 < n) {               // ragged tail (or everything, when the buffers are not dword-aligned)
         KernelParams Q = P;
         Q.first = n4; Q.n = n - n4;
         if (n4) Q.tick_out = nullptr;   // same tick as the main launch, which publishes it
-        launch_step(h, Q, io, explicit_u, false);
+        if (int rc = launch_step(h, Q, io, S.rest)) return rc;
     }
     HIP_TRY(h, hipGetLastError());
     return SOCCER_OK;
@@ -145,13 +153,12 @@ static soccer_rollout_args run_as_rollout(const soccer_step_args& f, int64_t len
     return r;
 }
 
-// may this step be part of a run at all: alone it takes step_kernel_swar<0, ..> (or, with step statistics, <2, ..> for the
-// histogram only), and a run of such steps takes the byte-parallel rollout with its actions read from the two streams
+// may this step be part of a run at all: alone its plan is the byte-parallel kernel with OUT 0 (or, with step statistics, OUT 2 for
+// the histogram only), and a run of such steps takes the byte-parallel rollout with its actions read from the two streams
 static bool step_can_fuse(const soccer_handle* h, const soccer_step_args* a) {
-    if (!h->graph_fuse || !h->own_stream || h->P.policy_a || h->P.policy_b || h->E == 1 || (h->P.n & 3ull)) return false;
-    if (a->u_step || a->u_reset || a->reward_a_f32 || a->reward_b_f32 || a->finished || a->last_return || a->prob_code || a->final_obs) return false;
+    if (!h->graph_fuse || !h->own_stream) return false;
     const soccer_rollout_args r = run_as_rollout(*a, 1, (int64_t)h->P.n, (int64_t)h->P.n);
-    return rollout_takes_swar(h, &r, nullptr);
+    return step_fusable(handle_facts(h), step_call(a), rollout_call(&r, nullptr, true));
 }
 
 // Over `len` steps no result stream may touch another stream of the run: a step's results must not be what a later step of

@@ -18,6 +18,8 @@ from gym_soccer_littman94_amd import planners as pl
 from oracle.oracle import Oracle
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from rollout_shape_cases import (BYTE_PARALLEL, GLOBAL, LDS, NONE, PER_LANE, SLIP_ROWS_BYTES, SOURCES,  # noqa: E402,F401
+                                 STAGING_BYTES, _check_shape, _table_bytes)
 from test_gpu_swar import _oracle_rollout, _rollout_vs_oracle  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -25,24 +27,6 @@ pytestmark = pytest.mark.gpu
 N, T = 4096 + 3, 48             # a ragged tail: the last three lanes go through the per-lane kernel on the same ticks
 STRIDE = 4096 + 4               # (rows a multiple of 4 apart, or the whole call would)
 OFFSET = 4 * 1000003
-BYTE_PARALLEL, PER_LANE = 1, 2
-NONE, LDS, GLOBAL = 0, 1, 2
-SLIP_TABLE_BYTES = (4096 + 40) * 4          # static LDS of the table form of the slip selection
-STAGING_BYTES = 16 * 256 * 4                # sixteen dwords per thread when an action stream is read
-SLIP_ROWS_BYTES = 36 * 4
-
-# action sources: (sampled in the kernel, mix_a, mix_b, fixed side)
-SOURCES = {
-    "uniform":            (True, False, False, None),
-    "both_mixed":         (True, True, True, None),
-    "mix_a":              (True, True, False, None),
-    "mix_b":              (True, False, True, None),
-    "fixed_a_stream_b":   (False, False, False, "player_a"),
-    "fixed_b_stream_a":   (False, False, False, "player_b"),
-    "fixed_a_uniform_b":  (True, False, False, "player_a"),
-    "fixed_b_mix_a":      (True, True, False, "player_b"),
-}
-
 # (width, height, slip, source, kernel, slip selection).  nS: 5x4 761, 7x6 3445, 9x6 5725, 10x7 9661, 11x7 11705.
 CASES = [
     # 5x4: every table in LDS under 48 KB; slip 0 / by table (0.2) / one by one (0.03)
@@ -114,40 +98,6 @@ def _floors(source):
         if use_a or use_b:
             assert seen["degenerate_rows"] >= 250, "visited rows with a threshold at 0 or 32768: %d" % seen["degenerate_rows"]
     return check
-
-
-def _table_bytes(nS, source):
-    """(bytes of the observation-keyed tables in LDS, the action_source the launch then has / has without them in LDS)"""
-    sample, use_a, use_b, fixed = SOURCES[source]
-    if source == "uniform":
-        return 0, 1, 1
-    if source == "both_mixed":
-        return 16 * nS, 2, 3
-    dm = 4 if source == "fixed_a_stream_b" else 5 if source == "fixed_b_stream_a" else 3
-    return 2 * 8 * nS + 2 * ((nS + 15) & ~15), dm, dm
-
-
-def _check_shape(sh, nS, n, steps, source, kernel, slip_sel, extras, launch_lanes=1 << 30):
-    """what rollout_shape() reports against the call's arguments; the placement follows from the reported lds_limit"""
-    sample, use_a, use_b, fixed = SOURCES[source]
-    tables = source != "uniform"
-    assert sh["kernel"] == kernel and sh["chunks"] == -(-steps // 4096) and sh["full"] == int(extras)
-    assert sh["slip_selection"] == slip_sel
-    if kernel == PER_LANE:
-        assert sh["action_source"] == 3 and sh["tail"] == 0 and sh["parts"] == 1
-        assert sh["table_placement"] == (GLOBAL if tables else NONE)
-        return
-    assert sh["tail"] == int(n % 4 != 0) and sh["parts"] == -(-(n & ~3) // launch_lanes)
-    staging = 0 if sample else STAGING_BYTES
-    static = SLIP_TABLE_BYTES if slip_sel == 2 else 0
-    need, dm_lds, dm_global = _table_bytes(nS, source)
-    # the tables go to LDS when they fit the limit next to the slip rows, the staging area (+ 16 B to align it) and the slip table
-    fits = tables and SLIP_ROWS_BYTES + need + (staging + 16 if staging else 0) + static <= sh["lds_limit"]
-    assert sh["table_placement"] == (NONE if not tables else LDS if fits else GLOBAL)
-    assert sh["action_source"] == (dm_lds if fits else dm_global)
-    tab = SLIP_ROWS_BYTES + (need if fits else 0)
-    assert sh["dynamic_lds_bytes"] == (((tab + 15) & ~15) + staging if staging else tab)
-    assert sh["dynamic_lds_bytes"] + static <= sh["lds_limit"]
 
 
 def _tuples(o, fl):
