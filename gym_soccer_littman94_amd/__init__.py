@@ -5,7 +5,7 @@ HIP kernels for gfx950 behind a C ABI (libsoccer_hip.so, include/soccer_hip.h).
 """
 from . import planners, policies  # noqa: F401
 from .compat import install_as_gym_soccer  # noqa: F401
-from .core import DeviceArray, GradientPlay, MinimaxQLearner, MinimaxQPopulation, OpponentModelPopulation, QLearner, QPopulation, RegretPopulation, SoccerBatch, WolfPHCLearner, WolfPopulation  # noqa: F401
+from .core import DeviceArray, GradientPlay, MinimaxQLearner, MinimaxQPopulation, OpponentModelPopulation, QLearner, QPopulation, RegretLearner, RegretPopulation, SoccerBatch, WolfPHCLearner, WolfPopulation  # noqa: F401
 from .envs import SoccerSimultaneousEnv, VectorSoccerEnv  # noqa: F401
 from .registration import make, register_all  # noqa: F401
 

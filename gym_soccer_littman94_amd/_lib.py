@@ -155,6 +155,19 @@ class RegretPopulationState(C.Structure):
                [("steps", C.POINTER(C.c_uint64))]
 
 
+class RegretLearnerConfig(C.Structure):
+    """soccer_regret_learner_config"""
+    _fields_ = [("discount_factor", C.c_double), ("alpha", C.c_double), ("decay", C.c_double), ("explor", C.c_double),
+                ("q_init", C.c_double), ("act_a", C.c_int32), ("act_b", C.c_int32), ("plus", C.c_int32), ("linear", C.c_int32),
+                ("policy_a", C.c_void_p), ("policy_b", C.c_void_p)]
+
+
+class RegretLearnerState(C.Structure):
+    """soccer_regret_learner_state"""
+    _fields_ = [(n, C.c_void_p) for n in ("Q_a", "Q_b", "R_a", "R_b", "Z_a", "Z_b", "visits", "updates")] + \
+               [("alpha", C.POINTER(C.c_double)), ("steps", C.POINTER(C.c_uint64))]
+
+
 MQ_UNIFORM, MQ_SELF, MQ_FIXED = 0, 1, 2
 QL_GREEDY, QL_UNIFORM, QL_FIXED = 0, 1, 2
 PHC_LEARN, PHC_UNIFORM, PHC_FIXED = 0, 1, 2
@@ -286,6 +299,12 @@ PROTOTYPES = {
     "soccer_regret_population_update": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6),
     "soccer_regret_population_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(RegretPopulationState)]),
     "soccer_regret_population_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(RegretPopulationState)]),
+    "soccer_regret_learner_create": (C.c_int, [C.c_void_p, C.POINTER(RegretLearnerConfig), C.POINTER(C.c_void_p)]),
+    "soccer_regret_learner_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "soccer_regret_learner_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "soccer_regret_learner_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6),
+    "soccer_regret_learner_read": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RegretLearnerState)]),
+    "soccer_regret_learner_load": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RegretLearnerState)]),
     "soccer_prob_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_double * 12)]),
     "soccer_get_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.POINTER(C.c_uint64)]),
     "soccer_reset_stats": (C.c_int, [C.c_void_p]),

@@ -12,10 +12,10 @@ from . import _lib
 from ._device import DeviceArray, _ptr
 from ._lib import Config, RolloutArgs, StepArgs
 from .learners import (GradientPlay, MinimaxQLearner, MinimaxQPopulation, OpponentModelPopulation, QLearner, QPopulation,  # noqa: F401
-                       RegretPopulation, WolfPHCLearner, WolfPopulation, _meta_of_cross_play, league_config, minimax_q_config,
-                       minimax_q_population_config, om_derive, om_model, om_population_config, q_learning_config,
-                       q_population_config, regret_average, regret_policy, regret_population_config, wolf_phc_config,
-                       wolf_population_config)
+                       RegretLearner, RegretPopulation, WolfPHCLearner, WolfPopulation, _meta_of_cross_play, league_config,
+                       minimax_q_config, minimax_q_population_config, om_derive, om_model, om_population_config, q_learning_config,
+                       q_population_config, regret_average, regret_learner_config, regret_policy, regret_population_config,
+                       wolf_phc_config, wolf_population_config)
 
 
 def meta_lds_bytes(n_a, n_b):
@@ -506,6 +506,12 @@ class SoccerBatch:
         member."""
         return RegretPopulation(self, discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, plus=plus, linear=linear,
                                 act_a=act_a, act_b=act_b)
+
+    def regret_matching(self, discount_factor, **params):
+        """A RegretLearner on this batch (two players, autoreset=True, at most 2**22 lanes): regret matchers for both players
+        with one table that every lane feeds.  params: alpha, decay, explor, q_init, plus (regret matching+), linear (linear
+        averaging), act_a / act_b: 'learn', 'uniform' or a fixed [nS, 5] mixed policy (learners.regret_learner_config)."""
+        return RegretLearner(self, discount_factor, **params)
 
     # -- hot path -------------------------------------------------------------------------------
     def reset(self, mask=None, u_reset=None, obs=None):

@@ -7,8 +7,8 @@
 //   soccer_planners.hip  the transition table, the single-agent planners, minimax value iteration, best responses, the matrix-game solver
 //   soccer_pairs.hip     the pair evaluators on one host skeleton: cross-play, match outcomes, state occupancy, policy gradients, and gradient play
 //   soccer_metagame.hip  soccer_solve_meta_games: the maximin mixtures of n_a x n_b matrix games
-//   soccer_learners.hip  the eight kinds of learners on one host skeleton: minimax-Q, independent Q, WoLF-PHC, a population of each, and a
-//                        population of opponent-modelling Q-learners and one of regret matchers
+//   soccer_learners.hip  the nine kinds of learners on one host skeleton: minimax-Q, independent Q, WoLF-PHC, a population of each, a
+//                        population of opponent-modelling Q-learners, and regret matchers in both forms
 //   soccer_comm.hip      the RCCL wrapper (host code only)
 //
 // Every unit carries its own code object: a kernel is instantiated, launched and given its attributes (hipFuncSetAttribute)
@@ -118,7 +118,7 @@ struct PendingRun {
     int64_t act_stride = 0, out_stride = 0; // elements between consecutive steps (len >= 2)
 };
 
-struct Learner;                             // soccer_learners.hip: what the eight kinds of learners have in common
+struct Learner;                             // soccer_learners.hip: what the nine kinds of learners have in common
 
 // What solve_pass (soccer_pairs.hip) works on: the buffers of one solve over the pairs of a pass, the pairs along the fastest axis.
 struct PassBufs {

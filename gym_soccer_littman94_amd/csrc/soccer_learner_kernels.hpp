@@ -1,7 +1,8 @@
 // soccer_learner_kernels.hpp — the minimax-Q learner (Littman 1994): learner_act_kernel, learner_reduce_kernel,
 // learner_update_kernel, learner_init_kernel; and the independent Q-learners of both players: q_act_kernel, q_reduce_kernel,
 // q_update_kernel, q_init_kernel (they share the act-and-step body, the reduce body and learner_thresholds); and the policy
-// hill-climbers on top of those: phc_act_kernel, phc_reduce_kernel, phc_update_kernel, phc_init_kernel; and the population
+// hill-climbers on top of those: phc_act_kernel, phc_reduce_kernel, phc_update_kernel, phc_init_kernel; and the regret
+// matchers in the same shape: rm_act_kernel, rm_reduce_kernel, rm_update_kernel, rm_init_kernel; and the population
 // of one-actor Q-learners, a learner per lane: pop_run_kernel, pop_league_run_kernel (against a league opponent),
 // pop_update_kernel, pop_init_kernel; and the population of
 // one-actor policy hill-climbers: phc_pop_run_kernel, phc_pop_update_kernel, phc_pop_init_kernel, phc_pop_adopt_kernel; and the
@@ -514,6 +515,160 @@ __global__ __launch_bounds__(kBlock) void phc_init_kernel(const PhcIO L, double 
     if (k == 0) L.updates[s] = 0ull;
     L.visits[cell] = 0ull; L.cnt[cell] = 0u; L.rsum[cell] = 0; L.sv[0][cell] = 0ll; L.sv[1][cell] = 0ll;
     if (cell == 0) { L.alpha[0] = alpha0; L.alpha[1] = alpha0; L.dscale[0] = 1.0; L.dscale[1] = 1.0; *L.steps = 0ull; }
+}
+
+// =================================================================================================
+// regret matchers of both players, one table (include/soccer_hip.h, "learners, regret matching")
+// =================================================================================================
+// The hill-climbers with the policy derived from cumulative regrets instead of stored.  RmIO begins with a QLearnerIO, so the
+// act body, the reduce body and learner_accumulate are the Q-learners' own (greedy[] is not used); Vq_p is the value of the
+// player's own policy, not the row maximum, and only rm_update_kernel knows.  rm_update_kernel is phc_update_kernel up to the
+// two lanes that own a player: they run step 5 and write R, Z, Vq_p and a LEARN player's threshold row of the next step.  A
+// state has one owner and R is read before it is written, so "the policy from R as it was before this step" needs no copy.
+// Everything there is unrolled over k: the rows stay in registers.
+struct RmIO : QLearnerIO {
+    double* R[2];                       // [nS][5] the cumulative regrets
+    double* Z[2];                       // [nS][5] the policy sums
+    unsigned long long* updates;        // [nS] learner steps that touched the state
+    const double* fixed[2];             // [nS][5] a FIXED player's rows (its Vq needs them); else nullptr
+    int32_t learn[2];                   // the player's R, Z and row are updated; else it is FIXED (fixed[p]) or UNIFORM (0.2 rows)
+    int32_t plus, linear;               // regrets floored at 0; a step's policy weighed by the state's update count
+};
+
+// policy(p, s) of the header for a LEARN player from its five regrets: rm_policy (of the population, below) on a row of five
+__device__ __forceinline__ void rm_policy5(const double (&R)[5], double (&pi)[5]) {
+    double pos[5], tot = 0.0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) { pos[k] = R[k] > 0.0 ? R[k] : 0.0; tot = tot + pos[k]; }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) pi[k] = tot > 0.0 ? pos[k] / tot : 0.2;
+}
+
+template <bool SLIP, bool LUT_LDS>
+__global__ __launch_bounds__(kBlock) void rm_act_kernel(const KernelParams P, const RmIO L) {
+    learner_act<SLIP, LUT_LDS, true>(P, L);
+}
+
+// soccer_regret_learner_update
+__global__ __launch_bounds__(kBlock) void rm_reduce_kernel(const RmIO L, long long n, const uint16_t* obs, const int8_t* act_a,
+                                                           const int8_t* act_b, const int8_t* reward, const uint8_t* terminated,
+                                                           const uint16_t* next_obs) {
+    learner_reduce(L, n, obs, act_a, act_b, reward, terminated, next_obs);
+}
+
+// MODE 0: steps 4-6 of a learner step.  MODE 1 (creation, soccer_regret_learner_load): Vq and the LEARN players' threshold
+// rows are recomputed from Q and R, row 0 included; everything else is left alone.
+template <int MODE>
+__global__ __launch_bounds__(kLearnerBlock) void rm_update_kernel(const RmIO L, int slot) {
+    __shared__ unsigned int sC[kQStates][25];
+    __shared__ int sR[kQStates][25];
+    __shared__ long long sS[2][kQStates][25];
+    __shared__ double sQ[kQStates][10];
+    __shared__ unsigned long long sN[kQStates];
+    const int st = (int)(threadIdx.x >> 5), lane = (int)(threadIdx.x & 31u);
+    const int s = (int)blockIdx.x * kQStates + st;
+    const bool live = s < L.nS && (MODE == 1 || s >= 1);        // index 0 is the terminal observation: Q_p[0] = 0 for good
+    const double alpha = L.alpha[slot];
+    unsigned int c = 0u;
+    if (MODE == 0 && live && lane < 25) {
+        // both players' sums are read here, before anything is zeroed
+        const size_t cell = (size_t)s * 25 + lane;
+        c = L.cnt[cell];
+        sC[st][lane] = c;
+        if (c != 0u) {
+            sR[st][lane] = L.rsum[cell]; sS[0][st][lane] = L.sv[0][cell]; sS[1][st][lane] = L.sv[1][cell];
+            L.visits[cell] += (unsigned long long)c;
+            L.cnt[cell] = 0u; L.rsum[cell] = 0; L.sv[0][cell] = 0ll; L.sv[1][cell] = 0ll;
+        } else {
+            sR[st][lane] = 0; sS[0][st][lane] = 0ll; sS[1][st][lane] = 0ll;
+        }
+    }
+    // the half-wave's 25 bits of the wave's ballot: was any cell of this state touched?
+    const bool any = MODE == 1 || (((unsigned long long)__ballot(c != 0u) >> (threadIdx.x & 32u)) & 0x1ffffffull) != 0ull;
+    __syncthreads();
+    if (live && lane < 10) {
+        const int p = lane / 5, k = lane - 5 * p;                // player, own action
+        const size_t row = (size_t)s * 5 + k;
+        double q = L.Q[p][row];
+        if (MODE == 0) {
+            unsigned int cc = 0u; long long R = 0ll, SV = 0ll;
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {                        // over the other player's action
+                const int x = p ? j * 5 + k : k * 5 + j;
+                cc += sC[st][x]; R += (long long)sR[st][x]; SV += sS[p][st][x];
+            }
+            if (cc != 0u) {
+                if (p) R = -R;                                   // player B's own reward
+                const double m = ((double)R + L.gamma * ((double)SV * kVqInv)) / (double)cc;
+                q = q + alpha * (m - q);
+                L.Q[p][row] = q;
+            }
+            if (lane == 0 && any) {                              // both player lanes need the count: through LDS, one writer
+                const unsigned long long n = L.updates[s] + 1ull;
+                L.updates[s] = n;
+                sN[st] = n;
+            }
+        }
+        sQ[st][lane] = q;
+    }
+    __syncthreads();
+    if (live && any && lane < 2) {
+        const int p = lane;
+        double Q[5], pi[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) Q[k] = sQ[st][p * 5 + k];
+        if (L.learn[p]) {
+            double* const gR = L.R[p] + (size_t)s * 5;
+            double R[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) R[k] = gR[k];
+            rm_policy5(R, pi);                                   // from R as it was before this step
+            if (MODE == 0) {                                     // step 5
+                double* const gZ = L.Z[p] + (size_t)s * 5;
+                const double w = L.linear ? (double)sN[st] : 1.0;
+                double u = 0.0;
+#pragma unroll
+                for (int k = 0; k < 5; ++k) u = u + pi[k] * Q[k];
+#pragma unroll
+                for (int k = 0; k < 5; ++k) {
+                    double x = R[k] + (Q[k] - u);
+                    if (L.plus) x = x > 0.0 ? x : 0.0;
+                    R[k] = x;
+                    gR[k] = x;
+                    gZ[k] = gZ[k] + w * pi[k];
+                }
+                rm_policy5(R, pi);                               // the policy the next step acts from
+            }
+            learner_thresholds(pi, L.explor, (p ? L.mix_b : L.mix_a) + (size_t)s * 4);
+        } else if (L.fixed[p]) {
+            const double* const row = L.fixed[p] + (size_t)s * 5;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) pi[k] = row[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) pi[k] = 0.2;
+        }
+        double v = 0.0;                                          // the value of the player's own policy stands where the maximum stood
+#pragma unroll
+        for (int k = 0; k < 5; ++k) v = v + pi[k] * Q[k];
+        L.Vq[p][s] = (long long)rint(v * kVqScale);
+    }
+    if (MODE == 0 && blockIdx.x == 0 && threadIdx.x == 0) { L.alpha[slot ^ 1] = alpha * L.decay; *L.steps += 1ull; }
+}
+
+// creation: Q_p = q_init on the live states, R = Z = 0, everything else zero (rm_update_kernel<1> then derives the rows)
+__global__ __launch_bounds__(kBlock) void rm_init_kernel(const RmIO L, double q_init, double alpha0) {
+    const int cell = (int)(blockIdx.x * kBlock + threadIdx.x);
+    if (cell >= L.nS * 25) return;
+    const int s = cell / 25, k = cell % 25;
+    if (k < 10) {
+        const size_t row = (size_t)s * 5 + k % 5;
+        L.Q[k / 5][row] = s ? q_init : 0.0;
+        L.R[k / 5][row] = 0.0; L.Z[k / 5][row] = 0.0;
+    }
+    if (k == 0) L.updates[s] = 0ull;
+    L.visits[cell] = 0ull; L.cnt[cell] = 0u; L.rsum[cell] = 0; L.sv[0][cell] = 0ll; L.sv[1][cell] = 0ll;
+    if (cell == 0) { L.alpha[0] = alpha0; L.alpha[1] = alpha0; *L.steps = 0ull; }
 }
 
 // =================================================================================================

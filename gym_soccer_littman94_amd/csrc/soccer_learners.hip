@@ -1,7 +1,7 @@
-// soccer_learners.hip — the eight kinds of learners (see soccer_handle.hpp): the minimax-Q learner soccer_minimax_q_*, the
-// independent Q-learners soccer_q_learner_*, the policy hill-climbers soccer_wolf_phc_*, and the populations of one-actor
-// learners, a member per lane: soccer_q_population_*, soccer_wolf_population_*, soccer_minimax_q_population_*,
-// soccer_om_population_*, soccer_regret_population_*.
+// soccer_learners.hip — the nine kinds of learners (see soccer_handle.hpp): the minimax-Q learner soccer_minimax_q_*, the
+// independent Q-learners soccer_q_learner_*, the policy hill-climbers soccer_wolf_phc_*, the regret matchers
+// soccer_regret_learner_*, and the populations of one-actor learners, a member per lane: soccer_q_population_*,
+// soccer_wolf_population_*, soccer_minimax_q_population_*, soccer_om_population_*, soccer_regret_population_*.
 //
 // What the kinds share comes first and is written once: the registry of live learners with its checks and destroy, the
 // kernel-shape dispatch, the prologue and the hyperparameter checks of a creation, the messages of a refused table
@@ -117,6 +117,15 @@ struct soccer_regret_population : Population {
     RmPopIO io{};
     int grid_blocks = 0;                // as soccer_q_population's
     explicit soccer_regret_population(soccer_handle* handle) : Population(handle, kKind, "the population of regret matchers") {}
+};
+
+// the regret matchers of one table: a FIXED player's rows are a buffer of their own (its Vq needs them)
+struct soccer_regret_learner : Learner {
+    static constexpr int kKind = 8;
+    static constexpr const char* kNoun = "learner";
+    RmIO io{};
+    int slot = 0;                       // alpha slot the NEXT update reads
+    explicit soccer_regret_learner(soccer_handle* handle) : Learner(handle, kKind, "the regret-matching learner") {}
 };
 #pragma GCC visibility pop
 
@@ -305,7 +314,8 @@ static hipError_t act(soccer_handle* h, const KernelParams& P, const IO& io) {
         const dim3 grid(grid_for(h, P.n)), block(kBlock);
         if constexpr (std::is_same_v<IO, LearnerIO>) hipLaunchKernelGGL((learner_act_kernel<slip, lds>), grid, block, h->smem_bytes, h->stream, P, io);
         else if constexpr (std::is_same_v<IO, QLearnerIO>) hipLaunchKernelGGL((q_act_kernel<slip, lds>), grid, block, h->smem_bytes, h->stream, P, io);
-        else hipLaunchKernelGGL((phc_act_kernel<slip, lds>), grid, block, h->smem_bytes, h->stream, P, io);
+        else if constexpr (std::is_same_v<IO, PhcIO>) hipLaunchKernelGGL((phc_act_kernel<slip, lds>), grid, block, h->smem_bytes, h->stream, P, io);
+        else hipLaunchKernelGGL((rm_act_kernel<slip, lds>), grid, block, h->smem_bytes, h->stream, P, io);
         return hipSuccess;
     });
 }
@@ -319,7 +329,8 @@ static void launch_update(T* q) {
     const dim3 block(kLearnerBlock);
     if constexpr (std::is_same_v<T, soccer_minimax_q>) hipLaunchKernelGGL(learner_update_kernel<0>, dim3(mq_update_grid(q->io.nS)), block, 0, q->h->stream, q->io, q->slot);
     else if constexpr (std::is_same_v<T, soccer_q_learner>) hipLaunchKernelGGL(q_update_kernel<0>, dim3(q_update_grid(q->io.nS)), block, 0, q->h->stream, q->io, q->slot);
-    else hipLaunchKernelGGL(phc_update_kernel<0>, dim3(q_update_grid(q->io.nS)), block, 0, q->h->stream, q->io, q->slot);
+    else if constexpr (std::is_same_v<T, soccer_wolf_phc>) hipLaunchKernelGGL(phc_update_kernel<0>, dim3(q_update_grid(q->io.nS)), block, 0, q->h->stream, q->io, q->slot);
+    else hipLaunchKernelGGL(rm_update_kernel<0>, dim3(q_update_grid(q->io.nS)), block, 0, q->h->stream, q->io, q->slot);
     q->slot ^= 1;
 }
 
@@ -1364,15 +1375,17 @@ static void rm_parts(V* Q_a, V* Q_b, V* R_a, V* R_b, V* Z_a, V* Z_b, U* updates,
     parts[6] = {updates, kRmUpdates, 1, kRow0Copy};
 }
 
-// rows 1.. of `members` tables [nS][5] of a checkpoint: every value finite, and >= 0 where `nonneg`
+// rows 1.. of `members` tables [nS][5] of a checkpoint: every value finite, and >= 0 where `nonneg` (members 0: one table, and
+// no member index in the message, as bounds_check)
 static int finite_check(soccer_handle* h, const char* what, const char* name, const double* v, size_t members, size_t nS, bool nonneg) {
-    for (size_t m = 0; m < members; ++m)
+    for (size_t m = 0; m < std::max<size_t>(members, 1); ++m)
         for (size_t s = 1; s < nS; ++s)
             for (size_t k = 0; k < 5; ++k) {
                 const double x = v[(m * nS + s) * 5 + k];
-                if (!std::isfinite(x) || (nonneg && x < 0.0))
-                    return fail(h, SOCCER_E_INVALID, "%s: %s[%zu][%zu][%zu] is %s", what, name, m, s, k,
-                                nonneg ? "negative or not a finite number" : "not a finite number");
+                if (std::isfinite(x) && !(nonneg && x < 0.0)) continue;
+                const char* const why = nonneg ? "negative or not a finite number" : "not a finite number";
+                if (!members) return fail(h, SOCCER_E_INVALID, "%s: %s[%zu][%zu] is %s", what, name, s, k, why);
+                return fail(h, SOCCER_E_INVALID, "%s: %s[%zu][%zu][%zu] is %s", what, name, m, s, k, why);
             }
     return SOCCER_OK;
 }
@@ -1494,5 +1507,135 @@ extern "C" int soccer_regret_population_load(soccer_handle* h, soccer_regret_pop
     if (int rc = pop_rows_load(h, PopTable{io.tab, nS, kPhcRow}, first, count, parts)) return rc;
     if (in->alpha && count) HIP_TRY(h, hipMemcpy(io.alpha + first, in->alpha, (size_t)count * 8, hipMemcpyHostToDevice));
     if (in->steps) HIP_TRY(h, hipMemcpy(io.steps, in->steps, 8, hipMemcpyHostToDevice));
+    return SOCCER_OK;
+}
+
+// =================================================================================================
+// the regret matchers of one table: soccer_regret_learner_* (a single learner on the skeleton above, as soccer_wolf_phc is; it
+// stands here, after the population, because it checks a checkpoint's regrets and policy sums with the population's finite_check)
+// =================================================================================================
+extern "C" int soccer_regret_learner_create(soccer_handle* h, const soccer_regret_learner_config* cfg, soccer_regret_learner** out) {
+    static const char* const what = "soccer_regret_learner_create";
+    if (int rc = create_check(h, cfg, out, what)) return rc;
+    if (int rc = single_check(h, cfg, what)) return rc;
+    if (!phc_kind(cfg->act_a) || !phc_kind(cfg->act_b))
+        return fail(h, SOCCER_E_INVALID, "act_a / act_b must be SOCCER_PHC_LEARN, SOCCER_PHC_UNIFORM or SOCCER_PHC_FIXED");
+    if ((cfg->plus != 0 && cfg->plus != 1) || (cfg->linear != 0 && cfg->linear != 1))
+        return fail(h, SOCCER_E_INVALID, "plus / linear must be 0 or 1");
+    if ((cfg->act_a == SOCCER_PHC_FIXED) != (cfg->policy_a != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_a goes with act_a == SOCCER_PHC_FIXED, and only with it");
+    if ((cfg->act_b == SOCCER_PHC_FIXED) != (cfg->policy_b != nullptr)) return fail(h, SOCCER_E_INVALID, "policy_b goes with act_b == SOCCER_PHC_FIXED, and only with it");
+    const int nS = h->rules.nS;
+    const int32_t kinds[2] = {cfg->act_a, cfg->act_b};
+    const double* policy[2] = {cfg->policy_a, cfg->policy_b};
+    std::vector<uint16_t> fixed[2];
+    if (cfg->policy_a) if (int rc = thresholds(h, "policy_a", cfg->policy_a, nS, fixed[0])) return rc;
+    if (cfg->policy_b) if (int rc = thresholds(h, "policy_b", cfg->policy_b, nS, fixed[1])) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    HIP_TRY(h, with_shape(h, [&](auto slip, auto lds) { return raise_lds_limit(h, rm_act_kernel<slip, lds>); }));
+    std::unique_ptr<soccer_regret_learner> owner(new soccer_regret_learner(h));
+    soccer_regret_learner* q = owner.get();
+    RmIO& io = q->io;
+    const size_t cells = (size_t)nS * 25;
+    double* dfixed[2] = {nullptr, nullptr};
+    int rc = SOCCER_OK;                 // (a failure frees what was taken: `owner` goes, the handle is as it was)
+    for (int p = 0; p < 2; ++p) {
+        if (!rc) rc = q->bufs.alloc(h, (size_t)nS * 5, &io.Q[p]);
+        if (!rc) rc = q->bufs.alloc(h, (size_t)nS * 5, &io.R[p]);
+        if (!rc) rc = q->bufs.alloc(h, (size_t)nS * 5, &io.Z[p]);
+        if (!rc) rc = q->bufs.alloc(h, (size_t)nS, &io.Vq[p]);
+        if (!rc) rc = q->bufs.alloc(h, cells, &io.sv[p]);
+        if (!rc && policy[p]) rc = q->bufs.alloc(h, (size_t)nS * 5, &dfixed[p]);
+    }
+    if (!rc) rc = q->bufs.alloc(h, cells, &io.visits);
+    if (!rc) rc = q->bufs.alloc(h, (size_t)nS, &io.updates);
+    if (!rc) rc = q->bufs.alloc(h, cells, &io.cnt);
+    if (!rc) rc = q->bufs.alloc(h, cells, &io.rsum);
+    if (!rc && cfg->act_a != SOCCER_PHC_UNIFORM) rc = q->bufs.alloc(h, (size_t)nS * 4, &io.mix_a);
+    if (!rc && cfg->act_b != SOCCER_PHC_UNIFORM) rc = q->bufs.alloc(h, (size_t)nS * 4, &io.mix_b);
+    if (!rc) rc = q->bufs.alloc(h, 2, &io.alpha);
+    if (!rc) rc = q->bufs.alloc(h, 1, &io.steps);
+    if (rc) return rc;
+    io.misuse = h->d_misuse;
+    io.gamma = cfg->discount_factor; io.decay = cfg->decay; io.explor = cfg->explor;
+    io.nS = nS;
+    io.plus = cfg->plus; io.linear = cfg->linear;
+    for (int p = 0; p < 2; ++p) { io.learn[p] = kinds[p] == SOCCER_PHC_LEARN ? 1 : 0; io.fixed[p] = dfixed[p]; }
+    hipLaunchKernelGGL(rm_init_kernel, dim3((unsigned)((cells + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream, io, cfg->q_init, cfg->alpha);
+    for (int p = 0; p < 2; ++p) {
+        if (!policy[p]) continue;
+        HIP_TRY(h, hipMemcpyAsync(p ? io.mix_b : io.mix_a, fixed[p].data(), fixed[p].size() * sizeof(uint16_t), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(dfixed[p], policy[p], (size_t)nS * 40, hipMemcpyHostToDevice, h->stream));
+    }
+    hipLaunchKernelGGL(rm_update_kernel<1>, dim3(q_update_grid(nS)), dim3(kLearnerBlock), 0, h->stream, io, 0);
+    return created(owner, out);
+}
+
+extern "C" int soccer_regret_learner_destroy(soccer_handle* h, soccer_regret_learner* q) { return destroy(h, q, "soccer_regret_learner_destroy"); }
+
+extern "C" int soccer_regret_learner_run(soccer_handle* h, soccer_regret_learner* q, int32_t n_steps) {
+    return learner_run(h, q, n_steps, "soccer_regret_learner_run");
+}
+
+extern "C" int soccer_regret_learner_update(soccer_handle* h, soccer_regret_learner* q, int64_t n, const uint16_t* obs, const int8_t* act_a,
+                                            const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs) {
+    if (int rc = learner_update_check(h, q, "soccer_regret_learner_update", n, obs, act_a, act_b, reward, terminated, next_obs)) return rc;
+    if (n > 0)
+        hipLaunchKernelGGL(rm_reduce_kernel, dim3(grid_for(h, (uint64_t)n)), dim3(kBlock), 0, h->stream, q->io, (long long)n,
+                           obs, act_a, act_b, reward, terminated, next_obs);
+    launch_update(q);
+    HIP_TRY(h, hipGetLastError());
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_regret_learner_read(soccer_handle* h, soccer_regret_learner* q, const soccer_regret_learner_state* out) {
+    if (int rc = check(h, q, "soccer_regret_learner_read")) return rc;
+    if (!out) return fail(h, SOCCER_E_INVALID, "soccer_regret_learner_read: out is NULL");
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    const RmIO& io = q->io;
+    const size_t nS = (size_t)io.nS;
+    double* const rows[6] = {out->Q_a, out->Q_b, out->R_a, out->R_b, out->Z_a, out->Z_b};
+    const double* const from[6] = {io.Q[0], io.Q[1], io.R[0], io.R[1], io.Z[0], io.Z[1]};
+    for (int i = 0; i < 6; ++i)
+        if (rows[i]) HIP_TRY(h, hipMemcpyAsync(rows[i], from[i], nS * 40, hipMemcpyDeviceToHost, h->stream));
+    if (out->visits) HIP_TRY(h, hipMemcpyAsync(out->visits, io.visits, nS * 200, hipMemcpyDeviceToHost, h->stream));
+    if (out->updates) HIP_TRY(h, hipMemcpyAsync(out->updates, io.updates, nS * 8, hipMemcpyDeviceToHost, h->stream));
+    if (out->alpha) HIP_TRY(h, hipMemcpyAsync(out->alpha, io.alpha + q->slot, 8, hipMemcpyDeviceToHost, h->stream));
+    if (out->steps) HIP_TRY(h, hipMemcpyAsync(out->steps, io.steps, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SOCCER_OK;
+}
+
+extern "C" int soccer_regret_learner_load(soccer_handle* h, soccer_regret_learner* q, const soccer_regret_learner_state* in) {
+    static const char* const what = "soccer_regret_learner_load";
+    if (int rc = check(h, q, what)) return rc;
+    if (!in || !in->Q_a || !in->Q_b) return fail(h, SOCCER_E_INVALID, "soccer_regret_learner_load: in / Q_a / Q_b is NULL");
+    const RmIO& io = q->io;
+    const size_t nS = (size_t)io.nS;
+    // R and Z of a player that does not LEARN stay the zeros creation gave them
+    const double* const rows[6] = {in->Q_a, in->Q_b, io.learn[0] ? in->R_a : nullptr, io.learn[1] ? in->R_b : nullptr,
+                                   io.learn[0] ? in->Z_a : nullptr, io.learn[1] ? in->Z_b : nullptr};
+    double* const to[6] = {io.Q[0], io.Q[1], io.R[0], io.R[1], io.Z[0], io.Z[1]};
+    static const char* const names[6] = {"Q_a", "Q_b", "R_a", "R_b", "Z_a", "Z_b"};
+    // everything is checked before anything is written
+    for (int i = 0; i < 2; ++i)
+        if (int rc = bounds_check(h, what, names[i], rows[i], 0, nS, 5)) return rc;
+    for (int i = 2; i < 6; ++i)
+        if (rows[i]) if (int rc = finite_check(h, what, names[i], rows[i], 0, nS, i >= 4 || io.plus != 0)) return rc;
+    if (in->alpha) if (int rc = unit_check(h, what, "alpha", in->alpha, 1)) return rc;
+    HIP_TRY(h, hipSetDevice(h->cfg.device));
+    for (int i = 0; i < 6; ++i) {
+        if (!rows[i]) continue;
+        HIP_TRY(h, hipMemsetAsync(to[i], 0, 40, h->stream));                      // row 0 is taken as zeros
+        HIP_TRY(h, hipMemcpyAsync(to[i] + 5, rows[i] + 5, (nS - 1) * 40, hipMemcpyHostToDevice, h->stream));
+    }
+    if (in->visits) HIP_TRY(h, hipMemcpyAsync(io.visits, in->visits, nS * 200, hipMemcpyHostToDevice, h->stream));
+    else HIP_TRY(h, hipMemsetAsync(io.visits, 0, nS * 200, h->stream));
+    if (in->updates) HIP_TRY(h, hipMemcpyAsync(io.updates, in->updates, nS * 8, hipMemcpyHostToDevice, h->stream));
+    else HIP_TRY(h, hipMemsetAsync(io.updates, 0, nS * 8, h->stream));
+    if (in->alpha) HIP_TRY(h, hipMemcpyAsync(io.alpha + q->slot, in->alpha, 8, hipMemcpyHostToDevice, h->stream));
+    if (in->steps) HIP_TRY(h, hipMemcpyAsync(io.steps, in->steps, 8, hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(rm_update_kernel<1>, dim3(q_update_grid(io.nS)), dim3(kLearnerBlock), 0, h->stream, io, q->slot);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));            // the caller's arrays are pageable host memory
     return SOCCER_OK;
 }

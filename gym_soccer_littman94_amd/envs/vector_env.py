@@ -512,6 +512,12 @@ class VectorSoccerEnv:
         assert self.multiagent, "regret_population needs a two-player environment (no player with a fixed policy)"
         return self._batch.regret_population(discount_factor, **params)
 
+    def regret_matching(self, discount_factor, **params):
+        """A RegretLearner (SoccerBatch.regret_matching) whose actors are this env's lanes: regret matchers for both players
+        with one table."""
+        assert self.multiagent, "regret_matching needs a two-player environment (no player with a fixed policy)"
+        return self._batch.regret_matching(discount_factor, **params)
+
     def minimax_q_population(self, discount_factor, **params):
         """A MinimaxQPopulation (SoccerBatch.minimax_q_population): a minimax-Q learner per lane of this env, each with its
         own Q, V and strategies."""

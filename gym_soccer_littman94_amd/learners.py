@@ -192,6 +192,24 @@ def regret_population_config(n, nS, discount_factor, alpha=1.0, decay=DECAY, exp
     return cfg, ((list(shared), list(each)), arrays)
 
 
+def _flags(**given):
+    for name, flag in given.items():
+        assert isinstance(flag, (bool, np.bool_)) or flag in (0, 1), "%s must be True or False" % name
+    return [int(bool(flag)) for flag in given.values()]
+
+
+def regret_learner_config(nS, discount_factor, alpha=1.0, decay=DECAY, explor=0.2, q_init=1.0, plus=True, linear=False,
+                          act_a="learn", act_b="learn"):
+    """Checks the parameters of the regret matchers of one table (AssertionError, before any library call) and returns
+    (soccer_regret_learner_config, the arrays it points into).  plus: regret matching+; linear: linear averaging; act_a /
+    act_b: 'learn', 'uniform' or a fixed [nS, 5] mixed policy."""
+    hyper = _scalars(discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init)
+    flags = _flags(plus=plus, linear=linear)
+    (kind_a, pol_a, _), (kind_b, pol_b, _) = (_kind("act_a", act_a, _PHC_KINDS, nS, where=True),
+                                              _kind("act_b", act_b, _PHC_KINDS, nS, where=True))
+    return _lib.RegretLearnerConfig(*hyper, kind_a, kind_b, *flags, _data(pol_a), _data(pol_b)), [pol_a, pol_b]
+
+
 def minimax_q_population_config(n, nS, discount_factor, alpha=1.0, decay=DECAY, explor=0.2, q_init=1.0, opponent="uniform"):
     """Checks the parameters of a population of minimax-Q learners (AssertionError, before any library call) and returns
     (soccer_minimax_q_population_config, the arrays it points into).  discount_factor, alpha, decay and explor are scalars
@@ -933,6 +951,64 @@ class RegretPopulation(_population_with_a_choice("avg")):
                 x = np.asarray(x, np.float64)
                 assert np.isfinite(x).all() and (not nonneg or (x >= 0.0).all()), "%s must be finite%s" % (k, " and >= 0" if nonneg else "")
         return self._load(dict(Q_a=Q_a, Q_b=Q_b, R_a=R_a, R_b=R_b, Z_a=Z_a, Z_b=Z_b, updates=updates, alpha=alpha, steps=steps), first)
+
+
+class RegretLearner(_Learner):
+    """Regret matchers for both players with ONE table that every lane feeds (the shared form of RegretPopulation) on a
+    two-player auto-reset SoccerBatch: Q_a, Q_b, the cumulative regrets R_a, R_b and the policy sums Z_a, Z_b [nS, 5] on the
+    device, the batch's lanes as actors (include/soccer_hip.h, "learners, regret matching").  plus floors the regrets at 0
+    (regret matching+), linear weighs a step's policy by the state's update count.  run() enqueues and returns; read() and
+    the properties synchronise and copy.  exploitability takes which='avg', the pair of average policies (the one that
+    carries the no-regret guarantee), or which='pi', the pair of current policies."""
+    _C = "soccer_regret_learner"
+    _STATE = _lib.RegretLearnerState
+    _FIELDS = tuple((k, _ROWS, np.float64) for k in ("Q_a", "Q_b", "R_a", "R_b", "Z_a", "Z_b")) + (
+        ("visits", (_S, 25), np.uint64), ("updates", (_S,), np.uint64), ("alpha", None, C.c_double), ("steps", None, C.c_uint64))
+    _WHICH = {"avg": ("avg_a", "avg_b"), "pi": ("pi_a", "pi_b")}
+
+    def __init__(self, batch, discount_factor, **params):
+        cfg, keep = regret_learner_config(batch.nS, discount_factor, **params)
+        self._create(batch, cfg)
+        self.discount_factor = float(discount_factor)
+        self.modes = (cfg.act_a, cfg.act_b)
+        self.plus, self.linear = bool(cfg.plus), bool(cfg.linear)
+        # a fixed player's rows [nS, 5]: read() hands them back (create has copied them to the device)
+        self._fixed = [None if x is None else x.copy() for x in keep]
+        del keep
+
+    def update(self, obs, act_a, act_b, reward, terminated, next_obs):
+        """One learner step's reduce / update / regret step on a batch of transitions (reward is player A's): DeviceArrays
+        (or device tensors) of one length, or numpy arrays, which are copied to the device first."""
+        return self._update(obs, act_a, act_b, reward, terminated, next_obs)
+
+    def read(self):
+        """dict: Q_a / Q_b, R_a / R_b, Z_a / Z_b [nS, 5], visits[nS, 25], updates[nS], alpha, steps; and, computed here by the
+        definition's expressions, pi_a / pi_b (the current policies) and avg_a / avg_b (the average policies) [nS, 5]; a fixed
+        or uniform player reads back its own rows for both.  Synchronises."""
+        out = self._read()
+        for p, name in enumerate("ab"):
+            if self.modes[p] == _lib.PHC_LEARN:
+                out["pi_" + name], out["avg_" + name] = regret_policy(out["R_" + name]), regret_average(out["Z_" + name])
+                continue
+            rows = np.full((self.nS, 5), 0.2) if self._fixed[p] is None else self._fixed[p].copy()
+            out["pi_" + name], out["avg_" + name] = rows, rows.copy()
+        return out
+
+    alpha, steps = _field("alpha"), _field("steps")
+
+    def exploitability(self, which="avg", theta=1e-10):
+        """How badly the best possible opponent beats the pair of average policies (which='avg') or of current policies
+        (which='pi') the learners hold now, at their discount: planners.exploitability.  Synchronises and copies."""
+        return self._exploitability(which, theta)
+
+    def load(self, Q_a, Q_b, R_a=None, R_b=None, Z_a=None, Z_b=None, visits=None, updates=None, alpha=None, steps=None):
+        """Resume from a checkpoint: everything derived is recomputed on the device.  Q in [-1, 1], R finite (and >= 0 under
+        plus), Z finite and >= 0.  With all of read()'s arrays and scalars a fresh learner continues bit for bit.  A regret or
+        policy-sum array that is None is left as it is (those of a player that does not learn are ignored); without `visits`
+        / `updates` the counts are zeroed.  A refused load changes nothing."""
+        assert Q_a is not None and Q_b is not None, "Q_a / Q_b are required"
+        return self._load(dict(Q_a=Q_a, Q_b=Q_b, R_a=R_a, R_b=R_b, Z_a=Z_a, Z_b=Z_b, visits=visits, updates=updates, alpha=alpha,
+                               steps=steps))
 
 
 class GradientPlay(_Learner):

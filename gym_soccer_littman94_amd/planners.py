@@ -172,6 +172,18 @@ def regret_population(env, n_steps, discount_factor, alpha=1.0, decay=None, expl
                   act_a=act_a, act_b=act_b)
 
 
+def regret_matching(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, plus=True, linear=False,
+                    act_a="learn", act_b="learn"):
+    """Regret matching for both players on the device with one table that every lane of `env` feeds (the shared form of
+    regret_population): n_steps learner steps from the lanes' current states (lanes that were never reset are reset first).
+    decay None: alpha falls to 1 % over the run; plus: regret matching+; linear: linear averaging; act_a / act_b: 'learn',
+    'uniform' or a fixed [nS, 5] mixed policy.  Returns (avg_a[nS, 5], avg_b, pi_a, pi_b, Q_a[nS, 5], Q_b, visits[nS, 25]): the
+    average policies first, they carry the guarantee; Q_b is in player B's own reward."""
+    return _train(env, "regret_matching", "regret_matching", n_steps, ("avg_a", "avg_b", "pi_a", "pi_b", "Q_a", "Q_b", "visits"),
+                  discount_factor=discount_factor, alpha=alpha, decay=decay, explor=explor, q_init=q_init, plus=plus, linear=linear,
+                  act_a=act_a, act_b=act_b)
+
+
 def minimax_q_population(env, n_steps, discount_factor, alpha=1.0, decay=None, explor=0.2, q_init=1.0, opponent="uniform", first=0,
                          count=None):
     """A population of minimax-Q learners on the device, a learner per lane of `env`, each with its own table, strategies

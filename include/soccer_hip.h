@@ -1273,8 +1273,8 @@ int soccer_om_population_load(soccer_handle* h, soccer_om_population* q, int64_t
  * Refusals, SOCCER_E_STATE during a capture, the misuse flags and the ownership of the memory are those of the
  * soccer_wolf_population_* calls (memory: n * n_states * 256 bytes of rows, 32 bytes of parameters per member and
  * n_states * 40 bytes per fixed policy; SOCCER_E_NOMEM leaves the handle usable).  Populations of all kinds and the shared
- * learners may share a handle.  Not offered: a league opponent, adopt / challengers, a shared-table form, a choice of
- * bootstrap, per-member flags. */
+ * learners may share a handle.  Not offered: a league opponent, adopt / challengers, a choice of bootstrap, per-member
+ * flags.  (The shared-table form is "learners, regret matching", below.) */
 typedef struct soccer_regret_population soccer_regret_population;
 typedef struct soccer_regret_population_config {
     double  discount_factor;        /* [0, 1) */
@@ -1326,6 +1326,88 @@ int soccer_regret_population_read(soccer_handle* h, soccer_regret_population* q,
  * load changes nothing.  read -> load of a range on a fresh population continues bit for bit. */
 int soccer_regret_population_load(soccer_handle* h, soccer_regret_population* q, int64_t first, int64_t count,
                                   const soccer_regret_population_state* in);
+
+/* ---- learners, regret matching (two-player handles; the regret matchers above with ONE table that every lane feeds)
+ * What soccer_wolf_phc is to its population, this is to the population of regret matchers: the guarantee of regret matching
+ * sits on the AVERAGE policy, and the average needs volume, which a batch gives.  Lives where soccer_wolf_phc lives: a
+ * two-player SOCCER_F_AUTORESET handle of at most 2^22 lanes, whose lanes are its actors; it may share the handle with every
+ * other learner.  State, float64 unless noted:
+ *     Q_a[n_states][5], Q_b[n_states][5] (Q_b in player B's own reward), the cumulative regrets R_a, R_b [n_states][5], the
+ *     policy sums Z_a, Z_b [n_states][5], visits[n_states][25] (uint64), updates[n_states] (uint64: the learner steps in which
+ *     the state was touched), alpha, steps
+ * The flags `plus` (regret matching+: regrets floored at 0) and `linear` (a step's policy weighed by the state's update count)
+ * are set at creation.  A player is SOCCER_PHC_LEARN, SOCCER_PHC_UNIFORM or SOCCER_PHC_FIXED, with one HOST [n_states][5] policy
+ * for a FIXED player, checked as a fixed policy is.  BOTH Q tables always learn, however the players act.
+ * policy(p, s) is that of "learners, a population of regret matchers", word for word: LEARN: the positive part of R_p[s], the
+ * sequential sum tot, pos[k] / tot, or 0.2 where tot is not > 0.0; UNIFORM: 0.2; FIXED: the caller's row at s.
+ * Derived, never state of their own:
+ *     v_p[s] = sum_k policy(p, s)[k] * Q_p[s][k], accumulated from 0.0 in k order;  Vq_p[s] = rint(v_p[s] * 2^40) as int64
+ * the value of the player's own current policy on the learners' integer grid; it stands where the Q-learners keep the row
+ * maximum.  Row 0 is the terminal observation and never a current state: row 0 of all six tables is 0 for good.
+ * One learner step, float64, one operation at a time, never contracted:
+ *   1. the behaviour rows: LEARN the threshold row of (1.0 - explor) * policy(p, s)[k] + explor / 5.0 (step 1 of minimax-Q);
+ *      FIXED the thresholds of the caller's policy, computed once on the host as soccer_wolf_phc does; UNIFORM the NULL row
+ *      table
+ *   2. act and step: the Q-learners' step 2 (the same Philox words, 15-bit halves and histogram; lanes that still need their
+ *      first reset and lanes whose observation is 0 contribute nothing)
+ *   3. reduce: the Q-learners' step 3 into the same four integer accumulators per joint cell, with Vq_p as it stood at the
+ *      end of the previous step
+ *   4. Q update: the Q-learners' step 4, for both tables; visits grow by the cell counts
+ *   5. for every live state s with any touched joint cell:  updates[s] += 1, n = (double)updates[s], w = linear ? n : 1.0;
+ *      then for each LEARN player, with pi = policy(p, s) from R AS IT WAS BEFORE this step and Q = Q_p[s] AFTER step 4:
+ *        u = sum_k pi[k] * Q[k], accumulated from 0.0 in k order
+ *        for every k:  R[k] = R[k] + (Q[k] - u);  under `plus`  R[k] = R[k] > 0.0 ? R[k] : 0.0;  Z[k] = Z[k] + w * pi[k]
+ *      (a player that does not learn leaves R and Z untouched: zeros); then, for BOTH players, Vq_p[s] from the new R and
+ *      the new Q, and a LEARN player's threshold row
+ *   6. alpha = alpha * decay, steps += 1
+ * Initially Q_p = q_init on the live states, R = Z = 0 (every LEARN row starts on the 0.2 fallback), the counts 0.  Derived by
+ * the reader, never state: pi_p = policy(p, .), and avg_p[s][k] = Z_p[s][k] / (the sum of Z_p[s], in the order of tot), 0.2
+ * where that sum is 0.  The state is a fixed function of (seed, parameters, number of steps): it does not depend on the launch
+ * split, on the grid or on the state layout.  A one-lane handle is NOT bit for bit a one-member population: the population
+ * bootstraps with the unquantised v, this form sums Vq over lanes and must stay on the grid.  Ranges, refusals, SOCCER_E_STATE
+ * during a capture, the misuse flags and the ownership of the memory (SOCCER_E_NOMEM leaves the handle usable) are those of the
+ * soccer_wolf_phc_* calls.  Not offered: a league or fixed-per-lane opponent, a choice of bootstrap. */
+typedef struct soccer_regret_learner soccer_regret_learner;
+typedef struct soccer_regret_learner_config {
+    double  discount_factor;        /* [0, 1) */
+    double  alpha;                  /* initial learning rate, [0, 1] */
+    double  decay;                  /* alpha's factor per learner step, (0, 1] */
+    double  explor;                 /* [0, 1] probability mass a LEARN player spreads uniformly over the five actions */
+    double  q_init;                 /* [-1, 1] */
+    int32_t act_a;                  /* SOCCER_PHC_* : how player A acts */
+    int32_t act_b;                  /* SOCCER_PHC_* : how player B acts */
+    int32_t plus;                   /* 0 or 1: regret matching+ */
+    int32_t linear;                 /* 0 or 1: linear averaging */
+    const double* policy_a;         /* act_a == SOCCER_PHC_FIXED: HOST [n_states][5] rows >= 0 summing to 1; else NULL */
+    const double* policy_b;         /* the same for act_b */
+} soccer_regret_learner_config;
+/* what soccer_regret_learner_read fills and soccer_regret_learner_load takes: HOST pointers, any may be NULL */
+typedef struct soccer_regret_learner_state {
+    double* Q_a; double* Q_b;       /* [n_states][5] */
+    double* R_a; double* R_b;       /* [n_states][5] */
+    double* Z_a; double* Z_b;       /* [n_states][5] */
+    uint64_t* visits;               /* [n_states][25] */
+    uint64_t* updates;              /* [n_states] */
+    double* alpha;                  /* one value */
+    uint64_t* steps;
+} soccer_regret_learner_state;
+int soccer_regret_learner_create(soccer_handle* h, const soccer_regret_learner_config* cfg, soccer_regret_learner** out);
+int soccer_regret_learner_destroy(soccer_handle* h, soccer_regret_learner* q);
+/* n_steps learner steps, two launches each, enqueued on the handle's stream: no synchronisation, no copy.  Consumes n_steps ticks. */
+int soccer_regret_learner_run(soccer_handle* h, soccer_regret_learner* q, int32_t n_steps);
+/* steps 3-6 on the caller's batch of n <= 2^22 transitions (DEVICE pointers; reward is player A's), with the checks and the
+ * misuse flags of soccer_minimax_q_update.  Consumes no tick. */
+int soccer_regret_learner_update(soccer_handle* h, soccer_regret_learner* q, int64_t n, const uint16_t* obs, const int8_t* act_a,
+                                 const int8_t* act_b, const int8_t* reward, const uint8_t* terminated, const uint16_t* next_obs);
+/* Fills every array `out` points to (R and Z of a player that does not learn are zeros).  Synchronises. */
+int soccer_regret_learner_read(soccer_handle* h, soccer_regret_learner* q, const soccer_regret_learner_state* out);
+/* Resume from a checkpoint; nothing of `in` is written.  Q_a / Q_b are required, in [-1, 1].  R_p / Z_p of a LEARN player: R
+ * finite, and >= 0 under `plus`; Z finite and >= 0 (SOCCER_E_INVALID, the message names array, state and action); NULL = left
+ * as it is; those of a player that does not LEARN are ignored.  Row 0 of all six tables is taken as zeros.  visits / updates:
+ * NULL = the counts are zeroed.  alpha (in [0, 1]) and steps: NULL = unchanged.  Everything is checked before anything is
+ * written: a refused load changes nothing.  Every derived row is recomputed, so read -> load on a fresh learner continues bit
+ * for bit. */
+int soccer_regret_learner_load(soccer_handle* h, soccer_regret_learner* q, const soccer_regret_learner_state* in);
 
 /* HOST output: prob[c*3+k] = slip-combination weight c (0: no slip, 1: B slips, 2: A slips,
  * 3: both; :211-222, evaluated left to right in float64) times outcome probability 1, 0.5, 0.25
